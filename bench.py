@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Headline (BASELINE.json configs[1]): columns/s of the Zhao-Carr microphysics MLP emulator
 (K = 711 inputs, 2 x 256 hidden, 396 outputs; projects/microphysics/train/dense.yaml:62-89 of
@@ -12,9 +12,14 @@ weak scaling; value = columns of all ranks / max-over-ranks time.
 
 The JSON line also carries
   roofline     -- the MLP kernel against the fp32 MFMA peak, timed with HIP events on the launch stream
+and, with --full only,
+  parity_max_rel -- the timed model object against the float64 oracle on 4096 of the timed columns
   cpu_baseline -- the numpy oracle of the same network on a bounded sample, on this box's host cores
   secondary    -- the HBM-bound coarsening kernels (C3072 -> C384 weighted_block_average, C384 mappm)
                   against the HBM roofline
+
+--dump-outputs DIR writes rank 0's outputs of the last timed step, a fixed sample of their columns
+(``dump_outputs``), as DIR/<output name>.npy; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -166,6 +171,24 @@ def zc_inputs_device(dev, n, seed):
         "air_temperature_after_last_gscond": t + torch.randn((NZ, n), device=dev, generator=g) * 0.5,
         "specific_humidity_after_last_gscond": q * u(0.9, 1.1),
     }
+
+
+DUMP_COLUMNS = 16384        # 791 output rows x 16384 columns x 4 bytes = 52 MB
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outs, out_dir, seed=0):
+    """Write ``predict``'s [feature, sample] outputs as ``out_dir/<name>.npy``, float32: the same fixed, seeded sample of
+    DUMP_COLUMNS columns (in ascending order) of every output, all columns where there are fewer."""
+    n = next(iter(outs.values())).shape[1]
+    cols = np.sort(np.random.default_rng(seed).choice(n, min(n, DUMP_COLUMNS), replace=False))
+    nbytes = 4 * len(cols) * sum(t.shape[0] for t in outs.values())
+    if nbytes > DUMP_LIMIT_BYTES:
+        raise ValueError(f"a dump of {nbytes} bytes exceeds {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outs.items():
+        picked = t.index_select(1, torch.from_numpy(cols).to(t.device))
+        np.save(os.path.join(out_dir, f"{name}.npy"), picked.cpu().numpy().astype(np.float32, copy=False))
 
 
 PMC_TRAFFIC_FILES = ("r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json")
@@ -1066,10 +1089,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)  # (the clocks ramp over the first ~6 launches after a pause)
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the first 4096 timed columns")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also check parity, time the CPU baselines and run the secondary workloads")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the oracle check of the first 4096 timed columns")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed sample of the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args.gpus)  # does not return
@@ -1112,7 +1140,7 @@ def main():
     # parity of the timed object on a slice of the timed inputs (rank 0; the oracle is the checker, never the thing timed):
     # device part now, oracle part after the timed loop
     sliced, parity, parity_variant = None, None, None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         try:
             sliced = parity_slice_predict(model, src)
             parity_variant = sliced["variant"]
@@ -1134,8 +1162,9 @@ def main():
     timer = HipTimer()
     t0 = time.perf_counter()
     timer.start(dev)
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    outs = step()
     timer.stop(dev)
     fence()
     elapsed = time.perf_counter() - t0
@@ -1144,6 +1173,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(outs, args.dump_outputs)
+    del outs
 
     line = None
     if rank == 0:
@@ -1180,7 +1212,8 @@ def main():
                 "parallelism": f"snapshot/tile sharding over {world} GPU(s), no collective on the data path",
                 "parity_max_rel": parity,
                 "parity_note": "max over the 11 outputs of max|gpu - f64 oracle| / max|oracle| on the first 4096 columns of a "
-                               f"full-size call of the timed model object ({parity_variant}); bar 1e-5",
+                               f"full-size call of the timed model object ({parity_variant}); bar 1e-5" if parity_variant is not None
+                               else "not checked in this run (--full checks it)",
             },
             "parity_max_rel": parity,
             "roofline": {
@@ -1195,7 +1228,7 @@ def main():
                 "kernel_ms": kernel_ms,
             },
         }
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             try:
                 line["cpu_baseline"] = cpu_baseline(spec)
             except Exception as err:  # noqa: BLE001
@@ -1203,7 +1236,7 @@ def main():
                                         "sample": f"failed: {type(err).__name__}: {err}"}
     del src
     torch.cuda.empty_cache()
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # (never lose the headline line to a secondary workload)
         if world == 1:
             try:

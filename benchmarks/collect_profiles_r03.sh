@@ -9,14 +9,14 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 set -x
 # 1. the bench line of this tree
-python3 $R/bench.py --steps 20 --warmup 10 > $O/r03_bench.json 2> $O/bench.err || exit 1
+python3 $R/bench.py --full --steps 20 --warmup 10 > $O/r03_bench.json 2> $O/bench.err || exit 1
 # 2. kernel statistics of the headline alone: >= 10 warm-ups under the profiler, no parity call, per-dispatch trace kept
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline -- python3 $R/bench.py --steps 10 --warmup 10 --no-cpu --no-secondary --no-parity > $O/stats_headline.log 2>&1 || exit 1
 # 3. ... and with the secondary workloads
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_all -- python3 $R/bench.py --steps 10 --warmup 10 --no-cpu --no-parity > $O/stats_all.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_all -- python3 $R/bench.py --full --steps 10 --warmup 10 --no-cpu --no-parity > $O/stats_all.log 2>&1 || exit 1
 # 4. HBM traffic of the headline and the coarsening kernels (FETCH_SIZE / WRITE_SIZE, separate passes)
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --no-parity > $O/pmc_fetch.log 2>&1 || exit 1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --no-parity > $O/pmc_write.log 2>&1 || exit 1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu --no-parity > $O/pmc_fetch.log 2>&1 || exit 1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu --no-parity > $O/pmc_write.log 2>&1 || exit 1
 # (gpurun merges at most 64 MiB back: of the two traffic passes keep the rows of the kernels that profiles/r03_pmc_traffic.json quotes)
 for d in pmc_fetch pmc_write; do
   for f in $O/$d/*/*_counter_collection.csv; do

@@ -2,7 +2,7 @@
 #   gpurun -- 'bash benchmarks/pipeline_streams_ab.sh'
 cd $GRAFT_REPO_ROOT
 run() {
-python bench.py --no-cpu --steps 10 2>/dev/null | python -c "
+python bench.py --full --no-cpu --steps 10 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', ' '.join(f\"{s['ms']:.2f}/{s.get('graph_replay_ms',0):.2f}\" for s in d['secondary'] if 'pipeline' in s['kernel']))"

@@ -321,3 +321,41 @@ def test_bench_launcher_never_touches_the_gpu_library(monkeypatch, tmp_path):
     assert exit_info.value.code == 2 and not started
     monkeypatch.undo()
     assert bench.visible_gpu_count() in (None, 0) or bench.visible_gpu_count() >= 1  # (file reads only; no GPU here)
+
+
+def test_bench_dump_outputs_writes_the_same_seeded_sample(tmp_path):
+    """``bench.py --dump-outputs DIR``: every output as DIR/<name>.npy, float32, the same ascending sample of columns on
+    every run, within the dump's byte limit; a dump over the limit is refused."""
+    import bench
+
+    n = 3 * bench.DUMP_COLUMNS
+    outs = {"dQ1": torch.rand((79, n), generator=torch.Generator().manual_seed(0)),
+            "total_precipitation": torch.rand((1, n), generator=torch.Generator().manual_seed(1))}
+    outs["dQ1"][0] = torch.arange(n)  # (row 0 names the column)
+    for run in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / run))
+    got = {name: np.load(tmp_path / "a" / f"{name}.npy") for name in outs}
+    assert {p.name for p in (tmp_path / "a").iterdir()} == {"dQ1.npy", "total_precipitation.npy"}
+    assert got["dQ1"].dtype == np.float32 and got["dQ1"].shape == (79, bench.DUMP_COLUMNS)
+    cols = got["dQ1"][0].astype(np.int64)
+    assert np.all(np.diff(cols) > 0) and cols[-1] < n
+    for name, t in outs.items():
+        np.testing.assert_array_equal(got[name], t.numpy()[:, cols])
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{name}.npy"), got[name])
+    few = {"dQ1": outs["dQ1"][:, :100]}
+    bench.dump_outputs(few, str(tmp_path / "few"))
+    np.testing.assert_array_equal(np.load(tmp_path / "few" / "dQ1.npy"), few["dQ1"].numpy())
+    with pytest.raises(ValueError, match="exceeds"):
+        bench.dump_outputs({"wide": torch.zeros((1100, n))}, str(tmp_path / "wide"))
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"]])
+def test_bench_refuses_steps_it_cannot_time(monkeypatch, argv):
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    with pytest.raises(SystemExit) as exit_info:
+        bench.main()
+    assert exit_info.value.code == 2
