@@ -78,6 +78,28 @@ class MlpDesc(ctypes.Structure):
     ]
 
 
+class ForestDesc(ctypes.Structure):
+    _fields_ = [
+        ("n_trees", c_int),
+        ("node_offset", POINTER(c_int64)),
+        ("children_left", POINTER(ctypes.c_int32)),
+        ("children_right", POINTER(ctypes.c_int32)),
+        ("feature", POINTER(ctypes.c_int32)),
+        ("threshold", POINTER(c_float)),
+        ("missing_go_to_left", POINTER(ctypes.c_uint8)),
+        ("leaf_row", POINTER(ctypes.c_int32)),
+        ("n_leaf_rows", c_int64),
+        ("leaf_values", POINTER(c_double)),
+        ("n_sources", c_int),
+        ("src_feat_start", POINTER(c_int)),
+        ("src_nfeat", POINTER(c_int)),
+        ("n_outputs", c_int),
+        ("out_nfeat", POINTER(c_int)),
+        ("mean", POINTER(c_double)),
+        ("std", POINTER(c_double)),
+    ]
+
+
 # name -> (restype, argtypes); every name here must be declared in include/fv3hip.h
 SIGNATURES = {
     "fv3hip_last_error": (c_char_p, []),
@@ -191,6 +213,17 @@ SIGNATURES = {
     "fv3hip_mlp3_destroy": (c_int, [c_void_p]),
     "fv3hip_mlp3_flops_per_sample": (c_int64, [c_void_p]),
     "fv3hip_mlp3_predict": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), c_int64, POINTER(c_void_p), POINTER(c_int64), c_void_p]),
+    "fv3hip_forest_create": (c_int, [POINTER(ForestDesc), POINTER(c_void_p)]),
+    "fv3hip_forest_destroy": (c_int, [c_void_p]),
+    "fv3hip_forest_predict": (
+        c_int,
+        [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), POINTER(c_int64), c_int64,
+         POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_void_p],
+    ),
+    "fv3hip_forest_apply": (
+        c_int,
+        [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), POINTER(c_int64), c_int64, c_void_p, c_void_p],
+    ),
     "fv3hip_timer_create": (c_int, [POINTER(c_void_p)]),
     "fv3hip_timer_start": (c_int, [c_void_p, c_void_p]),
     "fv3hip_timer_stop": (c_int, [c_void_p, c_void_p]),

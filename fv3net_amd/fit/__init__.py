@@ -13,10 +13,11 @@ from .data_transform import DATA_TRANSFORM_REGISTRY, ChainedDataTransform, DataT
 from .novelty import (MinMaxNoveltyDetector, NoveltyDetector, OCSVMNoveltyDetector, get_taper_function, taper_decay, taper_mask,
                       taper_ramp)
 from .transformed import OutOfSampleModel, TransformedPredictor
+from .forest import RandomForest
 
 __all__ = [
     "ChainedDataTransform", "ConstantOutputNoveltyDetector", "DATA_TRANSFORM_REGISTRY", "DataTransform", "MinMaxNoveltyDetector", "NoveltyDetector", "OCSVMNoveltyDetector",
-    "OutOfSampleModel", "TransformedPredictor", "get_taper_function", "taper_decay", "taper_mask", "taper_ramp",
+    "OutOfSampleModel", "RandomForest", "TransformedPredictor", "get_taper_function", "taper_decay", "taper_mask", "taper_ramp",
     "CombinedOutputModel", "ConstantOutputPredictor", "DenseHyperparameters", "DerivedMapping", "DerivedModel", "EnsembleModel", "SquashedOutputConfig",
     "SquashedOutputModel", "TaperConfig", "TaperedModel", "vertical_tapering_scale_factors", "HipDenseModel", "Predictor", "SAMPLE_DIM_NAME", "dump", "io",
     "load", "match_prediction_to_input_coords", "spec_from_arrays", "stack", "train_dense_model",

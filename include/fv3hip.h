@@ -477,6 +477,59 @@ int64_t fv3hip_mlp3_flops_per_sample(fv3hip_mlp3_t model);
 int fv3hip_mlp3_predict(fv3hip_mlp3_t model, const void *const *sources, const int64_t *src_feat_stride, int64_t n_samples,
                         void *const *outputs, const int64_t *out_feat_stride, void *stream);
 
+/*
+ * Random forest: fv3fit.sklearn.RandomForest (registered "sklearn", external/fv3fit/fv3fit/sklearn/_random_forest.py:65-377),
+ * i.e. sklearn's RandomForestRegressor / ExtraTreesRegressor .predict on the packed inputs followed by the target scaler's
+ * denormalize (_random_forest.py:247-259, _shared/scaler.py:65-73).  Bit-identical to sklearn:
+ *   - inputs are cast to float32 (numpy astype); at an internal node NaN goes left iff missing_go_to_left, any other x
+ *     goes left iff x <= threshold, where `threshold` is the largest float32 <= sklearn's float64 threshold;
+ *   - y = sum over trees, in tree order, of the leaf's float64 values; y /= n_trees; y = y * std + mean.
+ * Nodes are sklearn's tree_ arrays, concatenated: tree t owns nodes [node_offset[t], node_offset[t+1]) with tree-local ids.
+ * fv3hip_forest_create validates everything on the host before any HIP call (FV3HIP_EINVAL): n_trees >= 1; every internal
+ * node's children have larger ids than the node (so every walk ends); feature indices are inside the packed inputs; leaf
+ * rows are inside leaf_values.
+ */
+typedef struct {
+    int n_trees;
+    const int64_t *node_offset;        /* [n_trees + 1], node_offset[0] = 0 */
+    const int32_t *children_left;      /* [n_nodes] tree-local ids; -1 marks a leaf (sklearn's TREE_LEAF) */
+    const int32_t *children_right;     /* [n_nodes] */
+    const int32_t *feature;            /* [n_nodes] packed input feature of an internal node */
+    const float *threshold;            /* [n_nodes] largest float32 <= tree_.threshold */
+    const uint8_t *missing_go_to_left; /* [n_nodes] */
+    const int32_t *leaf_row;           /* [n_nodes] a leaf's row of leaf_values (ignored for internal nodes) */
+    int64_t n_leaf_rows;
+    const double *leaf_values;         /* [n_leaf_rows][n_out] (tree_.value[:, :, 0]) */
+    /* the packed inputs: features [src_feat_start[s], src_feat_start[s] + src_nfeat[s]) of each source in turn (the
+     * packer's clip, _shared/packer.py:113-169) */
+    int n_sources;                     /* <= 32 */
+    const int *src_feat_start;
+    const int *src_nfeat;
+    int n_outputs;                     /* <= 32 */
+    const int *out_nfeat;              /* n_out = sum(out_nfeat) */
+    const double *mean;                /* [n_out] target scaler */
+    const double *std;                 /* [n_out] */
+} fv3hip_forest_desc_t;
+
+typedef struct fv3hip_forest *fv3hip_forest_t;
+
+int fv3hip_forest_create(const fv3hip_forest_desc_t *desc, fv3hip_forest_t *out);
+int fv3hip_forest_destroy(fv3hip_forest_t forest);
+/* SklearnWrapper._predict_on_stacked_data (_random_forest.py:247-259: pack, model.predict, denormalize, unpack).
+ *   sources[s]: as in fv3hip_mlp_predict -- dtype src_dtype[s] (F32/F64, may differ between sources), element (feature f,
+ *               sample n) at f * src_feat_stride[s] + n * src_sample_stride[s];
+ *   outputs[j]: float64, element (f, n) at f * out_feat_stride[j] + n * out_sample_stride[j].
+ * Keeps a [tree][sample] scratch of leaf rows with the forest (grown on demand: warm up before capturing a graph). */
+int fv3hip_forest_predict(fv3hip_forest_t forest, const void *const *sources, const int *src_dtype,
+                          const int64_t *src_feat_stride, const int64_t *src_sample_stride, int64_t n_samples,
+                          double *const *outputs, const int64_t *out_feat_stride, const int64_t *out_sample_stride,
+                          void *stream);
+/* RandomForestRegressor.apply on the packed inputs: leaf_node[t * n_samples + n] = the tree-local id of the leaf sample n
+ * reaches in tree t (sklearn's forest.apply(X).T). */
+int fv3hip_forest_apply(fv3hip_forest_t forest, const void *const *sources, const int *src_dtype,
+                        const int64_t *src_feat_stride, const int64_t *src_sample_stride, int64_t n_samples,
+                        int32_t *leaf_node, void *stream);
+
 /* `n_workgroups` idle wavefronts of `microseconds` (<= 100000) each on `stream`: the host layer times a small one beside a large one
  * on another stream to learn which streams the runtime lets run side by side (cubedsphere/_device.py: the pipelines' side streams). */
 int fv3hip_spin(int64_t microseconds, int n_workgroups, void *stream);
