@@ -100,6 +100,51 @@ class ForestDesc(ctypes.Structure):
     ]
 
 
+class ReservoirTransformer(ctypes.Structure):
+    _fields_ = [
+        ("kind", c_int),
+        ("n_variables", c_int),
+        ("var_nz", POINTER(c_int)),
+        ("nx", c_int),
+        ("ny", c_int),
+        ("center", POINTER(c_float)),
+        ("scale", POINTER(c_float)),
+        ("mask", POINTER(c_double)),
+        ("mask_f32", c_int),
+    ]
+
+
+class ReservoirDesc(ctypes.Structure):
+    _fields_ = [
+        ("layout_x", c_int),
+        ("layout_y", c_int),
+        ("overlap", c_int),
+        ("rank_x", c_int),
+        ("rank_y", c_int),
+        ("state_size", c_int),
+        ("input_size", c_int),
+        ("input", ReservoirTransformer),
+        ("output", ReservoirTransformer),
+        ("hybrid", ReservoirTransformer),
+        ("w_in_indptr", POINTER(c_int64)),
+        ("w_in_indices", POINTER(ctypes.c_int32)),
+        ("w_in_data", POINTER(c_double)),
+        ("w_in_storage", c_int),
+        ("w_res_indptr", POINTER(c_int64)),
+        ("w_res_indices", POINTER(ctypes.c_int32)),
+        ("w_res_data", POINTER(c_double)),
+        ("input_mask", POINTER(c_double)),
+        ("input_mask_f32", c_int),
+        ("square", c_int),
+        ("n_hybrid", c_int),
+        ("hybrid_mask", POINTER(c_double)),
+        ("hybrid_mask_f32", c_int),
+        ("coefficients", POINTER(c_double)),
+        ("intercepts", POINTER(c_double)),
+        ("state", POINTER(c_double)),
+    ]
+
+
 # name -> (restype, argtypes); every name here must be declared in include/fv3hip.h
 SIGNATURES = {
     "fv3hip_last_error": (c_char_p, []),
@@ -224,6 +269,16 @@ SIGNATURES = {
         c_int,
         [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), POINTER(c_int64), c_int64, c_void_p, c_void_p],
     ),
+    "fv3hip_reservoir_create": (c_int, [POINTER(ReservoirDesc), POINTER(c_void_p)]),
+    "fv3hip_reservoir_destroy": (c_int, [c_void_p]),
+    "fv3hip_reservoir_increment": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), c_void_p]),
+    "fv3hip_reservoir_predict": (
+        c_int,
+        [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), POINTER(c_void_p), POINTER(c_int64), c_void_p],
+    ),
+    "fv3hip_reservoir_get_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "fv3hip_reservoir_set_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "fv3hip_reservoir_reset_state": (c_int, [c_void_p, c_void_p]),
     "fv3hip_timer_create": (c_int, [POINTER(c_void_p)]),
     "fv3hip_timer_start": (c_int, [c_void_p, c_void_p]),
     "fv3hip_timer_stop": (c_int, [c_void_p, c_void_p]),

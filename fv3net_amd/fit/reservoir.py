@@ -1,0 +1,424 @@
+"""Reservoir computing models: fv3fit's ``"pure-reservoir"`` / ``"hybrid-reservoir"`` (reservoir/model.py:36-337) and
+their dataset adapters ``"reservoir-adapter"`` / ``"hybrid-reservoir-adapter"`` (reservoir/adapters.py:92-301), stepping
+on the MI355X.
+
+The artifact is the reference's own layout, read and written with numpy and YAML only: ``reservoir/`` (W_in and W_res as
+``scipy.sparse.save_npz`` files, ``metadata.bin``, optional ``input_mask.npy`` and ``state.npy``), ``readout/``
+(``coefficients.npz``, which ``np.save`` writes despite its name, and ``intercepts.npy``), ``metadata.yaml``,
+``rank_divider.yaml`` and ``transformers/{input,output,hybrid}_transformer/``.  Training stays the reference's.
+
+Two behaviours of the reference are kept on purpose: the pure model squares the even *subdomains*
+of the state when ``square_half_hidden_state`` is set (``square_even_terms(state, axis=0)``, model.py:225) where the hybrid
+model squares even state elements (axis -1, model.py:122); and a ``scale-spatial-concat-z`` transformer rejects inputs
+whose (x, y, z) extent differs from its own.  ``get_model_from_subdomain`` gives the sub-model a copy of the parent's
+state row instead of sharing the parent's reservoir object.
+"""
+import os
+from typing import Hashable, List, Optional, Sequence
+
+import numpy as np
+import torch
+import yaml
+
+from ..cubedsphere._device import compute_device
+from ..reservoir import (SQUARE_ELEMENTS, SQUARE_NONE, SQUARE_SUBDOMAINS, WIN_AUTO, RankXYDivider, ReservoirModel,
+                         SparseMatrix, _yaml_load, load_transformer)
+from ..xr_compat import DataArray, Dataset, from_compat, to_compat
+from . import io
+from .predictor import Predictor
+
+
+class Reservoir:
+    """The reservoir's arrays (reservoir.py:33-200): W_in [state, input_size], W_res [state, state], optional input mask
+    and saved state, and the hyperparameters as written (training only needs them)."""
+
+    INPUT_WEIGHTS_NAME = "reservoir_W_in.npz"
+    RESERVOIR_WEIGHTS_NAME = "reservoir_W_res.npz"
+    METADATA_NAME = "metadata.bin"
+    INPUT_MASK_NAME = "input_mask.npy"
+    STATE_NAME = "state.npy"
+
+    def __init__(self, hyperparameters: dict, input_size: int, W_in: SparseMatrix, W_res: SparseMatrix,
+                 input_mask_array: Optional[np.ndarray] = None, state: Optional[np.ndarray] = None):
+        self.hyperparameters = dict(hyperparameters)
+        self.input_size = int(input_size)
+        self.W_in, self.W_res = W_in, W_res
+        self.input_mask_array = input_mask_array
+        self.state = state
+        if W_in.shape != (self.state_size, self.input_size) or W_res.shape != (self.state_size, self.state_size):
+            raise ValueError(f"W_in {W_in.shape} / W_res {W_res.shape} do not match state_size {self.state_size} and "
+                             f"input_size {self.input_size}")
+
+    @property
+    def state_size(self) -> int:
+        return int(self.hyperparameters["state_size"])
+
+    def dump(self, path: str) -> None:
+        os.makedirs(path, exist_ok=True)
+        self.W_in.dump(os.path.join(path, self.INPUT_WEIGHTS_NAME))
+        self.W_res.dump(os.path.join(path, self.RESERVOIR_WEIGHTS_NAME))
+        if self.input_mask_array is not None:
+            np.save(os.path.join(path, self.INPUT_MASK_NAME), self.input_mask_array, allow_pickle=False)
+        if self.state is not None:
+            np.save(os.path.join(path, self.STATE_NAME), self.state, allow_pickle=False)
+        with open(os.path.join(path, self.METADATA_NAME), "w") as f:
+            yaml.safe_dump({"reservoir_hyperparameters": self.hyperparameters, "input_size": self.input_size}, f)
+
+    @classmethod
+    def load(cls, path: str) -> "Reservoir":
+        with open(os.path.join(path, cls.METADATA_NAME)) as f:
+            meta = _yaml_load(f.read())
+
+        def optional(name):
+            p = os.path.join(path, name)
+            return np.load(p, allow_pickle=False) if os.path.exists(p) else None
+
+        return cls(meta["reservoir_hyperparameters"], meta["input_size"],
+                   SparseMatrix.load(os.path.join(path, cls.INPUT_WEIGHTS_NAME)),
+                   SparseMatrix.load(os.path.join(path, cls.RESERVOIR_WEIGHTS_NAME)),
+                   input_mask_array=optional(cls.INPUT_MASK_NAME), state=optional(cls.STATE_NAME))
+
+
+class ReservoirComputingReadout:
+    """coefficients [(subdomain), in, out] and intercepts [(subdomain), out] (readout.py:75-147)."""
+
+    COEFFICIENTS_NAME = "coefficients.npz"
+    INTERCEPTS_NAME = "intercepts.npy"
+
+    def __init__(self, coefficients: np.ndarray, intercepts: np.ndarray):
+        if coefficients.ndim not in (2, 3):
+            raise ValueError(f"Coefficients must be a 2D or 3D array. Got coefficients with shape {coefficients.shape}")
+        self.coefficients, self.intercepts = coefficients, intercepts
+
+    def get_subdomain_readout(self, subdomain: int) -> "ReservoirComputingReadout":
+        if self.coefficients.ndim == 2 and self.intercepts.ndim == 1:
+            raise ValueError("Cannot get subdomain readout from single domain readout")
+        return ReservoirComputingReadout(self.coefficients[subdomain], self.intercepts[subdomain])
+
+    def dump(self, path: str) -> None:
+        os.makedirs(path, exist_ok=True)
+        with open(os.path.join(path, self.COEFFICIENTS_NAME), "wb") as f:
+            np.save(f, self.coefficients, allow_pickle=False)
+        np.save(os.path.join(path, self.INTERCEPTS_NAME), self.intercepts, allow_pickle=False)
+
+    @classmethod
+    def load(cls, path: str) -> "ReservoirComputingReadout":
+        with open(os.path.join(path, cls.COEFFICIENTS_NAME), "rb") as f:
+            coefficients = np.load(f, allow_pickle=False)
+        return cls(coefficients, np.load(os.path.join(path, cls.INTERCEPTS_NAME), allow_pickle=False))
+
+
+class TransformerGroup:
+    INPUT_DIR, OUTPUT_DIR, HYBRID_DIR = "input_transformer", "output_transformer", "hybrid_transformer"
+
+    def __init__(self, input, output, hybrid):
+        self.input, self.output, self.hybrid = input, output, hybrid
+
+    def dump(self, path: str) -> None:
+        self.input.dump(os.path.join(path, self.INPUT_DIR))
+        self.output.dump(os.path.join(path, self.OUTPUT_DIR))
+        self.hybrid.dump(os.path.join(path, self.HYBRID_DIR))
+
+    @classmethod
+    def load(cls, path: str) -> "TransformerGroup":
+        return cls(*(load_transformer(os.path.join(path, d)) for d in (cls.INPUT_DIR, cls.OUTPUT_DIR, cls.HYBRID_DIR)))
+
+
+def _to_device(arr, dev) -> torch.Tensor:
+    t = arr if isinstance(arr, torch.Tensor) else torch.from_numpy(np.asarray(arr))
+    return t.to(dev)
+
+
+def _as_xyz(arr):
+    """(x, y) -> (x, y, 1) view; anything else as it is."""
+    if arr.ndim == 2:
+        return arr[:, :, None]
+    return arr
+
+
+def _is_device(arrays) -> bool:
+    return any(isinstance(a, torch.Tensor) and a.is_cuda for a in arrays)
+
+
+@io.register("pure-reservoir")
+class ReservoirComputingModel(Predictor):
+    RESERVOIR_SUBDIR = "reservoir"
+    READOUT_SUBDIR = "readout"
+    METADATA_NAME = "metadata.yaml"
+    RANK_DIVIDER_NAME = "rank_divider.yaml"
+    TRANSFORMERS_SUBDIR = "transformers"
+    _SQUARE = SQUARE_SUBDOMAINS
+
+    def __init__(self, input_variables: Sequence[Hashable], output_variables: Sequence[Hashable], reservoir: Reservoir,
+                 readout: ReservoirComputingReadout, rank_divider: RankXYDivider, transformers: TransformerGroup,
+                 square_half_hidden_state: bool = False, w_in_storage: int = WIN_AUTO):
+        super().__init__(list(input_variables), list(output_variables))
+        self.reservoir, self.readout = reservoir, readout
+        self.rank_divider, self.transformers = rank_divider, transformers
+        self.square_half_hidden_state = bool(square_half_hidden_state)
+        self.w_in_storage = w_in_storage
+        self._output_rank_divider = rank_divider.get_no_overlap_rank_divider().get_new_zdim_rank_divider(
+            transformers.output.n_latent_dims)
+        self._device_model: Optional[ReservoirModel] = None
+
+    # -- device ------------------------------------------------------------------------------
+    _n_hybrid = 0
+    _hybrid_mask = None
+
+    def _model(self) -> ReservoirModel:
+        if self._device_model is None:
+            ns = self.rank_divider.n_subdomains
+            c = self.readout.coefficients
+            b = self.readout.intercepts
+            state = self.reservoir.state
+            mask = self.reservoir.input_mask_array
+            self._device_model = ReservoirModel(
+                self.rank_divider, self.transformers.input, self.transformers.output, self.reservoir.W_in,
+                self.reservoir.W_res, c.reshape((ns,) + c.shape[-2:]), b.reshape(ns, b.shape[-1]),
+                square=self._SQUARE if self.square_half_hidden_state else SQUARE_NONE,
+                input_mask=None if mask is None else np.asarray(mask).reshape(-1, self.reservoir.input_size)[-ns:],
+                hybrid_transformer=self.transformers.hybrid, n_hybrid=self._n_hybrid, hybrid_mask=self._hybrid_mask,
+                state=None if state is None else np.asarray(state).reshape(ns, -1), w_in_storage=self.w_in_storage,
+                device=compute_device())
+        return self._device_model
+
+    def _check_inputs(self, arrays, tf, extent):
+        tf.check_inputs([tuple(a.shape) for a in arrays])
+        for i, (a, nz) in enumerate(zip(arrays, tf.original_feature_sizes)):
+            if tuple(a.shape) != (*extent, nz):
+                raise ValueError(f"input array {i} has shape {tuple(a.shape)}, expected {(*extent, nz)}")
+
+    def get_state(self) -> np.ndarray:
+        """The reservoir state [subdomain, state_size] (a host copy)."""
+        return self._model().get_state().cpu().numpy()
+
+    def set_state(self, state) -> None:
+        self._model().set_state(state)
+
+    # -- the reference's surface -------------------------------------------------------------
+    def reset_state(self):
+        self._model().reset_state()
+
+    def increment_state(self, prediction_with_overlap: Sequence) -> None:
+        arrays = [_as_xyz(a) for a in prediction_with_overlap]
+        self._check_inputs(arrays, self.transformers.input, self.rank_divider.overlap_rank_extent)
+        m = self._model()
+        m.increment([_to_device(a, m.device) for a in arrays])
+
+    def synchronize(self, synchronization_time_series: Sequence) -> None:
+        """Reset, then one increment per time step of the [time, x, y, z] arrays."""
+        series = list(synchronization_time_series)
+        n_t = int(series[0].shape[0])
+        self.reset_state()
+        for t in range(n_t):
+            self.increment_state([a[t] for a in series])
+
+    def _outputs(self, outs: List[torch.Tensor], device_out: bool):
+        return outs if device_out else [t.cpu().numpy() for t in outs]
+
+    def predict(self, device_output: bool = False):
+        """The decoded readout of the current state: one (x, y, z) array per output variable (numpy unless
+        ``device_output``)."""
+        return self._outputs(self._model().predict(), device_output)
+
+    def get_model_from_subdomain(self, subdomain_index: int) -> "ReservoirComputingModel":
+        """A model of subdomain ``subdomain_index`` alone, starting from that subdomain's current state."""
+        if self.rank_divider.n_subdomains == 1:
+            raise ValueError("Model must have multiple subdomains to split.")
+        divider = RankXYDivider((1, 1), self.rank_divider.overlap, overlap_rank_extent=self.rank_divider.subdomain_extent,
+                                z_feature_size=self.rank_divider.z_feature_size)
+        mask = self.reservoir.input_mask_array
+        if mask is not None and np.ndim(mask) == 2 and np.shape(mask)[0] == self.rank_divider.n_subdomains:
+            mask = np.asarray(mask)[subdomain_index]
+        state = self.get_state()[subdomain_index][None] if self._device_model is not None else (
+            None if self.reservoir.state is None else np.asarray(self.reservoir.state).reshape(
+                self.rank_divider.n_subdomains, -1)[subdomain_index][None])
+        reservoir = Reservoir(self.reservoir.hyperparameters, self.reservoir.input_size, self.reservoir.W_in,
+                              self.reservoir.W_res, input_mask_array=mask, state=state)
+        return self._sub_model(reservoir, self.readout.get_subdomain_readout(subdomain_index), divider, subdomain_index)
+
+    def _sub_model(self, reservoir, readout, divider, subdomain_index):
+        return ReservoirComputingModel(self.input_variables, self.output_variables, reservoir, readout, divider,
+                                       self.transformers, self.square_half_hidden_state, self.w_in_storage)
+
+    # -- serialisation -----------------------------------------------------------------------
+    def dump(self, path: str) -> None:
+        os.makedirs(path, exist_ok=True)
+        self.reservoir.dump(os.path.join(path, self.RESERVOIR_SUBDIR))
+        self.readout.dump(os.path.join(path, self.READOUT_SUBDIR))
+        with open(os.path.join(path, self.METADATA_NAME), "w") as f:
+            yaml.safe_dump({"square_half_hidden_state": self.square_half_hidden_state,
+                            "input_variables": [str(v) for v in self.input_variables],
+                            "output_variables": [str(v) for v in self.output_variables]}, f)
+        self.rank_divider.dump(os.path.join(path, self.RANK_DIVIDER_NAME))
+        self.transformers.dump(os.path.join(path, self.TRANSFORMERS_SUBDIR))
+
+    @classmethod
+    def _load_parts(cls, path: str):
+        with open(os.path.join(path, cls.METADATA_NAME)) as f:
+            meta = _yaml_load(f.read())
+        return dict(input_variables=meta["input_variables"], output_variables=meta["output_variables"],
+                    reservoir=Reservoir.load(os.path.join(path, cls.RESERVOIR_SUBDIR)),
+                    readout=ReservoirComputingReadout.load(os.path.join(path, cls.READOUT_SUBDIR)),
+                    rank_divider=RankXYDivider.load(os.path.join(path, cls.RANK_DIVIDER_NAME)),
+                    transformers=TransformerGroup.load(os.path.join(path, cls.TRANSFORMERS_SUBDIR)),
+                    square_half_hidden_state=meta["square_half_hidden_state"])
+
+    @classmethod
+    def load(cls, path: str) -> "ReservoirComputingModel":
+        return cls(**cls._load_parts(path))
+
+
+@io.register("hybrid-reservoir")
+class HybridReservoirComputingModel(ReservoirComputingModel):
+    HYBRID_VARIABLES_NAME = "hybrid_variables.yaml"
+    HYBRID_MASK_NAME = "hybrid_input_mask.npy"
+    _SQUARE = SQUARE_ELEMENTS
+
+    def __init__(self, input_variables, hybrid_variables, output_variables, reservoir, readout, rank_divider,
+                 transformers, square_half_hidden_state: bool = False, hybrid_input_mask: Optional[np.ndarray] = None,
+                 w_in_storage: int = WIN_AUTO):
+        super().__init__(input_variables, output_variables, reservoir, readout, rank_divider, transformers,
+                         square_half_hidden_state, w_in_storage)
+        self.hybrid_variables = list(hybrid_variables)
+        self._hybrid_input_mask = hybrid_input_mask
+        self._hybrid_mask = hybrid_input_mask
+        no_overlap = rank_divider.get_no_overlap_rank_divider()
+        self._hybrid_rank_divider = no_overlap.get_new_zdim_rank_divider(transformers.hybrid.n_latent_dims)
+        self._n_hybrid = self._hybrid_rank_divider.flat_subdomain_len
+
+    def predict(self, hybrid_input: Sequence, device_output: Optional[bool] = None):
+        """The readout of the current state and the hybrid inputs (x, y, z arrays without overlap)."""
+        arrays = [_as_xyz(a) for a in hybrid_input]
+        self._check_inputs(arrays, self.transformers.hybrid, self.rank_divider.rank_extent)
+        m = self._model()
+        outs = m.predict([_to_device(a, m.device) for a in arrays])
+        return self._outputs(outs, _is_device(arrays) if device_output is None else device_output)
+
+    def _sub_model(self, reservoir, readout, divider, subdomain_index):
+        mask = self._hybrid_input_mask
+        if mask is not None and np.ndim(mask) == 2 and np.shape(mask)[0] == self.rank_divider.n_subdomains:
+            mask = np.asarray(mask)[subdomain_index]
+        return HybridReservoirComputingModel(self.input_variables, self.hybrid_variables, self.output_variables, reservoir,
+                                             readout, divider, self.transformers, self.square_half_hidden_state,
+                                             hybrid_input_mask=mask, w_in_storage=self.w_in_storage)
+
+    def dump(self, path: str) -> None:
+        super().dump(path)
+        with open(os.path.join(path, self.HYBRID_VARIABLES_NAME), "w") as f:
+            yaml.safe_dump({"hybrid_variables": [str(v) for v in self.hybrid_variables]}, f)
+        if self._hybrid_input_mask is not None:
+            np.save(os.path.join(path, self.HYBRID_MASK_NAME), self._hybrid_input_mask, allow_pickle=False)
+
+    @classmethod
+    def load(cls, path: str) -> "HybridReservoirComputingModel":
+        parts = cls._load_parts(path)
+        with open(os.path.join(path, cls.HYBRID_VARIABLES_NAME)) as f:
+            hybrid_variables = _yaml_load(f.read())["hybrid_variables"]
+        mask_path = os.path.join(path, cls.HYBRID_MASK_NAME)
+        mask = np.load(mask_path, allow_pickle=False) if os.path.exists(mask_path) else None
+        return cls(parts.pop("input_variables"), hybrid_variables, parts.pop("output_variables"), **parts,
+                   hybrid_input_mask=mask)
+
+
+# ---------------------------------------------------------------------------------------------
+# dataset adapters (adapters.py)
+# ---------------------------------------------------------------------------------------------
+
+_DIM_ORDER = ("x", "y", "z")
+
+
+def _input_arrays(ds: Dataset, variables) -> list:
+    """Each variable as an (x, y, z) array view (a missing z is a 1-level field); the dataset is not modified."""
+    out = []
+    for v in variables:
+        da = ds[v]
+        if any(d not in _DIM_ORDER for d in da.dims) or "x" not in da.dims or "y" not in da.dims:
+            raise ValueError(f"variable {v!r} must have dims x, y and optionally z, got {da.dims}")
+        order = [da.dims.index(d) for d in _DIM_ORDER if d in da.dims]
+        data = da.data.permute(*order) if isinstance(da.data, torch.Tensor) else np.transpose(np.asarray(da.data), order)
+        out.append(data if "z" in da.dims else data[:, :, None])
+    return out
+
+
+def _output_dataset(variables, arrays, output_dims) -> Dataset:
+    """DatasetAdapter.output_array_to_ds: a trailing z of 1 is squeezed, then dims follow ``output_dims``."""
+    ds = Dataset()
+    for name, arr in zip(variables, arrays):
+        if arr.shape[-1] == 1:
+            ds[name] = DataArray(arr[:, :, 0], dims=("x", "y"))
+        else:
+            ds[name] = DataArray(arr, dims=_DIM_ORDER)
+    order = [d for d in (output_dims or _DIM_ORDER) if d in ds.dims]
+    return ds.transpose(*order)
+
+
+@io.register("reservoir-adapter")
+class ReservoirDatasetAdapter(Predictor):
+    MODEL_DIR = "reservoir_model"
+
+    def __init__(self, model: ReservoirComputingModel, input_variables=None, output_variables=None):
+        super().__init__(model.input_variables, model.output_variables)
+        self.model = model
+        self.nonhybrid_input_variables = model.input_variables
+
+    @property
+    def input_overlap(self) -> int:
+        return self.model.rank_divider.overlap
+
+    @property
+    def is_hybrid(self) -> bool:
+        return False
+
+    def predict(self, inputs):
+        x = to_compat(inputs) if inputs is not None else None
+        dims = list(x.dims) if x is not None and len(x) else None
+        device_out = x is not None and _is_device([da.data for da in x.values()])
+        result = _output_dataset(self.output_variables, self.model.predict(device_output=device_out), dims)
+        return from_compat(result, inputs)
+
+    def increment_state(self, inputs):
+        self.model.increment_state(_input_arrays(to_compat(inputs), self.model.input_variables))
+
+    def reset_state(self):
+        self.model.reset_state()
+
+    def get_model_from_subdomain(self, subdomain_index: int) -> "ReservoirDatasetAdapter":
+        return type(self)(self.model.get_model_from_subdomain(subdomain_index))
+
+    def dump(self, path: str) -> None:
+        self.model.dump(os.path.join(path, self.MODEL_DIR))
+
+    @classmethod
+    def load(cls, path: str) -> "ReservoirDatasetAdapter":
+        return cls(ReservoirComputingModel.load(os.path.join(path, cls.MODEL_DIR)))
+
+
+@io.register("hybrid-reservoir-adapter")
+class HybridReservoirDatasetAdapter(ReservoirDatasetAdapter):
+    MODEL_DIR = "hybrid_reservoir_model"
+
+    def __init__(self, model: HybridReservoirComputingModel, input_variables=None, output_variables=None):
+        super().__init__(model)
+        self.input_variables = list(dict.fromkeys(list(model.input_variables) + list(model.hybrid_variables)))
+        self.hybrid_variables = model.hybrid_variables
+
+    @property
+    def is_hybrid(self) -> bool:
+        return True
+
+    def predict(self, inputs):
+        x = to_compat(inputs)
+        arrays = _input_arrays(x, self.model.hybrid_variables)
+        result = _output_dataset(self.output_variables, self.model.predict(arrays), list(x.dims))
+        return from_compat(result, inputs)
+
+    @classmethod
+    def load(cls, path: str) -> "HybridReservoirDatasetAdapter":
+        return cls(HybridReservoirComputingModel.load(os.path.join(path, cls.MODEL_DIR)))
+
+
+def split_multi_subdomain_model(model) -> list:
+    """One single-subdomain model per subdomain (adapters.py:240-255)."""
+    divider = model.model.rank_divider if isinstance(model, ReservoirDatasetAdapter) else model.rank_divider
+    return [model.get_model_from_subdomain(i) for i in range(divider.n_subdomains)]

@@ -530,6 +530,81 @@ int fv3hip_forest_apply(fv3hip_forest_t forest, const void *const *sources, cons
                         const int64_t *src_feat_stride, const int64_t *src_sample_stride, int64_t n_samples,
                         int32_t *leaf_node, void *stream);
 
+/*
+ * Reservoir computing: fv3fit.reservoir's ReservoirComputingModel / HybridReservoirComputingModel (registered
+ * "pure-reservoir" / "hybrid-reservoir", external/fv3fit/fv3fit/reservoir/model.py:36-337), per step:
+ *   increment  state[s] = tanh(u[s] * input_mask[s] @ W_in.T + state[s] @ W_res.T)      (reservoir.py:68-82)
+ *              u[s] = the input transformer's encoding of the inputs, subdomain s of the rank divider, flattened;
+ *   predict    y[s] = f(state[s]) @ C[s][:S] (+ hybrid[s] @ C[s][S:]) + b[s]               (readout.py:98-99)
+ *              merged over the no-overlap subdomains and decoded by the output transformer into each output array.
+ * Subdomain s covers x block s % layout_x and y block s / layout_x (pace's TilePartitioner); a subdomain's flat feature
+ * index is (x * sub_y + y) * z_latent + z.  Sums are float64; the state is double-buffered in device memory.
+ * fv3hip_reservoir_create validates everything on the host before any HIP call (FV3HIP_EINVAL).
+ */
+#define FV3HIP_RESERVOIR_DO_NOTHING 0    /* "do-nothing-transformer": concatenation along z, float64 */
+#define FV3HIP_RESERVOIR_SCALE_SPATIAL 1 /* "scale-spatial-concat-z-transformer": float32 (x - c) / (s + 1e-7f) */
+#define FV3HIP_RESERVOIR_SQUARE_NONE 0
+#define FV3HIP_RESERVOIR_SQUARE_SUBDOMAINS 1 /* square_even_terms(state, axis=0): even subdomains (model.py:225) */
+#define FV3HIP_RESERVOIR_SQUARE_ELEMENTS 2   /* square_even_terms(state, axis=-1): even state elements (model.py:122) */
+#define FV3HIP_RESERVOIR_WIN_AUTO 0          /* dense when nnz / (state_size * input_size) >= 0.5 */
+#define FV3HIP_RESERVOIR_WIN_DENSE 1
+#define FV3HIP_RESERVOIR_WIN_CSR 2
+typedef struct {
+    int kind;                 /* FV3HIP_RESERVOIR_DO_NOTHING / _SCALE_SPATIAL */
+    int n_variables;          /* <= 16 */
+    const int *var_nz;        /* [n_variables] z size of each variable (scale-spatial: all equal) */
+    int nx, ny;               /* scale-spatial: the x, y of its spatial features (must equal the extent it encodes) */
+    const float *center;      /* scale-spatial: [n_variables * nx * ny * nz] */
+    const float *scale;
+    const double *mask;       /* scale-spatial, optional: [nx][ny][n_variables * nz] */
+    int mask_f32;             /* the mask was float32 (a float32 product is rounded to float32) */
+} fv3hip_reservoir_transformer_t;
+
+typedef struct {
+    int layout_x, layout_y;   /* subdomain layout */
+    int overlap;
+    int rank_x, rank_y;       /* rank extent without the overlap */
+    int state_size;
+    int input_size;           /* sub_x * sub_y * input latent z, sub = rank / layout + 2 * overlap */
+    fv3hip_reservoir_transformer_t input, output, hybrid;
+    /* W_in [state_size][input_size] and W_res [state_size][state_size] as CSR (column indices need not be sorted) */
+    const int64_t *w_in_indptr;
+    const int32_t *w_in_indices;
+    const double *w_in_data;
+    int w_in_storage;         /* FV3HIP_RESERVOIR_WIN_* */
+    const int64_t *w_res_indptr;
+    const int32_t *w_res_indices;
+    const double *w_res_data;
+    const double *input_mask; /* optional [n_subdomains][input_size] */
+    int input_mask_f32;
+    int square;               /* FV3HIP_RESERVOIR_SQUARE_* */
+    int n_hybrid;             /* hybrid features per subdomain (0: pure model): sub_x' * sub_y' * hybrid latent z, no overlap */
+    const double *hybrid_mask; /* optional [n_subdomains][n_hybrid] */
+    int hybrid_mask_f32;
+    const double *coefficients; /* [n_subdomains][state_size + n_hybrid][n_out], n_out = (rank_x / layout_x) *
+                                   (rank_y / layout_y) * output latent z */
+    const double *intercepts;   /* [n_subdomains][n_out] */
+    const double *state;        /* optional initial state [n_subdomains][state_size] (else zeros) */
+} fv3hip_reservoir_desc_t;
+
+typedef struct fv3hip_reservoir *fv3hip_reservoir_t;
+
+int fv3hip_reservoir_create(const fv3hip_reservoir_desc_t *desc, fv3hip_reservoir_t *out);
+int fv3hip_reservoir_destroy(fv3hip_reservoir_t model);
+/* One reservoir step.  sources[v]: input variable v, dtype src_dtype[v] (F32/F64), element (x, y, z) of the overlapped
+ * rank extent at x * strides[3v] + y * strides[3v+1] + z * strides[3v+2].  No host synchronisation. */
+int fv3hip_reservoir_increment(fv3hip_reservoir_t model, const void *const *sources, const int *src_dtype,
+                               const int64_t *strides, void *stream);
+/* The readout of the current state.  hybrid_sources: as sources above over the rank extent without overlap (NULL for a
+ * pure model).  outputs[v]: output variable v, float32 (scale-spatial output transformer) or float64 (do-nothing),
+ * element (x, y, z) at x * out_strides[3v] + y * out_strides[3v+1] + z * out_strides[3v+2]. */
+int fv3hip_reservoir_predict(fv3hip_reservoir_t model, const void *const *hybrid_sources, const int *hybrid_dtype,
+                             const int64_t *hybrid_strides, void *const *outputs, const int64_t *out_strides, void *stream);
+/* state: [n_subdomains][state_size] float64 device arrays, ordered on `stream`. */
+int fv3hip_reservoir_get_state(fv3hip_reservoir_t model, double *state, void *stream);
+int fv3hip_reservoir_set_state(fv3hip_reservoir_t model, const double *state, void *stream);
+int fv3hip_reservoir_reset_state(fv3hip_reservoir_t model, void *stream);
+
 /* `n_workgroups` idle wavefronts of `microseconds` (<= 100000) each on `stream`: the host layer times a small one beside a large one
  * on another stream to learn which streams the runtime lets run side by side (cubedsphere/_device.py: the pipelines' side streams). */
 int fv3hip_spin(int64_t microseconds, int n_workgroups, void *stream);
