@@ -17,7 +17,8 @@ OP_SUM, OP_MEAN, OP_MIN, OP_MAX, OP_MEDIAN, OP_MODE = range(6)
 NAN_SKIP, NAN_PROPAGATE, NAN_OMIT = range(3)
 LAYOUT_COL_LEVEL, LAYOUT_LEVEL_COL = 0, 1
 TRANSFORM_NONE, TRANSFORM_LOG = 0, 1
-ACT_LINEAR, ACT_RELU = 0, 1
+ACT_LINEAR, ACT_RELU, ACT_TANH = 0, 1, 2
+CONV_HALO_INPUT, CONV_HALO_STRIPS, CONV_HALO_CUBE = 0, 1, 2
 ARITH_EXACT, ARITH_FAST = 0, 1
 ABI_VERSION = 3
 
@@ -97,6 +98,27 @@ class ForestDesc(ctypes.Structure):
         ("out_nfeat", POINTER(c_int)),
         ("mean", POINTER(c_double)),
         ("std", POINTER(c_double)),
+    ]
+
+
+class ConvDesc(ctypes.Structure):
+    _fields_ = [
+        ("n_inputs", c_int),
+        ("in_nfeat", POINTER(c_int)),
+        ("in_center", POINTER(c_float)),
+        ("in_scale", POINTER(c_float)),
+        ("n_hidden", c_int),
+        ("kernel_size", c_int),
+        ("filters", c_int),
+        ("activation", c_int),
+        ("hidden_kernels", POINTER(POINTER(c_float))),
+        ("hidden_biases", POINTER(POINTER(c_float))),
+        ("n_outputs", c_int),
+        ("out_nfeat", POINTER(c_int)),
+        ("out_kernel", POINTER(c_float)),
+        ("out_bias", POINTER(c_float)),
+        ("out_scale", POINTER(c_float)),
+        ("out_center", POINTER(c_float)),
     ]
 
 
@@ -268,6 +290,14 @@ SIGNATURES = {
     "fv3hip_forest_apply": (
         c_int,
         [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), POINTER(c_int64), c_int64, c_void_p, c_void_p],
+    ),
+    "fv3hip_conv_create": (c_int, [POINTER(ConvDesc), POINTER(c_void_p)]),
+    "fv3hip_conv_destroy": (c_int, [c_void_p]),
+    "fv3hip_conv_workspace_bytes": (c_size_t, [c_void_p, c_int64, c_int, c_int, c_int]),
+    "fv3hip_conv_predict": (
+        c_int,
+        [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int,
+         POINTER(c_void_p), POINTER(c_int64), c_void_p, c_size_t, c_void_p],
     ),
     "fv3hip_reservoir_create": (c_int, [POINTER(ReservoirDesc), POINTER(c_void_p)]),
     "fv3hip_reservoir_destroy": (c_int, [c_void_p]),

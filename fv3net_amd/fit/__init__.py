@@ -14,12 +14,13 @@ from .novelty import (MinMaxNoveltyDetector, NoveltyDetector, OCSVMNoveltyDetect
                       taper_ramp)
 from .transformed import OutOfSampleModel, TransformedPredictor
 from .forest import RandomForest
+from .conv import HipConvolutionalModel, conv_spec_from_arrays
 from .reservoir import (HybridReservoirComputingModel, HybridReservoirDatasetAdapter, ReservoirComputingModel,
                         ReservoirDatasetAdapter, split_multi_subdomain_model)
 
 __all__ = [
     "ChainedDataTransform", "ConstantOutputNoveltyDetector", "DATA_TRANSFORM_REGISTRY", "DataTransform", "MinMaxNoveltyDetector", "NoveltyDetector", "OCSVMNoveltyDetector",
-    "OutOfSampleModel", "RandomForest", "HybridReservoirComputingModel", "HybridReservoirDatasetAdapter",
+    "OutOfSampleModel", "RandomForest", "HipConvolutionalModel", "conv_spec_from_arrays", "HybridReservoirComputingModel", "HybridReservoirDatasetAdapter",
     "ReservoirComputingModel", "ReservoirDatasetAdapter", "split_multi_subdomain_model", "TransformedPredictor", "get_taper_function", "taper_decay", "taper_mask", "taper_ramp",
     "CombinedOutputModel", "ConstantOutputPredictor", "DenseHyperparameters", "DerivedMapping", "DerivedModel", "EnsembleModel", "SquashedOutputConfig",
     "SquashedOutputModel", "TaperConfig", "TaperedModel", "vertical_tapering_scale_factors", "HipDenseModel", "Predictor", "SAMPLE_DIM_NAME", "dump", "io",

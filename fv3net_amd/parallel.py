@@ -187,6 +187,16 @@ def exchange_edge_rows(local_rows: torch.Tensor, n_tiles: int = 6) -> torch.Tens
     return torch.cat([b[:c] for b, c in zip(bufs, counts)], dim=0)
 
 
+def exchange_edge_strips(local_strips: torch.Tensor, n_tiles: int = 6) -> torch.Tensor:
+    """The depth-``h`` form of :func:`exchange_edge_rows` for the halos of a convolutional model: all-gather the edge strips
+    of the tiles each rank owns (``local_strips`` [n_local, 4, h, C, n], from ``cubedsphere.halos.edge_strips``; tiles dealt by
+    :func:`tiles_of_rank`) into the [n_tiles, 4, h, C, n] table from which every rank picks the halo of its own tiles
+    (``cubedsphere.halos.halo_strips``).  One collective of 4 h / n of the data; device data goes through the host on gloo."""
+    if local_strips.dim() < 4 or local_strips.shape[1] != 4:
+        raise ValueError(f"edge strips are [n_local, 4, h, ..., n], got {tuple(local_strips.shape)}")
+    return exchange_edge_rows(local_strips, n_tiles)
+
+
 def interp_tiles_to_edges_sharded(local: torch.Tensor, axis: str, n_tiles: int = 6, step: int = 1) -> torch.Tensor:
     """``cubedsphere.grid.interp_tiles_to_edges`` for tile-sharded data: ``local`` [n_local, ..., n, n]
     holds this rank's tiles (:func:`tiles_of_rank`); the halo rows come from one all-gather."""

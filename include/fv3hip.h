@@ -374,6 +374,7 @@ int fv3hip_mappm_block_mean(const void *pe1, const void *const *q1, const void *
 
 #define FV3HIP_ACT_LINEAR 0
 #define FV3HIP_ACT_RELU 1
+#define FV3HIP_ACT_TANH 2   /* convolutional models only */
 
 /*
  * Description of the fused predict graph of
@@ -529,6 +530,55 @@ int fv3hip_forest_predict(fv3hip_forest_t forest, const void *const *sources, co
 int fv3hip_forest_apply(fv3hip_forest_t forest, const void *const *sources, const int *src_dtype,
                         const int64_t *src_feat_stride, const int64_t *src_sample_stride, int64_t n_samples,
                         int32_t *leaf_node, void *stream);
+
+/*
+ * Convolutional network: fv3fit's "convolutional" model (external/fv3fit/fv3fit/keras/_models/convolutional.py:141-210,
+ * shared/convolutional_network.py:136-195).  Per sample, on [x, y, channel] fields:
+ *   x^ = (x - in_center) / in_scale per channel, the variables concatenated along the channel axis (C channels);
+ *   n_hidden = depth - 1 layers of k x k "valid" cross-correlation to `filters` channels (kernel [k][k][c_in][filters], first
+ *   kernel axis along x), + bias (a null entry: none), activation; each shrinks x and y by k - 1;
+ *   one 1 x 1 linear head per output on the last hidden layer (out_kernel [filters][sum of out_nfeat], the outputs'
+ *   channels concatenated), then y * out_scale + out_center.
+ * The input is the field with a halo of h = (k - 1) / 2 * n_hidden cells on every side; halo_mode says where it comes from.
+ * fv3hip_conv_create validates everything on the host before any HIP call (FV3HIP_EINVAL; k > 7: FV3HIP_EUNSUPPORTED).
+ */
+#define FV3HIP_CONV_HALO_INPUT 0   /* the sources carry the halo: extent (nx + 2 h, ny + 2 h) */
+#define FV3HIP_CONV_HALO_STRIPS 1  /* strips[sample][side][line][channel][n]: side 0..3 = x-low, x-high, y-low, y-high, line 0
+                                    * next to the tile, n along the tile's other axis, C channels concatenated; nx == ny */
+#define FV3HIP_CONV_HALO_CUBE 2    /* n_tiles == 6: read from the neighbouring faces (append_halos, halos.py:135-160) */
+typedef struct {
+    int n_inputs;                 /* input variables, at most 8 */
+    const int *in_nfeat;          /* [n_inputs] channels of each */
+    const float *in_center;       /* [C] */
+    const float *in_scale;        /* [C] std + epsilon, not zero */
+    int n_hidden;                 /* depth - 1 >= 1 */
+    int kernel_size;              /* odd */
+    int filters;
+    int activation;               /* FV3HIP_ACT_* of the hidden layers */
+    const float *const *hidden_kernels;
+    const float *const *hidden_biases;   /* null, or [n_hidden] with null entries: no bias */
+    int n_outputs;                /* at most 8 */
+    const int *out_nfeat;
+    const float *out_kernel;
+    const float *out_bias;
+    const float *out_scale;
+    const float *out_center;
+} fv3hip_conv_desc_t;
+
+typedef struct fv3hip_conv *fv3hip_conv_t;
+
+int fv3hip_conv_create(const fv3hip_conv_desc_t *desc, fv3hip_conv_t *out);
+int fv3hip_conv_destroy(fv3hip_conv_t model);
+/* Bytes of the hidden layers' outputs ([sample][x][y][filters] float32, two buffers when n_hidden > 1). */
+size_t fv3hip_conv_workspace_bytes(fv3hip_conv_t model, int64_t n_batch, int n_tiles, int nx, int ny);
+/* Sample (b, t), b < n_batch, t < n_tiles.  sources[i]: dtype src_dtype[i] (F32 / F64), element (b, t, x, y, channel c) at
+ * b * s[0] + t * s[1] + x * s[2] + y * s[3] + c * s[4] with s = src_strides + 5 i.  outputs[j]: float32 [.., nx, ny, out_nfeat[j]]
+ * addressed the same way through out_strides + 5 j.  strips: dtype strips_dtype, read in mode STRIPS only.  The caller owns
+ * every buffer, the workspace included; nothing is allocated or synchronised. */
+int fv3hip_conv_predict(fv3hip_conv_t model, const void *const *sources, const int *src_dtype, const int64_t *src_strides,
+                        int64_t n_batch, int n_tiles, int nx, int ny, int halo_mode, const void *strips, int strips_dtype,
+                        float *const *outputs, const int64_t *out_strides, void *workspace, size_t workspace_bytes,
+                        void *stream);
 
 /*
  * Reservoir computing: fv3fit.reservoir's ReservoirComputingModel / HybridReservoirComputingModel (registered
