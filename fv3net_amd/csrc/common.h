@@ -44,4 +44,12 @@ inline int check_launch(const char *what)
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// Running maximum of np.max: NaN once any value is NaN, so that `logit == max` is hot nowhere in a column of class logits
+// with a NaN (the one-hot decode of emulation.hip and local.hip: logits == np.max(logits), ties all hot).
+template <typename T>
+__device__ __forceinline__ T running_max(T mx, T v)
+{
+    return (v > mx || v != v) ? v : mx;
+}
+
 }  // namespace fv3hip

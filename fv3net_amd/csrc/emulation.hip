@@ -34,6 +34,26 @@ __device__ __forceinline__ void st(void *p, int64_t i, T v)
     static_cast<T *>(p)[i] = v;
 }
 
+// np.maximum / np.minimum: a NaN in either operand comes out (a ? b : c selects drop it)
+template <typename T>
+__device__ __forceinline__ T nan_max(T a, T b)
+{
+    return (a != a) ? a : (a > b ? a : b);   // (b != b) falls through to b
+}
+template <typename T>
+__device__ __forceinline__ T nan_min(T a, T b)
+{
+    return (a != a) ? a : (a < b ? a : b);
+}
+// `array < constant` as numpy compares it: in the ARRAY's dtype (a Python float is cast to float32 next to a float32
+// array), not in the promoted dtype of the whole expression -- float32(1e-4) < 1e-4 in float64, but not in float32.
+// `v` is the element as loaded (exact in either type).
+template <typename T>
+__device__ __forceinline__ bool less_in_dtype(T v, int dt, double c)
+{
+    return dt == FV3HIP_F32 ? (float)v < (float)c : (double)v < c;
+}
+
 constexpr double kCp = 1.0046e3, kLv = 2.5e6, kHfus = 3.3358e5, kGravity = 9.80665, kRhoWater = 1000.0;
 
 template <typename T>
@@ -42,7 +62,7 @@ __global__ void squash_kernel(const void *cloud, int cdt, const void *hum, int h
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const T c = ld<T>(cloud, cdt, i);
-        const T co = (c < bound) ? (T)0 : c;
+        const T co = less_in_dtype<T>(c, cdt, (double)bound) ? (T)0 : c;
         // (the squashed cloud keeps the cloud's own dtype, as np.where(cloud < bound, 0, cloud) does)
         if (cloud_out_dt == FV3HIP_F64) static_cast<double *>(cloud_out)[i] = (double)co;
         else static_cast<float *>(cloud_out)[i] = (float)co;
@@ -58,23 +78,24 @@ __global__ void infer_cloud_kernel(const void *cloud_in, const void *qv_in, int 
         cloud_out[i] = ld<T>(cloud_in, sdt, i) - (ld<T>(qv_emul, edt, i) - ld<T>(qv_in, sdt, i));
 }
 
-// which cloud goes into the conservation step (zhao_carr.py:180-246)
+// which cloud goes into the conservation step (zhao_carr.py:180-246).  The auxiliary array only decides (its dtype is
+// not part of the result's promotion), so it is read and compared as float64, which holds either dtype exactly.
 template <typename T>
 __device__ __forceinline__ T choose_cloud(int mode, T c_emul, T c_in, const void *aux, int adt, int64_t i, int64_t n,
                                           int n_class, int cls)
 {
     switch (mode) {
-        case FV3HIP_ZC_FORTRAN_VANISHES: return ld<T>(aux, adt, i) < (T)1e-15 ? (T)0 : c_emul;
-        case FV3HIP_ZC_FORTRAN_IDENTICAL: return ld<T>(aux, adt, i) == c_in ? c_in : c_emul;
+        case FV3HIP_ZC_FORTRAN_VANISHES: return less_in_dtype<double>(ld<double>(aux, adt, i), adt, 1e-15) ? (T)0 : c_emul;
+        case FV3HIP_ZC_FORTRAN_IDENTICAL: return ld<double>(aux, adt, i) == (double)c_in ? c_in : c_emul;
         case FV3HIP_ZC_CLASS_ZERO_CLOUD:
         case FV3HIP_ZC_CLASS_ZERO_TEND: {
             // one-hot by arg-max with ties all hot: logit[cls] == max over classes (zhao_carr.py:193-198)
-            T mx = ld<T>(aux, adt, i);
+            double mx = ld<double>(aux, adt, i);
             for (int c = 1; c < n_class; ++c) {
-                const T v = ld<T>(aux, adt, (int64_t)c * n + i);
-                mx = v > mx ? v : mx;
+                const double v = ld<double>(aux, adt, (int64_t)c * n + i);
+                mx = running_max(mx, v);
             }
-            const bool hot = ld<T>(aux, adt, (int64_t)cls * n + i) == mx;
+            const bool hot = ld<double>(aux, adt, (int64_t)cls * n + i) == mx;
             return hot ? (mode == FV3HIP_ZC_CLASS_ZERO_CLOUD ? (T)0 : c_in) : c_emul;
         }
         default: return c_emul;
@@ -108,6 +129,16 @@ __global__ void gscond_conserve_kernel(const void *cloud_in, const void *qv_in, 
     }
 }
 
+// one element of the ice/water flag scan as a map of the incoming flag, in the state's own dtype S
+template <typename S>
+__device__ __forceinline__ unsigned flag_map(const void *t_in, const void *cloud_in, int64_t i)
+{
+    const S tc = static_cast<const S *>(t_in)[i] - (S)273.16;
+    if (tc < (S)-15) return 3u;                                     // constant 1
+    if (tc > (S)0) return 0u;                                       // constant 0
+    return static_cast<const S *>(cloud_in)[i] > (S)1e-20 ? 2u : 0u;  // identity : constant 0
+}
+
 // Phase-dependent latent heat: the ice/water flag is a scan along the LAST axis from its end
 // (zhao_carr.py:114-138; see the quirk noted in oracle/emulation_np.py):
 //   t < -15 -> 1;  t > 0 -> 0;  otherwise 1 iff the previous (higher index) flag is 1 and cloud > 1e-20.
@@ -130,12 +161,11 @@ __global__ __launch_bounds__(256) void gscond_conserve_phase_kernel(const void *
     const int64_t hi = n1 - (int64_t)threadIdx.x * seg;            // exclusive
     const int64_t lo = hi - seg > 0 ? hi - seg : 0;
     const int64_t n = n0 * n1;
+    // (state[T] - 273.16 and both comparisons are formed in the STATE's dtype, as numpy does before the flag meets a
+    // float64 emulator: float32(273.16) - float32(273.16) is 0, its float64 difference from 273.16 is 3.7e-6 > 0)
     auto elem_map = [&](int64_t k) -> unsigned {
         const int64_t i = row * n1 + k;
-        const T tc = ld<T>(t_in, sdt, i) - (T)273.16;
-        if (tc < (T)-15) return 3u;               // constant 1
-        if (tc > (T)0) return 0u;                 // constant 0
-        return ld<T>(cloud_in, sdt, i) > (T)1e-20 ? 2u : 0u;  // identity : constant 0
+        return sdt == FV3HIP_F64 ? flag_map<double>(t_in, cloud_in, i) : flag_map<float>(t_in, cloud_in, i);
     };
     unsigned m = 2u;  // identity
     for (int64_t k = hi - 1; k >= lo && hi > 0; --k) {
@@ -178,10 +208,10 @@ __global__ void precpd_conserve_kernel(const void *cloud_g, const void *qv_g, co
             const T dp = ld<T>(delp, sdt, i), cg = ld<T>(cloud_g, sdt, i), qg = ld<T>(qv_g, sdt, i);
             T src = (T)-1 * (ld<T>(cloud_p, edt, i) - cg) * dp / (T)kGravity;
             T sink = (ld<T>(qv_p, edt, i) - qg) * dp / (T)kGravity;
-            src = src > (T)0 ? src : (T)0;
-            sink = sink > (T)0 ? sink : (T)0;
+            src = nan_max(src, (T)0);    // np.maximum(x, 0), np.minimum(total, evaporation): a NaN from the emulator
+            sink = nan_max(sink, (T)0);  // stays a NaN, in this level and, through `total`, in all below it
             total = total + src;
-            const T ev = total < sink ? total : sink;
+            const T ev = nan_min(total, sink);
             total = total - ev;
             const T evap = ev / dp * (T)kGravity;
             cloud_out[i] = cg + ((T)-1 * src) / dp * (T)kGravity;
@@ -197,19 +227,22 @@ __global__ void precip_simple_kernel(const void *cloud_g, const void *qv_g, cons
                                      const void *qv_p, int edt, int64_t n0, int64_t n1, T *precip_out)
 {
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n1; s += (int64_t)gridDim.x * blockDim.x) {
-        T before = 0, after = 0;
+        // Each column mass is formed in its arrays' own dtypes, as numpy does: `before` is all state (float32 products and a
+        // float32 sum for a float32 state, even next to a float64 emulator), `after` meets delp and so has the promoted T.
+        float before_f = 0;
+        double before_d = 0;
+        T after = 0;
         for (int64_t k = 0; k < n0; ++k) {  // np.sum over axis 0: sequential in k
             const int64_t i = k * n1 + s;
-            const T dp = ld<T>(delp, sdt, i);
-            // (qv + qc is formed in the arrays' own dtype before it meets delp, as numpy does:
-            // float32 emulator outputs are added in float32)
-            const T wb = sdt == FV3HIP_F64 ? (T)(ld<double>(qv_g, sdt, i) + ld<double>(cloud_g, sdt, i))
-                                           : (T)(ld<float>(qv_g, sdt, i) + ld<float>(cloud_g, sdt, i));
+            if (sdt == FV3HIP_F64)
+                before_d += (ld<double>(qv_g, sdt, i) + ld<double>(cloud_g, sdt, i)) * ld<double>(delp, sdt, i) / kGravity;
+            else
+                before_f += (ld<float>(qv_g, sdt, i) + ld<float>(cloud_g, sdt, i)) * ld<float>(delp, sdt, i) / (float)kGravity;
             const T wa = edt == FV3HIP_F64 ? (T)(ld<double>(qv_p, edt, i) + ld<double>(cloud_p, edt, i))
                                            : (T)(ld<float>(qv_p, edt, i) + ld<float>(cloud_p, edt, i));
-            before += wb * dp / (T)kGravity;
-            after += wa * dp / (T)kGravity;
+            after += wa * ld<T>(delp, sdt, i) / (T)kGravity;
         }
+        const T before = sdt == FV3HIP_F64 ? (T)before_d : (T)before_f;
         precip_out[s] = (before - after) / (T)kRhoWater;
     }
 }
@@ -220,8 +253,8 @@ __global__ void clamp_kernel(const T *x, int64_t n, T lo, T hi, int has_lo, int 
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         T v = x[i];
         // np.maximum / np.minimum propagate NaN
-        if (has_lo) v = (v != v) ? v : (v > lo ? v : lo);
-        if (has_hi) v = (v != v) ? v : (v < hi ? v : hi);
+        if (has_lo) v = nan_max(v, lo);
+        if (has_hi) v = nan_min(v, hi);
         out[i] = v;
     }
 }
@@ -246,7 +279,7 @@ __global__ void class_zero_kernel(const T *x, const void *logits, int ldt, int n
         double mx = ld<double>(logits, ldt, i);
         for (int c = 1; c < n_class; ++c) {
             const double v = ld<double>(logits, ldt, (int64_t)c * n + i);
-            mx = v > mx ? v : mx;
+            mx = running_max(mx, v);
         }
         out[i] = (ld<double>(logits, ldt, (int64_t)cls * n + i) == mx) ? (T)0 : x[i];
     }
@@ -373,9 +406,11 @@ extern "C" int fv3hip_zc_precpd_conserve(const void *cloud_g, const void *qv_g, 
                                          void *precip_out, void *stream)
 {
     FV3HIP_REQUIRE(n0 >= 0 && n1 >= 0, "negative extent");
-    ZC_COMMON_CHECKS(n0 * n1);
+    ZC_COMMON_CHECKS(n1);
     FV3HIP_REQUIRE(float_code(state_dtype) && float_code(emul_dtype), "arrays must be F32 or F64");
-    FV3HIP_REQUIRE(cloud_g && qv_g && t_g && delp && cloud_p && qv_p && cloud_out && qv_out && t_out && precip_out, "null pointer");
+    // (no levels: the arrays are empty and may be null; the column totals are still written, as numpy's zeros)
+    FV3HIP_REQUIRE(precip_out && (n0 == 0 || (cloud_g && qv_g && t_g && delp && cloud_p && qv_p && cloud_out && qv_out && t_out)),
+                   "null pointer");
     hipStream_t st = as_stream(stream);
     if (out_dtype == FV3HIP_F64)
         hipLaunchKernelGGL((precpd_conserve_kernel<double>), dim3(grid_for(n1)), dim3(256), 0, st, cloud_g, qv_g, t_g, delp,
@@ -395,7 +430,7 @@ extern "C" int fv3hip_zc_precip_simple(const void *cloud_g, const void *qv_g, co
     FV3HIP_REQUIRE(n0 >= 0 && n1 >= 0, "negative extent");
     ZC_COMMON_CHECKS(n1);
     FV3HIP_REQUIRE(float_code(state_dtype) && float_code(emul_dtype), "arrays must be F32 or F64");
-    FV3HIP_REQUIRE(cloud_g && qv_g && delp && cloud_p && qv_p && precip_out, "null pointer");
+    FV3HIP_REQUIRE(precip_out && (n0 == 0 || (cloud_g && qv_g && delp && cloud_p && qv_p)), "null pointer");
     hipStream_t st = as_stream(stream);
     if (out_dtype == FV3HIP_F64)
         hipLaunchKernelGGL((precip_simple_kernel<double>), dim3(grid_for(n1)), dim3(256), 0, st, cloud_g, qv_g, delp,

@@ -108,7 +108,7 @@ __global__ void classify_onehot_kernel(const void *__restrict__ logits, int dtyp
         for (int c = 1; c < n_class; ++c) {
             const double v = dtype == FV3HIP_F64 ? static_cast<const double *>(logits)[(int64_t)c * n + i]
                                                  : (double)static_cast<const float *>(logits)[(int64_t)c * n + i];
-            mx = v > mx ? v : mx;
+            mx = running_max(mx, v);
         }
         uint8_t both = 0;
         for (int c = 0; c < n_class; ++c) {

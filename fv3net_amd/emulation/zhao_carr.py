@@ -3,7 +3,8 @@
 dictionaries of [feature(z), sample] arrays).  Each function is one HIP launch
 (``csrc/emulation.hip``); numpy arrays are uploaded and the results come back as numpy, device
 tensors stay on the device.  Arithmetic follows numpy's promotion: float64 as soon as one operand
-(the Fortran state) is float64.
+(the Fortran state) is float64.  The state arrays of a call share one dtype, and so do the emulator's
+(``_group``): a mixture of float32 and float64 inside either is refused.
 """
 
 import numpy as np
@@ -55,17 +56,31 @@ class PrecpdOutput:
 _CODE = {torch.float32: _lib.F32, torch.float64: _lib.F64}
 
 
+# what numpy makes of a non-float array next to a float32 one: bool, 8 / 16-bit integers and float16 stay float32 (and hold
+# exactly in it), int32 / int64 make float64
+_AS_FLOAT32 = (torch.bool, torch.int8, torch.uint8, torch.int16, torch.float16)
+
+
 def _dev(a) -> torch.Tensor:
     t = on_device(a)
     if t.dtype not in _CODE:
-        t = t.to(torch.float64)  # numpy promotes integer / bool operands to float64
+        t = t.to(torch.float32 if t.dtype in _AS_FLOAT32 else torch.float64)
     return t.contiguous()
 
 
-def _same_dtype(*ts):
-    """State arrays travel as one dtype (float64 if any is)."""
-    dt = torch.float64 if any(t.dtype == torch.float64 for t in ts) else torch.float32
-    return [t if t.dtype == dt else t.to(dt) for t in ts], dt
+def _group(what: str, *arrays):
+    """The arrays of one dictionary that a kernel reads under ONE dtype code -> (contiguous device tensors, that dtype).
+    Their float dtypes must agree (non-float arrays count as ``_dev`` converts them).  numpy promotes a mixed group
+    operation by operation: some differences are still formed in float32, some fields come back float32, a float32
+    temperature is compared with the flag thresholds as float32 -- which one dtype code cannot express, so a mixed group
+    is refused rather than promoted to something numpy does not compute."""
+    ts = [_dev(a) for a in arrays]
+    if len({t.dtype for t in ts}) > 1:
+        given = [str(getattr(a, "dtype", type(a).__name__)).replace("torch.", "") for a in arrays]
+        raise TypeError(f"the {what} arrays of one call must share one float dtype (bool and 8 / 16-bit integers count as "
+                        f"float32, int32 / int64 as float64), got {given}: numpy would promote them operation by operation; "
+                        "cast them to one dtype first")
+    return ts, ts[0].dtype
 
 
 def _out_dtype(*dts):
@@ -107,7 +122,7 @@ def squash_precpd(state, emulator, cloud_squash):
 
 
 def infer_gscond_cloud_from_conservation(state, emulator):
-    (c_in, qv_in), sdt = _same_dtype(_dev(state[Input.cloud_water]), _dev(state[Input.humidity]))
+    (c_in, qv_in), sdt = _group("state", state[Input.cloud_water], state[Input.humidity])
     qv_e = _dev(emulator[GscondOutput.humidity])
     odt = _out_dtype(sdt, qv_e.dtype)
     out = torch.empty(c_in.shape, dtype=odt, device=c_in.device)
@@ -121,21 +136,18 @@ _MODES = {"none": 0, "fortran_vanishes": 1, "fortran_identical": 2, "class_zero_
 
 def _gscond_conserve(state, emulator, mode: str, phase_dependent: bool):
     """The gscond mask ``mode`` followed by ``_update_with_net_condensation`` (zhao_carr.py:97-246)."""
-    (c_in, qv_in, t_in), sdt = _same_dtype(_dev(state[Input.cloud_water]), _dev(state[Input.humidity]),
-                                           _dev(state[Input.temperature]))
+    (c_in, qv_in, t_in), sdt = _group("state", state[Input.cloud_water], state[Input.humidity], state[Input.temperature])
     c_e = _dev(emulator[GscondOutput.cloud_water])
     aux, n_class, cls = None, 0, 0
-    dts = [sdt, c_e.dtype]
     if mode in ("fortran_vanishes", "fortran_identical"):
         aux = _dev(state[GscondOutput.cloud_water])
-        dts.append(aux.dtype)
     elif mode in ("class_zero_cloud", "class_zero_tend"):
         aux = _dev(emulator["gscond_classes"])
         n_class = int(aux.shape[0])
         if n_class != len(CLASS_NAMES):
             raise ValueError(f"gscond_classes must hold {len(CLASS_NAMES)} classes along its first axis, got {n_class}")
         cls = CLASS_NAMES.index(ZERO_CLOUD if mode == "class_zero_cloud" else ZERO_TENDENCY)
-    odt = _out_dtype(*dts)
+    odt = _out_dtype(sdt, c_e.dtype)  # (the auxiliary array only decides: np.where's result does not take its dtype)
     n0, n1 = _n01(c_in)
     outs = [torch.empty(c_in.shape, dtype=odt, device=c_in.device) for _ in range(3)]
     _lib.call_on(c_in.device, "fv3hip_zc_gscond_conserve", _ptr(c_in), _ptr(qv_in), _ptr(t_in), _CODE[sdt], _ptr(c_e), _CODE[c_e.dtype],
@@ -180,9 +192,9 @@ def mask_zero_cloud_classifier_precpd(state, emulator):
 
 
 def enforce_conservative_precpd(state, emulator):
-    (c_g, qv_g, t_g, delp), sdt = _same_dtype(_dev(state[GscondOutput.cloud_water]), _dev(state[GscondOutput.humidity]),
-                                              _dev(state[GscondOutput.temperature]), _dev(state[Input.delp]))
-    (c_p, qv_p), edt = _same_dtype(_dev(emulator[PrecpdOutput.cloud_water]), _dev(emulator[PrecpdOutput.humidity]))
+    (c_g, qv_g, t_g, delp), sdt = _group("state", state[GscondOutput.cloud_water], state[GscondOutput.humidity],
+                                         state[GscondOutput.temperature], state[Input.delp])
+    (c_p, qv_p), edt = _group("emulator", emulator[PrecpdOutput.cloud_water], emulator[PrecpdOutput.humidity])
     if c_g.dim() != 2:
         raise ValueError("Expected 2D inputs to the strict conservative precip function")
     odt = _out_dtype(sdt, edt)
@@ -199,9 +211,8 @@ def enforce_conservative_precpd(state, emulator):
 def conservative_precip_simple(state, emulator, sum_axis=0):
     if sum_axis != 0:
         raise NotImplementedError("conservative_precip_simple sums over the first (level) axis")
-    (c_g, qv_g, delp), sdt = _same_dtype(_dev(state[GscondOutput.cloud_water]), _dev(state[GscondOutput.humidity]),
-                                         _dev(state[Input.delp]))
-    (c_p, qv_p), edt = _same_dtype(_dev(emulator[PrecpdOutput.cloud_water]), _dev(emulator[PrecpdOutput.humidity]))
+    (c_g, qv_g, delp), sdt = _group("state", state[GscondOutput.cloud_water], state[GscondOutput.humidity], state[Input.delp])
+    (c_p, qv_p), edt = _group("emulator", emulator[PrecpdOutput.cloud_water], emulator[PrecpdOutput.humidity])
     odt = _out_dtype(sdt, edt)
     n0, n1 = int(c_g.shape[0]), int(np.prod(c_g.shape[1:]))
     precip = torch.empty(tuple(c_g.shape[1:]), dtype=odt, device=c_g.device)

@@ -800,6 +800,11 @@ int fv3hip_interpolate_2d(const void *xp, const void *x, const void *y, int64_t 
  * (external/emulation/emulation/config.py:175-221).  Arrays are contiguous [n0][n1] = [level][sample]
  * (the Fortran hook's layout) or flat (n); every array carries a dtype code (FV3HIP_F32/F64);
  * arithmetic and outputs use out_dtype = F64 if any operand is float64 (numpy's promotion), else F32.
+ * NaN in gives NaN out wherever numpy gives it: the maxima / minima propagate a NaN from either operand
+ * (np.maximum / np.minimum), the selects drop it where np.where does, and a column of logits with a NaN
+ * has no hot class (logits == np.max(logits)).  Comparisons with a constant (bound, 273.16, -15, 1e-15,
+ * 1e-20) are made in the compared array's own dtype, as numpy makes them.  An auxiliary array that only
+ * decides (aux, logits) is compared as float64 and is not part of out_dtype.
  */
 #define FV3HIP_ZC_NO_MASK 0            /* enforce_conservative_*: the emulator's cloud as is          */
 #define FV3HIP_ZC_FORTRAN_VANISHES 1   /* mask_where_fortran_cloud_vanishes_gscond: aux = state cloud after gscond */
@@ -824,7 +829,8 @@ int fv3hip_zc_gscond_conserve(const void *cloud_in, const void *qv_in, const voi
                               const void *aux, int aux_dtype, int n_class, int cls, int64_t n0,
                               int64_t n1, int phase_dependent, int out_dtype, void *cloud_out,
                               void *qv_out, void *t_out, void *stream);
-/* enforce_conservative_precpd (zhao_carr.py:249-323): strict TOA (last level) to surface budget. */
+/* enforce_conservative_precpd (zhao_carr.py:249-323): strict TOA (last level) to surface budget.
+ * n0 == 0: precip_out[n1] is zero (the other arrays are empty and may be NULL); likewise below. */
 int fv3hip_zc_precpd_conserve(const void *cloud_g, const void *qv_g, const void *t_g,
                               const void *delp, int state_dtype, const void *cloud_p,
                               const void *qv_p, int emul_dtype, int64_t n0, int64_t n1,

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import emulation_cases
 from oracle import emulation_np as E
 
 pytestmark = pytest.mark.gpu
@@ -19,32 +20,7 @@ def device():
     return torch.device("cuda", 0)
 
 
-def _state(rng, n0=79, n1=257, dt=np.float64):
-    t = rng.uniform(230, 300, (n0, n1))
-    qv = 10 ** rng.uniform(-6, -2, (n0, n1))
-    qc = np.where(rng.random((n0, n1)) < 0.5, 0.0, 10 ** rng.uniform(-9, -3, (n0, n1)))
-    state = {E.T_IN: t, E.QV_IN: qv, E.CLOUD_IN: qc, E.DELP: rng.uniform(300, 1500, (n0, n1))}
-    dq = rng.normal(0, 2e-4, (n0, n1))
-    state[E.CLOUD_G] = np.where(rng.random((n0, n1)) < 0.3, qc, np.maximum(qc + dq, 0))
-    state[E.QV_G] = qv - (state[E.CLOUD_G] - qc)
-    state[E.T_G] = t + 2.5e6 / 1004.6 * (state[E.CLOUD_G] - qc)
-    return {k: v.astype(dt) for k, v in state.items()}
-
-
-def _emulator(rng, state, dt=np.float32):
-    sh = state[E.T_IN].shape
-    em = {
-        E.CLOUD_G: state[E.CLOUD_IN] + rng.normal(0, 3e-4, sh),
-        E.QV_G: state[E.QV_IN] + rng.normal(0, 3e-4, sh),
-        E.T_G: state[E.T_IN] + rng.normal(0, 1, sh),
-        E.CLOUD_P: state[E.CLOUD_G] + rng.normal(0, 3e-4, sh),
-        E.QV_P: state[E.QV_G] + rng.normal(0, 3e-4, sh),
-        E.T_P: state[E.T_G] + rng.normal(0, 1, sh),
-        E.PRECIP: rng.uniform(0, 1e-3, sh[1]),
-        "gscond_classes": rng.normal(0, 1, (4,) + sh),
-        "precpd_classes": rng.normal(0, 1, (4,) + sh),
-    }
-    return {k: v.astype(dt) for k, v in em.items()}
+_state, _emulator = emulation_cases.state, emulation_cases.emulator  # the ordinary draws, shared with test_gpu_emulation_edges.py
 
 
 def _close(res, ref, name):
