@@ -138,6 +138,8 @@ struct MlpLaunch {
     int out64;
     int n_log_chunks;   // layer-1 chunks [0, n_log_chunks) hold log-transformed inputs (the host orders them first)
     int n_logfast_chunks;  // the leading ones of them that are all-log with every eps >= FLT_MIN
+    int l1_short_log;      // the last log chunk's real rows fill at most 8 of its 16 k-pair slots, the rest is zero padding, and
+                           // plain chunks follow: the fast-I/O kernels run that chunk with 8 slots
     int epi_fast;      // sources and outputs are sample-contiguous and 16-byte aligned, n_samples % 32 == 0: fast-I/O kernel
     int has_limits;    // any output limit or zero mask
     int n_residual;
@@ -156,7 +158,7 @@ struct MlpLaunch {
 __host__ __device__ constexpr int rho(int r) { return (r & 3) + 8 * (r >> 2); }
 
 #ifndef MLP_STAMP_PHASE
-#define MLP_STAMP_PHASE 0  // per-slot stamps: 0/1/2 layer-1 XBULK chunks by log mode, 10 hidden, 20+NT output
+#define MLP_STAMP_PHASE 0  // per-slot stamps: 0/1/2 layer-1 XBULK chunks by log mode, 3 the 8-slot last log chunk, 10 hidden, 20 output
 #endif
 #ifdef MLP_STAMPS
 #define SLOT_STAMP(phase, s)                                          \
@@ -587,9 +589,16 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
             // the workgroup tile starting at sample n0 is requested in slot 1 (4 x 16-byte loads per
             // thread) and normalised and written to xs[xb ^ 1] in slots 9..12.
             // (kc1_c: slots of the chunk -- 16, or 8 in the L1SHORT kernels, whose single layer-1 chunk holds at most 16
-            // inputs: the k-pairs beyond them would multiply zeros; the input tile is then finished in slots 4..7)
+            // inputs: the k-pairs beyond them would multiply zeros; the input tile is then finished in slots 4..7.
+            // 8 also for the last chunk of a log block that the host padded with at least 16 zero rows (l1_short_log):
+            // a dropped slot would add +-0 to every accumulator.  There a full chunk follows, which reads all 32 rows
+            // of the input tile with no barrier but this chunk's own in between, so the whole tile is finished in slot 6,
+            // ahead of that barrier -- and five slots after its request rather than three.)
             auto l1_chunk_bulk = [&](int cn, int64_t n0, auto with_log, auto kc1_c) __attribute__((always_inline)) {
-                constexpr int KC1 = decltype(kc1_c)::value, FIN0 = (KC1 == 16) ? 8 : 3;
+                constexpr int KC1 = decltype(kc1_c)::value;
+                constexpr bool SHORT_LOG = KC1 == 8 && !L1SHORT;
+                constexpr int FIN0 = (KC1 == 16) ? 8 : SHORT_LOG ? 5 : 3;
+                constexpr int SPH = SHORT_LOG ? 3 : (int)decltype(with_log)::value;  // (stamped builds: the phase)
                 const int gnext = (g + 1 < G) ? g + 1 : 0;
                 const float *xsb = xs + xb * 32 * kTileSamples + half * kTileSamples + wave * 32 + (lane & 31);
                 const float *xsn = xs + (xb ^ 1) * 32 * kTileSamples + half * kTileSamples + wave * 32 + (lane & 31);
@@ -606,7 +615,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
                 const XNorm *xn_g = (const XNorm *)xn_c;
 #pragma unroll
                 for (int s = 0; s < KC1; ++s) {
-                    SLOT_STAMP((int)decltype(with_log)::value, s);
+                    SLOT_STAMP(SPH, s);
                     run_slot(h, HT_c{}, HG_c{}, Q5_c{}, s, KC1, b_cur, [&](int s_) {
                         // (the last slot runs this after the chunk barrier: xs[xb ^ 1] is complete)
                         b_cur = (s_ + 1 < KC1) ? xsb[2 * (s_ + 1) * kTileSamples] : xsn[0];
@@ -623,11 +632,18 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
 #pragma unroll
                             for (int i = 0; i < 4; ++i) xn4[i] = xn_g[8 * i];
                         }
-                        if (s_ > FIN0 && s_ <= FIN0 + 4) bulk_finish_e(xn4[s_ - FIN0 - 1], s_ - FIN0 - 1, xb ^ 1, with_log);
+                        if constexpr (SHORT_LOG) {
+                            if (s_ == FIN0 + 1) {
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) bulk_finish_e(xn4[i], i, xb ^ 1, with_log);
+                            }
+                        } else {
+                            if (s_ > FIN0 && s_ <= FIN0 + 4) bulk_finish_e(xn4[s_ - FIN0 - 1], s_ - FIN0 - 1, xb ^ 1, with_log);
+                        }
                         stage_step(s_, KC1, gnext, par ^ 1);
                     });
                 }
-                CHUNK_STAMP_END((int)decltype(with_log)::value, KC1);
+                CHUNK_STAMP_END(SPH, KC1);
                 par ^= 1;
                 xb ^= 1;
                 ++g;
@@ -647,6 +663,11 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
                     int c = 0;  // chunk c prepares the inputs of chunk c + 1
                     for (; c + 1 < NF; ++c) l1_chunk_bulk(c + 1, n0, M2_{}, KC16_{});
                     for (; c + 1 < L; ++c) l1_chunk_bulk(c + 1, n0, M1_{}, KC16_{});
+                    // (c = L - 1, the last log chunk, whose call prepares the first plain one: 8 slots if the rest is padding)
+                    if (p.l1_short_log) {
+                        l1_chunk_bulk(c + 1, n0, M0_{}, std::integral_constant<int, 8>{});
+                        ++c;
+                    }
                     for (; c < NC - 1; ++c) l1_chunk_bulk(c + 1, n0, M0_{}, KC16_{});
                     if (NF > 0) l1_chunk_bulk(0, n1, M2_{}, KC16_{});
                     else if (L > 0) l1_chunk_bulk(0, n1, M1_{}, KC16_{});
@@ -793,21 +814,23 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
             f32x4 e_before[RES_SIDE ? 4 : 1];
             const int64_t e_loff = (n0t + e_wcol) * 4;
             // (mode 2) `before` row addresses of tile t in slot s0, the four loads in slot s0 + 1
-            auto epi_res_fetch = [&](int t, int s_, int s0) __attribute__((always_inline)) {
+            auto epi_res_fetch = [&](const ORes *ob, int s_, int s0) __attribute__((always_inline)) {  // ob = ores + t * 32 + e_wrow
                 if (s_ == s0) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) e_src[RES_SIDE ? j : 0] = ores[t * 32 + e_wrow + 8 * j].src_row;
+                    for (int j = 0; j < 4; ++j) e_src[RES_SIDE ? j : 0] = ob[8 * j].src_row;
                 }
                 if (s_ == s0 + 1) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) e_before[RES_SIDE ? j : 0] = *(GCF32x4)(e_src[RES_SIDE ? j : 0] + e_loff);
                 }
             };
+            const OFast *e_ofb = ofast;  // (mode 2) the tile's table rows for this lane, as opaque LDS bases: see out_chunk
+            const ORes *e_orb = ores;
             auto epi_side = [&](const f32x16 &y, int t, int s_, auto mode_c) __attribute__((always_inline)) {
                 constexpr int MODE = decltype(mode_c)::value;
                 if (MODE == 0 && n0t >= p.n_samples) return;  // (modes 1, 2: only for full tiles)
                 if (s_ == 1) epi_put_tile(y);
-                if constexpr (MODE == 2 && RES_SIDE) epi_res_fetch(t, s_, 0);
+                if constexpr (MODE == 2 && RES_SIDE) epi_res_fetch(e_orb, s_, 0);
                 if (s_ == 9 || s_ == 10) {
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
@@ -820,16 +843,20 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
                         const int row = e_wrow + 8 * (2 * (s_ - 8) + i);
-                        e_of[i] = ofast[t * 32 + row];
+                        if constexpr (MODE == 2 && RES_SIDE) {
+                            e_of[i] = e_ofb[8 * (2 * (s_ - 8) + i)];
+                            e_out[i] = e_orb[8 * (2 * (s_ - 8) + i)].out_row;
+                        } else {
+                            e_of[i] = ofast[t * 32 + row];
+                        }
                         e_v[i] = *reinterpret_cast<const f32x4 *>(scr + row * 32 + e_wcol);
-                        if constexpr (MODE == 2 && RES_SIDE) e_out[i] = ores[t * 32 + row].out_row;
                     }
                 }
             };
             // (mode 2) the last tile's epilogue, matrix pipe idle: the `before` loads first, the rows' own stores while they fly
             auto epi_res_last = [&](const f32x16 &y, int t) {
-                epi_res_fetch(t, 0, 0);
-                epi_res_fetch(t, 1, 0);
+                epi_res_fetch(ores + t * 32 + e_wrow, 0, 0);
+                epi_res_fetch(ores + t * 32 + e_wrow, 1, 0);
                 epi_put_tile(y);
                 f32x4 v[4];
 #pragma unroll
@@ -954,6 +981,16 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
             // (slot 12) it is re-initialised with the bias of tile t+1.
             auto out_chunk = [&](f32x16 &y, f32x16 &yo, int t, auto has_prev_c, auto mode_c) __attribute__((always_inline)) {
                 const int gnext = (g + 1 == G) ? 0 : g + 1;
+                if constexpr (decltype(mode_c)::value == 2 && RES_SIDE && decltype(has_prev_c)::value) {
+                    // (one address add per table and chunk: the rows' entries are then read at immediate offsets)
+                    typedef const OFast __attribute__((address_space(3))) *LOFast;
+                    typedef const ORes __attribute__((address_space(3))) *LORes;
+                    LOFast ofb = (LOFast)(ofast + (NHO + t - 1) * 32 + e_wrow);
+                    LORes orb = (LORes)(ores + (NHO + t - 1) * 32 + e_wrow);
+                    asm volatile("" : "+v"(ofb), "+v"(orb));
+                    e_ofb = (const OFast *)ofb;
+                    e_orb = (const ORes *)orb;
+                }
 #pragma unroll
                 for (int s = 0; s < KC_O; ++s) {
                     SLOT_STAMP(20, s);
@@ -1604,6 +1641,7 @@ struct fv3hip_mlp {
     int64_t flops = 0;
     int has_limits = 0;
     int n_log_chunks = 0, n_logfast_chunks = 0;
+    int l1_short_log = 0;  // see MlpLaunch
     unsigned int w_bytes = 0;
     void *d_sink = nullptr;
     size_t sink_bytes = 0;
@@ -1650,6 +1688,7 @@ int upload(const std::vector<T> &v, void **dptr)
 struct InputTable {
     std::vector<KEntry> ktab;
     std::vector<int> perm;     // table row -> original input feature, -1 = padding
+    int n_log = 0;             // input features that take the logarithm
     int n_log_padded = 0;      // rows at the head of the table that take the logarithm (padded to whole 32-row chunks if room)
     bool eps_normal = true;    // every logarithm's floor is a normal number
 };
@@ -1677,6 +1716,7 @@ void build_input_table(const fv3hip_mlp_desc_t *d, int K, int n_ktab, InputTable
     for (int k2 = 0; k2 < K; ++k2)
         if (orig[k2].transform == FV3HIP_TRANSFORM_LOG) t.perm.push_back(k2);
     const int n_log = (int)t.perm.size();
+    t.n_log = n_log;
     // if the chunk count allows, pad the log block to whole chunks (entries -1: zero weight rows reading a constant,
     // eps = 1 so that the logarithm is of a normal number) -- then no chunk mixes both kinds and every log chunk takes
     // the fast path
@@ -1957,6 +1997,8 @@ extern "C" int fv3hip_mlp_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp_t *out)
     std::vector<int> &perm = it.perm;
     m->n_log_chunks = (it.n_log_padded + 31) / 32;
     m->n_logfast_chunks = it.eps_normal ? it.n_log_padded / 32 : 0;
+    // the log block was padded to whole chunks, the real rows of its last chunk fit 8 k-pair slots and a plain chunk follows
+    m->l1_short_log = (it.n_log_padded % 32 == 0 && it.n_log % 32 >= 1 && it.n_log % 32 <= 16 && m->n_log_chunks < m->n_chunks1) ? 1 : 0;
     // ---- packed weight stream ----
     // (+ one maximal chunk of zero padding: the two-half staging may read past a short last chunk)
     std::vector<float> w((size_t)(n_hid_chunks * CH_H + n_out_chunks * CH_O + (CH_H > CH_O ? CH_H : CH_O)) * 4, 0.f);
@@ -2254,6 +2296,7 @@ extern "C" int fv3hip_mlp_predict(fv3hip_mlp_t m, const void *const *sources, co
     }
     lp.n_log_chunks = m->n_log_chunks;
     lp.n_logfast_chunks = m->n_logfast_chunks;
+    lp.l1_short_log = m->l1_short_log;
     lp.n_residual = m->n_residual;
     lp.n_samples = n_samples;
     lp.n_tiles = ceil_div(n_samples, kTileSamples);
