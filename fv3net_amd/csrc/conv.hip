@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kBlock) void conv_layer_kernel(const LayerArgs a)
                 float v = acc[mi][nt][r];
                 if (a.bias) v += a.bias[n];
                 if (a.act == FV3HIP_ACT_RELU)
-                    v = v > 0.f ? v : 0.f;
+                    v = v < 0.f ? 0.f : v;   // (a NaN stays a NaN, as in np.maximum(v, 0) and Keras' relu: see mlp.hip)
                 else if (a.act == FV3HIP_ACT_TANH)
                     v = tanhf(v);
                 if (a.oscale) v = v * a.oscale[n] + a.ocenter[n];
