@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../include/fv3hip.h"
 
@@ -39,6 +40,18 @@ inline int check_launch(const char *what)
 {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(FV3HIP_EHIP, "launch of %s failed: %s", what, hipGetErrorString(e));
+    return FV3HIP_OK;
+}
+
+// A host vector to a fresh device buffer (an empty one: no buffer).  On failure the caller destroys its handle, which
+// frees what was uploaded before.
+template <typename T>
+int upload(const std::vector<T> &v, void **dptr)
+{
+    *dptr = nullptr;
+    if (v.empty()) return FV3HIP_OK;
+    FV3HIP_CHECK_HIP(hipMalloc(dptr, v.size() * sizeof(T)));
+    FV3HIP_CHECK_HIP(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return FV3HIP_OK;
 }
 

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mlp_desc.h"
 
 namespace fv3hip {
 namespace {
@@ -75,16 +76,6 @@ constexpr int kMaxK = 2048;       // network inputs whose per-feature table stil
 constexpr int kThreads = 256;     // 4 waves, one per SIMD
 constexpr int kTileSamples = 128; // 32 per wave
 
-struct KEntry {  // one network input feature (32 bytes)
-    int src;     // source array, -1 for padding
-    int feat;    // feature (level) index inside the source
-    float center;
-    float scale;
-    int transform;
-    float eps;
-    int pad0, pad1;
-};
-
 struct XAddr {  // per call: where network input k is read from (16 bytes)
     int64_t row;       // byte address of (feature, sample 0)
     unsigned int ss;   // byte stride between samples (< 4 GiB)
@@ -111,12 +102,15 @@ struct ORes {       // 32 bytes; residual output  after = before + value
     unsigned int src_ss, out_ss, pad0, pad1;
 };
 
-struct OEntry {  // one network output feature as the host describes it (32 bytes, global memory)
-    float scale, center, lo, hi;
-    float mask;
-    int out_feat;  // (output slot << 20) | feature inside the slot; -1 for padding
-    int res;       // (residual slot << 8) | residual source; -1 for none
-    int pad0;
+// sources and outputs of one call, in elements: base address, feature stride, sample stride (the last member of every
+// launch structure: fv3hip_mlp_predict fills one and each launch takes it by assignment)
+struct MlpIo {
+    const void *src[kMaxSources];
+    int64_t src_fs[kMaxSources];
+    int64_t src_ss[kMaxSources];
+    void *out[kMaxOutputs];
+    int64_t out_fs[kMaxOutputs];
+    int64_t out_ss[kMaxOutputs];
 };
 
 struct MlpLaunch {
@@ -146,16 +140,8 @@ struct MlpLaunch {
     int64_t n_samples;
     int64_t n_tiles;
     unsigned long long *stamps;  // diagnostic builds only (-DMLP_STAMPS): [wave][8] cycle sums
-    const void *src[kMaxSources];
-    int64_t src_fs[kMaxSources];
-    int64_t src_ss[kMaxSources];
-    void *out[kMaxOutputs];
-    int64_t out_fs[kMaxOutputs];
-    int64_t out_ss[kMaxOutputs];
+    MlpIo io;
 };
-
-// row of a 32x32 accumulator held by register r of a lane in half h is rho(r) + 4*h
-__host__ __device__ constexpr int rho(int r) { return (r & 3) + 8 * (r >> 2); }
 
 #ifndef MLP_STAMP_PHASE
 #define MLP_STAMP_PHASE 0  // per-slot stamps: 0/1/2 layer-1 XBULK chunks by log mode, 3 the 8-slot last log chunk, 10 hidden, 20 output
@@ -227,7 +213,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
         // read to issue an input load and one to finish it -- no dependent LDS chain in a slot.
         typedef const int64_t __attribute__((address_space(4))) *KargPtr64;
         typedef const char __attribute__((address_space(4))) *KargBytes64;
-        KargPtr64 ksrc = (KargPtr64)((KargBytes64)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MlpLaunch, src));
+        KargPtr64 ksrc = (KargPtr64)((KargBytes64)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MlpLaunch, io.src));
         for (int i = tid; i < p.n_ktab; i += kThreads) {
             const KEntry e = p.ktab[i];
             const int sidx = e.src < 0 ? 0 : e.src;
@@ -248,7 +234,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
         }
         // Per-feature output tables: absolute row addresses for this call, so that the epilogue is
         // one LDS read, a multiply-add, one address computation and a store per value.
-        KargPtr64 kout = (KargPtr64)((KargBytes64)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MlpLaunch, out));
+        KargPtr64 kout = (KargPtr64)((KargBytes64)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MlpLaunch, io.out));
         const int64_t osz = p.out64 ? 8 : 4;
         for (int i = tid; i < p.n_otab; i += kThreads) {
             const OEntry e = p.otab[i];
@@ -440,11 +426,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
             brawd[SRC64 ? i : 0][1] = *(GD2)(addr + (a.ss ? 16 : 0));
         } else {
             typedef const f32x4 __attribute__((address_space(1))) *GF4;
-#ifdef MLP_NT_X
-            braw[SRC64 ? 0 : i] = __builtin_nontemporal_load((GF4)addr);
-#else
             braw[SRC64 ? 0 : i] = *(GF4)addr;
-#endif
         }
     };
     auto bulk_issue = [&](int c, int64_t tile_n0) {
@@ -1144,15 +1126,10 @@ struct SmallLaunch {
     const float *bo;   // [Fp]           output scale and centre folded in
     const KEntry *ktab;
     const OEntry *otab;
-    int n_ktab, Wp, HT, n_hidden, Fp, n_otiles, n_hout_tiles, out64, has_limits, hout_slot;
+    int n_ktab, Wp, HT, n_hidden, Fp, n_otiles, n_hout_tiles, out64, has_limits;
     int64_t n_samples;
     unsigned long long *stamps;  // diagnostic builds only (-DSMALL_STAMPS): [workgroup][wave][8] cycle stamps
-    const void *src[kMaxSources];
-    int64_t src_fs[kMaxSources];
-    int64_t src_ss[kMaxSources];
-    void *out[kMaxOutputs];
-    int64_t out_fs[kMaxOutputs];
-    int64_t out_ss[kMaxOutputs];
+    MlpIo io;
 };
 
 constexpr int kSmallWaves = 8;     // 512 threads: two waves per SIMD hide each other's operand loads
@@ -1162,7 +1139,7 @@ constexpr int kSmallChunk = 128;   // input features staged per step (2 x 16 KB 
 __device__ __forceinline__ int64_t otab_base_early(const SmallLaunch &p, int slot, int what)
 {
     const int64_t osz = p.out64 ? 8 : 4;
-    return what == 0 ? reinterpret_cast<int64_t>(p.out[slot]) : what == 1 ? p.out_fs[slot] * osz : p.out_ss[slot] * osz;
+    return what == 0 ? reinterpret_cast<int64_t>(p.io.out[slot]) : what == 1 ? p.io.out_fs[slot] * osz : p.io.out_ss[slot] * osz;
 }
 
 #ifdef SMALL_STAMPS
@@ -1273,8 +1250,8 @@ __global__ __launch_bounds__(kSmallWaves * 64) void mlp_small_kernel(const Small
     for (int i = tid; i < p.n_ktab; i += NT) {
         const KEntry e = p.ktab[i];
         XRow x;
-        x.row = e.src < 0 ? 0 : reinterpret_cast<int64_t>(p.src[e.src]) + (int64_t)e.feat * p.src_fs[e.src] * ESZ;
-        x.ss = e.src < 0 ? 0u : (unsigned int)(p.src_ss[e.src] * ESZ);
+        x.row = e.src < 0 ? 0 : reinterpret_cast<int64_t>(p.io.src[e.src]) + (int64_t)e.feat * p.io.src_fs[e.src] * ESZ;
+        x.ss = e.src < 0 ? 0u : (unsigned int)(p.io.src_ss[e.src] * ESZ);
         x.center = e.center;
         x.eps = e.eps;
         x.is_log = (e.transform == FV3HIP_TRANSFORM_LOG) ? 1 : 0;
@@ -1282,14 +1259,14 @@ __global__ __launch_bounds__(kSmallWaves * 64) void mlp_small_kernel(const Small
         kt[i] = x;
     }
     if (tid < kMaxOutputs) {
-        otab_base[tid] = reinterpret_cast<int64_t>(p.out[tid]);
-        otab_base[kMaxOutputs + tid] = p.out_fs[tid] * osz;
-        otab_base[2 * kMaxOutputs + tid] = p.out_ss[tid] * osz;
+        otab_base[tid] = reinterpret_cast<int64_t>(p.io.out[tid]);
+        otab_base[kMaxOutputs + tid] = p.io.out_fs[tid] * osz;
+        otab_base[2 * kMaxOutputs + tid] = p.io.out_ss[tid] * osz;
     }
     if (tid < kMaxSources) {
-        stab_base[tid] = reinterpret_cast<int64_t>(p.src[tid]);
-        stab_base[kMaxSources + tid] = p.src_fs[tid] * ESZ;
-        stab_base[2 * kMaxSources + tid] = p.src_ss[tid] * ESZ;
+        stab_base[tid] = reinterpret_cast<int64_t>(p.io.src[tid]);
+        stab_base[kMaxSources + tid] = p.io.src_fs[tid] * ESZ;
+        stab_base[2 * kMaxSources + tid] = p.io.src_ss[tid] * ESZ;
     }
     // the output slots of the hidden activations (hidden-output models): read now, used after the last hidden layer
     int hout_feat[MAXT][16];
@@ -1505,12 +1482,7 @@ struct LayeredIo {
     float *x;           // scratch [rows][np]
     int64_t np, n0, n_samples;  // padded slab width; first sample of the slab; samples of the call
     int n_rows, out64, has_limits;
-    const void *src[kMaxSources];
-    int64_t src_fs[kMaxSources];
-    int64_t src_ss[kMaxSources];
-    void *out[kMaxOutputs];
-    int64_t out_fs[kMaxOutputs];
-    int64_t out_ss[kMaxOutputs];
+    MlpIo io;
 };
 
 // grid (np / 256, n_ktab): row k of the normalised input matrix for the slab's samples (a ragged end repeats the last sample)
@@ -1525,8 +1497,8 @@ __global__ __launch_bounds__(256) void layered_gather_kernel(const LayeredIo p)
     if (e.src >= 0) {
         int64_t ns = p.n0 + j;
         if (ns >= p.n_samples) ns = p.n_samples - 1;
-        const Raw *row = static_cast<const Raw *>(p.src[e.src]) + (int64_t)e.feat * p.src_fs[e.src];
-        v = (float)row[ns * p.src_ss[e.src]];
+        const Raw *row = static_cast<const Raw *>(p.io.src[e.src]) + (int64_t)e.feat * p.io.src_fs[e.src];
+        v = (float)row[ns * p.io.src_ss[e.src]];
         if (e.transform == FV3HIP_TRANSFORM_LOG) v = logf(v < e.eps ? e.eps : v);
         v = v - e.center;  // (1 / std lives in the first layer's weights)
     }
@@ -1612,15 +1584,15 @@ __global__ __launch_bounds__(256) void layered_scatter_kernel(const LayeredIo p)
         x = x * e.mask;
     }
     const int slot = e.out_feat >> 20, q = e.out_feat & 0xFFFFF;
-    const int64_t at = (int64_t)q * p.out_fs[slot] + ns * p.out_ss[slot];
-    if (p.out64) static_cast<double *>(p.out[slot])[at] = (double)x;
-    else static_cast<float *>(p.out[slot])[at] = x;
+    const int64_t at = (int64_t)q * p.io.out_fs[slot] + ns * p.io.out_ss[slot];
+    if (p.out64) static_cast<double *>(p.io.out[slot])[at] = (double)x;
+    else static_cast<float *>(p.io.out[slot])[at] = x;
     if (e.res >= 0) {  // residual output: after = before + value
         const int rslot = e.res >> 8, rs = e.res & 0xFF;
-        const float before = (float)static_cast<const Raw *>(p.src[rs])[(int64_t)q * p.src_fs[rs] + ns * p.src_ss[rs]];
-        const int64_t rat = (int64_t)q * p.out_fs[rslot] + ns * p.out_ss[rslot];
-        if (p.out64) static_cast<double *>(p.out[rslot])[rat] = (double)(before + x);
-        else static_cast<float *>(p.out[rslot])[rat] = before + x;
+        const float before = (float)static_cast<const Raw *>(p.io.src[rs])[(int64_t)q * p.io.src_fs[rs] + ns * p.io.src_ss[rs]];
+        const int64_t rat = (int64_t)q * p.io.out_fs[rslot] + ns * p.io.out_ss[rslot];
+        if (p.out64) static_cast<double *>(p.io.out[rslot])[rat] = (double)(before + x);
+        else static_cast<float *>(p.io.out[rslot])[rat] = before + x;
     }
 }
 
@@ -1674,174 +1646,27 @@ int launch_one(const MlpLaunch &lp, int grid, size_t lds, hipStream_t st)
     return check_launch("mlp_fused_kernel");
 }
 
-template <typename T>
-int upload(const std::vector<T> &v, void **dptr)
+template <bool SRC64>
+int launch_small(const SmallLaunch &sp, int grid, size_t lds, hipStream_t st)
 {
-    *dptr = nullptr;
-    if (v.empty()) return FV3HIP_OK;
-    FV3HIP_CHECK_HIP(hipMalloc(dptr, v.size() * sizeof(T)));
-    FV3HIP_CHECK_HIP(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return FV3HIP_OK;
+    auto kern = mlp_small_kernel<SRC64>;
+    FV3HIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSmallWaves * 64), lds, st, sp);
+    return check_launch("mlp_small_kernel");
 }
 
-// ---- the tables both kernel families and the layered path read ----
-struct InputTable {
-    std::vector<KEntry> ktab;
-    std::vector<int> perm;     // table row -> original input feature, -1 = padding
-    int n_log = 0;             // input features that take the logarithm
-    int n_log_padded = 0;      // rows at the head of the table that take the logarithm (padded to whole 32-row chunks if room)
-    bool eps_normal = true;    // every logarithm's floor is a normal number
-};
-
-// Network input k' is original input feature perm[k']: the log-transformed features come first (any order of the
-// contraction index is the same dense layer), so that whole 32-row chunks are either with or without the transform.
-void build_input_table(const fv3hip_mlp_desc_t *d, int K, int n_ktab, InputTable &t)
+// the layered path's gather (grid.y = table rows) or scatter (grid.y = output features) of one slab
+int launch_layered_io(void (*kern)(LayeredIo), const char *what, const LayeredIo &io, dim3 grid, hipStream_t st)
 {
-    t.ktab.assign(n_ktab, KEntry{-1, 0, 0.f, 1.f, 0, 0.f, 0, 0});
-    t.perm.clear();
-    t.perm.reserve(n_ktab);
-    std::vector<KEntry> orig(K);
-    int k = 0;
-    for (int i = 0; i < d->n_inputs; ++i)
-        for (int f = 0; f < d->in_nfeat[i]; ++f, ++k) {
-            KEntry &e = orig[k];
-            e = KEntry{-1, 0, 0.f, 1.f, 0, 0.f, 0, 0};
-            e.src = d->in_source[i];
-            e.feat = d->in_feat_start[i] + f;
-            e.center = d->in_center ? d->in_center[k] : 0.f;
-            e.scale = d->in_scale ? (float)(1.0 / (double)d->in_scale[k]) : 1.f;  // reciprocal
-            e.transform = d->in_transform ? d->in_transform[i] : 0;
-            e.eps = d->in_eps ? d->in_eps[i] : 0.f;
-        }
-    for (int k2 = 0; k2 < K; ++k2)
-        if (orig[k2].transform == FV3HIP_TRANSFORM_LOG) t.perm.push_back(k2);
-    const int n_log = (int)t.perm.size();
-    t.n_log = n_log;
-    // if the chunk count allows, pad the log block to whole chunks (entries -1: zero weight rows reading a constant,
-    // eps = 1 so that the logarithm is of a normal number) -- then no chunk mixes both kinds and every log chunk takes
-    // the fast path
-    const int n_pad = (32 - n_log % 32) % 32;
-    if (n_log > 0 && n_log + n_pad + (K - n_log) <= n_ktab)
-        for (int i = 0; i < n_pad; ++i) t.perm.push_back(-1);
-    t.n_log_padded = (int)t.perm.size();
-    for (int k2 = 0; k2 < K; ++k2)
-        if (orig[k2].transform != FV3HIP_TRANSFORM_LOG) t.perm.push_back(k2);
-    for (size_t k2 = 0; k2 < t.perm.size(); ++k2) {
-        if (t.perm[k2] >= 0) {
-            t.ktab[k2] = orig[t.perm[k2]];
-        } else {
-            t.ktab[k2].transform = FV3HIP_TRANSFORM_LOG;
-            t.ktab[k2].eps = 1.f;
-        }
-    }
-    t.eps_normal = true;
-    for (int k2 = 0; k2 < t.n_log_padded; ++k2) t.eps_normal = t.eps_normal && t.ktab[k2].eps >= FLT_MIN;
-}
-
-// Rows [0, n_hidden_rows): the last hidden layer's features (hidden-output models), stored to the slot after the outputs
-// and the residual outputs; rows first_out + f: output feature f.
-void build_output_table(const fv3hip_mlp_desc_t *d, int n_otab, int first_out, int n_hidden_rows, std::vector<OEntry> &otab)
-{
-    otab.assign(n_otab, OEntry{1.f, 0.f, -INFINITY, INFINITY, 1.f, -1, -1, 0});
-    for (int q = 0; q < n_hidden_rows; ++q) otab[q].out_feat = ((d->n_outputs + d->n_residual) << 20) | q;
-    int f = 0;
-    for (int j = 0; j < d->n_outputs; ++j) {
-        int res = -1;
-        for (int r = 0; r < d->n_residual; ++r)
-            if (d->res_output[r] == j) res = ((d->n_outputs + r) << 8) | d->res_source[r];
-        for (int q = 0; q < d->out_nfeat[j]; ++q, ++f) {
-            OEntry &e = otab[first_out + f];
-            e.scale = d->out_scale ? d->out_scale[f] : 1.f;
-            e.center = d->out_center ? d->out_center[f] : 0.f;
-            e.lo = d->out_min ? d->out_min[f] : -INFINITY;
-            e.hi = d->out_max ? d->out_max[f] : INFINITY;
-            e.mask = d->out_mask ? d->out_mask[f] : 1.f;
-            e.out_feat = (j << 20) | q;
-            e.res = res;
-        }
-    }
-}
-
-}  // namespace
-
-namespace {
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-int create_layered(const fv3hip_mlp_desc_t *d, int K, fv3hip_mlp_t *out)
-{
-    int F = 0;
-    for (int j = 0; j < d->n_outputs; ++j) {
-        FV3HIP_REQUIRE(d->out_nfeat[j] >= 1 && d->out_nfeat[j] < (1 << 20), "bad out_nfeat[%d]", j);
-        F += d->out_nfeat[j];
-    }
-    for (int r = 0; r < d->n_residual; ++r) {
-        FV3HIP_REQUIRE(d->res_source[r] >= 0 && d->res_source[r] < d->n_sources, "res_source[%d] out of range", r);
-        FV3HIP_REQUIRE(d->res_output[r] >= 0 && d->res_output[r] < d->n_outputs, "res_output[%d] out of range", r);
-    }
-    const int nh = d->n_hidden, width = nh ? d->width : K;
-    FV3HIP_REQUIRE(K < 65536 && F < 65536 && width < 65536, "more than 65 535 features in a layer");
-    fv3hip_mlp *m = new fv3hip_mlp();
-    hipGetDevice(&m->device);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, m->device) == hipSuccess) m->n_cu = prop.multiProcessorCount;
-    m->layered = 1;
-    m->relu = d->hidden_activation == FV3HIP_ACT_RELU;
-    m->n_sources = d->n_sources;
-    m->n_inputs = d->n_inputs;
-    m->K = K;
-    m->width = width;
-    m->n_hidden = nh;
-    m->n_outputs = d->n_outputs;
-    m->F = F;
-    m->n_residual = d->n_residual;
-    m->has_limits = (d->out_min || d->out_max || d->out_mask) ? 1 : 0;
-    m->n_ktab = round_up(K, 32);
-    m->Wp = nh ? round_up(width, 64) : 0;
-    m->Fp = round_up(F, 64);
-    m->n_otab = m->Fp;
-    m->flops = nh ? 2 * ((int64_t)K * width + (int64_t)(nh - 1) * width * width + (int64_t)width * F) : 2 * (int64_t)K * F;
-    InputTable it;
-    build_input_table(d, K, m->n_ktab, it);
-    std::vector<OEntry> otab;
-    build_output_table(d, m->n_otab, 0, 0, otab);
-    const int Wp = m->Wp, Fp = m->Fp, kin_o = nh ? Wp : m->n_ktab;
-    auto oscale = [&](int f) { return d->out_scale ? d->out_scale[f] : 1.f; };
-    std::vector<float> w1((size_t)(nh ? m->n_ktab * (size_t)Wp : 0), 0.f), wh((size_t)(nh > 1 ? nh - 1 : 0) * Wp * Wp, 0.f),
-        wo((size_t)kin_o * Fp, 0.f), bh((size_t)nh * Wp, 0.f), bo((size_t)Fp, 0.f);
-    for (size_t k = 0; k < it.perm.size(); ++k) {
-        if (it.perm[k] < 0) continue;
-        if (nh)
-            for (int f = 0; f < width; ++f) w1[k * Wp + f] = d->hidden_kernels[0][(size_t)it.perm[k] * width + f] * it.ktab[k].scale;
-        else  // the only layer carries both foldings: 1 / std of its input row, the scale of its output column
-            for (int f = 0; f < F; ++f)
-                wo[k * Fp + f] = (float)((double)d->out_kernel[(size_t)it.perm[k] * F + f] * (double)it.ktab[k].scale * (double)oscale(f));
-    }
-    for (int l = 1; l < nh; ++l)
-        for (int k = 0; k < width; ++k)
-            for (int f = 0; f < width; ++f) wh[((size_t)(l - 1) * Wp + k) * Wp + f] = d->hidden_kernels[l][(size_t)k * width + f];
-    for (int l = 0; l < nh; ++l)
-        for (int f = 0; f < width; ++f) bh[(size_t)l * Wp + f] = d->hidden_biases[l][f];
-    if (nh)
-        for (int k = 0; k < width; ++k)
-            for (int f = 0; f < F; ++f) wo[(size_t)k * Fp + f] = d->out_kernel[(size_t)k * F + f] * oscale(f);
-    for (int f = 0; f < F; ++f)
-        bo[f] = (float)((double)d->out_bias[f] * oscale(f) + (d->out_center ? d->out_center[f] : 0.f));
-    int rc;
-    if ((rc = upload(w1, &m->d_w1)) || (rc = upload(wh, &m->d_wh)) || (rc = upload(wo, &m->d_wo)) || (rc = upload(bh, &m->d_bh)) ||
-        (rc = upload(bo, &m->d_bo)) || (rc = upload(it.ktab, &m->d_ktab)) || (rc = upload(otab, &m->d_otab))) {
-        fv3hip_mlp_destroy(m);
-        return rc;
-    }
-    *out = m;
-    return FV3HIP_OK;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, io);
+    return check_launch(what);
 }
 
 // One slab of at most kLayeredSlab samples at a time through gather -> layers -> scatter (the scratch stays bounded:
 // 2 x rows x slab x 4 bytes, whatever the call's size); all on the caller's stream, so slabs follow each other.
 constexpr int64_t kLayeredSlab = 65536;
 
-int predict_layered(fv3hip_mlp *m, const MlpLaunch &lp, bool src64, int out_dtype, int64_t n_samples, hipStream_t st)
+int predict_layered(fv3hip_mlp *m, const MlpIo &mio, bool src64, int out_dtype, int64_t n_samples, hipStream_t st)
 {
     const int rows = std::max(m->n_ktab, std::max(m->Wp, m->Fp));
     const int64_t np_max = (std::min(n_samples, kLayeredSlab) + 255) / 256 * 256;
@@ -1863,12 +1688,7 @@ int predict_layered(fv3hip_mlp *m, const MlpLaunch &lp, bool src64, int out_dtyp
     io.n_samples = n_samples;
     io.out64 = (out_dtype == FV3HIP_F64);
     io.has_limits = m->has_limits;
-    memcpy(io.src, lp.src, sizeof(io.src));
-    memcpy(io.src_fs, lp.src_fs, sizeof(io.src_fs));
-    memcpy(io.src_ss, lp.src_ss, sizeof(io.src_ss));
-    memcpy(io.out, lp.out, sizeof(io.out));
-    memcpy(io.out_fs, lp.out_fs, sizeof(io.out_fs));
-    memcpy(io.out_ss, lp.out_ss, sizeof(io.out_ss));
+    io.io = mio;
     snprintf(m->last_variant, sizeof(m->last_variant), "layered (gather, %d x layered_dense_kernel, scatter; slabs of %lld samples)",
              m->n_hidden + 1, (long long)kLayeredSlab);
     for (int64_t n0 = 0; n0 < n_samples; n0 += kLayeredSlab) {
@@ -1878,9 +1698,7 @@ int predict_layered(fv3hip_mlp *m, const MlpLaunch &lp, bool src64, int out_dtyp
         io.np = np;
         io.x = cur;
         const dim3 gg((unsigned)(np / 256), (unsigned)m->n_ktab);
-        if (src64) hipLaunchKernelGGL(layered_gather_kernel<true>, gg, dim3(256), 0, st, io);
-        else hipLaunchKernelGGL(layered_gather_kernel<false>, gg, dim3(256), 0, st, io);
-        int rc = check_launch("layered_gather_kernel");
+        int rc = launch_layered_io(src64 ? layered_gather_kernel<true> : layered_gather_kernel<false>, "layered_gather_kernel", io, gg, st);
         if (rc) return rc;
         auto dense = [&](const void *w, const void *b, int kp, int fp, int relu) {
             LayeredDense dp;
@@ -1903,78 +1721,43 @@ int predict_layered(fv3hip_mlp *m, const MlpLaunch &lp, bool src64, int out_dtyp
         if ((rc = dense(m->d_wo, m->d_bo, m->n_hidden ? m->Wp : m->n_ktab, m->Fp, 0))) return rc;
         io.x = cur;
         const dim3 gs((unsigned)(np / 256), (unsigned)m->F);
-        if (src64) hipLaunchKernelGGL(layered_scatter_kernel<true>, gs, dim3(256), 0, st, io);
-        else hipLaunchKernelGGL(layered_scatter_kernel<false>, gs, dim3(256), 0, st, io);
-        if ((rc = check_launch("layered_scatter_kernel"))) return rc;
+        if ((rc = launch_layered_io(src64 ? layered_scatter_kernel<true> : layered_scatter_kernel<false>, "layered_scatter_kernel", io, gs, st)))
+            return rc;
     }
     return FV3HIP_OK;
 }
 
 }  // namespace
 
-extern "C" int fv3hip_mlp_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp_t *out)
+namespace {
+
+// ---- create: what is specific to each path; fv3hip_mlp_create below is the skeleton ----
+
+// Layered path (what the fused kernels do not hold goes layer by layer, see layered_dense_kernel): tables and matrices
+// padded for its kernels, Wp and Fp multiples of 64; nothing is packed.
+int layered_geometry(const MlpDims &dm, fv3hip_mlp *m)
 {
-    FV3HIP_REQUIRE(d && out, "null pointer");
-    *out = nullptr;
-    FV3HIP_REQUIRE(d->n_sources >= 1 && d->n_sources <= kMaxSources, "n_sources must be in [1, %d], got %d", kMaxSources, d->n_sources);
-    FV3HIP_REQUIRE(d->n_inputs >= 1, "n_inputs must be >= 1");
-    const int hout = d->hidden_output ? 1 : 0;
-    FV3HIP_REQUIRE(d->n_outputs >= 1 || (d->n_outputs == 0 && hout), "n_outputs must be >= 1 (or 0 with hidden_output)");
-    FV3HIP_REQUIRE(d->n_residual >= 0 && d->n_outputs + d->n_residual + hout <= kMaxOutputs,
-                   "n_outputs + n_residual (+ the hidden output) must be <= %d", kMaxOutputs);
-    FV3HIP_REQUIRE(d->width >= 1, "width must be >= 1");
-    FV3HIP_REQUIRE(d->n_hidden >= 0, "negative n_hidden");
-    FV3HIP_REQUIRE(d->hidden_activation == FV3HIP_ACT_RELU || d->hidden_activation == FV3HIP_ACT_LINEAR, "unknown activation %d", d->hidden_activation);
+    FV3HIP_REQUIRE(dm.K < 65536 && dm.F < 65536 && m->width < 65536, "more than 65 535 features in a layer");
+    m->n_ktab = round_up(dm.K, 32);
+    m->Wp = m->n_hidden ? round_up(m->width, 64) : 0;
+    m->Fp = round_up(dm.F, 64);
+    m->n_otab = m->Fp;
+    return FV3HIP_OK;
+}
 
-    int K = 0;
-    for (int i = 0; i < d->n_inputs; ++i) {
-        FV3HIP_REQUIRE(d->in_source[i] >= 0 && d->in_source[i] < d->n_sources, "in_source[%d] out of range", i);
-        FV3HIP_REQUIRE(d->in_nfeat[i] >= 1 && d->in_feat_start[i] >= 0, "bad feature range for input %d", i);
-        K += d->in_nfeat[i];
-    }
-    // what the fused kernels do not hold goes layer by layer (see layered_dense_kernel)
-    const bool layered = d->n_hidden < 1 || d->width > 256 || K > kMaxK || d->hidden_activation != FV3HIP_ACT_RELU;
-    if (layered) {
-        if (hout) return fail(FV3HIP_EUNSUPPORTED, "hidden-output models need 1+ ReLU hidden layers of width <= 256 and <= %d inputs", kMaxK);
-        FV3HIP_REQUIRE(d->n_hidden == 0 || d->width >= 1, "width must be >= 1");
-        return create_layered(d, K, out);
-    }
-    int F = 0;
-    for (int j = 0; j < d->n_outputs; ++j) {
-        FV3HIP_REQUIRE(d->out_nfeat[j] >= 1 && d->out_nfeat[j] < (1 << 20), "bad out_nfeat[%d]", j);
-        F += d->out_nfeat[j];
-    }
-    for (int r = 0; r < d->n_residual; ++r) {
-        FV3HIP_REQUIRE(d->res_source[r] >= 0 && d->res_source[r] < d->n_sources, "res_source[%d] out of range", r);
-        FV3HIP_REQUIRE(d->res_output[r] >= 0 && d->res_output[r] < d->n_outputs, "res_output[%d] out of range", r);
-    }
-
-    // pick the kernel variant: the smallest hidden tiling that holds `width`
-    const int width = d->width;
-    const int nt_out = (F + 31) / 32;
+// Fused path: the kernel variant (the smallest hidden tiling that holds `width`) and the sizes of its tables.
+int fused_geometry(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m)
+{
+    const int F = dm.F, nt_out = (F + 31) / 32;
     int HT = 0;
     for (int v : kHiddenTilings)
-        if (!HT && v * 32 >= width) HT = v;
-    FV3HIP_REQUIRE(HT > 0, "no kernel variant for width %d", width);
-
-    fv3hip_mlp *m = new fv3hip_mlp();
-    hipGetDevice(&m->device);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, m->device) == hipSuccess) m->n_cu = prop.multiProcessorCount;
+        if (!HT && v * 32 >= m->width) HT = v;
+    FV3HIP_REQUIRE(HT > 0, "no kernel variant for width %d", m->width);
     m->HT = HT;
-    m->n_sources = d->n_sources;
-    m->n_inputs = d->n_inputs;
-    m->K = K;
-    m->width = width;
-    m->n_hidden = d->n_hidden;
-    m->n_outputs = d->n_outputs;
-    m->F = F;
-    m->n_residual = d->n_residual;
-    m->has_limits = (d->out_min || d->out_max || d->out_mask) ? 1 : 0;
-    m->n_chunks1 = ((K + 1) / 2 + 15) / 16;
+    m->n_chunks1 = ((dm.K + 1) / 2 + 15) / 16;
     m->n_otiles = nt_out;
     m->n_ktab = 2 * 16 * m->n_chunks1;
-    m->n_hout_tiles = hout ? HT : 0;
+    m->n_hout_tiles = dm.hout ? HT : 0;
     m->n_otab = 32 * (m->n_hout_tiles + nt_out);
     m->n_bias = d->n_hidden * HT * 32 + nt_out * 32;
     if (F >= 1 && F <= 4 && !m->has_limits && d->n_residual == 0) {  // eligible for the small-output path (see the kernel)
@@ -1982,31 +1765,36 @@ extern "C" int fv3hip_mlp_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp_t *out)
         m->smallf_off = m->n_bias;
         m->n_bias += HT * 32 * 4;
     }
-    m->flops = 2 * ((int64_t)K * width + (int64_t)(d->n_hidden - 1) * width * width + (int64_t)width * F);
+    m->Wp = HT * 32;  // (mlp_small_kernel's plain copies)
+    m->Fp = (nt_out > 0 ? nt_out : 1) * 32;
+    return FV3HIP_OK;
+}
 
+// Fused path: the packed weight stream and the bias block, rows in the order of the input table `it`.
+int pack_fused(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m, const InputTable &it, std::vector<float> &w, std::vector<float> &bias)
+{
+    const int HT = m->HT, width = m->width, F = dm.F, nt_out = m->n_otiles;
+    const std::vector<KEntry> &ktab = it.ktab;
+    const std::vector<int> &perm = it.perm;
     const int HG = (HT + 3) / 4;
     const int GS = (HT == 1) ? 4 : 8, NGO = GS / 4, KC_O = HT * 16 / GS;  // as in the kernel
     const int64_t CH_H = 16 * HG * 64, CH_O = (int64_t)KC_O * NGO * 64;  // float4 per chunk
     const int n_hid_chunks = m->n_chunks1 + (d->n_hidden - 1) * HT;
     const int n_out_chunks = nt_out;
-
-    // ---- input table ----
-    InputTable it;
-    build_input_table(d, K, m->n_ktab, it);
-    std::vector<KEntry> &ktab = it.ktab;
-    std::vector<int> &perm = it.perm;
     m->n_log_chunks = (it.n_log_padded + 31) / 32;
     m->n_logfast_chunks = it.eps_normal ? it.n_log_padded / 32 : 0;
     // the log block was padded to whole chunks, the real rows of its last chunk fit 8 k-pair slots and a plain chunk follows
     m->l1_short_log = (it.n_log_padded % 32 == 0 && it.n_log % 32 >= 1 && it.n_log % 32 <= 16 && m->n_log_chunks < m->n_chunks1) ? 1 : 0;
     // ---- packed weight stream ----
     // (+ one maximal chunk of zero padding: the two-half staging may read past a short last chunk)
-    std::vector<float> w((size_t)(n_hid_chunks * CH_H + n_out_chunks * CH_O + (CH_H > CH_O ? CH_H : CH_O)) * 4, 0.f);
+    const size_t n_w = (size_t)(n_hid_chunks * CH_H + n_out_chunks * CH_O + (CH_H > CH_O ? CH_H : CH_O)) * 4;
+    FV3HIP_REQUIRE(n_w * sizeof(float) < (1ull << 31), "model too large: the packed weight stream exceeds 2 GiB");
+    m->w_bytes = (unsigned int)(n_w * sizeof(float));
+    w.assign(n_w, 0.f);
     auto hid_slot = [&](int g, int s, int j, int lane, int e) -> float & {
         return w[(size_t)((g * CH_H + ((int64_t)(s * HG + j) * 64 + lane)) * 4 + e)];
     };
-    // layer 1: k = 2 * kpair + half.  The inputs' 1 / (std + eps) is folded into the row of the kernel that
-    // multiplies them (one rounding per weight, once): the kernel only subtracts the mean.
+    // layer 1: k = 2 * kpair + half, the row scaled by the input's folded 1 / (std + eps) (ktab[k].scale)
     {
         const float *W = d->hidden_kernels[0];
         for (int g = 0; g < m->n_chunks1; ++g)
@@ -2035,10 +1823,9 @@ extern "C" int fv3hip_mlp_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp_t *out)
                         }
         }
     }
-    // output layer (the outputs' denormalisation y * scale + center is folded into kernel and bias, so
-    // the accumulator already holds the physical value), tile-major: chunk t = output features 32t..32t+31 over the whole contraction;
-    // slot s holds k-pairs GS*s .. GS*s+GS-1, four per float4: k-pair m pairs hidden activations
-    // k = 32*(m/16) + rho(m%16) + 4*half (the accumulator layout of the last hidden layer)
+    // output layer (scale folded into the kernel, scale and centre into the bias), tile-major: chunk t = output features
+    // 32t..32t+31 over the whole contraction; slot s holds k-pairs GS*s .. GS*s+GS-1, four per float4: k-pair m pairs hidden
+    // activations k = 32*(m/16) + rho(m%16) + 4*half (the accumulator layout of the last hidden layer)
     {
         const float *W = d->out_kernel;
         const size_t base = (size_t)n_hid_chunks * CH_H * 4;
@@ -2051,17 +1838,11 @@ extern "C" int fv3hip_mlp_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp_t *out)
                             const int k = 32 * (mm / 16) + rho(mm % 16) + 4 * (lane >> 5);
                             const int f = 32 * t + (lane & 31);
                             if (k < width && f < F)
-                                w[base + (size_t)((t * CH_O + ((int64_t)(s * NGO + j) * 64 + lane)) * 4 + e)] =
-                                    W[(size_t)k * F + f] * (d->out_scale ? d->out_scale[f] : 1.f);
+                                w[base + (size_t)((t * CH_O + ((int64_t)(s * NGO + j) * 64 + lane)) * 4 + e)] = W[(size_t)k * F + f] * oscale(d, f);
                         }
     }
-    // ---- output table ----
-    // (hidden-output models: the table starts with the last hidden layer's features, stored to the output slot
-    // after the outputs and the residual outputs)
-    std::vector<OEntry> otab;
-    build_output_table(d, m->n_otab, 32 * m->n_hout_tiles, hout ? width : 0, otab);
     // ---- biases: [layer][tile][reg][half] ----
-    std::vector<float> bias(m->n_bias, 0.f);
+    bias.assign(m->n_bias, 0.f);
     for (int l = 0; l < d->n_hidden; ++l)
         for (int t = 0; t < HT; ++t)
             for (int r = 0; r < 16; ++r)
@@ -2073,11 +1854,8 @@ extern "C" int fv3hip_mlp_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp_t *out)
         for (int r = 0; r < 16; ++r)
             for (int hf = 0; hf < 2; ++hf) {
                 const int f = 32 * t + rho(r) + 4 * hf;
-                if (f < F)
-                    bias[(size_t)d->n_hidden * HT * 32 + (size_t)t * 32 + r * 2 + hf] =
-                        (float)((double)d->out_bias[f] * (d->out_scale ? d->out_scale[f] : 1.f) + (d->out_center ? d->out_center[f] : 0.f));
+                if (f < F) bias[(size_t)d->n_hidden * HT * 32 + (size_t)t * 32 + r * 2 + hf] = folded_out_bias(d, f);
             }
-
     if (m->smallf_n)  // [half][output f][hidden tile t][accumulator register r] -> feature k = 32 t + rho(r) + 4 half; scale folded in
         for (int hf = 0; hf < 2; ++hf)
             for (int f = 0; f < F; ++f)
@@ -2085,50 +1863,70 @@ extern "C" int fv3hip_mlp_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp_t *out)
                     for (int r = 0; r < 16; ++r) {
                         const int k = 32 * t + rho(r) + 4 * hf;
                         if (k < width)
-                            bias[(size_t)m->smallf_off + (size_t)(((hf * 4 + f) * HT + t) * 16 + r)] =
-                                d->out_kernel[(size_t)k * F + f] * (d->out_scale ? d->out_scale[f] : 1.f);
+                            bias[(size_t)m->smallf_off + (size_t)(((hf * 4 + f) * HT + t) * 16 + r)] = d->out_kernel[(size_t)k * F + f] * oscale(d, f);
                     }
-
-    // ---- plain copies for mlp_small_kernel: the same folded values, rows in table order ----
-    const int Wp = HT * 32, Fp = (nt_out > 0 ? nt_out : 1) * 32;
-    m->Wp = Wp;
-    m->Fp = Fp;
-    std::vector<float> w1((size_t)m->n_ktab * Wp, 0.f), wh((size_t)(d->n_hidden > 1 ? d->n_hidden - 1 : 1) * Wp * Wp, 0.f),
-        wo((size_t)Wp * Fp, 0.f), bh((size_t)d->n_hidden * Wp, 0.f), bo((size_t)Fp, 0.f);
-    for (size_t k = 0; k < perm.size(); ++k)
-        if (perm[k] >= 0)
-            for (int f = 0; f < width; ++f) w1[k * Wp + f] = d->hidden_kernels[0][(size_t)perm[k] * width + f] * ktab[k].scale;
-    for (int l = 1; l < d->n_hidden; ++l)
-        for (int k = 0; k < width; ++k)
-            for (int f = 0; f < width; ++f) wh[((size_t)(l - 1) * Wp + k) * Wp + f] = d->hidden_kernels[l][(size_t)k * width + f];
-    for (int l = 0; l < d->n_hidden; ++l)
-        for (int f = 0; f < width; ++f) bh[(size_t)l * Wp + f] = d->hidden_biases[l][f];
-    for (int k = 0; k < width; ++k)
-        for (int f = 0; f < F; ++f) wo[(size_t)k * Fp + f] = d->out_kernel[(size_t)k * F + f] * (d->out_scale ? d->out_scale[f] : 1.f);
-    for (int f = 0; f < F; ++f)
-        bo[f] = (float)((double)d->out_bias[f] * (d->out_scale ? d->out_scale[f] : 1.f) + (d->out_center ? d->out_center[f] : 0.f));
-
-    int rc;
-    if ((rc = upload(w1, &m->d_w1)) || (rc = upload(wh, &m->d_wh)) || (rc = upload(wo, &m->d_wo)) || (rc = upload(bh, &m->d_bh)) ||
-        (rc = upload(bo, &m->d_bo))) {
-        fv3hip_mlp_destroy(m);
-        return rc;
-    }
-    FV3HIP_REQUIRE(w.size() * sizeof(float) < (1ull << 31), "model too large: the packed weight stream exceeds 2 GiB");
-    m->w_bytes = (unsigned int)(w.size() * sizeof(float));
-    if ((rc = upload(w, &m->d_w)) || (rc = upload(ktab, &m->d_ktab)) || (rc = upload(otab, &m->d_otab)) ||
-        (rc = upload(bias, &m->d_bias))) {
-        fv3hip_mlp_destroy(m);
-        return rc;
-    }
     const size_t wb = 2 * (size_t)((CH_H > CH_O) ? CH_H : CH_O) * 16;
     // (the fast-I/O kernels add the 32 KB input tiles at launch)
     m->lds_bytes = wb + (size_t)m->n_ktab * sizeof(KEntry) +
                    (size_t)m->n_otab * (sizeof(OFast) + sizeof(OSlow) + (d->n_residual ? sizeof(ORes) : 0)) +
                    (size_t)((m->n_bias + 3) & ~3) * sizeof(float) + (size_t)(3 * kMaxSources + 3 * kMaxOutputs) * 8;
-    if (m->lds_bytes > 160 * 1024) {
+    if (m->lds_bytes > 160 * 1024) return fail(FV3HIP_EUNSUPPORTED, "model tables need %zu bytes of LDS (> 160 KiB)", m->lds_bytes);
+    return FV3HIP_OK;
+}
+
+// Everything after `new`: any failure leaves a handle that fv3hip_mlp_create destroys.
+int fill_model(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m)
+{
+    hipGetDevice(&m->device);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, m->device) == hipSuccess) m->n_cu = prop.multiProcessorCount;
+    m->relu = d->hidden_activation == FV3HIP_ACT_RELU;
+    m->n_sources = d->n_sources;
+    m->n_inputs = d->n_inputs;
+    m->K = dm.K;
+    m->width = d->n_hidden ? d->width : dm.K;  // (no hidden layer: the output layer reads the inputs)
+    m->n_hidden = d->n_hidden;
+    m->n_outputs = d->n_outputs;
+    m->F = dm.F;
+    m->n_residual = d->n_residual;
+    m->has_limits = (d->out_min || d->out_max || d->out_mask) ? 1 : 0;
+    m->flops = mlp_flops(dm.K, m->width, d->n_hidden, dm.F);
+    int rc;
+    if ((rc = m->layered ? layered_geometry(dm, m) : fused_geometry(d, dm, m))) return rc;
+    // the tables (hidden-output models: the output table starts with the last hidden layer's features)
+    InputTable it;
+    build_input_table(d, dm.K, m->n_ktab, it);
+    std::vector<OEntry> otab;
+    build_output_table(d, m->n_otab, 32 * m->n_hout_tiles, dm.hout ? m->width : 0, otab);
+    std::vector<float> w, bias;
+    if (!m->layered && (rc = pack_fused(d, dm, m, it, w, bias))) return rc;
+    // the layered path's matrices / the plain copies for mlp_small_kernel
+    PlainWeights pw;
+    build_plain_weights(d, dm.F, m->n_ktab, m->Wp, m->Fp, it, pw);
+    if ((rc = upload(pw.w1, &m->d_w1)) || (rc = upload(pw.wh, &m->d_wh)) || (rc = upload(pw.wo, &m->d_wo)) ||
+        (rc = upload(pw.bh, &m->d_bh)) || (rc = upload(pw.bo, &m->d_bo)) || (rc = upload(w, &m->d_w)) ||
+        (rc = upload(it.ktab, &m->d_ktab)) || (rc = upload(otab, &m->d_otab)) || (rc = upload(bias, &m->d_bias)))
+        return rc;
+    return FV3HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int fv3hip_mlp_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp_t *out)
+{
+    if (out) *out = nullptr;
+    MlpDims dm;
+    int rc = check_mlp_desc(d, out, kMaxSources, kMaxOutputs, dm);
+    if (rc) return rc;
+    // what the fused kernels do not hold goes layer by layer (see layered_dense_kernel)
+    const bool layered = d->n_hidden < 1 || d->width > 256 || dm.K > kMaxK || d->hidden_activation != FV3HIP_ACT_RELU;
+    if (layered && dm.hout)
+        return fail(FV3HIP_EUNSUPPORTED, "hidden-output models need 1+ ReLU hidden layers of width <= 256 and <= %d inputs", kMaxK);
+    fv3hip_mlp *m = new fv3hip_mlp();
+    m->layered = layered;
+    if ((rc = fill_model(d, dm, m))) {
         fv3hip_mlp_destroy(m);
-        return fail(FV3HIP_EUNSUPPORTED, "model tables need %zu bytes of LDS (> 160 KiB)", m->lds_bytes);
+        return rc;
     }
     *out = m;
     return FV3HIP_OK;
@@ -2186,8 +1984,8 @@ extern "C" int fv3hip_mlp_predict(fv3hip_mlp_t m, const void *const *sources, co
     FV3HIP_REQUIRE(sources && src_dtype && src_feat_stride && src_sample_stride && outputs &&
                        out_feat_stride && out_sample_stride, "null pointer");
     FV3HIP_REQUIRE(out_dtype == FV3HIP_F32 || out_dtype == FV3HIP_F64, "out_dtype must be F32 or F64");
-    MlpLaunch lp;
-    memset(&lp, 0, sizeof(lp));
+    MlpIo io;
+    memset(&io, 0, sizeof(io));
     const int dt0 = src_dtype[0];
     const bool src64 = (dt0 == FV3HIP_F64);
     FV3HIP_REQUIRE(dt0 == FV3HIP_F32 || dt0 == FV3HIP_F64, "source dtype must be F32 or F64");
@@ -2198,21 +1996,21 @@ extern "C" int fv3hip_mlp_predict(fv3hip_mlp_t m, const void *const *sources, co
                        "sample stride of source %d must be in [0, 4 GiB)", i);
         if (src_dtype[i] != dt0)
             return fail(FV3HIP_EUNSUPPORTED, "all sources must share one dtype (source 0 is %d, source %d is %d)", dt0, i, src_dtype[i]);
-        lp.src[i] = sources[i];
-        lp.src_fs[i] = src_feat_stride[i];
-        lp.src_ss[i] = src_sample_stride[i];
+        io.src[i] = sources[i];
+        io.src_fs[i] = src_feat_stride[i];
+        io.src_ss[i] = src_sample_stride[i];
     }
-    for (int i = m->n_sources; i < kMaxSources; ++i) lp.src[i] = sources[0];
+    for (int i = m->n_sources; i < kMaxSources; ++i) io.src[i] = sources[0];
     const int n_slots = m->n_outputs + m->n_residual + (m->n_hout_tiles ? 1 : 0);
     for (int j = 0; j < n_slots; ++j) {
         FV3HIP_REQUIRE(outputs[j], "output %d is null", j);
         FV3HIP_REQUIRE(out_sample_stride[j] >= 0 && out_sample_stride[j] * (out_dtype == FV3HIP_F64 ? 8 : 4) < ((int64_t)1 << 32),
                        "sample stride of output %d must be in [0, 4 GiB)", j);
-        lp.out[j] = outputs[j];
-        lp.out_fs[j] = out_feat_stride[j];
-        lp.out_ss[j] = out_sample_stride[j];
+        io.out[j] = outputs[j];
+        io.out_fs[j] = out_feat_stride[j];
+        io.out_ss[j] = out_sample_stride[j];
     }
-    if (m->layered) return predict_layered(m, lp, src64, out_dtype, n_samples, as_stream(stream));
+    if (m->layered) return predict_layered(m, io, src64, out_dtype, n_samples, as_stream(stream));
     // ---- few samples: the feature-split kernel while the big one would leave CUs without a tile (see mlp_small_kernel) ----
     {
         static const int64_t small_max = [] {
@@ -2247,28 +2045,17 @@ extern "C" int fv3hip_mlp_predict(fv3hip_mlp_t m, const void *const *sources, co
 #ifdef SMALL_STAMPS
             sp.stamps = g_small_stamps;
 #endif
-            memcpy(sp.src, lp.src, sizeof(sp.src));
-            memcpy(sp.src_fs, lp.src_fs, sizeof(sp.src_fs));
-            memcpy(sp.src_ss, lp.src_ss, sizeof(sp.src_ss));
-            memcpy(sp.out, lp.out, sizeof(sp.out));
-            memcpy(sp.out_fs, lp.out_fs, sizeof(sp.out_fs));
-            memcpy(sp.out_ss, lp.out_ss, sizeof(sp.out_ss));
+            sp.io = io;
             const int grid_s = (int)ceil_div(n_samples, (int64_t)32);
             hipStream_t st_s = as_stream(stream);
             snprintf(m->last_variant, sizeof(m->last_variant), "mlp_small_kernel<%s> (32-sample workgroups, features split over %d waves)",
                      src64 ? "true" : "false", kSmallWaves);
-            if (src64) {
-                auto kern = mlp_small_kernel<true>;
-                FV3HIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
-                hipLaunchKernelGGL(kern, dim3(grid_s), dim3(kSmallWaves * 64), lds_small, st_s, sp);
-            } else {
-                auto kern = mlp_small_kernel<false>;
-                FV3HIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
-                hipLaunchKernelGGL(kern, dim3(grid_s), dim3(kSmallWaves * 64), lds_small, st_s, sp);
-            }
-            return check_launch("mlp_small_kernel");
+            return src64 ? launch_small<true>(sp, grid_s, lds_small, st_s) : launch_small<false>(sp, grid_s, lds_small, st_s);
         }
     }
+    MlpLaunch lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.io = io;
     lp.w = static_cast<const f32x4 *>(m->d_w);
     lp.w_bytes = m->w_bytes;
     lp.ktab = static_cast<const KEntry *>(m->d_ktab);

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mlp_desc.h"
 
 namespace fv3hip {
 namespace {
@@ -56,8 +57,6 @@ constexpr int kHT = 8;          // hidden feature tiles (width 256)
 constexpr int kMaxSrc = 16;
 constexpr int kMaxOut = 32;
 constexpr int kMaxKs1 = 64;     // layer-1 k-steps (<= 1024 input features after padding every input to a multiple of 16)
-
-__host__ __device__ constexpr int rho3(int r) { return (r & 3) + 8 * (r >> 2); }
 
 // one layer-1 k-step: its 16 contraction indices are 16 consecutive features of ONE input (inputs are padded to whole
 // k-steps), so its rows are `base + (8 half + j) fs4`, fetched by bounds-checked buffer loads (a padding row reads 0)
@@ -138,7 +137,7 @@ __device__ __forceinline__ void lds_tile_tables_sync(uint32_t bias, uint32_t row
                  : "memory");
 }
 // The 16-byte epilogue: a wave's 32 x 32 output tile goes through its own LDS patch ([feature][sample], rows of 36 floats) so
-// that a lane ends up with four consecutive samples of one feature.  Write: the lane's 16 values (features rho3(r) + 4 half
+// that a lane ends up with four consecutive samples of one feature.  Write: the lane's 16 values (features rho(r) + 4 half
 // of its sample).  Read: features l / 8 + 8 i (i = 0..3), samples 4 (l % 8)..+3 -- together with the row addresses of those
 // features from a feature-ordered table (8 bytes per feature).
 constexpr int kPatchRow = 36 * 4;   // bytes
@@ -310,9 +309,9 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(const Mlp3Launch p)
         ce[(i >> 3) * 16 + 8 + (i & 7)] = p.eps[i];
     }
     for (int i = tid; i < OT * 32; i += 256) {
-        // table slot (t, rb, hf, jj) holds feature 32 t + rho3(8 rb + jj) + 4 hf
+        // table slot (t, rb, hf, jj) holds feature 32 t + rho(8 rb + jj) + 4 hf
         const int t = i >> 5, rb = (i >> 4) & 1, hf = (i >> 3) & 1, jj = i & 7;
-        const int f = FAST ? i : 32 * t + rho3(8 * rb + jj) + 4 * hf;
+        const int f = FAST ? i : 32 * t + rho(8 * rb + jj) + 4 * hf;
         const int of = p.ofeat[f], rs = p.ores[f];
         const int64_t sink = reinterpret_cast<int64_t>(p.sink);
         orow[i] = of < 0 ? sink : reinterpret_cast<int64_t>(p.out[of >> 20]) + (int64_t)(of & 0xFFFFF) * p.out_fs[of >> 20] * 4;
@@ -329,7 +328,7 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(const Mlp3Launch p)
         float *bias_f = reinterpret_cast<float *>(smem + 3 * (size_t)CHB + (p.n_hidden * kHT + OT) * 128 + p.n_ks1 * 128 + 3 * OT * 256 +
                                                   4 * (32 * kPatchRow));
         for (int i = tid; i < OT * 32; i += 256) {
-            const int t = i >> 5, fl = i & 31, hf = (fl >> 2) & 1, r = (fl & 3) + 4 * (fl >> 3);   // fl = rho3(r) + 4 hf
+            const int t = i >> 5, fl = i & 31, hf = (fl >> 2) & 1, r = (fl & 3) + 4 * (fl >> 3);   // fl = rho(r) + 4 hf
             bias_f[i] = p.bias[((p.n_hidden * kHT + t) * 2 + hf) * 16 + r];
         }
     }
@@ -599,7 +598,7 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(const Mlp3Launch p)
                     constexpr int T = decltype(t_c)::value;
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        *reinterpret_cast<global_float *>(reinterpret_cast<int64_t>(hrow) + (int64_t)(32 * T + rho3(r)) * p.hout_fs * 4) = h[T][r];
+                        *reinterpret_cast<global_float *>(reinterpret_cast<int64_t>(hrow) + (int64_t)(32 * T + rho(r)) * p.hout_fs * 4) = h[T][r];
                 });
             }
         }
@@ -801,18 +800,6 @@ struct fv3hip_mlp3 {
     std::vector<int> ks_src, ks_feat0, ks_rows, res_source;
 };
 
-namespace {
-template <typename T>
-int upload3(const std::vector<T> &v, void **dptr)
-{
-    *dptr = nullptr;
-    if (v.empty()) return FV3HIP_OK;
-    FV3HIP_CHECK_HIP(hipMalloc(dptr, v.size() * sizeof(T)));
-    FV3HIP_CHECK_HIP(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return FV3HIP_OK;
-}
-}  // namespace
-
 #ifdef MLP3_STAMPS
 static unsigned long long *g_mlp3_stamps = nullptr;
 extern "C" void fv3hip_diag_set_mlp3_stamps(void *p) { g_mlp3_stamps = static_cast<unsigned long long *>(p); }
@@ -832,20 +819,15 @@ extern "C" int64_t fv3hip_mlp3_flops_per_sample(fv3hip_mlp3_t m) { return m ? m-
 
 extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out)
 {
-    FV3HIP_REQUIRE(d && out, "null pointer");
-    *out = nullptr;
-    const int hout = d->hidden_output ? 1 : 0;
-    FV3HIP_REQUIRE(d->n_sources >= 1 && d->n_sources <= kMaxSrc && d->n_inputs >= 1, "bad counts");
-    FV3HIP_REQUIRE(d->n_outputs >= 1 || (d->n_outputs == 0 && hout), "n_outputs must be >= 1 (or 0 with hidden_output)");
-    FV3HIP_REQUIRE(d->n_outputs + d->n_residual + hout <= kMaxOut, "too many outputs");
+    if (out) *out = nullptr;
+    MlpDims dm;
+    int rc = check_mlp_desc(d, out, kMaxSrc, kMaxOut, dm);
+    if (rc) return rc;
     if (d->width != 256 || d->n_hidden < 1 || d->hidden_activation != FV3HIP_ACT_RELU)
         return fail(FV3HIP_EUNSUPPORTED, "the split-bf16 kernel takes ReLU networks of hidden width 256");
     if (d->out_min || d->out_max || d->out_mask)
         return fail(FV3HIP_EUNSUPPORTED, "the split-bf16 kernel does not implement output limits / masks");
-    const int W = 256;
-    int K = 0, F = 0;
-    for (int i = 0; i < d->n_inputs; ++i) K += d->in_nfeat[i];
-    for (int j = 0; j < d->n_outputs; ++j) F += d->out_nfeat[j];
+    const int W = 256, F = dm.F;
     const int small_out = (F >= 1 && F <= 4 && d->n_residual == 0) ? F : 0;   // (output layer on the vector ALU, see the kernel)
     const int has_out = (F > 0 && !small_out) ? 1 : 0;
     const int n_ot = has_out ? (F + 31) / 32 : 1;   // (no output layer on the matrix cores: the one-tile instantiation, that phase skipped)
@@ -867,7 +849,7 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
             if (is_log == (pass == 0)) {
                 for (int f = 0; f < d->in_nfeat[i]; ++f)
                     slots.push_back(Slot{d->in_source[i], d->in_feat_start[i] + f, d->in_center ? d->in_center[k + f] : 0.f,
-                                         d->in_scale ? (float)(1.0 / (double)d->in_scale[k + f]) : 1.f, eps, k + f});
+                                         in_rscale(d, k + f), eps, k + f});
                 while (slots.size() % 16) slots.push_back(Slot{-1, 0, 0.f, 0.f, 1.f, -1});
                 for (int f0 = 0; f0 < d->in_nfeat[i]; f0 += 16) {
                     ks_src.push_back(d->in_source[i]);
@@ -882,34 +864,31 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
     if (slots.size() / 16 > (size_t)kMaxKs1)
         return fail(FV3HIP_EUNSUPPORTED, "the split-bf16 kernel takes at most %d layer-1 k-steps of 16 input features (got %zu)", kMaxKs1,
                     slots.size() / 16);
-    {
-        fv3hip_mlp3 *m = new fv3hip_mlp3();
-        hipGetDevice(&m->device);
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, m->device) == hipSuccess) m->n_cu = prop.multiProcessorCount;
-        m->n_sources = d->n_sources;
-        m->n_outputs = d->n_outputs;
-        m->n_residual = d->n_residual;
-        m->n_hidden = d->n_hidden;
-        m->n_ks1 = (int)slots.size() / 16;
-        m->n_log_ks = n_log_slots / 16;
-        m->n_ot = n_ot;
-        m->has_out = has_out;
-        m->small_out = small_out;
-        m->hout = hout;
-        m->flops = 2 * ((int64_t)K * W + (int64_t)(d->n_hidden - 1) * W * W + (int64_t)W * F);
-        m->ks_src = ks_src;
-        m->ks_feat0 = ks_feat0;
-        m->ks_rows = ks_rows;
-        for (int r = 0; r < d->n_residual; ++r) m->res_source.push_back(d->res_source[r]);
-        *out = m;
-    }
-    fv3hip_mlp3 *m = *out;
-    const int n_ks1 = m->n_ks1;
+    const int n_ks1 = (int)slots.size() / 16;
     const int CH_H = 3 * kHT * 64, CH_O = ((3 * n_ot * 64 + 255) / 256) * 256;
     const int n_hid_chunks = n_ks1 + 16 * (d->n_hidden - 1);
     if (n_hid_chunks + (has_out ? 16 : 0) < 2)
         return fail(FV3HIP_EUNSUPPORTED, "the split-bf16 kernel needs at least two k-steps per tile");
+    // (the handle is created once nothing can refuse the model any more but the device; `*out` is set at the very end)
+    fv3hip_mlp3 *m = new fv3hip_mlp3();
+    hipGetDevice(&m->device);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, m->device) == hipSuccess) m->n_cu = prop.multiProcessorCount;
+    m->n_sources = d->n_sources;
+    m->n_outputs = d->n_outputs;
+    m->n_residual = d->n_residual;
+    m->n_hidden = d->n_hidden;
+    m->n_ks1 = n_ks1;
+    m->n_log_ks = n_log_slots / 16;
+    m->n_ot = n_ot;
+    m->has_out = has_out;
+    m->small_out = small_out;
+    m->hout = dm.hout;
+    m->flops = mlp_flops(dm.K, W, d->n_hidden, F);
+    m->ks_src = ks_src;
+    m->ks_feat0 = ks_feat0;
+    m->ks_rows = ks_rows;
+    m->res_source.assign(d->res_source, d->res_source + d->n_residual);
     std::vector<unsigned short> w(((size_t)n_hid_chunks * CH_H + (size_t)(has_out ? 16 : 0) * CH_O) * 8, 0);
     auto put = [&](size_t chunk_base_f4, int nt, int t, int lane, int j, float value) {
         float r = value;
@@ -930,7 +909,7 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
                 }
     // hidden layers and the output layer: k-slot (ks, half, j) = feature 32 (ks / 2) + rho(8 (ks % 2) + j) + 4 half of the
     // previous layer (its accumulator layout)
-    auto kfeat = [](int ks, int hf, int j) { return 32 * (ks / 2) + rho3(8 * (ks % 2) + j) + 4 * hf; };
+    auto kfeat = [](int ks, int hf, int j) { return 32 * (ks / 2) + rho(8 * (ks % 2) + j) + 4 * hf; };
     for (int l = 1; l < d->n_hidden; ++l)
         for (int ks = 0; ks < 16; ++ks)
             for (int t = 0; t < kHT; ++t)
@@ -944,20 +923,18 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
                 for (int j = 0; j < 8; ++j) {
                     const int f = 32 * t + (lane & 31);
                     put((size_t)n_hid_chunks * CH_H + (size_t)ks * CH_O, n_ot, t, lane, j,
-                        f < F ? d->out_kernel[(size_t)kfeat(ks, lane >> 5, j) * F + f] * (d->out_scale ? d->out_scale[f] : 1.f) : 0.f);
+                        f < F ? d->out_kernel[(size_t)kfeat(ks, lane >> 5, j) * F + f] * oscale(d, f) : 0.f);
                 }
     std::vector<float> bias((size_t)d->n_hidden * kHT * 32 + (size_t)n_ot * 32, 0.f);
     for (int l = 0; l < d->n_hidden; ++l)
         for (int t = 0; t < kHT; ++t)
             for (int r = 0; r < 16; ++r)
-                for (int hf = 0; hf < 2; ++hf) bias[(((size_t)l * kHT + t) * 2 + hf) * 16 + r] = d->hidden_biases[l][32 * t + rho3(r) + 4 * hf];
+                for (int hf = 0; hf < 2; ++hf) bias[(((size_t)l * kHT + t) * 2 + hf) * 16 + r] = d->hidden_biases[l][32 * t + rho(r) + 4 * hf];
     for (int t = 0; t < n_ot; ++t)
         for (int r = 0; r < 16; ++r)
             for (int hf = 0; hf < 2; ++hf) {
-                const int f = 32 * t + rho3(r) + 4 * hf;
-                if (f < F)
-                    bias[(((size_t)d->n_hidden * kHT + t) * 2 + hf) * 16 + r] =
-                        (float)((double)d->out_bias[f] * (d->out_scale ? d->out_scale[f] : 1.f) + (d->out_center ? d->out_center[f] : 0.f));
+                const int f = 32 * t + rho(r) + 4 * hf;
+                if (f < F) bias[(((size_t)d->n_hidden * kHT + t) * 2 + hf) * 16 + r] = folded_out_bias(d, f);
             }
     std::vector<float> center(slots.size()), eps(slots.size());
     for (size_t i = 0; i < slots.size(); ++i) {
@@ -970,9 +947,7 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
     {
         int f = 0;
         for (int j = 0; j < d->n_outputs; ++j) {
-            int res = -1;
-            for (int r = 0; r < d->n_residual; ++r)
-                if (d->res_output[r] == j) res = ((d->n_outputs + r) << 8) | d->res_source[r];
+            const int res = residual_code(d, j);
             for (int q = 0; q < d->out_nfeat[j]; ++q, ++f) {
                 ofeat[f] = (j << 20) | q;
                 ores[f] = res;
@@ -980,22 +955,18 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
         }
     }
     std::vector<float> wsmall;
-    if (small_out) {   // [tile][output c][half][register r] <- out_kernel[feature 32 t + rho3(r) + 4 half][c] * scale_c; then the biases
+    if (small_out) {   // [tile][output c][half][register r] <- out_kernel[feature 32 t + rho(r) + 4 half][c] * scale_c; then the biases
         wsmall.assign(8 * 4 * 2 * 16 + 4, 0.f);
         for (int t = 0; t < kHT; ++t)
             for (int c = 0; c < F; ++c)
                 for (int hf = 0; hf < 2; ++hf)
                     for (int r = 0; r < 16; ++r)
-                        wsmall[((t * 4 + c) * 2 + hf) * 16 + r] =
-                            d->out_kernel[(size_t)(32 * t + rho3(r) + 4 * hf) * F + c] * (d->out_scale ? d->out_scale[c] : 1.f);
-        for (int c = 0; c < F; ++c)
-            wsmall[8 * 4 * 2 * 16 + c] = (float)((double)d->out_bias[c] * (d->out_scale ? d->out_scale[c] : 1.f) + (d->out_center ? d->out_center[c] : 0.f));
+                        wsmall[((t * 4 + c) * 2 + hf) * 16 + r] = d->out_kernel[(size_t)(32 * t + rho(r) + 4 * hf) * F + c] * oscale(d, c);
+        for (int c = 0; c < F; ++c) wsmall[8 * 4 * 2 * 16 + c] = folded_out_bias(d, c);
     }
-    int rc;
-    if ((rc = upload3(wsmall, &m->d_wsmall)) || (rc = upload3(w, &m->d_w)) || (rc = upload3(bias, &m->d_bias)) || (rc = upload3(center, &m->d_center)) ||
-        (rc = upload3(eps, &m->d_eps)) || (rc = upload3(ofeat, &m->d_ofeat)) || (rc = upload3(ores, &m->d_ores))) {
+    if ((rc = upload(wsmall, &m->d_wsmall)) || (rc = upload(w, &m->d_w)) || (rc = upload(bias, &m->d_bias)) || (rc = upload(center, &m->d_center)) ||
+        (rc = upload(eps, &m->d_eps)) || (rc = upload(ofeat, &m->d_ofeat)) || (rc = upload(ores, &m->d_ores))) {
         fv3hip_mlp3_destroy(m);
-        *out = nullptr;
         return rc;
     }
     const size_t ch_max = (size_t)((CH_H > CH_O) ? CH_H : CH_O);
@@ -1007,10 +978,11 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
         m->lds_fast += 8 * 4 * 2 * 16 * 4 + 16;
     }
     if (m->lds_bytes > 160 * 1024) {
+        const size_t need = m->lds_bytes;
         fv3hip_mlp3_destroy(m);
-        *out = nullptr;
-        return fail(FV3HIP_EUNSUPPORTED, "the split-bf16 kernel's tables need %zu bytes of LDS (> 160 KiB)", m->lds_bytes);
+        return fail(FV3HIP_EUNSUPPORTED, "the split-bf16 kernel's tables need %zu bytes of LDS (> 160 KiB)", need);
     }
+    *out = m;
     return FV3HIP_OK;
 }
 
