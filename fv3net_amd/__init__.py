@@ -10,6 +10,10 @@ package is the thin Python host side that mirrors the reference's own interfaces
 ``fv3net_amd.thermo``       the three ``vcm.calc.thermo`` pressure helpers on the path
 ``fv3net_amd.fit``          ``fv3fit`` Predictor API, io registry, dense predictor
 ``fv3net_amd.emulation``    ``emulation`` microphysics hook
+``fv3net_amd.select``       ``vcm.select`` zonal / meridional means over bins
+``fv3net_amd.histogram``    ``vcm.histogram`` / ``vcm.histogram2d`` (explicit edges)
+``fv3net_amd.calc``         ``vcm.calc.calc`` ``local_time`` and ``weighted_average``
+``fv3net_amd.diagnostics``  the offline report's ``compute_diagnostics``, streaming
 ``fv3net_amd.ops``          array-level entry points (torch device tensors in / out)
 ========================  ==========================================================
 

@@ -309,6 +309,12 @@ SIGNATURES = {
     "fv3hip_reservoir_get_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fv3hip_reservoir_set_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fv3hip_reservoir_reset_state": (c_int, [c_void_p, c_void_p]),
+    "fv3hip_group_sums_chunk": (c_int, []),
+    "fv3hip_group_sums_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "fv3hip_group_sums": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p,
+                                  c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fv3hip_histogram": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "fv3hip_histogram2d": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "fv3hip_timer_create": (c_int, [POINTER(c_void_p)]),
     "fv3hip_timer_start": (c_int, [c_void_p, c_void_p]),
     "fv3hip_timer_stop": (c_int, [c_void_p, c_void_p]),

@@ -984,6 +984,133 @@ def _scratch_rows(dev, n: int, numel: int) -> list:
     return [have[i * numel:(i + 1) * numel] for i in range(n)]
 
 
+class GroupPlan:
+    """Which cells ``group_sums`` adds into which group: ``order`` (int32 cell ids ``batch * n_inner + i``, sorted by group
+    with a stable sort), ``start`` (int64 [n_groups + 1]) and the work items the groups are cut into (at most
+    ``group_sums_chunk()`` cells each) -- all on the device; ``counts`` (cells per group) is a host array."""
+
+    __slots__ = ("n_batch", "n_inner", "n_groups", "n_items", "order", "start", "item_group", "item_chunk", "group_item", "counts")
+
+    def __init__(self, **kwargs):
+        for k, v in kwargs.items():
+            setattr(self, k, v)
+
+
+def group_sums_chunk() -> int:
+    """Cells per work item of ``group_sums`` (``fv3hip_group_sums_chunk``)."""
+    return int(_lib.load().fv3hip_group_sums_chunk())
+
+
+def group_plan(group_id: torch.Tensor, n_groups: int) -> GroupPlan:
+    """The plan of ``group_sums`` for the integer group ids ``group_id`` [n_batch, n_inner]; an id < 0 or >= ``n_groups``
+    leaves the cell in no group.  The sort is torch's stable device sort (index plumbing, no field arithmetic); the cells
+    per group come to the host once, to cut the groups into work items."""
+    dev = _require_device(group_id)
+    if group_id.dim() != 2 or group_id.dtype not in (torch.int32, torch.int64):
+        raise ValueError("group_id must be an int32 / int64 tensor [n_batch, n_inner]")
+    n_groups = int(n_groups)
+    n_batch, n_inner = int(group_id.shape[0]), int(group_id.shape[1])
+    if n_groups < 0 or n_batch * n_inner > 0x7FFFFFFF:
+        raise ValueError("n_groups must not be negative, and cell ids must fit int32")
+    gid = group_id.reshape(-1).to(torch.int64)
+    key = torch.where((gid >= 0) & (gid < n_groups), gid, torch.full_like(gid, n_groups))
+    _, idx = torch.sort(key, stable=True)
+    counts = torch.bincount(key, minlength=n_groups + 1)[:n_groups].cpu().numpy().astype(np.int64)
+    start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    chunk = group_sums_chunk()
+    per_group = -(-counts // chunk)
+    group_item = np.concatenate([[0], np.cumsum(per_group)]).astype(np.int64)
+    n_items = int(group_item[-1])
+    item_group = np.repeat(np.arange(n_groups, dtype=np.int32), per_group)
+    item_chunk = (np.arange(n_items, dtype=np.int64) - group_item[:-1][item_group]).astype(np.int32)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    return GroupPlan(n_batch=n_batch, n_inner=n_inner, n_groups=n_groups, n_items=n_items,
+                     order=idx[:int(start[-1])].to(torch.int32).contiguous(), start=up(start), item_group=up(item_group),
+                     item_chunk=up(item_chunk), group_item=up(group_item), counts=counts)
+
+
+def group_sums(a: torch.Tensor, b: Optional[torch.Tensor], weights: Optional[torch.Tensor], plan: GroupPlan,
+               z_axis: Optional[int] = None) -> torch.Tensor:
+    """float64 [10, n_groups, nz] sums over the cells of each group of ``plan`` (``fv3hip_group_sums``): with ``d = a - b``,
+    0: sum w, 1: sum w where a is not NaN, 2: sum w a, 3: sum (w a) a, 4-6: the same for ``b``, 7-9: for ``d``; NaN terms
+    are skipped (``nansum``), ``b`` None leaves 4-9 zero, ``weights`` None is 1.  ``a`` (and ``b``) view as
+    [n_batch, nz, n_inner] around ``z_axis`` (None: no level axis, nz = 1); ``weights`` as [n_batch, n_inner].  Bitwise
+    identical from run to run."""
+    tensors = [t for t in (a, b, weights) if t is not None]
+    dev = _require_device(plan.order, *tensors)
+    code = _float_code(a)
+    a = a.contiguous()
+    if z_axis is None:
+        nb, nz, ni = plan.n_batch, 1, plan.n_inner
+        if a.numel() != nb * ni:
+            raise ValueError(f"the field has {a.numel()} cells, the plan {nb} x {ni}")
+    else:
+        _, nb, nz, ni = _column_view(a, z_axis)
+        if (nb, ni) != (plan.n_batch, plan.n_inner):
+            raise ValueError(f"the field views as [{nb}, {nz}, {ni}], the plan is for [{plan.n_batch}, {plan.n_inner}] cells")
+    if b is not None:
+        if tuple(b.shape) != tuple(a.shape):
+            raise ValueError("a and b must have the same shape")
+        b = cast(b, a.dtype).contiguous()
+    w_code = _lib.F64
+    if weights is not None:
+        w_code = _float_code(weights)
+        weights = weights.contiguous()
+        if weights.numel() != nb * ni:
+            raise ValueError(f"weights have {weights.numel()} cells, the plan {nb} x {ni}")
+    out = torch.empty((10, plan.n_groups, nz), dtype=torch.float64, device=dev)
+    nbytes = int(_lib.load().fv3hip_group_sums_workspace_bytes(plan.n_items, nz))
+    ws = _workspace(dev, nbytes)
+    _lib.call_on(dev, "fv3hip_group_sums", _ptr(a), _ptr(b), code, _ptr(weights), w_code, nb, nz, ni, _ptr(plan.order),
+                 plan.order.numel(), _ptr(plan.start), plan.n_groups, _ptr(plan.item_group), _ptr(plan.item_chunk), plan.n_items,
+                 _ptr(plan.group_item), _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
+    return out
+
+
+def _edges(edges: torch.Tensor, dev) -> torch.Tensor:
+    if edges.dim() != 1 or edges.numel() < 2:
+        raise ValueError("bin edges must be a 1-D array of at least two values")
+    return cast(edges.to(dev), torch.float64).contiguous()
+
+
+def histogram_counts(x: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
+    """``np.histogram(x, bins=edges)[0]`` for explicit edges (a device tensor), int64 [len(edges) - 1]: bins are
+    ``edges[i] <= x < edges[i + 1]``, the last one closed; NaN and values outside are dropped.  Up to 4096 bins."""
+    dev = _require_device(x, edges)
+    x = _as_float(x).contiguous()
+    edges = _edges(edges, dev)
+    n_bins = int(edges.numel()) - 1
+    if n_bins > 4096:
+        raise ValueError(f"at most 4096 bins, got {n_bins}")
+    counts = torch.empty(n_bins, dtype=torch.int64, device=dev)
+    _lib.call_on(dev, "fv3hip_histogram", _ptr(x), _float_code(x), x.numel(), _ptr(edges), n_bins, _ptr(counts), _stream(dev))
+    return counts
+
+
+def histogram2d_counts(x: torch.Tensor, y: torch.Tensor, xedges: torch.Tensor, yedges: torch.Tensor) -> torch.Tensor:
+    """``np.histogram2d(x.ravel(), y.ravel(), bins=[xedges, yedges])[0]`` as int64 [nx, ny]; a pair is dropped if either
+    member is NaN or outside its edges.  Up to 128 x 128 bins."""
+    dev = _require_device(x, y, xedges, yedges)
+    if x.numel() != y.numel():
+        raise ValueError("x and y must have the same number of values")
+    x, y = _as_float(x), _as_float(y)
+    dt = _promoted(x, y)
+    x, y = cast(x, dt).contiguous(), cast(y, dt).contiguous()
+    xedges, yedges = _edges(xedges, dev), _edges(yedges, dev)
+    nx, ny = int(xedges.numel()) - 1, int(yedges.numel()) - 1
+    if nx > 128 or ny > 128:
+        raise ValueError(f"at most 128 x 128 bins, got {nx} x {ny}")
+    counts = torch.empty((nx, ny), dtype=torch.int64, device=dev)
+    _lib.call_on(dev, "fv3hip_histogram2d", _ptr(x), _ptr(y), _float_code(x), x.numel(), _ptr(xedges), nx, _ptr(yedges), ny,
+                 _ptr(counts), _stream(dev))
+    return counts
+
+
+def _as_float(t: torch.Tensor) -> torch.Tensor:
+    """Integer data as float64 (what numpy's comparison against float64 edges sees); float data as it is."""
+    return t if t.dtype in (torch.float32, torch.float64) else cast(t, torch.float64)
+
+
 class HipTimer:
     """HIP events recorded on torch's current stream (used by bench.py)."""
 

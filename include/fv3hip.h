@@ -865,6 +865,47 @@ int fv3hip_level_fill(const void *emul, int emul_dtype, const void *src, int src
                       double fill_value, int64_t n0, int64_t n1, int64_t start, int64_t stop,
                       void *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Reductions of the offline diagnostics (additive to ABI v3)
+ * ------------------------------------------------------------------------------------------ */
+
+/*
+ * Sums per (group, level) over an indexed cell list: the domain means, zonal / meridional bins and the diurnal cycle of
+ * workflows/diagnostics/fv3net/diagnostics/offline/compute_diagnostics.py (with _shared/transform.py:288-318 and
+ * vcm/select.py:18-77).
+ *   a, b      [n_batch][nz][n_inner] of `dtype` (b may be NULL); weights [n_batch][n_inner] of `w_dtype` (NULL: 1)
+ *   order     [n_order] int32 cell ids batch * n_inner + i, sorted by group (stable); start [n_groups + 1]: group g owns
+ *             order[start[g] : start[g + 1]); cells in no group are absent
+ *   items     work item k reduces cells [start[g] + c * CHUNK, min(that + CHUNK, start[g + 1])) of g = item_group[k],
+ *             c = item_chunk[k] (CHUNK = fv3hip_group_sums_chunk()); the items of a group are consecutive, in chunk
+ *             order: group g owns items [group_item[g], group_item[g + 1])
+ *   sums      double [10][n_groups][nz]; in float64 with d = a - b and every product rounded once:
+ *             0: sum w   1: sum w over a not NaN   2: sum w a   3: sum (w a) a   4-6: as 1-3 for b   7-9: as 1-3 for d
+ *             A term enters its sum unless it is NaN (an infinity stays); with b NULL 4-9 are 0.
+ *   workspace at least fv3hip_group_sums_workspace_bytes(n_items, nz) bytes
+ * All index arrays are device memory.  One workgroup per (item, level) with a fixed reduction tree, a second kernel adds
+ * a group's items in order: no floating-point atomics, results are bitwise identical from run to run.
+ */
+int fv3hip_group_sums_chunk(void);
+size_t fv3hip_group_sums_workspace_bytes(int64_t n_items, int nz);
+int fv3hip_group_sums(const void *a, const void *b, int dtype, const void *weights, int w_dtype,
+                      int64_t n_batch, int nz, int64_t n_inner, const int32_t *order,
+                      int64_t n_order, const int64_t *start, int64_t n_groups,
+                      const int32_t *item_group, const int32_t *item_chunk, int64_t n_items,
+                      const int64_t *group_item, double *sums, void *workspace,
+                      size_t workspace_bytes, void *stream);
+/*
+ * np.histogram / np.histogram2d with array bins (vcm/calc/histogram.py): x (and y) [n] of `dtype`, converted to double;
+ * DEVICE float64 edges [n_bins + 1]; bin i holds edges[i] <= v < edges[i + 1], the last bin also v == edges[n_bins]; NaN
+ * and values outside are dropped (in 2-D the pair).  counts: int64 [n_bins] / [nx_bins][ny_bins], zeroed by the call.
+ * Up to 4096 bins, in 2-D 128 x 128; more is FV3HIP_EINVAL.
+ */
+int fv3hip_histogram(const void *x, int dtype, int64_t n, const double *edges, int n_bins,
+                     int64_t *counts, void *stream);
+int fv3hip_histogram2d(const void *x, const void *y, int dtype, int64_t n, const double *xedges,
+                       int nx_bins, const double *yedges, int ny_bins, int64_t *counts,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
