@@ -301,6 +301,7 @@ SIGNATURES = {
     ),
     "fv3hip_reservoir_create": (c_int, [POINTER(ReservoirDesc), POINTER(c_void_p)]),
     "fv3hip_reservoir_destroy": (c_int, [c_void_p]),
+    "fv3hip_reservoir_plan": (c_int, [c_void_p, POINTER(c_int64)]),
     "fv3hip_reservoir_increment": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), c_void_p]),
     "fv3hip_reservoir_predict": (
         c_int,

@@ -611,6 +611,21 @@ extern "C" int fv3hip_reservoir_destroy(fv3hip_reservoir_t m)
     return FV3HIP_OK;
 }
 
+extern "C" int fv3hip_reservoir_plan(fv3hip_reservoir_t m, int64_t out[8])
+{
+    FV3HIP_REQUIRE(m, "null reservoir handle");
+    FV3HIP_REQUIRE(out, "null plan");
+    out[0] = m->dense ? 1 : 0;
+    out[1] = m->in_sb;
+    out[2] = m->in_chunk;
+    out[3] = m->in_split;
+    out[4] = m->out_chunk;
+    out[5] = m->out_split;
+    out[6] = m->ldw;
+    out[7] = m->ldc;
+    return FV3HIP_OK;
+}
+
 extern "C" int fv3hip_reservoir_increment(fv3hip_reservoir_t m, const void *const *sources, const int *src_dtype,
                                           const int64_t *strides, void *stream)
 {

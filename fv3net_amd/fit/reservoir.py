@@ -11,7 +11,9 @@ Two behaviours of the reference are kept on purpose: the 
 of the state when ``square_half_hidden_state`` is set (``square_even_terms(state, axis=0)``, model.py:225) where the hybrid
 model squares even state elements (axis -1, model.py:122); and a ``scale-spatial-concat-z`` transformer rejects inputs
 whose (x, y, z) extent differs from its own.  ``get_model_from_subdomain`` gives the sub-model a copy of the parent's
-state row instead of sharing the parent's reservoir object.
+state row instead of sharing the parent's reservoir object.  ``w_in_storage`` (``reservoir.WIN_AUTO`` / ``WIN_DENSE`` /
+``WIN_CSR``): dense storage, which AUTO picks from half the entries of ``W_in`` stored up, spreads a non-finite input over every
+state row of its subdomain where scipy's product reaches only the rows with a stored weight.
 """
 import os
 from typing import Hashable, List, Optional, Sequence

@@ -404,7 +404,12 @@ class ReservoirModel:
     """Device handle of a reservoir model (``fv3hip_reservoir_t``): state, weights and readout on one GPU.
 
     ``divider``: the input rank divider (with overlap); ``w_in`` [state, input_size] and ``w_res`` [state, state] as
-    ``SparseMatrix``; ``coefficients`` [subdomain, state + n_hybrid, n_out] and ``intercepts`` [subdomain, n_out]."""
+    ``SparseMatrix``; ``coefficients`` [subdomain, state + n_hybrid, n_out] and ``intercepts`` [subdomain, n_out].
+
+    ``w_in_storage``: ``WIN_CSR`` walks the stored entries of ``W_in`` as scipy's product does; ``WIN_DENSE`` multiplies the
+    zero-padded matrix, so a non-finite input makes every state row of its subdomain NaN, not only the rows with a stored
+    weight in that column.  ``WIN_AUTO`` picks dense storage from half the entries stored up and
+    inherits this difference."""
 
     def __init__(self, divider: RankXYDivider, input_transformer, output_transformer, w_in: SparseMatrix,
                  w_res: SparseMatrix, coefficients: np.ndarray, intercepts: np.ndarray, square: int = SQUARE_NONE,
@@ -482,6 +487,16 @@ class ReservoirModel:
         return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors]),
                 (ctypes.c_int * n)(*[_lib.F64 if t.dtype == torch.float64 else _lib.F32 for t in tensors]),
                 (ctypes.c_int64 * (3 * n))(*strides))
+
+    _PLAN_FIELDS = ("dense", "in_sb", "in_chunk", "in_split", "out_chunk", "out_split", "ldw", "ldc")
+
+    def plan(self) -> dict:
+        """The launch plan the library chose at creation (read-only): whether ``W_in`` is dense, the subdomains per wave,
+        rows per slice and slice count of the dense input product, rows per slice and slice count of the readout, and the
+        padded ``W_in`` row count and readout row length."""
+        out = (ctypes.c_int64 * 8)()
+        _lib.call("fv3hip_reservoir_plan", self._handle, out)
+        return dict(zip(self._PLAN_FIELDS, (int(v) for v in out)))
 
     def increment(self, inputs: Sequence[torch.Tensor]) -> None:
         """One ``increment_state`` from device (x, y, z) arrays over the overlapped rank extent (shapes checked by the

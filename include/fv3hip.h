@@ -641,6 +641,10 @@ typedef struct fv3hip_reservoir *fv3hip_reservoir_t;
 
 int fv3hip_reservoir_create(const fv3hip_reservoir_desc_t *desc, fv3hip_reservoir_t *out);
 int fv3hip_reservoir_destroy(fv3hip_reservoir_t model);
+/* The launch plan chosen at creation, read-only (host values, no HIP call): out = {dense W_in storage (0 / 1), subdomains
+ * per wave of the dense product, input rows per slice, input slices, readout rows per slice, readout slices, padded W_in
+ * row count, padded readout row length}.  With CSR storage the four W_in entries are 1, 0, 1 and 0. */
+int fv3hip_reservoir_plan(fv3hip_reservoir_t model, int64_t out[8]);
 /* One reservoir step.  sources[v]: input variable v, dtype src_dtype[v] (F32/F64), element (x, y, z) of the overlapped
  * rank extent at x * strides[3v] + y * strides[3v+1] + z * strides[3v+2].  No host synchronisation. */
 int fv3hip_reservoir_increment(fv3hip_reservoir_t model, const void *const *sources, const int *src_dtype,

@@ -231,3 +231,11 @@ def test_create_refuses_transformer_mismatch():
     d.input.kind = 7
     assert lib.fv3hip_reservoir_create(ctypes.byref(d), ctypes.byref(h)) == _lib.EINVAL
     assert lib.fv3hip_reservoir_create(None, ctypes.byref(h)) == _lib.EINVAL
+
+
+def test_plan_refuses_null_arguments():
+    """fv3hip_reservoir_plan reads host values only; a null handle or a null output is EINVAL, not a crash."""
+    lib = _lib.load()
+    out = (ctypes.c_int64 * 8)()
+    assert lib.fv3hip_reservoir_plan(None, out) == _lib.EINVAL
+    assert b"null reservoir handle" in lib.fv3hip_last_error()
