@@ -217,6 +217,73 @@ __device__ __forceinline__ void ppm_limiters1(float dm, float a1, float &a2, flo
     }
 }
 
+// dc(k) for 2 <= k <= km-1 (mappm.f90:658-668): dpa..dpc = dp(k-1..k+1), qa..qc = q(k-1..k+1)
+__device__ __forceinline__ float ppm_dc(float dpa, float dpb, float dpc, float qa, float qb, float qc)
+{
+    const float d4b = dpa + dpb, d4c = dpb + dpc;  // d4(k), d4(k+1)
+    const float c1 = (dpa + 0.5f * dpb) / d4c;
+    const float c2 = (dpc + 0.5f * dpb) / d4b;
+    const float df2 = dpb * (c1 * (qc - qb) + c2 * (qb - qa)) / (d4b + dpc);
+    return f_sign(f_min3(fabsf(df2), f_max3(qa, qb, qc) - qb, qb - f_min3(qa, qb, qc)), df2);
+}
+
+// a4(2,k) for 3 <= k <= km-1 (mappm.f90:674-683): dpz..dpc = dp(k-2..k+1), qa = q(k-1), qb = q(k), dca = dc(k-1), dcb = dc(k)
+__device__ __forceinline__ float ppm_al(float dpz, float dpa, float dpb, float dpc, float qa, float qb, float dca, float dcb)
+{
+    const float d4a = dpz + dpa, d4b = dpa + dpb, d4c = dpb + dpc;  // d4(k-1), d4(k), d4(k+1)
+    const float c1 = (qb - qa) * dpa / d4b;
+    const float a1 = d4a / (d4b + dpa);
+    const float a2 = d4c / (d4b + dpb);
+    return qa + c1 + 2.f / (d4a + d4c) * (dpb * (c1 * (a1 - a2) + a2 * dca) - dpa * a1 * dcb);
+}
+
+// Top boundary (mappm.f90:689-725): al1 = a4(2,1), al2 = a4(2,2) and dc1 = dc(1) from d1, d2 = dp(1), dp(2), q1, q2 = q(1), q(2)
+// and al3 = a4(2,3)
+__device__ __forceinline__ void ppm_top(float d1, float d2, float q1, float q2, float al3, int iv, float &al1, float &al2,
+                                        float &dc1)
+{
+    const float qm = (d2 * q1 + d1 * q2) / (d1 + d2);
+    const float dq = 2.f * (q2 - q1) / (d1 + d2);
+    const float c1 = 4.f * (al3 - qm - d2 * dq) / (d2 * (2.f * d2 * d2 + d1 * (d2 + 3.f * d1)));
+    const float c3 = dq - 0.5f * c1 * (d2 * (5.f * d1 + d2) - 3.f * d1 * d1);
+    al2 = qm - 0.25f * c1 * d1 * d2 * (d2 + 3.f * d1);
+    al1 = d1 * (2.f * c1 * (d1 * d1) - c3) + al2;
+    al2 = f_max2(al2, f_min2(q1, q2));
+    al2 = f_min2(al2, f_max2(q1, q2));
+    dc1 = 0.5f * (al2 - q1);
+    if (iv == 0) {
+        al1 = f_max2(0.f, al1);
+        al2 = f_max2(0.f, al2);
+    } else if (iv == -1) {
+        if (al1 * q1 <= 0.f) al1 = 0.f;
+    } else if (iv == 2 || iv == -2) {
+        al1 = q1;
+        // a4(3,i,1) = a4(1,i,1) is overwritten afterwards by a4(3,i,1) = a4(2,i,2)
+    }
+}
+
+// Bottom boundary (mappm.f90:729-761): alk = a4(2,km), ark = a4(3,km) and dck = dc(km) from d1, d2 = dp(km), dp(km-1),
+// qk, qk1 = q(km), q(km-1) and al_km1 = a4(2,km-1)
+__device__ __forceinline__ void ppm_bottom(float d1, float d2, float qk, float qk1, float al_km1, int iv, float &alk, float &ark,
+                                           float &dck)
+{
+    const float qm = (d2 * qk + d1 * qk1) / (d1 + d2);
+    const float dq = 2.f * (qk1 - qk) / (d1 + d2);
+    const float c1 = (al_km1 - qm - d2 * dq) / (d2 * (2.f * d2 * d2 + d1 * (d2 + 3.f * d1)));
+    const float c3 = dq - 2.0f * c1 * (d2 * (5.f * d1 + d2) - 3.f * d1 * d1);
+    alk = qm - c1 * d1 * d2 * (d2 + 3.f * d1);
+    ark = d1 * (8.f * c1 * (d1 * d1) - c3) + alk;
+    alk = f_max2(alk, f_min2(qk, qk1));
+    alk = f_min2(alk, f_max2(qk, qk1));
+    dck = 0.5f * (qk - alk);
+    if (iv == 0) {
+        alk = f_max2(0.f, alk);
+        ark = f_max2(0.f, ark);
+    } else if (iv < 0) {
+        if (qk * ark <= 0.f) ark = 0.f;
+    }
+}
+
 // element (column, level k) of an array with `nlev` levels lives at base + (k-1)*ks
 struct ColumnAddr {
     int64_t ks, o_pe1, o_q1, o_pe2, o_q2;
@@ -501,8 +568,6 @@ __device__ __noinline__ void mappm_column_exact(const Tin *__restrict__ pe1_, co
     auto Q = [&](int k) { return (float)q1_[o_q1 + (int64_t)(k - 1) * ks]; };
     auto PE2 = [&](int k) { return (float)pe2_[o_pe2 + (int64_t)(k - 1) * addr.ks2]; };
     auto DP = [&](int k) { return PE1(k + 1) - PE1(k); };          // dp1(i,k)
-    auto DELQ = [&](int k) { return Q(k + 1) - Q(k); };            // delq(i,k)
-    auto D4 = [&](int k) { return DP(k - 1) + DP(k); };            // d4(i,k)
 
     const int64_t plane = (int64_t)km * ws_cols;
     float *AL = ws + 0 * plane + lc, *AR = ws + 1 * plane + lc, *A6 = ws + 2 * plane + lc,
@@ -514,65 +579,20 @@ __device__ __noinline__ void mappm_column_exact(const Tin *__restrict__ pe1_, co
         cs_profile_column(Q, DP, AL, AR, A6, DC, H2, ws_cols, km, iv, kord);
     } else {
     // ---- ppm_profile (mappm.f90:651-683) ----
-    for (int k = 2; k <= km1; ++k) {
-        const float dpk = DP(k), d4k = D4(k), d4k1 = D4(k + 1);
-        const float c1 = (DP(k - 1) + 0.5f * dpk) / d4k1;
-        const float c2 = (DP(k + 1) + 0.5f * dpk) / d4k;
-        const float df2 = dpk * (c1 * DELQ(k) + c2 * DELQ(k - 1)) / (d4k + DP(k + 1));
-        const float qm1 = Q(k - 1), q0 = Q(k), qp1 = Q(k + 1);
-        W_(DC, k) = f_sign(f_min3(fabsf(df2), f_max3(qm1, q0, qp1) - q0, q0 - f_min3(qm1, q0, qp1)), df2);
-    }
-    for (int k = 3; k <= km1; ++k) {
-        const float d4k = D4(k);
-        const float c1 = DELQ(k - 1) * DP(k - 1) / d4k;
-        const float a1 = D4(k - 1) / (d4k + DP(k - 1));
-        const float a2 = D4(k + 1) / (d4k + DP(k));
-        W_(AL, k) = Q(k - 1) + c1 +
-                    2.f / (D4(k - 1) + D4(k + 1)) *
-                        (DP(k) * (c1 * (a1 - a2) + a2 * W_(DC, k - 1)) - DP(k - 1) * a1 * W_(DC, k));
-    }
+    for (int k = 2; k <= km1; ++k) W_(DC, k) = ppm_dc(DP(k - 1), DP(k), DP(k + 1), Q(k - 1), Q(k), Q(k + 1));
+    for (int k = 3; k <= km1; ++k)
+        W_(AL, k) = ppm_al(DP(k - 2), DP(k - 1), DP(k), DP(k + 1), Q(k - 1), Q(k), W_(DC, k - 1), W_(DC, k));
     {
-        // Top (mappm.f90:689-725)
-        const float d1 = DP(1), d2 = DP(2);
-        const float qm = (d2 * Q(1) + d1 * Q(2)) / (d1 + d2);
-        const float dq = 2.f * (Q(2) - Q(1)) / (d1 + d2);
-        const float c1 = 4.f * (W_(AL, 3) - qm - d2 * dq) / (d2 * (2.f * d2 * d2 + d1 * (d2 + 3.f * d1)));
-        const float c3 = dq - 0.5f * c1 * (d2 * (5.f * d1 + d2) - 3.f * d1 * d1);
-        float al2 = qm - 0.25f * c1 * d1 * d2 * (d2 + 3.f * d1);
-        float al1 = d1 * (2.f * c1 * (d1 * d1) - c3) + al2;
-        al2 = f_max2(al2, f_min2(Q(1), Q(2)));
-        al2 = f_min2(al2, f_max2(Q(1), Q(2)));
-        W_(DC, 1) = 0.5f * (al2 - Q(1));
-        if (iv == 0) {
-            al1 = f_max2(0.f, al1);
-            al2 = f_max2(0.f, al2);
-        } else if (iv == -1) {
-            if (al1 * Q(1) <= 0.f) al1 = 0.f;
-        } else if (iv == 2 || iv == -2) {
-            al1 = Q(1);
-            // a4(3,i,1) = a4(1,i,1) is overwritten below by a4(3,i,1) = a4(2,i,2)
-        }
+        float al1, al2, dc1;
+        ppm_top(DP(1), DP(2), Q(1), Q(2), W_(AL, 3), iv, al1, al2, dc1);
+        W_(DC, 1) = dc1;
         W_(AL, 1) = al1;
         W_(AL, 2) = al2;
     }
     {
-        // Bottom (mappm.f90:729-761)
-        const float d1 = DP(km), d2 = DP(km1);
-        const float qm = (d2 * Q(km) + d1 * Q(km1)) / (d1 + d2);
-        const float dq = 2.f * (Q(km1) - Q(km)) / (d1 + d2);
-        const float c1 = (W_(AL, km1) - qm - d2 * dq) / (d2 * (2.f * d2 * d2 + d1 * (d2 + 3.f * d1)));
-        const float c3 = dq - 2.0f * c1 * (d2 * (5.f * d1 + d2) - 3.f * d1 * d1);
-        float alk = qm - c1 * d1 * d2 * (d2 + 3.f * d1);
-        float ark = d1 * (8.f * c1 * (d1 * d1) - c3) + alk;
-        alk = f_max2(alk, f_min2(Q(km), Q(km1)));
-        alk = f_min2(alk, f_max2(Q(km), Q(km1)));
-        W_(DC, km) = 0.5f * (Q(km) - alk);
-        if (iv == 0) {
-            alk = f_max2(0.f, alk);
-            ark = f_max2(0.f, ark);
-        } else if (iv < 0) {
-            if (Q(km) * ark <= 0.f) ark = 0.f;
-        }
+        float alk, ark, dck;
+        ppm_bottom(DP(km), DP(km1), Q(km), Q(km1), W_(AL, km1), iv, alk, ark, dck);
+        W_(DC, km) = dck;
         W_(AL, km) = alk;
         W_(AR, km) = ark;
     }
@@ -708,7 +728,7 @@ __global__ __launch_bounds__(256) void mappm_simple_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
-// mappm, fast path (kord <= 6, km >= 8): one thread per column, no workspace traffic.
+// mappm, fast path (kord <= 6): one thread per column, no workspace traffic.
 //
 // The Fortran walks TARGET layers and, for each, searches and integrates over source layers,
 // reading a4(2:4, L) at a data-dependent L.  Here the sweep is SOURCE-layer major: the wave
@@ -720,24 +740,45 @@ __global__ __launch_bounds__(256) void mappm_simple_kernel(
 // columns whose pe1 and pe2 are finite and non-decreasing the result is bit-identical to the
 // sequential routine.  A lane that meets anything else (NaN or non-monotone pressures, a
 // top-edge search that finds no layer) reruns its column through mappm_column_exact.
+//
+// The sweep serves NF fields that share their source and target pressures (the restart pipelines
+// remap 4 fv_core fields and 9 tracers between the same two pressure grids, regridz.py:163-185): the
+// control flow, the target-interface ring, the pressure loads and every pressure-only term of the
+// reconstruction (the c1/c2/a1/a2 ratios, 2/(d4a+d4c), PR, PL, TT) are computed once per column
+// instead of once per field -- about 7 of the ~10 IEEE divisions per layer.  Per field the operations
+// and their order do not depend on NF (the field loops are unrolled and the compiler merges the
+// identical pressure-only subexpressions), so each field's result is bit-identical to a
+// single-field call.  `bad` depends on the pressures only: one worklist for all NF fields.
 // ---------------------------------------------------------------------------------------
-template <typename Tin>
+constexpr int kMaxMultiFields = kSweepMaxFields;
+struct MultiFieldPtrs {
+    const void *q1[kMaxMultiFields];
+    float *q2[kMaxMultiFields];
+};
+
+template <typename Tin, int NF>
 __global__ __launch_bounds__(256) void mappm_merge_kernel(
-    const Tin *__restrict__ pe1_, const Tin *__restrict__ q1_, const Tin *__restrict__ pe2_,
-    float *__restrict__ q2_, int64_t col0, int64_t col_end, int64_t n_inner, int km, int kn, int iv,
-    int kord, int layout, unsigned int *__restrict__ n_bad, unsigned int *__restrict__ bad_cols)
+    const Tin *__restrict__ pe1_, const MultiFieldPtrs fp, const Tin *__restrict__ pe2_, int64_t col0, int64_t col_end,
+    int64_t n_inner, int km, int kn, int iv, int kord, int layout, unsigned int *__restrict__ n_bad,
+    unsigned int *__restrict__ bad_cols)
 {
     const int64_t lc = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const int64_t col = col0 + lc;
     if (col >= col_end) return;
     const ColumnAddr addr = column_addr(col, n_inner, km, kn, layout);
     const int64_t ks = addr.ks;
-    const Tin *pp1 = pe1_ + addr.o_pe1, *pq1 = q1_ + addr.o_q1, *pp2 = pe2_ + addr.o_pe2;
-    float *pq2 = q2_ + addr.o_q2;
+    const Tin *pp1 = pe1_ + addr.o_pe1, *pp2 = pe2_ + addr.o_pe2;
+    const Tin *pq1[NF];
+    float *pq2[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        pq1[f] = static_cast<const Tin *>(fp.q1[f]) + addr.o_q1;
+        pq2[f] = fp.q2[f] + addr.o_q2;
+    }
     auto PE1 = [&](int k) { return (float)pp1[(int64_t)(k - 1) * ks]; };
-    auto Q = [&](int k) { return (float)pq1[(int64_t)(k - 1) * ks]; };
+    auto Q = [&](int f, int k) { return (float)pq1[f][(int64_t)(k - 1) * ks]; };
     auto PE2g = [&](int k) { return (float)pp2[(int64_t)(k - 1) * ks]; };
-    auto OUT = [&](int k, float v) { pq2[(int64_t)(k - 1) * ks] = v; };
+    auto OUT = [&](int f, int k, float v) { pq2[f][(int64_t)(k - 1) * ks] = v; };
     __shared__ float ring_lds[16 * 256];
 
     const int km1 = km - 1;
@@ -749,55 +790,31 @@ __global__ __launch_bounds__(256) void mappm_merge_kernel(
 
     // ---- head of the column: pe1(1..5), q1(1..4), and the two values the pre-checks need ----
     float pe_a = PE1(1), pe_b = PE1(2), pe_c = PE1(3), pe_d = PE1(4), pe_e = PE1(5);
-    float q0 = Q(1), qp1 = Q(2), qp2 = Q(3), qp3 = Q(4);
-    const float pe1_top = pe_a, pe1_bot = PE1(km + 1), q_top = q0, q_bot = Q(km);
+    const float pe1_top = pe_a, pe1_bot = PE1(km + 1);
+    float q0[NF], qp1[NF], qp2[NF], qp3[NF], q_top[NF], q_bot[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        q0[f] = Q(f, 1);
+        qp1[f] = Q(f, 2);
+        qp2[f] = Q(f, 3);
+        qp3[f] = Q(f, 4);
+        q_top[f] = q0[f];
+        q_bot[f] = Q(f, km);
+    }
     bool bad = !(pe_b >= pe_a) | !(pe_c >= pe_b) | !(pe_d >= pe_c) | !(pe_e >= pe_d);
     float d0 = pe_b - pe_a, dp1 = pe_c - pe_b, dp2 = pe_d - pe_c, dp3 = pe_e - pe_d;  // dp(L..L+3)
-    float dm1 = 0.f, qm1 = 0.f;                                                       // dp(L-1), q(L-1)
 
-    // dc(k) for 2 <= k <= km-1 (mappm.f90:658-668) from the values around level k
-    auto DCI = [&](float dpa, float dpb, float dpc, float qa, float qb, float qc) {
-        const float d4b = dpa + dpb, d4c = dpb + dpc;  // d4(k), d4(k+1)
-        const float c1 = (dpa + 0.5f * dpb) / d4c;
-        const float c2 = (dpc + 0.5f * dpb) / d4b;
-        const float df2 = dpb * (c1 * (qc - qb) + c2 * (qb - qa)) / (d4b + dpc);
-        return f_sign(f_min3(fabsf(df2), f_max3(qa, qb, qc) - qb, qb - f_min3(qa, qb, qc)), df2);
-    };
-    // a4(2,k) for 3 <= k <= km-1 (mappm.f90:674-683): dpz..dpc = dp(k-2..k+1), qa = q(k-1), qb = q(k)
-    auto INT = [&](float dpz, float dpa, float dpb, float dpc, float qa, float qb, float dca, float dcb) {
-        const float d4a = dpz + dpa, d4b = dpa + dpb, d4c = dpb + dpc;  // d4(k-1), d4(k), d4(k+1)
-        const float c1 = (qb - qa) * dpa / d4b;
-        const float a1 = d4a / (d4b + dpa);
-        const float a2 = d4c / (d4b + dpb);
-        return qa + c1 + 2.f / (d4a + d4c) * (dpb * (c1 * (a1 - a2) + a2 * dca) - dpa * a1 * dcb);
-    };
-
-    // ---- prologue: dc(2), dc(3), al(3), then the top boundary (mappm.f90:689-725) ----
-    float dc1 = DCI(d0, dp1, dp2, q0, qp1, qp2);                 // dc(2)
-    const float dc_3 = DCI(dp1, dp2, dp3, qp1, qp2, qp3);        // dc(3)
-    const float al_3 = INT(d0, dp1, dp2, dp3, qp1, qp2, dc1, dc_3);
-    float al0, al1, dc0, ar_km = 0.f;
-    {
-        const float d1 = d0, d2 = dp1;
-        const float qm = (d2 * q0 + d1 * qp1) / (d1 + d2);
-        const float dq = 2.f * (qp1 - q0) / (d1 + d2);
-        const float c1 = 4.f * (al_3 - qm - d2 * dq) / (d2 * (2.f * d2 * d2 + d1 * (d2 + 3.f * d1)));
-        const float c3 = dq - 0.5f * c1 * (d2 * (5.f * d1 + d2) - 3.f * d1 * d1);
-        float a2 = qm - 0.25f * c1 * d1 * d2 * (d2 + 3.f * d1);
-        float a1 = d1 * (2.f * c1 * (d1 * d1) - c3) + a2;
-        a2 = f_max2(a2, f_min2(q0, qp1));
-        a2 = f_min2(a2, f_max2(q0, qp1));
-        dc0 = 0.5f * (a2 - q0);
-        if (iv == 0) {
-            a1 = f_max2(0.f, a1);
-            a2 = f_max2(0.f, a2);
-        } else if (iv == -1) {
-            if (a1 * q0 <= 0.f) a1 = 0.f;
-        } else if (iv == 2 || iv == -2) {
-            a1 = q0;
-        }
-        al0 = a1;
-        al1 = a2;
+    // ---- prologue: dc(2), dc(3), al(3), then the top boundary ----
+    float al0[NF], al1[NF], al2[NF], dc0[NF], dc1[NF], dc2[NF], ar_km[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        dc1[f] = ppm_dc(d0, dp1, dp2, q0[f], qp1[f], qp2[f]);                   // dc(2)
+        const float dc_3 = ppm_dc(dp1, dp2, dp3, qp1[f], qp2[f], qp3[f]);       // dc(3)
+        const float al_3 = ppm_al(d0, dp1, dp2, dp3, qp1[f], qp2[f], dc1[f], dc_3);
+        ppm_top(d0, dp1, q0[f], qp1[f], al_3, iv, al0[f], al1[f], dc0[f]);
+        al2[f] = 0.f;
+        dc2[f] = 0.f;
+        ar_km[f] = 0.f;
     }
 
     // ---- per-lane target cursor ----
@@ -831,282 +848,12 @@ __global__ __launch_bounds__(256) void mappm_merge_kernel(
     int k = 1;
     float p2k = PE2(1), p2k1 = PE2(2);  // pe2(k), pe2(k+1)
     bool accum = false;
-    float qsum = 0.f, dpsum = 0.f;
-    auto advance = [&]() {
-        ++k;
-        if (!(p2k1 >= p2k)) bad = true;  // also catches NaN
-        p2k = p2k1;
-        p2k1 = PE2(k + 1 <= kn + 1 ? k + 1 : kn + 1);
-    };
-    if (!(p2k1 >= p2k)) bad = true;
-    while (k <= kn && !bad && p2k <= pe1_top) {
-        OUT(k, q_top);
-        advance();
-    }
-    bool live = (k <= kn) && !bad && !(p2k >= pe1_bot);
-
-    float q_in = 0.f, pe_in = pe_e;  // q(L+3), pe1(L+4) for the NEXT iteration's window, in flight
-    float al2 = 0.f, dc2 = 0.f;
-    for (int L = 1; L <= km; ++L) {
-        // ---- (1) everything requested during the previous iteration lands here ----
-        if (jp > jw) RING(jw) = pv0;
-        if (jp > jw + 1) RING(jw + 1) = pv1;
-        jw = jp;
-        if (L > 1) {  // level L becomes the current one
-            if (!(pe_in >= pe_e)) bad = true;
-            qm1 = q0; q0 = qp1; qp1 = qp2; qp2 = qp3; qp3 = q_in;
-            dm1 = d0; d0 = dp1; dp1 = dp2; dp2 = dp3; dp3 = pe_in - pe_e;
-            pe_a = pe_b; pe_b = pe_c; pe_c = pe_d; pe_d = pe_e; pe_e = pe_in;
-            al0 = al1; al1 = al2;
-            dc0 = dc1; dc1 = dc2;
-        }
-        // ---- (2) reconstruction of level L+2 from the window dp(L-1..L+3), q(L..L+3) ----
-        const int kk = L + 2;
-        al2 = 0.f;
-        dc2 = 0.f;
-        if (kk <= km1) {
-            dc2 = DCI(dp1, dp2, dp3, qp1, qp2, qp3);           // dc(L+2)
-            al2 = INT(d0, dp1, dp2, dp3, qp1, qp2, dc1, dc2);  // al(L+2)
-        } else if (kk == km) {
-            // bottom boundary (mappm.f90:729-761): al(km), ar(km), dc(km) from al(km-1) = al1
-            const float d1 = dp2, d2 = dp1;   // dp(km), dp(km-1)
-            const float qk = qp2, qk1 = qp1;  // q(km), q(km-1)
-            const float qm = (d2 * qk + d1 * qk1) / (d1 + d2);
-            const float dq = 2.f * (qk1 - qk) / (d1 + d2);
-            const float c1 = (al1 - qm - d2 * dq) / (d2 * (2.f * d2 * d2 + d1 * (d2 + 3.f * d1)));
-            const float c3 = dq - 2.0f * c1 * (d2 * (5.f * d1 + d2) - 3.f * d1 * d1);
-            float alk = qm - c1 * d1 * d2 * (d2 + 3.f * d1);
-            float ark = d1 * (8.f * c1 * (d1 * d1) - c3) + alk;
-            alk = f_max2(alk, f_min2(qk, qk1));
-            alk = f_min2(alk, f_max2(qk, qk1));
-            dc2 = 0.5f * (qk - alk);
-            if (iv == 0) {
-                alk = f_max2(0.f, alk);
-                ark = f_max2(0.f, ark);
-            } else if (iv < 0) {
-                if (qk * ark <= 0.f) ark = 0.f;
-            }
-            al2 = alk;
-            ar_km = ark;
-        }
-        // ---- (3) requests for the next iteration: q(L+4), pe1(L+5), up to two target interfaces ----
-        if (L + 4 <= km) {
-            q_in = Q(L + 4);
-            pe_in = PE1(L + 5);
-        }
-        if (jp <= kn + 1 && jp < k + kRing) {
-            pv0 = PE2g(jp);
-            ++jp;
-            if (jp <= kn + 1 && jp < k + kRing) {
-                pv1 = PE2g(jp);
-                ++jp;
-            }
-        }
-
-        const bool edge = (L <= 2) | (L >= km1);
-        // ---- (4) finalise layer L: A6 and the limiter (mappm.f90:773-849) ----
-        float al = al0, ar = (L == km) ? ar_km : al1, a6 = 0.f;
-        if (edge | int_recompute_a6) a6 = 3.f * (2.f * q0 - (al + ar));
-        if (edge | int_limit) ppm_limiters1(dc0, q0, al, ar, a6, edge ? 0 : lmt_int);
-        const float pL = pe_a, pL1 = pe_b;
-
-        // ---- (5) emit the target layers that end inside layer L ----
-        // Per layer a lane goes through zero or more emitting events (the bottom part of an
-        // accumulating target; targets lying entirely inside the layer) and then exactly one
-        // non-emitting one (start a target that leaves the layer / add the whole layer / nothing).
-        // an accumulating target can end in this layer only once, before any target that lies inside it:
-        // that step is taken out of the loop, so that lanes closing a target and lanes emitting inside
-        // ones do not serialise each other's branch
-        if (live && accum && !(p2k1 > pL1)) {
-            const float delp = p2k1 - pL;
-            const float PR = delp / d0;
-            qsum = qsum + delp * (al + 0.5f * PR * (ar - al + a6 * (1.f - r23 * PR)));
-            dpsum = dpsum + delp;
-            OUT(k, qsum / dpsum);
-            accum = false;
-            advance();
-            live = (k <= kn) && !bad && !(p2k >= pe1_bot);
-        }
-        while (live && !accum && (p2k >= pL && p2k <= pL1) && (p2k1 <= pL1)) {
-            const float PR = (p2k1 - pL) / d0;
-            const float PL = (p2k - pL) / d0;
-            const float TT = r3 * (PR * (PR + PL) + PL * PL);
-            OUT(k, al + 0.5f * (a6 + ar - al) * (PR + PL) - a6 * TT);
-            advance();
-            live = (k <= kn) && !bad && !(p2k >= pe1_bot);
-        }
-        if (live) {
-            if (accum) {  // whole layer (mappm.f90:99-104)
-                qsum = qsum + d0 * q0;
-                dpsum = dpsum + d0;
-            } else if (p2k >= pL && p2k <= pL1) {  // fractional area (mappm.f90:85-92)
-                const float PL = (p2k - pL) / d0;
-                const float delp = pL1 - p2k;
-                const float TT = r3 * (1.f + PL * (1.f + PL));
-                qsum = delp * (al + 0.5f * (a6 + ar - al) * (1.f + PL) - a6 * TT);
-                dpsum = delp;
-                accum = true;
-            }
-        }
-    }
-    (void)qm1;
-    (void)dm1;
-
-    // ---- past the old surface (mappm.f90:115-121), then the run that copies q1(km) ----
-    if (k <= kn && !bad && accum) {
-        const float delp = p2k1 - pe1_bot;
-        if (delp > 0.f) {
-            qsum = qsum + delp * q_bot;
-            dpsum = dpsum + delp;
-        }
-        OUT(k, qsum / dpsum);
-        advance();
-    }
-    while (k <= kn && !bad) {
-        if (p2k >= pe1_bot) {
-            OUT(k, q_bot);
-            advance();
-        } else {
-            bad = true;  // a top-edge search that no source layer satisfied
-        }
-    }
-    if (bad) bad_cols[atomicAdd(n_bad, 1u)] = (unsigned int)lc;  // redone by mappm_fallback_kernel
-}
-
-// ---------------------------------------------------------------------------------------
-// The merge sweep for NF fields that share their source and target pressures (the restart pipelines
-// remap 4 fv_core fields and 9 tracers between the same two pressure grids, regridz.py:163-185): the
-// control flow, the target-interface ring, the pressure loads and every pressure-only term of the
-// reconstruction (the c1/c2/a1/a2 ratios, 2/(d4a+d4c), PR, PL, TT) are computed once per column
-// instead of once per field -- about 7 of the ~10 IEEE divisions per layer.  Per field the operations
-// and their order are those of mappm_merge_kernel (the field loops are unrolled and the compiler
-// merges the identical pressure-only subexpressions), so each field's result is bit-identical to a
-// single-field call.  `bad` depends on the pressures only: one worklist for all NF fields.
-// ---------------------------------------------------------------------------------------
-constexpr int kMaxMultiFields = 4;
-struct MultiFieldPtrs {
-    const void *q1[kMaxMultiFields];
-    float *q2[kMaxMultiFields];
-};
-
-template <typename Tin, int NF>
-__global__ __launch_bounds__(256) void mappm_merge_multi_kernel(
-    const Tin *__restrict__ pe1_, const MultiFieldPtrs fp, const Tin *__restrict__ pe2_, int64_t col0, int64_t col_end,
-    int64_t n_inner, int km, int kn, int iv, int kord, int layout, unsigned int *__restrict__ n_bad,
-    unsigned int *__restrict__ bad_cols)
-{
-    const int64_t lc = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    const int64_t col = col0 + lc;
-    if (col >= col_end) return;
-    const ColumnAddr addr = column_addr(col, n_inner, km, kn, layout);
-    const int64_t ks = addr.ks;
-    const Tin *pp1 = pe1_ + addr.o_pe1, *pp2 = pe2_ + addr.o_pe2;
-    const Tin *pq1[NF];
-    float *pq2[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-        pq1[f] = static_cast<const Tin *>(fp.q1[f]) + addr.o_q1;
-        pq2[f] = fp.q2[f] + addr.o_q2;
-    }
-    auto PE1 = [&](int k) { return (float)pp1[(int64_t)(k - 1) * ks]; };
-    auto Q = [&](int f, int k) { return (float)pq1[f][(int64_t)(k - 1) * ks]; };
-    auto PE2g = [&](int k) { return (float)pp2[(int64_t)(k - 1) * ks]; };
-    auto OUT = [&](int f, int k, float v) { pq2[f][(int64_t)(k - 1) * ks] = v; };
-    __shared__ float ring_lds[16 * 256];
-
-    const int km1 = km - 1;
-    int lmt_int = kord - 3;
-    lmt_int = (lmt_int > 0) ? lmt_int : 0;
-    if (iv == 0) lmt_int = (lmt_int < 2) ? lmt_int : 2;
-    const bool int_recompute_a6 = (kord != 4), int_limit = (kord != 6);
-    const float r3 = 1.f / 3.f, r23 = 2.f / 3.f;
-
-    float pe_a = PE1(1), pe_b = PE1(2), pe_c = PE1(3), pe_d = PE1(4), pe_e = PE1(5);
-    const float pe1_top = pe_a, pe1_bot = PE1(km + 1);
-    float q0[NF], qp1[NF], qp2[NF], qp3[NF], q_top[NF], q_bot[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-        q0[f] = Q(f, 1);
-        qp1[f] = Q(f, 2);
-        qp2[f] = Q(f, 3);
-        qp3[f] = Q(f, 4);
-        q_top[f] = q0[f];
-        q_bot[f] = Q(f, km);
-    }
-    bool bad = !(pe_b >= pe_a) | !(pe_c >= pe_b) | !(pe_d >= pe_c) | !(pe_e >= pe_d);
-    float d0 = pe_b - pe_a, dp1 = pe_c - pe_b, dp2 = pe_d - pe_c, dp3 = pe_e - pe_d;
-
-    auto DCI = [&](float dpa, float dpb, float dpc, float qa, float qb, float qc) {
-        const float d4b = dpa + dpb, d4c = dpb + dpc;
-        const float c1 = (dpa + 0.5f * dpb) / d4c;
-        const float c2 = (dpc + 0.5f * dpb) / d4b;
-        const float df2 = dpb * (c1 * (qc - qb) + c2 * (qb - qa)) / (d4b + dpc);
-        return f_sign(f_min3(fabsf(df2), f_max3(qa, qb, qc) - qb, qb - f_min3(qa, qb, qc)), df2);
-    };
-    auto INT = [&](float dpz, float dpa, float dpb, float dpc, float qa, float qb, float dca, float dcb) {
-        const float d4a = dpz + dpa, d4b = dpa + dpb, d4c = dpb + dpc;
-        const float c1 = (qb - qa) * dpa / d4b;
-        const float a1 = d4a / (d4b + dpa);
-        const float a2 = d4c / (d4b + dpb);
-        return qa + c1 + 2.f / (d4a + d4c) * (dpb * (c1 * (a1 - a2) + a2 * dca) - dpa * a1 * dcb);
-    };
-
-    float al0[NF], al1[NF], al2[NF], dc0[NF], dc1[NF], dc2[NF], ar_km[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-        dc1[f] = DCI(d0, dp1, dp2, q0[f], qp1[f], qp2[f]);                   // dc(2)
-        const float dc_3 = DCI(dp1, dp2, dp3, qp1[f], qp2[f], qp3[f]);       // dc(3)
-        const float al_3 = INT(d0, dp1, dp2, dp3, qp1[f], qp2[f], dc1[f], dc_3);
-        const float d1 = d0, d2 = dp1;
-        const float qm = (d2 * q0[f] + d1 * qp1[f]) / (d1 + d2);
-        const float dq = 2.f * (qp1[f] - q0[f]) / (d1 + d2);
-        const float c1 = 4.f * (al_3 - qm - d2 * dq) / (d2 * (2.f * d2 * d2 + d1 * (d2 + 3.f * d1)));
-        const float c3 = dq - 0.5f * c1 * (d2 * (5.f * d1 + d2) - 3.f * d1 * d1);
-        float a2 = qm - 0.25f * c1 * d1 * d2 * (d2 + 3.f * d1);
-        float a1 = d1 * (2.f * c1 * (d1 * d1) - c3) + a2;
-        a2 = f_max2(a2, f_min2(q0[f], qp1[f]));
-        a2 = f_min2(a2, f_max2(q0[f], qp1[f]));
-        dc0[f] = 0.5f * (a2 - q0[f]);
-        if (iv == 0) {
-            a1 = f_max2(0.f, a1);
-            a2 = f_max2(0.f, a2);
-        } else if (iv == -1) {
-            if (a1 * q0[f] <= 0.f) a1 = 0.f;
-        } else if (iv == 2 || iv == -2) {
-            a1 = q0[f];
-        }
-        al0[f] = a1;
-        al1[f] = a2;
-        al2[f] = 0.f;
-        dc2[f] = 0.f;
-        ar_km[f] = 0.f;
-    }
-
-    constexpr int kRing = 16;
-    float *ring = ring_lds + threadIdx.x;
-    auto RING = [&](int j) -> float & { return ring[(j & (kRing - 1)) * 256]; };
-    int jw = 1;
-    {
-        float tmp[kRing];
-#pragma unroll
-        for (int i = 0; i < kRing; ++i) tmp[i] = PE2g((i + 1 <= kn + 1) ? i + 1 : kn + 1);
-#pragma unroll
-        for (int i = 0; i < kRing; ++i) RING(i + 1) = tmp[i];
-        jw = (kRing < kn + 1 ? kRing : kn + 1) + 1;
-    }
-    int jp = jw;
-    float pv0 = 0.f, pv1 = 0.f;
-    auto PE2 = [&](int j) { return (j < jw) ? RING(j) : PE2g(j); };
-
-    int k = 1;
-    float p2k = PE2(1), p2k1 = PE2(2);
-    bool accum = false;
     float qsum[NF], dpsum = 0.f;
 #pragma unroll
     for (int f = 0; f < NF; ++f) qsum[f] = 0.f;
     auto advance = [&]() {
         ++k;
-        if (!(p2k1 >= p2k)) bad = true;
+        if (!(p2k1 >= p2k)) bad = true;  // also catches NaN
         p2k = p2k1;
         p2k1 = PE2(k + 1 <= kn + 1 ? k + 1 : kn + 1);
     };
@@ -1118,14 +865,15 @@ __global__ __launch_bounds__(256) void mappm_merge_multi_kernel(
     }
     bool live = (k <= kn) && !bad && !(p2k >= pe1_bot);
 
-    float q_in[NF], pe_in = pe_e;
+    float q_in[NF], pe_in = pe_e;  // q(L+3), pe1(L+4) for the NEXT iteration's window, in flight
 #pragma unroll
     for (int f = 0; f < NF; ++f) q_in[f] = 0.f;
     for (int L = 1; L <= km; ++L) {
+        // ---- (1) everything requested during the previous iteration lands here ----
         if (jp > jw) RING(jw) = pv0;
         if (jp > jw + 1) RING(jw + 1) = pv1;
         jw = jp;
-        if (L > 1) {
+        if (L > 1) {  // level L becomes the current one
             if (!(pe_in >= pe_e)) bad = true;
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
@@ -1136,36 +884,17 @@ __global__ __launch_bounds__(256) void mappm_merge_multi_kernel(
             d0 = dp1; dp1 = dp2; dp2 = dp3; dp3 = pe_in - pe_e;
             pe_a = pe_b; pe_b = pe_c; pe_c = pe_d; pe_d = pe_e; pe_e = pe_in;
         }
+        // ---- (2) reconstruction of level L+2 from the window dp(L..L+3), q(L..L+3) ----
         const int kk = L + 2;
         if (kk <= km1) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
-                dc2[f] = DCI(dp1, dp2, dp3, qp1[f], qp2[f], qp3[f]);
-                al2[f] = INT(d0, dp1, dp2, dp3, qp1[f], qp2[f], dc1[f], dc2[f]);
+                dc2[f] = ppm_dc(dp1, dp2, dp3, qp1[f], qp2[f], qp3[f]);            // dc(L+2)
+                al2[f] = ppm_al(d0, dp1, dp2, dp3, qp1[f], qp2[f], dc1[f], dc2[f]);  // al(L+2)
             }
-        } else if (kk == km) {
+        } else if (kk == km) {  // bottom boundary: al(km), ar(km), dc(km) from al(km-1) = al1
 #pragma unroll
-            for (int f = 0; f < NF; ++f) {
-                const float d1 = dp2, d2 = dp1;
-                const float qk = qp2[f], qk1 = qp1[f];
-                const float qm = (d2 * qk + d1 * qk1) / (d1 + d2);
-                const float dq = 2.f * (qk1 - qk) / (d1 + d2);
-                const float c1 = (al1[f] - qm - d2 * dq) / (d2 * (2.f * d2 * d2 + d1 * (d2 + 3.f * d1)));
-                const float c3 = dq - 2.0f * c1 * (d2 * (5.f * d1 + d2) - 3.f * d1 * d1);
-                float alk = qm - c1 * d1 * d2 * (d2 + 3.f * d1);
-                float ark = d1 * (8.f * c1 * (d1 * d1) - c3) + alk;
-                alk = f_max2(alk, f_min2(qk, qk1));
-                alk = f_min2(alk, f_max2(qk, qk1));
-                dc2[f] = 0.5f * (qk - alk);
-                if (iv == 0) {
-                    alk = f_max2(0.f, alk);
-                    ark = f_max2(0.f, ark);
-                } else if (iv < 0) {
-                    if (qk * ark <= 0.f) ark = 0.f;
-                }
-                al2[f] = alk;
-                ar_km[f] = ark;
-            }
+            for (int f = 0; f < NF; ++f) ppm_bottom(dp2, dp1, qp2[f], qp1[f], al1[f], iv, al2[f], ar_km[f], dc2[f]);
         } else {
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
@@ -1173,6 +902,7 @@ __global__ __launch_bounds__(256) void mappm_merge_multi_kernel(
                 dc2[f] = 0.f;
             }
         }
+        // ---- (3) requests for the next iteration: q(L+4), pe1(L+5), up to two target interfaces ----
         if (L + 4 <= km) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) q_in[f] = Q(f, L + 4);
@@ -1188,6 +918,7 @@ __global__ __launch_bounds__(256) void mappm_merge_multi_kernel(
         }
 
         const bool edge = (L <= 2) | (L >= km1);
+        // ---- (4) finalise layer L: A6 and the limiter (mappm.f90:773-849) ----
         float al[NF], ar[NF], a6[NF];
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
@@ -1199,7 +930,14 @@ __global__ __launch_bounds__(256) void mappm_merge_multi_kernel(
         }
         const float pL = pe_a, pL1 = pe_b;
 
-        if (live && accum && !(p2k1 > pL1)) {  // (see mappm_merge_kernel)
+        // ---- (5) emit the target layers that end inside layer L ----
+        // Per layer a lane goes through zero or more emitting events (the bottom part of an
+        // accumulating target; targets lying entirely inside the layer) and then exactly one
+        // non-emitting one (start a target that leaves the layer / add the whole layer / nothing).
+        // an accumulating target can end in this layer only once, before any target that lies inside it:
+        // that step is taken out of the loop, so that lanes closing a target and lanes emitting inside
+        // ones do not serialise each other's branch
+        if (live && accum && !(p2k1 > pL1)) {
             const float delp = p2k1 - pL;
             const float PR = delp / d0;
             dpsum = dpsum + delp;
@@ -1222,11 +960,11 @@ __global__ __launch_bounds__(256) void mappm_merge_multi_kernel(
             live = (k <= kn) && !bad && !(p2k >= pe1_bot);
         }
         if (live) {
-            if (accum) {
+            if (accum) {  // whole layer (mappm.f90:99-104)
 #pragma unroll
                 for (int f = 0; f < NF; ++f) qsum[f] = qsum[f] + d0 * q0[f];
                 dpsum = dpsum + d0;
-            } else if (p2k >= pL && p2k <= pL1) {
+            } else if (p2k >= pL && p2k <= pL1) {  // fractional area (mappm.f90:85-92)
                 const float PL = (p2k - pL) / d0;
                 const float delp = pL1 - p2k;
                 const float TT = r3 * (1.f + PL * (1.f + PL));
@@ -1239,6 +977,7 @@ __global__ __launch_bounds__(256) void mappm_merge_multi_kernel(
         }
     }
 
+    // ---- past the old surface (mappm.f90:115-121), then the run that copies q1(km) ----
     if (k <= kn && !bad && accum) {
         const float delp = p2k1 - pe1_bot;
         if (delp > 0.f) {
@@ -1256,10 +995,10 @@ __global__ __launch_bounds__(256) void mappm_merge_multi_kernel(
             for (int f = 0; f < NF; ++f) OUT(f, k, q_bot[f]);
             advance();
         } else {
-            bad = true;
+            bad = true;  // a top-edge search that no source layer satisfied
         }
     }
-    if (bad) bad_cols[atomicAdd(n_bad, 1u)] = (unsigned int)lc;
+    if (bad) bad_cols[atomicAdd(n_bad, 1u)] = (unsigned int)lc;  // redone by mappm_fallback_kernel
 }
 
 // The columns the merge sweep gave up on (listed by their index inside the chunk), through the
@@ -1550,176 +1289,184 @@ extern "C" size_t fv3hip_mappm_workspace_bytes(int64_t ncol, int km)
     return kCounterBytes + ws_list_bytes(ncol) + (size_t)kMappmPlanes * (size_t)km * (size_t)ws_slots(ncol) * sizeof(float);
 }
 
-extern "C" int fv3hip_mappm(const void *pe1, const void *q1, const void *pe2, int in_dtype, float *q2,
-                            int64_t n_batch, int64_t n_inner, int km, int kn, int iv, int kord,
-                            int layout, int arith, void *workspace, size_t workspace_bytes, void *stream)
+namespace {
+
+// The argument checks that the four remap entry points share (the entries on [.., z, y, x] arrays pass LEVEL_COL).
+int check_remap_args(int arith, int in_dtype, int layout, int64_t n_batch, int64_t n_inner, int km, int kn, int iv, int kord)
 {
-    FV3HIP_REQUIRE(in_dtype == FV3HIP_F32 || in_dtype == FV3HIP_F64, "in_dtype must be F32 or F64, got %d", in_dtype);
     FV3HIP_REQUIRE(arith == FV3HIP_ARITH_EXACT || arith == FV3HIP_ARITH_FAST, "unknown arithmetic mode %d", arith);
+    FV3HIP_REQUIRE(in_dtype == FV3HIP_F32 || in_dtype == FV3HIP_F64, "in_dtype must be F32 or F64, got %d", in_dtype);
     FV3HIP_REQUIRE(layout == FV3HIP_LAYOUT_COL_LEVEL || layout == FV3HIP_LAYOUT_LEVEL_COL, "unknown layout %d", layout);
     FV3HIP_REQUIRE(n_batch >= 0 && n_inner >= 0 && kn >= 0, "negative extent");
     FV3HIP_REQUIRE(iv >= -2 && iv <= 2, "iv must be in [-2, 2], got %d", iv);
     if (kord > 7 && iv == -2)
         return fail(FV3HIP_EUNSUPPORTED, "kord=%d with iv=-2: cs_profile would read the array qs that mappm never sets (mappm.f90:34,51,152-176)", kord);
     FV3HIP_REQUIRE(km >= 4, "km must be >= 4 (ppm_profile reads a4(2,i,3)), got %d", km);
-    if (layout == FV3HIP_LAYOUT_COL_LEVEL)
-        FV3HIP_REQUIRE(n_inner == 1, "COL_LEVEL layout requires n_inner == 1");
-    const int64_t ncol = n_batch * n_inner;
-    if (ncol == 0 || kn == 0) return FV3HIP_OK;
-    FV3HIP_REQUIRE(pe1 && q1 && pe2 && q2, "null pointer");
-    FV3HIP_REQUIRE(workspace && workspace_bytes >= fv3hip_mappm_workspace_bytes(ncol, km),
-                   "workspace too small: need %zu bytes, got %zu", fv3hip_mappm_workspace_bytes(ncol, km), workspace_bytes);
-    hipStream_t st = as_stream(stream);
-    const int64_t ws_cols = ws_slots(ncol);
-    unsigned int *n_bad = static_cast<unsigned int *>(workspace);
-    unsigned int *bad_cols = reinterpret_cast<unsigned int *>(static_cast<char *>(workspace) + kCounterBytes);
-    float *planes = reinterpret_cast<float *>(static_cast<char *>(workspace) + kCounterBytes + ws_list_bytes(ncol));
-    // kord <= 6: the register-window merge sweep, then the (normally empty) list of columns it gave
-    // up on through the sequential routine; kord == 7 (Huynh's constraint needs a wider stencil)
-    // goes through the sequential routine directly
-    const bool fast = (kord <= 6);
-    // the sweep kernel (remap.hip) where it applies: native layout, kord <= 3, whole waves per batch plane
-    const bool sweep = mappm_sweep_eligible(n_inner, km, kn, kord, layout, in_dtype);
+    if (layout == FV3HIP_LAYOUT_COL_LEVEL) FV3HIP_REQUIRE(n_inner == 1, "COL_LEVEL layout requires n_inner == 1");
+    return FV3HIP_OK;
+}
+
+// the workspace's three parts (ws_slots, ws_list_bytes above) for a call of ncol columns
+struct RemapWorkspace {
+    unsigned int *n_bad, *bad_cols;
+    float *planes;
+    int64_t ws_cols;
+};
+
+int carve_workspace(void *workspace, size_t workspace_bytes, size_t need, int64_t ncol, RemapWorkspace &w)
+{
+    FV3HIP_REQUIRE(workspace && workspace_bytes >= need, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    char *base = static_cast<char *>(workspace);
+    w.n_bad = reinterpret_cast<unsigned int *>(base);
+    w.bad_cols = reinterpret_cast<unsigned int *>(base + kCounterBytes);
+    w.planes = reinterpret_cast<float *>(base + kCounterBytes + ws_list_bytes(ncol));
+    w.ws_cols = ws_slots(ncol);
+    return FV3HIP_OK;
+}
+
+// What every remap launch takes: a group of up to kMaxMultiFields fields, the first column of the chunk, the extents, the lists.
+SweepArgs sweep_args(const void *pe1, const void *pe2, const void *const *q1, float *const *q2, int nf, int64_t col0, int64_t n_inner,
+                     int km, int kn, int iv, const RemapWorkspace &w)
+{
+    SweepArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.pe1 = pe1;
+    sa.pe2 = pe2;
+    for (int f = 0; f < nf; ++f) {
+        sa.q1[f] = q1[f];
+        sa.q2[f] = q2[f];
+    }
+    sa.col0 = col0;
+    sa.n_inner = n_inner;
+    sa.km = km;
+    sa.kn = kn;
+    sa.iv = iv;
+    sa.n_bad = w.n_bad;
+    sa.bad_cols = w.bad_cols;
+    return sa;
+}
+
+// For each chunk of kMappmChunk columns (the lists and the planes are sized for one), for each group of up to kMaxMultiFields
+// fields: zero the counters, body(col0, col_end, f0, nf), check the launches.
+template <typename Body>
+int for_each_chunk_and_group(int64_t ncol, int n_fields, const RemapWorkspace &w, hipStream_t st, const char *what, Body body)
+{
     for (int64_t col0 = 0; col0 < ncol; col0 += kMappmChunk) {
         const int64_t col_end = (col0 + kMappmChunk < ncol) ? col0 + kMappmChunk : ncol;
-        const int64_t blocks = ceil_div(col_end - col0, 256);
-        if (fast) {
-            FV3HIP_CHECK_HIP(hipMemsetAsync(n_bad, 0, 16, st));
-            const int64_t fb_threads = (col_end - col0 < kFallbackSlots) ? (col_end - col0) : kFallbackSlots;
-            const int64_t fb_blocks = ceil_div(fb_threads, 256);
-            if (sweep) {
-                SweepArgs sa;
-                memset(&sa, 0, sizeof(sa));
-                sa.pe1 = pe1;
-                sa.pe2 = pe2;
-                sa.q1[0] = q1;
-                sa.q2[0] = q2;
-                sa.col0 = col0;
-                sa.n_inner = n_inner;
-                sa.km = km;
-                sa.kn = kn;
-                sa.iv = iv;
-                sa.n_bad = n_bad;
-                sa.bad_cols = bad_cols;
-                mappm_sweep_launch(sa, 1, in_dtype, col_end, arith == FV3HIP_ARITH_FAST, st);
-            }
-#define LAUNCH_(T)                                                                                       \
-    if (!sweep)                                                                                          \
-        hipLaunchKernelGGL((mappm_merge_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st,            \
-                           static_cast<const T *>(pe1), static_cast<const T *>(q1), static_cast<const T *>(pe2), \
-                           q2, col0, col_end, n_inner, km, kn, iv, kord, layout, n_bad, bad_cols);       \
-    hipLaunchKernelGGL((mappm_fallback_kernel<T>), dim3((unsigned)fb_blocks), dim3(256), 0, st,          \
-                       static_cast<const T *>(pe1), static_cast<const T *>(q1), static_cast<const T *>(pe2), \
-                       q2, col0, n_inner, km, kn, iv, kord, layout, n_bad, bad_cols, planes, ws_cols)
-            if (in_dtype == FV3HIP_F32) { LAUNCH_(float); } else { LAUNCH_(double); }
-#undef LAUNCH_
-        } else {
-#define LAUNCH_(T)                                                                                       \
-    hipLaunchKernelGGL((mappm_simple_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st,               \
-                       static_cast<const T *>(pe1), static_cast<const T *>(q1), static_cast<const T *>(pe2), \
-                       q2, col0, col_end, n_inner, km, kn, iv, kord, layout, planes, ws_cols)
-            if (in_dtype == FV3HIP_F32) { LAUNCH_(float); } else { LAUNCH_(double); }
-#undef LAUNCH_
+        for (int f0 = 0; f0 < n_fields; f0 += kMaxMultiFields) {
+            const int nf = (n_fields - f0 < kMaxMultiFields) ? n_fields - f0 : kMaxMultiFields;
+            FV3HIP_CHECK_HIP(hipMemsetAsync(w.n_bad, 0, 16, st));
+            body(col0, col_end, f0, nf);
+            const int rc = check_launch(what);
+            if (rc) return rc;
         }
-        int rc = check_launch("mappm kernel");
-        if (rc) return rc;
     }
     return FV3HIP_OK;
 }
 
-namespace {
 template <typename T, int NF>
-void launch_merge_multi(const void *pe1, const MultiFieldPtrs &fp, const void *pe2, int64_t col0, int64_t col_end, int64_t n_inner,
-                        int km, int kn, int iv, int kord, int layout, unsigned int *n_bad, unsigned int *bad_cols, hipStream_t st)
+void launch_merge_nf(const SweepArgs &a, int64_t col_end, int kord, int layout, hipStream_t st)
 {
-    const int64_t blocks = ceil_div(col_end - col0, 256);
-    hipLaunchKernelGGL((mappm_merge_multi_kernel<T, NF>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const T *>(pe1), fp,
-                       static_cast<const T *>(pe2), col0, col_end, n_inner, km, kn, iv, kord, layout, n_bad, bad_cols);
+    MultiFieldPtrs fp;
+    for (int f = 0; f < kMaxMultiFields; ++f) {
+        fp.q1[f] = a.q1[f];
+        fp.q2[f] = a.q2[f];
+    }
+    hipLaunchKernelGGL((mappm_merge_kernel<T, NF>), dim3((unsigned)ceil_div(col_end - a.col0, 256)), dim3(256), 0, st,
+                       static_cast<const T *>(a.pe1), fp, static_cast<const T *>(a.pe2), a.col0, col_end, a.n_inner, a.km, a.kn, a.iv,
+                       kord, layout, a.n_bad, a.bad_cols);
 }
+
+template <typename T>
+void launch_merge(const SweepArgs &a, int nf, int64_t col_end, int kord, int layout, hipStream_t st)
+{
+    switch (nf) {
+        case 1: launch_merge_nf<T, 1>(a, col_end, kord, layout, st); break;
+        case 2: launch_merge_nf<T, 2>(a, col_end, kord, layout, st); break;
+        case 3: launch_merge_nf<T, 3>(a, col_end, kord, layout, st); break;
+        default: launch_merge_nf<T, 4>(a, col_end, kord, layout, st); break;
+    }
+}
+
+// The sequential routine for each of the nf fields of `a`, on a chunk of n columns: the columns the chunk's list names, as
+// indices from list_col0 (mappm_fallback_kernel); with list_col0 = kWholeChunk every column of the chunk (mappm_simple_kernel)
+constexpr int64_t kWholeChunk = -1;
+template <typename T>
+void launch_fallback(const SweepArgs &a, int nf, int64_t n, int64_t list_col0, int kord, int layout, const RemapWorkspace &w,
+                     hipStream_t st)
+{
+    const T *pe1 = static_cast<const T *>(a.pe1), *pe2 = static_cast<const T *>(a.pe2);
+    const int64_t fb_threads = (n < kFallbackSlots) ? n : kFallbackSlots;
+    for (int f = 0; f < nf; ++f) {
+        const T *q1 = static_cast<const T *>(a.q1[f]);
+        if (list_col0 == kWholeChunk)
+            hipLaunchKernelGGL((mappm_simple_kernel<T>), dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, pe1, q1, pe2, a.q2[f],
+                               a.col0, a.col0 + n, a.n_inner, a.km, a.kn, a.iv, kord, layout, w.planes, w.ws_cols);
+        else
+            hipLaunchKernelGGL((mappm_fallback_kernel<T>), dim3((unsigned)ceil_div(fb_threads, 256)), dim3(256), 0, st, pe1, q1, pe2,
+                               a.q2[f], list_col0, a.n_inner, a.km, a.kn, a.iv, kord, layout, a.n_bad, a.bad_cols, w.planes, w.ws_cols,
+                               a.pe2_f, a.nx, a.pe2_nx, a.pe2_plane);
+    }
+}
+
+void launch_fallback(int in_dtype, const SweepArgs &a, int nf, int64_t n, int64_t list_col0, int kord, int layout,
+                     const RemapWorkspace &w, hipStream_t st)
+{
+    if (in_dtype == FV3HIP_F32) launch_fallback<float>(a, nf, n, list_col0, kord, layout, w, st);
+    else launch_fallback<double>(a, nf, n, list_col0, kord, layout, w, st);
+}
+
+// fv3hip_mappm (one field) and fv3hip_mappm_multi.  kord <= 6: the sweep kernel (remap.hip) where it applies -- native layout,
+// kord <= 3, whole waves per batch plane -- else the register-window merge sweep, then the (normally empty) list of columns
+// either gave up on through the sequential routine; kord >= 7 (Huynh's constraint and cs_profile need a wider stencil) goes
+// through the sequential routine directly, field by field.
+int remap_fields(const void *pe1, const void *const *q1, const void *pe2, int in_dtype, float *const *q2, int n_fields, int64_t n_batch,
+                 int64_t n_inner, int km, int kn, int iv, int kord, int layout, int arith, void *workspace, size_t workspace_bytes,
+                 void *stream)
+{
+    int rc = check_remap_args(arith, in_dtype, layout, n_batch, n_inner, km, kn, iv, kord);
+    if (rc) return rc;
+    const int64_t ncol = n_batch * n_inner;
+    if (ncol == 0 || kn == 0) return FV3HIP_OK;
+    FV3HIP_REQUIRE(pe1 && pe2, "null pointer");
+    for (int f = 0; f < n_fields; ++f) FV3HIP_REQUIRE(q1[f] && q2[f], "null field pointer");
+    RemapWorkspace w;
+    rc = carve_workspace(workspace, workspace_bytes, fv3hip_mappm_workspace_bytes(ncol, km), ncol, w);
+    if (rc) return rc;
+    hipStream_t st = as_stream(stream);
+    const bool sweep = mappm_sweep_eligible(n_inner, km, kn, kord, layout, in_dtype);
+    return for_each_chunk_and_group(ncol, n_fields, w, st, "mappm kernel", [&](int64_t col0, int64_t col_end, int f0, int nf) {
+        const SweepArgs sa = sweep_args(pe1, pe2, q1 + f0, q2 + f0, nf, col0, n_inner, km, kn, iv, w);
+        if (kord > 6) {
+            launch_fallback(in_dtype, sa, nf, col_end - col0, kWholeChunk, kord, layout, w, st);
+            return;
+        }
+        if (sweep) mappm_sweep_launch(sa, nf, in_dtype, col_end, arith == FV3HIP_ARITH_FAST, st);
+        else if (in_dtype == FV3HIP_F32) launch_merge<float>(sa, nf, col_end, kord, layout, st);
+        else launch_merge<double>(sa, nf, col_end, kord, layout, st);
+        launch_fallback(in_dtype, sa, nf, col_end - col0, col0, kord, layout, w, st);
+    });
+}
+
 }  // namespace
+
+extern "C" int fv3hip_mappm(const void *pe1, const void *q1, const void *pe2, int in_dtype, float *q2,
+                            int64_t n_batch, int64_t n_inner, int km, int kn, int iv, int kord,
+                            int layout, int arith, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return remap_fields(pe1, &q1, pe2, in_dtype, &q2, 1, n_batch, n_inner, km, kn, iv, kord, layout, arith, workspace, workspace_bytes,
+                        stream);
+}
 
 extern "C" int fv3hip_mappm_multi(const void *pe1, const void *const *q1, const void *pe2, int in_dtype, float *const *q2,
                                   int n_fields, int64_t n_batch, int64_t n_inner, int km, int kn, int iv, int kord, int layout,
                                   int arith, void *workspace, size_t workspace_bytes, void *stream)
 {
-    FV3HIP_REQUIRE(arith == FV3HIP_ARITH_EXACT || arith == FV3HIP_ARITH_FAST, "unknown arithmetic mode %d", arith);
     FV3HIP_REQUIRE(n_fields >= 0, "negative field count");
     if (n_fields == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(q1 && q2, "null pointer");
-    if (kord > 6 || n_fields == 1) {  // kord >= 7 goes through the sequential routine
-        for (int f = 0; f < n_fields; ++f) {
-            const int rc = fv3hip_mappm(pe1, q1[f], pe2, in_dtype, q2[f], n_batch, n_inner, km, kn, iv, kord, layout, arith, workspace,
-                                        workspace_bytes, stream);
-            if (rc) return rc;
-        }
-        return FV3HIP_OK;
-    }
-    FV3HIP_REQUIRE(in_dtype == FV3HIP_F32 || in_dtype == FV3HIP_F64, "in_dtype must be F32 or F64, got %d", in_dtype);
-    FV3HIP_REQUIRE(layout == FV3HIP_LAYOUT_COL_LEVEL || layout == FV3HIP_LAYOUT_LEVEL_COL, "unknown layout %d", layout);
-    FV3HIP_REQUIRE(n_batch >= 0 && n_inner >= 0 && kn >= 0, "negative extent");
-    FV3HIP_REQUIRE(iv >= -2 && iv <= 2, "iv must be in [-2, 2], got %d", iv);
-    FV3HIP_REQUIRE(km >= 4, "km must be >= 4 (ppm_profile reads a4(2,i,3)), got %d", km);
-    if (layout == FV3HIP_LAYOUT_COL_LEVEL) FV3HIP_REQUIRE(n_inner == 1, "COL_LEVEL layout requires n_inner == 1");
-    const int64_t ncol = n_batch * n_inner;
-    if (ncol == 0 || kn == 0) return FV3HIP_OK;
-    FV3HIP_REQUIRE(pe1 && pe2, "null pointer");
-    for (int f = 0; f < n_fields; ++f) FV3HIP_REQUIRE(q1[f] && q2[f], "null field pointer");
-    FV3HIP_REQUIRE(workspace && workspace_bytes >= fv3hip_mappm_workspace_bytes(ncol, km),
-                   "workspace too small: need %zu bytes, got %zu", fv3hip_mappm_workspace_bytes(ncol, km), workspace_bytes);
-    hipStream_t st = as_stream(stream);
-    const int64_t ws_cols = ws_slots(ncol);
-    unsigned int *n_bad = static_cast<unsigned int *>(workspace);
-    unsigned int *bad_cols = reinterpret_cast<unsigned int *>(static_cast<char *>(workspace) + kCounterBytes);
-    float *planes = reinterpret_cast<float *>(static_cast<char *>(workspace) + kCounterBytes + ws_list_bytes(ncol));
-    for (int64_t col0 = 0; col0 < ncol; col0 += kMappmChunk) {
-        const int64_t col_end = (col0 + kMappmChunk < ncol) ? col0 + kMappmChunk : ncol;
-        const int64_t fb_threads = (col_end - col0 < kFallbackSlots) ? (col_end - col0) : kFallbackSlots;
-        const int64_t fb_blocks = ceil_div(fb_threads, 256);
-        for (int f0 = 0; f0 < n_fields; f0 += kMaxMultiFields) {
-            const int nf = (n_fields - f0 < kMaxMultiFields) ? n_fields - f0 : kMaxMultiFields;
-            MultiFieldPtrs fp;
-            for (int f = 0; f < kMaxMultiFields; ++f) {
-                fp.q1[f] = f < nf ? q1[f0 + f] : nullptr;
-                fp.q2[f] = f < nf ? q2[f0 + f] : nullptr;
-            }
-            FV3HIP_CHECK_HIP(hipMemsetAsync(n_bad, 0, 16, st));
-            const bool sweep = mappm_sweep_eligible(n_inner, km, kn, kord, layout, in_dtype);
-            if (sweep) {
-                SweepArgs sa;
-                memset(&sa, 0, sizeof(sa));
-                sa.pe1 = pe1;
-                sa.pe2 = pe2;
-                for (int f = 0; f < nf; ++f) {
-                    sa.q1[f] = fp.q1[f];
-                    sa.q2[f] = fp.q2[f];
-                }
-                sa.col0 = col0;
-                sa.n_inner = n_inner;
-                sa.km = km;
-                sa.kn = kn;
-                sa.iv = iv;
-                sa.n_bad = n_bad;
-                sa.bad_cols = bad_cols;
-                mappm_sweep_launch(sa, nf, in_dtype, col_end, arith == FV3HIP_ARITH_FAST, st);
-            }
-#define LAUNCH_(T)                                                                                                          \
-    if (!sweep) switch (nf) {                                                                                               \
-        case 1: launch_merge_multi<T, 1>(pe1, fp, pe2, col0, col_end, n_inner, km, kn, iv, kord, layout, n_bad, bad_cols, st); break; \
-        case 2: launch_merge_multi<T, 2>(pe1, fp, pe2, col0, col_end, n_inner, km, kn, iv, kord, layout, n_bad, bad_cols, st); break; \
-        case 3: launch_merge_multi<T, 3>(pe1, fp, pe2, col0, col_end, n_inner, km, kn, iv, kord, layout, n_bad, bad_cols, st); break; \
-        default: launch_merge_multi<T, 4>(pe1, fp, pe2, col0, col_end, n_inner, km, kn, iv, kord, layout, n_bad, bad_cols, st); break; \
-    }                                                                                                                       \
-    for (int f = 0; f < nf; ++f)                                                                                            \
-        hipLaunchKernelGGL((mappm_fallback_kernel<T>), dim3((unsigned)fb_blocks), dim3(256), 0, st, static_cast<const T *>(pe1), \
-                           static_cast<const T *>(fp.q1[f]), static_cast<const T *>(pe2), fp.q2[f], col0, n_inner, km, kn, iv,    \
-                           kord, layout, n_bad, bad_cols, planes, ws_cols)
-            if (in_dtype == FV3HIP_F32) { LAUNCH_(float); } else { LAUNCH_(double); }
-#undef LAUNCH_
-            const int rc = check_launch("mappm multi-field kernel");
-            if (rc) return rc;
-        }
-    }
-    return FV3HIP_OK;
+    return remap_fields(pe1, q1, pe2, in_dtype, q2, n_fields, n_batch, n_inner, km, kn, iv, kord, layout, arith, workspace,
+                        workspace_bytes, stream);
 }
 
 // mappm_multi with the target interfaces on a horizontally coarser grid: pe2 is [n_batch][kn + 1][nyc][nxc] and every fine column
@@ -1730,17 +1477,15 @@ extern "C" int fv3hip_mappm_multi_coarse_target(const void *pe1, const void *con
                                                 int n_fields, int64_t n_batch, int ny, int nx, int factor, int km, int kn, int iv, int kord,
                                                 int arith, void *workspace, size_t workspace_bytes, void *stream)
 {
-    FV3HIP_REQUIRE(arith == FV3HIP_ARITH_EXACT || arith == FV3HIP_ARITH_FAST, "unknown arithmetic mode %d", arith);
     FV3HIP_REQUIRE(n_fields >= 0, "negative field count");
     if (n_fields == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(q1 && q2, "null pointer");
-    FV3HIP_REQUIRE(in_dtype == FV3HIP_F32 || in_dtype == FV3HIP_F64, "in_dtype must be F32 or F64, got %d", in_dtype);
-    FV3HIP_REQUIRE(n_batch >= 0 && ny >= 0 && nx >= 0 && kn >= 0, "negative extent");
+    FV3HIP_REQUIRE(ny >= 0 && nx >= 0, "negative extent");
+    const int64_t n_inner = (int64_t)ny * nx, ncol = n_batch * n_inner;
+    int rc = check_remap_args(arith, in_dtype, FV3HIP_LAYOUT_LEVEL_COL, n_batch, n_inner, km, kn, iv, kord);
+    if (rc) return rc;
     FV3HIP_REQUIRE(factor >= 1 && coarse_divides(ny, factor) && coarse_divides(nx, factor),
                    "extents (%d, %d) are not multiples of the factor %d (an odd extent is staggered: n - 1 must be)", ny, nx, factor);
-    FV3HIP_REQUIRE(iv >= -2 && iv <= 2, "iv must be in [-2, 2], got %d", iv);
-    FV3HIP_REQUIRE(km >= 4, "km must be >= 4 (ppm_profile reads a4(2,i,3)), got %d", km);
-    const int64_t n_inner = (int64_t)ny * nx, ncol = n_batch * n_inner;
     if (ncol == 0 || kn == 0) return FV3HIP_OK;
     const int nyc = coarse_extent(ny, factor), nxc = coarse_extent(nx, factor);
     const int64_t plane2 = (int64_t)nyc * nxc;
@@ -1748,52 +1493,19 @@ extern "C" int fv3hip_mappm_multi_coarse_target(const void *pe1, const void *con
         return fail(FV3HIP_EUNSUPPORTED, "coarse-target remap needs factor >= 2 and a shape the sweep kernel takes");
     FV3HIP_REQUIRE(pe1 && pe2_coarse, "null pointer");
     for (int f = 0; f < n_fields; ++f) FV3HIP_REQUIRE(q1[f] && q2[f], "null field pointer");
-    FV3HIP_REQUIRE(workspace && workspace_bytes >= fv3hip_mappm_workspace_bytes(ncol, km),
-                   "workspace too small: need %zu bytes, got %zu", fv3hip_mappm_workspace_bytes(ncol, km), workspace_bytes);
+    RemapWorkspace w;
+    rc = carve_workspace(workspace, workspace_bytes, fv3hip_mappm_workspace_bytes(ncol, km), ncol, w);
+    if (rc) return rc;
     hipStream_t st = as_stream(stream);
-    const int64_t ws_cols = ws_slots(ncol);
-    unsigned int *n_bad = static_cast<unsigned int *>(workspace);
-    unsigned int *bad_cols = reinterpret_cast<unsigned int *>(static_cast<char *>(workspace) + kCounterBytes);
-    float *planes = reinterpret_cast<float *>(static_cast<char *>(workspace) + kCounterBytes + ws_list_bytes(ncol));
-    for (int64_t col0 = 0; col0 < ncol; col0 += kMappmChunk) {
-        const int64_t col_end = (col0 + kMappmChunk < ncol) ? col0 + kMappmChunk : ncol;
-        const int64_t fb_threads = (col_end - col0 < kFallbackSlots) ? (col_end - col0) : kFallbackSlots;
-        const int64_t fb_blocks = ceil_div(fb_threads, 256);
-        for (int f0 = 0; f0 < n_fields; f0 += kMaxMultiFields) {
-            const int nf = (n_fields - f0 < kMaxMultiFields) ? n_fields - f0 : kMaxMultiFields;
-            FV3HIP_CHECK_HIP(hipMemsetAsync(n_bad, 0, 16, st));
-            SweepArgs sa;
-            memset(&sa, 0, sizeof(sa));
-            sa.pe1 = pe1;
-            sa.pe2 = pe2_coarse;
-            for (int f = 0; f < nf; ++f) {
-                sa.q1[f] = q1[f0 + f];
-                sa.q2[f] = q2[f0 + f];
-            }
-            sa.col0 = col0;
-            sa.n_inner = n_inner;
-            sa.km = km;
-            sa.kn = kn;
-            sa.iv = iv;
-            sa.n_bad = n_bad;
-            sa.bad_cols = bad_cols;
-            sa.pe2_f = factor;
-            sa.nx = nx;
-            sa.pe2_nx = nxc;
-            sa.pe2_plane = plane2;
-            mappm_sweep_launch(sa, nf, in_dtype, col_end, arith == FV3HIP_ARITH_FAST, st);
-#define LAUNCH_(T)                                                                                                                  \
-    for (int f = 0; f < nf; ++f)                                                                                                    \
-        hipLaunchKernelGGL((mappm_fallback_kernel<T>), dim3((unsigned)fb_blocks), dim3(256), 0, st, static_cast<const T *>(pe1),    \
-                           static_cast<const T *>(q1[f0 + f]), static_cast<const T *>(pe2_coarse), q2[f0 + f], col0, n_inner, km, kn, iv, \
-                           kord, (int)FV3HIP_LAYOUT_LEVEL_COL, n_bad, bad_cols, planes, ws_cols, factor, nx, nxc, plane2)
-            if (in_dtype == FV3HIP_F32) { LAUNCH_(float); } else { LAUNCH_(double); }
-#undef LAUNCH_
-            const int rc = check_launch("mappm coarse-target kernels");
-            if (rc) return rc;
-        }
-    }
-    return FV3HIP_OK;
+    return for_each_chunk_and_group(ncol, n_fields, w, st, "mappm coarse-target kernels", [&](int64_t col0, int64_t col_end, int f0, int nf) {
+        SweepArgs sa = sweep_args(pe1, pe2_coarse, q1 + f0, q2 + f0, nf, col0, n_inner, km, kn, iv, w);
+        sa.pe2_f = factor;
+        sa.nx = nx;
+        sa.pe2_nx = nxc;
+        sa.pe2_plane = plane2;
+        mappm_sweep_launch(sa, nf, in_dtype, col_end, arith == FV3HIP_ARITH_FAST, st);
+        launch_fallback(in_dtype, sa, nf, col_end - col0, col0, kord, FV3HIP_LAYOUT_LEVEL_COL, w, st);
+    });
 }
 
 extern "C" size_t fv3hip_mappm_block_mean_workspace_bytes(int64_t ncol, int km)
@@ -1807,86 +1519,50 @@ extern "C" int fv3hip_mappm_block_mean(const void *pe1, const void *const *q1, c
                                        float *const *scratch, float *const *mean, int n_fields, int64_t n_batch, int ny, int nx, int factor,
                                        int km, int kn, int iv, int kord, int arith, void *workspace, size_t workspace_bytes, void *stream)
 {
-    FV3HIP_REQUIRE(arith == FV3HIP_ARITH_EXACT || arith == FV3HIP_ARITH_FAST, "unknown arithmetic mode %d", arith);
     FV3HIP_REQUIRE(n_fields >= 0, "negative field count");
     if (n_fields == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(q1 && scratch && mean, "null pointer");
-    FV3HIP_REQUIRE(in_dtype == FV3HIP_F32 || in_dtype == FV3HIP_F64, "in_dtype must be F32 or F64, got %d", in_dtype);
-    FV3HIP_REQUIRE(n_batch >= 0 && ny >= 0 && nx >= 0 && kn >= 0, "negative extent");
-    FV3HIP_REQUIRE(iv >= -2 && iv <= 2, "iv must be in [-2, 2], got %d", iv);
-    FV3HIP_REQUIRE(km >= 4, "km must be >= 4 (ppm_profile reads a4(2,i,3)), got %d", km);
+    FV3HIP_REQUIRE(ny >= 0 && nx >= 0, "negative extent");
+    const int64_t n_inner = (int64_t)ny * nx, ncol = n_batch * n_inner;
+    int rc = check_remap_args(arith, in_dtype, FV3HIP_LAYOUT_LEVEL_COL, n_batch, n_inner, km, kn, iv, kord);
+    if (rc) return rc;
     FV3HIP_REQUIRE(area_repeat >= 1, "area_repeat must be >= 1");
     FV3HIP_REQUIRE(cmp_offset >= 0 && cmp_levels >= kn + cmp_offset, "compared levels: %d rows cannot serve %d layers at offset %d",
                    cmp_levels, kn, cmp_offset);
-    const int64_t n_inner = (int64_t)ny * nx, ncol = n_batch * n_inner;
     if (ncol == 0 || kn == 0) return FV3HIP_OK;
     if (!mappm_mean_eligible(ny, nx, factor, km, kn, kord, in_dtype) || ncol >= ((int64_t)1 << 32))
         return fail(FV3HIP_EUNSUPPORTED, "the fused remap + block mean needs factor 8, extents that are multiples of 8, kord <= 3, km >= 8, kn < 128");
-    const int nyc = ny / factor, nxc = nx / factor;
-    const int64_t plane2 = (int64_t)nyc * nxc;
+    const int nxc = nx / factor;
+    const int64_t plane2 = (int64_t)(ny / factor) * nxc;
     FV3HIP_REQUIRE(pe1 && pe2_coarse && level_coarse && area, "null pointer");
     for (int f = 0; f < n_fields; ++f) FV3HIP_REQUIRE(q1[f] && scratch[f] && mean[f], "null field pointer");
-    FV3HIP_REQUIRE(workspace && workspace_bytes >= fv3hip_mappm_block_mean_workspace_bytes(ncol, km),
-                   "workspace too small: need %zu bytes, got %zu", fv3hip_mappm_block_mean_workspace_bytes(ncol, km), workspace_bytes);
-    hipStream_t st = as_stream(stream);
-    const int64_t ws_cols = ws_slots(ncol);
-    unsigned int *n_bad = static_cast<unsigned int *>(workspace);
-    unsigned int *bad_cols = reinterpret_cast<unsigned int *>(static_cast<char *>(workspace) + kCounterBytes);
-    float *planes = reinterpret_cast<float *>(static_cast<char *>(workspace) + kCounterBytes + ws_list_bytes(ncol));
+    RemapWorkspace w;
+    rc = carve_workspace(workspace, workspace_bytes, fv3hip_mappm_block_mean_workspace_bytes(ncol, km), ncol, w);
+    if (rc) return rc;
     unsigned int *bad_blocks = reinterpret_cast<unsigned int *>(static_cast<char *>(workspace) + fv3hip_mappm_workspace_bytes(ncol, km));
-    unsigned int *rest_blocks = bad_blocks + kMappmChunk / 64;
+    hipStream_t st = as_stream(stream);
     // a launch = kMappmChunk columns' worth of blocks (the lists are sized for that); `col0` counts 64 columns per block
-    for (int64_t col0 = 0; col0 < ncol; col0 += kMappmChunk) {
-        const int64_t col_end = (col0 + kMappmChunk < ncol) ? col0 + kMappmChunk : ncol;
-        const int64_t fb_threads = (col_end - col0 < kFallbackSlots) ? (col_end - col0) : kFallbackSlots;
-        const int64_t fb_blocks = ceil_div(fb_threads, 256);
-        for (int f0 = 0; f0 < n_fields; f0 += kMaxMultiFields) {
-            const int nf = (n_fields - f0 < kMaxMultiFields) ? n_fields - f0 : kMaxMultiFields;
-            FV3HIP_CHECK_HIP(hipMemsetAsync(n_bad, 0, 16, st));
-            SweepArgs sa;
-            memset(&sa, 0, sizeof(sa));
-            sa.pe1 = pe1;
-            sa.pe2 = pe2_coarse;
-            for (int f = 0; f < nf; ++f) {
-                sa.q1[f] = q1[f0 + f];
-                sa.q2[f] = scratch[f0 + f];
-                sa.mean[f] = mean[f0 + f];
-            }
-            sa.col0 = col0;
-            sa.n_inner = n_inner;
-            sa.km = km;
-            sa.kn = kn;
-            sa.iv = iv;
-            sa.n_bad = n_bad;
-            sa.bad_cols = bad_cols;
-            sa.bad_blocks = bad_blocks;
-            sa.rest_blocks = rest_blocks;
-            sa.pe2_f = factor;
-            sa.nx = nx;
-            sa.pe2_nx = nxc;
-            sa.pe2_plane = plane2;
-            sa.area = area;
-            sa.area_repeat = area_repeat;
-            sa.lvl = level_coarse;
-            sa.cmp_levels = cmp_levels;
-            sa.cmp_offset = cmp_offset;
-            mappm_mean_launch(sa, nf, in_dtype, col_end, arith == FV3HIP_ARITH_FAST, st);
-            mappm_mean_rest_launch(sa, nf, in_dtype, (col_end - col0) / 64, st);
-            // blocks with an ill-formed column (normally none): all their columns through the sequential routine into the
-            // scratch rows (absolute column indices in the list: col0 = 0), then their means from there
-#define LAUNCH_(T)                                                                                                                  \
-    for (int f = 0; f < nf; ++f)                                                                                                    \
-        hipLaunchKernelGGL((mappm_fallback_kernel<T>), dim3((unsigned)fb_blocks), dim3(256), 0, st, static_cast<const T *>(pe1),    \
-                           static_cast<const T *>(q1[f0 + f]), static_cast<const T *>(pe2_coarse), scratch[f0 + f], (int64_t)0, n_inner, km, \
-                           kn, iv, kord, (int)FV3HIP_LAYOUT_LEVEL_COL, n_bad, bad_cols, planes, ws_cols, factor, nx, nxc, plane2)
-            if (in_dtype == FV3HIP_F32) { LAUNCH_(float); } else { LAUNCH_(double); }
-#undef LAUNCH_
-            mappm_mean_redo_launch(sa, nf, in_dtype, st);
-            const int rc = check_launch("mappm block-mean kernels");
-            if (rc) return rc;
-        }
-    }
-    return FV3HIP_OK;
+    return for_each_chunk_and_group(ncol, n_fields, w, st, "mappm block-mean kernels", [&](int64_t col0, int64_t col_end, int f0, int nf) {
+        SweepArgs sa = sweep_args(pe1, pe2_coarse, q1 + f0, scratch + f0, nf, col0, n_inner, km, kn, iv, w);
+        for (int f = 0; f < nf; ++f) sa.mean[f] = mean[f0 + f];
+        sa.bad_blocks = bad_blocks;
+        sa.rest_blocks = bad_blocks + kMappmChunk / 64;
+        sa.pe2_f = factor;
+        sa.nx = nx;
+        sa.pe2_nx = nxc;
+        sa.pe2_plane = plane2;
+        sa.area = area;
+        sa.area_repeat = area_repeat;
+        sa.lvl = level_coarse;
+        sa.cmp_levels = cmp_levels;
+        sa.cmp_offset = cmp_offset;
+        mappm_mean_launch(sa, nf, in_dtype, col_end, arith == FV3HIP_ARITH_FAST, st);
+        mappm_mean_rest_launch(sa, nf, in_dtype, (col_end - col0) / 64, st);
+        // blocks with an ill-formed column (normally none): all their columns through the sequential routine into the
+        // scratch rows (absolute column indices in the list: col0 = 0), then their means from there
+        launch_fallback(in_dtype, sa, nf, col_end - col0, 0, kord, FV3HIP_LAYOUT_LEVEL_COL, w, st);
+        mappm_mean_redo_launch(sa, nf, in_dtype, st);
+    });
 }
 
 extern "C" int fv3hip_interpolate_2d(const void *xp, const void *x, const void *y, int64_t n_batch, int64_t n_inner, int n_in,

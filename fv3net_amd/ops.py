@@ -756,6 +756,19 @@ def _arith_code(arith: Optional[str]) -> int:
     return _lib.ARITH_FAST if mode == "fast" else _lib.ARITH_EXACT
 
 
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _remap_inputs(pe1: torch.Tensor, pe2: torch.Tensor, fields):
+    """The remap's arrays in one float dtype (float64 if any of them is) and contiguous."""
+    dtypes = {t.dtype for t in (pe1, pe2, *fields)}
+    if len(dtypes) > 1:
+        common = torch.float64 if torch.float64 in dtypes else torch.float32
+        pe1, pe2, fields = pe1.to(common), pe2.to(common), [q.to(common) for q in fields]
+    return pe1.contiguous(), pe2.contiguous(), [q.contiguous() for q in fields]
+
+
 def mappm(
     pe1: torch.Tensor,
     q1: torch.Tensor,
@@ -771,38 +784,7 @@ def mappm(
     must match.  ``z_axis=-1`` is the [column, level] layout f2py callers use; any other
     position is handled in place as the native [.., level, .. columns ..] layout.
     Returns float32 with kn levels along ``z_axis``."""
-    dev = _require_device(pe1, q1, pe2)
-    if not (pe1.dtype == q1.dtype == pe2.dtype):
-        common = torch.float64 if torch.float64 in (pe1.dtype, q1.dtype, pe2.dtype) else torch.float32
-        pe1, q1, pe2 = pe1.to(common), q1.to(common), pe2.to(common)
-    pe1, q1, pe2 = pe1.contiguous(), q1.contiguous(), pe2.contiguous()
-    nd = q1.dim()
-    z_axis = z_axis % nd
-    km, kn = int(q1.shape[z_axis]), int(pe2.shape[z_axis]) - 1
-    if int(pe1.shape[z_axis]) != km + 1:
-        raise ValueError("f_in must have a vertical dimension one shorter than p_in")
-
-    def others(t):
-        return tuple(t.shape[:z_axis]) + tuple(t.shape[z_axis + 1:])
-
-    if not (others(pe1) == others(q1) == others(pe2)):
-        raise ValueError("All dimensions except vertical must be same size for p_in, f_in and p_out")
-    n_batch, n_inner = _prod(q1.shape[:z_axis]), _prod(q1.shape[z_axis + 1:])
-    if z_axis == nd - 1:
-        layout, nb, ni = _lib.LAYOUT_COL_LEVEL, n_batch, 1
-    else:
-        layout, nb, ni = _lib.LAYOUT_LEVEL_COL, n_batch, n_inner
-    shape = list(q1.shape)
-    shape[z_axis] = kn
-    out = torch.empty(shape, dtype=torch.float32, device=dev)
-    ncol = nb * ni
-    nbytes = int(_lib.load().fv3hip_mappm_workspace_bytes(ncol, km))
-    ws = _workspace(dev, nbytes)
-    _lib.call_on(dev,
-        "fv3hip_mappm", _ptr(pe1), _ptr(q1), _ptr(pe2), _float_code(q1), _ptr(out), nb, ni, km, kn,
-        int(iv), int(kord), layout, _arith_code(arith), _ptr(ws), ws.numel(), _stream(dev),
-    )
-    return out
+    return mappm_multi(pe1, [q1], pe2, iv=iv, kord=kord, z_axis=z_axis, arith=arith)[0]
 
 
 def mappm_multi(pe1: torch.Tensor, fields: Sequence[torch.Tensor], pe2: torch.Tensor, iv: int = 1, kord: int = 1,
@@ -815,11 +797,7 @@ def mappm_multi(pe1: torch.Tensor, fields: Sequence[torch.Tensor], pe2: torch.Te
     if not fields:
         return []
     dev = _require_device(pe1, pe2, *fields)
-    dtypes = {t.dtype for t in (pe1, pe2, *fields)}
-    if len(dtypes) > 1:
-        common = torch.float64 if torch.float64 in dtypes else torch.float32
-        pe1, pe2, fields = pe1.to(common), pe2.to(common), [q.to(common) for q in fields]
-    pe1, pe2, fields = pe1.contiguous(), pe2.contiguous(), [q.contiguous() for q in fields]
+    pe1, pe2, fields = _remap_inputs(pe1, pe2, fields)
     q1 = fields[0]
     nd = q1.dim()
     z_axis = z_axis % nd
@@ -841,11 +819,8 @@ def mappm_multi(pe1: torch.Tensor, fields: Sequence[torch.Tensor], pe2: torch.Te
     shape[z_axis] = kn
     outs = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in fields]
     ws = _workspace(dev, int(_lib.load().fv3hip_mappm_workspace_bytes(nb * ni, km)))
-    n = len(fields)
-    q_ptrs = (ctypes.c_void_p * n)(*[q.data_ptr() for q in fields])
-    o_ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
-    _lib.call_on(dev, "fv3hip_mappm_multi", _ptr(pe1), q_ptrs, _ptr(pe2), _float_code(q1), o_ptrs, n, nb, ni, km, kn, int(iv), int(kord),
-              layout, _arith_code(arith), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.call_on(dev, "fv3hip_mappm_multi", _ptr(pe1), _ptr_array(fields), _ptr(pe2), _float_code(q1), _ptr_array(outs), len(fields),
+                 nb, ni, km, kn, int(iv), int(kord), layout, _arith_code(arith), _ptr(ws), ws.numel(), _stream(dev))
     return outs
 
 
@@ -868,11 +843,7 @@ def mappm_multi_coarse_target(pe1: torch.Tensor, fields: Sequence[torch.Tensor],
     if nd < 3 or z_axis % nd != nd - 3 or factor < 2:
         return fallback()
     dev = _require_device(pe1, pe2_coarse, *fields)
-    dtypes = {t.dtype for t in (pe1, pe2_coarse, *fields)}
-    if len(dtypes) > 1:
-        common = torch.float64 if torch.float64 in dtypes else torch.float32
-        pe1, pe2_coarse, fields = pe1.to(common), pe2_coarse.to(common), [q.to(common) for q in fields]
-    pe1, pe2_coarse, fields = pe1.contiguous(), pe2_coarse.contiguous(), [q.contiguous() for q in fields]
+    pe1, pe2_coarse, fields = _remap_inputs(pe1, pe2_coarse, fields)
     q1 = fields[0]
     km, kn = int(q1.shape[-3]), int(pe2_coarse.shape[-3]) - 1
     ny, nx = int(q1.shape[-2]), int(q1.shape[-1])
@@ -886,12 +857,10 @@ def mappm_multi_coarse_target(pe1: torch.Tensor, fields: Sequence[torch.Tensor],
     nb = _prod(q1.shape[:-3])
     outs = [torch.empty(tuple(q1.shape[:-3]) + (kn, ny, nx), dtype=torch.float32, device=dev) for _ in fields]
     ws = _workspace(dev, int(_lib.load().fv3hip_mappm_workspace_bytes(nb * ny * nx, km)))
-    n = len(fields)
-    q_ptrs = (ctypes.c_void_p * n)(*[q.data_ptr() for q in fields])
-    o_ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
     try:
-        _lib.call_on(dev, "fv3hip_mappm_multi_coarse_target", _ptr(pe1), q_ptrs, _ptr(pe2_coarse), _float_code(q1), o_ptrs, n, nb, ny, nx,
-                     factor, km, kn, int(iv), int(kord), _arith_code(arith), _ptr(ws), ws.numel(), _stream(dev))
+        _lib.call_on(dev, "fv3hip_mappm_multi_coarse_target", _ptr(pe1), _ptr_array(fields), _ptr(pe2_coarse), _float_code(q1),
+                     _ptr_array(outs), len(fields), nb, ny, nx, factor, km, kn, int(iv), int(kord), _arith_code(arith), _ptr(ws),
+                     ws.numel(), _stream(dev))
     except _lib.Fv3HipError as err:
         if err.code != _lib.EUNSUPPORTED:
             raise
@@ -952,12 +921,10 @@ def mappm_block_mean(pe1: torch.Tensor, fields: Sequence[torch.Tensor], pe2_coar
     # fine-size rows that only evicted values and redone blocks pass through: one allocation, kept per (device, stream, size)
     scratch = _scratch_rows(dev, n, nb * kn * ny * nx)
     outs = [torch.empty(batch + (kn,) + coarse_hw, dtype=torch.float32, device=dev) for _ in fields]
-    q_ptrs = (ctypes.c_void_p * n)(*[q.data_ptr() for q in fields])
-    s_ptrs = (ctypes.c_void_p * n)(*[scratch[i % len(scratch)].data_ptr() for i in range(n)])  # (a sweep takes four fields)
-    o_ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    s_ptrs = _ptr_array([scratch[i % len(scratch)] for i in range(n)])  # (a sweep takes four fields)
     try:
-        _lib.call_on(dev, "fv3hip_mappm_block_mean", _ptr(pe1), q_ptrs, _ptr(pe2_coarse), _ptr(lvl), kn + cmp_offset, cmp_offset,
-                     _float_code(q1), _ptr(area), area_repeat, s_ptrs, o_ptrs, n, nb, ny, nx, 8, km, kn, int(iv), int(kord),
+        _lib.call_on(dev, "fv3hip_mappm_block_mean", _ptr(pe1), _ptr_array(fields), _ptr(pe2_coarse), _ptr(lvl), kn + cmp_offset, cmp_offset,
+                     _float_code(q1), _ptr(area), area_repeat, s_ptrs, _ptr_array(outs), n, nb, ny, nx, 8, km, kn, int(iv), int(kord),
                      _arith_code(arith), _ptr(ws), ws.numel(), _stream(dev))
     except _lib.Fv3HipError as err:
         if err.code != _lib.EUNSUPPORTED:

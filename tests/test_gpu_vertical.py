@@ -5,6 +5,7 @@ so the HIP result must be BIT-IDENTICAL to the C restatement (which tests/test_o
 pins bit-for-bit to the reference's own Fortran).  pressure_at_interface is a sequential
 cumulative sum in the array dtype: bit-identical to numpy.cumsum.
 """
+import functools
 import json
 import os
 
@@ -325,6 +326,42 @@ def test_mappm_multi_field_bit_exact(device, n_fields, iv, kord):
     for f, q in enumerate(fields):
         ref = mappm_c.mappm(pe1, q, pe2, iv, kord)
         assert _bits_equal(ops.as_numpy(res[f]), ref), (f, np.nanmax(np.abs(ops.as_numpy(res[f]) - ref)))
+
+
+@functools.lru_cache(maxsize=None)
+def _short_columns(km, kn):
+    """130 short columns, three scalings of their field, and the oracle's result for every (iv, kord) the test below
+    runs: computed once per shape, shared by its float32 and float64 cases, never modified."""
+    rng = np.random.default_rng(1000 * km + kn)
+    pe1, q, pe2 = _columns(rng, 130, km, kn)
+    fields = [q, q * np.float32(-0.37), q * np.float32(12.5)]
+    refs = {(iv, kord): [mappm_c.mappm(pe1, f, pe2, iv, kord) for f in fields] for iv in (-2, -1, 0, 1, 2) for kord in (1, 4, 6, 7)}
+    assert all(np.isfinite(r).all() for rs in refs.values() for r in rs)
+    return pe1, fields, pe2, refs
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+@pytest.mark.parametrize("kn", [3, 11])
+@pytest.mark.parametrize("km", [4, 5, 6, 8])
+def test_mappm_short_columns_single_and_multi_field_bit_exact(device, km, kn, dt):
+    """Columns so short that the boundary formulas meet each other: at km = 4 the merge kernel computes the bottom
+    boundary in the iteration right after the prologue's top boundary, at km = 5 and 6 the interior edge value is computed
+    for one or two levels only.  130 columns in the [column, level] layout are not whole waves of a batch plane, so kord <= 6
+    takes the merge kernel (never the sweep kernel) and kord = 7 the sequential routine.  A single-field call, a call with
+    three scalings of the field and a one-field multi call all give the oracle's bits."""
+    from fv3net_amd import ops
+
+    pe1, fields, pe2, refs = _short_columns(km, kn)
+    d_pe1, d_pe2 = _dev(pe1.astype(dt), device), _dev(pe2.astype(dt), device)
+    d_fields = [_dev(f.astype(dt), device) for f in fields]
+    for (iv, kord), ref in refs.items():
+        single = ops.as_numpy(ops.mappm(d_pe1, d_fields[0], d_pe2, iv=iv, kord=kord))
+        assert _bits_equal(single, ref[0]), (iv, kord)
+        multi = ops.mappm_multi(d_pe1, d_fields, d_pe2, iv=iv, kord=kord)
+        for f, want in enumerate(ref):
+            assert _bits_equal(ops.as_numpy(multi[f]), want), (iv, kord, f)
+        one = ops.as_numpy(ops.mappm_multi(d_pe1, d_fields[:1], d_pe2, iv=iv, kord=kord)[0])
+        assert np.array_equal(single.view(np.uint32), one.view(np.uint32)), (iv, kord)
 
 
 def test_mappm_multi_level_col_layout_f64_and_errors(device):
