@@ -17,9 +17,10 @@ namespace fv3hip {
 namespace {
 
 template <typename T>
-__device__ __forceinline__ bool is_nan(T x)
+__device__ __forceinline__ bool nan_of(T x)
 {
-    return x != x;
+    if constexpr (std::is_floating_point_v<T>) return x != x;
+    return false;
 }
 
 // N elements of T as one register tuple; 16-byte ones become global_load_dwordx4.
@@ -32,19 +33,7 @@ using Vec = typename VecOf<T, N>::type;
 
 template <typename A, typename B>
 struct Promote {
-    using type = float;
-};
-template <>
-struct Promote<double, double> {
-    using type = double;
-};
-template <>
-struct Promote<double, float> {
-    using type = double;
-};
-template <>
-struct Promote<float, double> {
-    using type = double;
+    using type = std::conditional_t<std::is_same_v<A, double> || std::is_same_v<B, double>, double, float>;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -76,8 +65,8 @@ __global__ void wavg_generic_kernel(const To *__restrict__ obj, const Tw *__rest
             for (int dx = 0; dx < bx; ++dx) {
                 const Tw w0 = pw[(int64_t)dy * nx + dx];
                 const P p = (P)po[(int64_t)dy * nx + dx] * (P)w0;
-                if (!is_nan(p)) num += p;
-                if (!is_nan(w0)) den += w0;
+                if (!nan_of(p)) num += p;
+                if (!nan_of(w0)) den += w0;
             }
         }
         out[idx] = num / (P)den;
@@ -91,7 +80,110 @@ __global__ void wavg_generic_kernel(const To *__restrict__ obj, const Tw *__rest
 //   BPL  = blocks held by one lane         (VEC / F, when F <  VEC)
 // Thread s of a spatial slab handles vector column xv = s % (nx/VEC) of block row
 // Y = s / (nx/VEC); gridDim.y walks (weight slice, z-chunk) pairs.
+// The pieces below are shared by wavg_block_kernel and mass_wavg_block_kernel; block_sums is
+// the summation order that remap.hip's fused mean reproduces bit for bit.
 // ---------------------------------------------------------------------------------------
+template <typename P, int F>
+struct BlockTile {
+    static constexpr int VEC = 16 / sizeof(P);
+    static constexpr int LPB = (F >= VEC) ? F / VEC : 1;
+    static constexpr int BPL = (F >= VEC) ? 1 : VEC / F;
+    static constexpr int EPB = VEC / BPL;  // elements of one lane's vector that fall in one block
+};
+template <typename T, typename P, int F>
+using BlockSums = T[BlockTile<P, F>::BPL];  // one lane's partial sums
+
+// Where this thread sits in its slab; threads past the slab stay for the shuffles with zeros for data.
+struct SlabPos {
+    bool active;
+    int Y, xv;
+    int64_t sp;  // offset inside one slice
+};
+
+template <typename P, int F>
+__device__ __forceinline__ SlabPos slab_pos(int ny, int nx)
+{
+    constexpr int VEC = BlockTile<P, F>::VEC;
+    const int XV = nx / VEC;
+    const int64_t S = (int64_t)(ny / F) * XV;
+    const int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    SlabPos p;
+    p.active = s < S;
+    p.Y = p.active ? (int)(s / XV) : 0;
+    p.xv = p.active ? (int)(s % XV) : 0;
+    p.sp = (int64_t)p.Y * F * nx + (int64_t)p.xv * VEC;
+    return p;
+}
+
+// Entry gy of the (weight slice, z-chunk) walk: slice g and the outer slices [o_begin, o_end) of its chunk.
+struct ZChunk {
+    int64_t g, o_begin, o_end;
+};
+
+__device__ __forceinline__ ZChunk z_chunk(int64_t gy, int64_t repeat, int zsplit, int64_t n_outer)
+{
+    const int64_t zper = (repeat + zsplit - 1) / zsplit;
+    ZChunk z;
+    z.g = gy / zsplit;
+    z.o_begin = z.g * repeat + (int)(gy % zsplit) * zper;
+    z.o_end = z.o_begin + zper;
+    if (z.o_end > (z.g + 1) * repeat) z.o_end = (z.g + 1) * repeat;
+    if (z.o_end > n_outer) z.o_end = n_outer;
+    return z;
+}
+
+// VEC elements at base + off, zeros for a thread that has none; NT: streamed data that is read once.
+template <bool NT, int VEC, typename T>
+__device__ __forceinline__ Vec<T, VEC> load_row(const T *base, int64_t off, bool active)
+{
+    Vec<T, VEC> v;
+    if (active) {
+        const Vec<T, VEC> *p = reinterpret_cast<const Vec<T, VEC> *>(base + off);
+        v = NT ? __builtin_nontemporal_load(p) : *p;
+    } else {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) v[e] = 0;
+    }
+    return v;
+}
+
+// acc[b] = sum of the terms of block b of this lane over the F x VEC tile whose row dy is row(dy): dy outer, e inner,
+// each term already rounded, a NaN term counted as zero; then the LPB lanes of a block are added, m = 1, 2, 4, ...
+template <typename P, int F, typename T, typename Row>
+__device__ __forceinline__ void block_sums(BlockSums<T, P, F> &acc, Row row)
+{
+    using B = BlockTile<P, F>;
+#pragma unroll
+    for (int b = 0; b < B::BPL; ++b) acc[b] = 0;
+#pragma unroll
+    for (int dy = 0; dy < F; ++dy) {
+        const Vec<T, B::VEC> t = row(dy);
+#pragma unroll
+        for (int e = 0; e < B::VEC; ++e) acc[e / B::EPB] += nan_of(t[e]) ? (T)0 : t[e];
+    }
+#pragma unroll
+    for (int m = 1; m < B::LPB; m <<= 1) acc[0] += __shfl_xor(acc[0], m);
+}
+
+// out[o][Y][X] = num / den for the BPL blocks of this lane, stored by the first lane of each block
+template <typename P, int F, typename D>
+__device__ __forceinline__ void store_means(P *__restrict__ out, int64_t o, int ny, int nx, const SlabPos &s,
+                                            const BlockSums<P, P, F> &num, const BlockSums<D, P, F> &den)
+{
+    using B = BlockTile<P, F>;
+    if (s.active && (s.xv % B::LPB) == 0) {
+        P *dst = out + (o * (ny / F) + s.Y) * (int64_t)(nx / F) + (int64_t)(s.xv / B::LPB) * B::BPL;
+        if (B::BPL == 1) {
+            dst[0] = num[0] / (P)den[0];
+        } else {
+            Vec<P, B::BPL> r;
+#pragma unroll
+            for (int b = 0; b < B::BPL; ++b) r[b] = num[b] / (P)den[b];
+            *reinterpret_cast<Vec<P, B::BPL> *>(dst) = r;
+        }
+    }
+}
+
 template <typename To, typename Tw, int F>
 __global__ __launch_bounds__(256) void wavg_block_kernel(
     const To *__restrict__ obj, const Tw *__restrict__ w,
@@ -99,102 +191,39 @@ __global__ __launch_bounds__(256) void wavg_block_kernel(
     int64_t w_repeat, int zsplit, int64_t n_gy)
 {
     using P = typename Promote<To, Tw>::type;
-    constexpr int VEC = 16 / sizeof(P);
-    constexpr int LPB = (F >= VEC) ? F / VEC : 1;
-    constexpr int BPL = (F >= VEC) ? 1 : VEC / F;
-    constexpr int EPB = VEC / BPL;  // elements of one lane's vector that fall in one block
+    constexpr int VEC = BlockTile<P, F>::VEC, BPL = BlockTile<P, F>::BPL;
     constexpr bool kCacheW = (F * VEC <= 64);
-
-    const int XV = nx / VEC;
-    const int nyo = ny / F, nxo = nx / F;
-    const int64_t S = (int64_t)nyo * XV;
-    const int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    const bool active = s < S;
-    const int Y = active ? (int)(s / XV) : 0;
-    const int xv = active ? (int)(s % XV) : 0;
-    const int64_t sp = (int64_t)Y * F * nx + (int64_t)xv * VEC;  // offset inside one slice
+    const SlabPos s = slab_pos<P, F>(ny, nx);
     const int64_t slice = (int64_t)ny * nx;
-    const int64_t zper = (w_repeat + zsplit - 1) / zsplit;
 
     for (int64_t gy = blockIdx.y; gy < n_gy; gy += gridDim.y) {
-        const int64_t g = gy / zsplit;
-        const int part = (int)(gy % zsplit);
-        const int64_t o_begin = g * w_repeat + part * zper;
-        int64_t o_end = o_begin + zper;
-        if (o_end > (g + 1) * w_repeat) o_end = (g + 1) * w_repeat;
-        if (o_end > n_outer) o_end = n_outer;
-
-        const Tw *pw = w + g * slice + sp;
+        const ZChunk z = z_chunk(gy, w_repeat, zsplit, n_outer);
+        const Tw *pw = w + z.g * slice + s.sp;
         P wreg[kCacheW ? F : 1][VEC];
         Tw den[BPL];  // accumulated in the weights' dtype, like weights.coarsen(...).sum()
+        block_sums<P, F>(den, [&](int dy) {
+            const Vec<Tw, VEC> wv = load_row<false, VEC>(pw, (int64_t)dy * nx, s.active);
+            if constexpr (kCacheW) {
 #pragma unroll
-        for (int b = 0; b < BPL; ++b) den[b] = 0;
-#pragma unroll
-        for (int dy = 0; dy < F; ++dy) {
-            Vec<Tw, VEC> wv;
-            if (active) {
-                wv = *reinterpret_cast<const Vec<Tw, VEC> *>(pw + (int64_t)dy * nx);
-            } else {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) wv[e] = 0;
+                for (int e = 0; e < VEC; ++e) wreg[dy][e] = (P)wv[e];
             }
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const Tw w0 = wv[e];
-                if (kCacheW) wreg[kCacheW ? dy : 0][e] = (P)w0;
-                den[e / EPB] += is_nan(w0) ? (Tw)0 : w0;
-            }
-        }
-#pragma unroll
-        for (int m = 1; m < LPB; m <<= 1) den[0] += __shfl_xor(den[0], m);
-
-        for (int64_t o = o_begin; o < o_end; ++o) {
-            const To *po = obj + o * slice + sp;
+            return wv;
+        });
+        for (int64_t o = z.o_begin; o < z.o_end; ++o) {
+            const To *po = obj + o * slice + s.sp;
             Vec<To, VEC> ov[F];
 #pragma unroll
-            for (int dy = 0; dy < F; ++dy) {
-                if (active) {
-                    ov[dy] = __builtin_nontemporal_load(
-                        reinterpret_cast<const Vec<To, VEC> *>(po + (int64_t)dy * nx));
-                } else {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) ov[dy][e] = 0;
-                }
-            }
+            for (int dy = 0; dy < F; ++dy) ov[dy] = load_row<true, VEC>(po, (int64_t)dy * nx, s.active);
             P num[BPL];
-#pragma unroll
-            for (int b = 0; b < BPL; ++b) num[b] = 0;
-#pragma unroll
-            for (int dy = 0; dy < F; ++dy) {
+            block_sums<P, F>(num, [&](int dy) {
                 Vec<Tw, VEC> wv;
-                if (!kCacheW) {
-                    if (active) {
-                        wv = *reinterpret_cast<const Vec<Tw, VEC> *>(pw + (int64_t)dy * nx);
-                    } else {
+                if constexpr (!kCacheW) wv = load_row<false, VEC>(pw, (int64_t)dy * nx, s.active);
+                Vec<P, VEC> p;
 #pragma unroll
-                        for (int e = 0; e < VEC; ++e) wv[e] = 0;
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    const P ww = kCacheW ? wreg[kCacheW ? dy : 0][e] : (P)wv[e];
-                    const P p = (P)ov[dy][e] * ww;
-                    num[e / EPB] += is_nan(p) ? (P)0 : p;
-                }
-            }
-#pragma unroll
-            for (int m = 1; m < LPB; m <<= 1) num[0] += __shfl_xor(num[0], m);
-            if (active && (xv % LPB) == 0) {
-                P *dst = out + (o * nyo + Y) * (int64_t)nxo + (int64_t)(xv / LPB) * BPL;
-                if (BPL == 1) {
-                    dst[0] = num[0] / (P)den[0];
-                } else {
-                    Vec<P, BPL> r;
-#pragma unroll
-                    for (int b = 0; b < BPL; ++b) r[b] = num[b] / (P)den[b];
-                    *reinterpret_cast<Vec<P, BPL> *>(dst) = r;
-                }
-            }
+                for (int e = 0; e < VEC; ++e) p[e] = (P)ov[dy][e] * (kCacheW ? wreg[kCacheW ? dy : 0][e] : (P)wv[e]);
+                return p;
+            });
+            store_means<P, F>(out, o, ny, nx, s, num, den);
         }
     }
 }
@@ -219,219 +248,146 @@ __global__ __launch_bounds__(256) void mass_wavg_block_kernel(
     int64_t a_repeat, int zsplit, int64_t n_gy)
 {
     using P = typename Promote<Tf, Ta>::type;
-    constexpr int VEC = 16 / sizeof(P);
-    constexpr int LPB = (F >= VEC) ? F / VEC : 1;
-    constexpr int BPL = (F >= VEC) ? 1 : VEC / F;
-    constexpr int EPB = VEC / BPL;
-
-    const int XV = nx / VEC;
-    const int nyo = ny / F, nxo = nx / F;
-    const int64_t S = (int64_t)nyo * XV;
-    const int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    const bool active = s < S;
-    const int Y = active ? (int)(s / XV) : 0;
-    const int xv = active ? (int)(s % XV) : 0;
-    const int64_t sp = (int64_t)Y * F * nx + (int64_t)xv * VEC;
+    constexpr int VEC = BlockTile<P, F>::VEC, BPL = BlockTile<P, F>::BPL;
+    const SlabPos s = slab_pos<P, F>(ny, nx);
     const int64_t slice = (int64_t)ny * nx;
-    const int64_t zper = (a_repeat + zsplit - 1) / zsplit;
 
     for (int64_t gy = blockIdx.y; gy < n_gy; gy += gridDim.y) {
-        const int64_t g = gy / zsplit;
-        const int part = (int)(gy % zsplit);
-        const int64_t o_begin = g * a_repeat + part * zper;
-        int64_t o_end = o_begin + zper;
-        if (o_end > (g + 1) * a_repeat) o_end = (g + 1) * a_repeat;
-        if (o_end > n_outer) o_end = n_outer;
+        const ZChunk z = z_chunk(gy, a_repeat, zsplit, n_outer);
         // the block's area stays in registers over the levels that share it
         P areg[F][VEC];
 #pragma unroll
         for (int dy = 0; dy < F; ++dy) {
-            Vec<Ta, VEC> av;
-            if (active) {
-                av = *reinterpret_cast<const Vec<Ta, VEC> *>(area + g * slice + sp + (int64_t)dy * nx);
-            } else {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) av[e] = 0;
-            }
+            const Vec<Ta, VEC> av = load_row<false, VEC>(area, z.g * slice + s.sp + (int64_t)dy * nx, s.active);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) areg[dy][e] = (P)av[e];
         }
-        for (int64_t o = o_begin; o < o_end; ++o) {
+        for (int64_t o = z.o_begin; o < z.o_end; ++o) {
             P wreg[F][VEC];
             P den[BPL];
-#pragma unroll
-            for (int b = 0; b < BPL; ++b) den[b] = 0;
-#pragma unroll
-            for (int dy = 0; dy < F; ++dy) {
-                Vec<Tf, VEC> dv;
-                if (active && delp) {
-                    dv = __builtin_nontemporal_load(reinterpret_cast<const Vec<Tf, VEC> *>(delp + o * slice + sp + (int64_t)dy * nx));
-                } else {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) dv[e] = 0;
-                }
+            block_sums<P, F>(den, [&](int dy) {
+                const Vec<Tf, VEC> dv = load_row<true, VEC>(delp, o * slice + s.sp + (int64_t)dy * nx, s.active && delp);
+                Vec<P, VEC> wv;
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
                     // (delp == nullptr: plain 2-D weights shared by the NF fields -- the surface-data means)
-                    const P w0 = delp ? (P)dv[e] * areg[dy][e] : (active ? areg[dy][e] : (P)0);
-                    wreg[dy][e] = w0;
-                    den[e / EPB] += is_nan(w0) ? (P)0 : w0;
+                    wv[e] = wreg[dy][e] = delp ? (P)dv[e] * areg[dy][e] : (s.active ? areg[dy][e] : (P)0);
                 }
-            }
-#pragma unroll
-            for (int m = 1; m < LPB; m <<= 1) den[0] += __shfl_xor(den[0], m);
+                return wv;
+            });
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
-                const Tf *po = static_cast<const Tf *>(fp.obj[f]) + o * slice + sp;
                 Vec<Tf, VEC> ov[F];
 #pragma unroll
-                for (int dy = 0; dy < F; ++dy) {
-                    if (active) {
-                        ov[dy] = __builtin_nontemporal_load(reinterpret_cast<const Vec<Tf, VEC> *>(po + (int64_t)dy * nx));
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < VEC; ++e) ov[dy][e] = 0;
-                    }
-                }
+                for (int dy = 0; dy < F; ++dy)
+                    ov[dy] = load_row<true, VEC>(static_cast<const Tf *>(fp.obj[f]), o * slice + s.sp + (int64_t)dy * nx, s.active);
                 P num[BPL];
+                block_sums<P, F>(num, [&](int dy) {
+                    Vec<P, VEC> p;
 #pragma unroll
-                for (int b = 0; b < BPL; ++b) num[b] = 0;
-#pragma unroll
-                for (int dy = 0; dy < F; ++dy) {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) {
-                        const P p = (P)ov[dy][e] * wreg[dy][e];
-                        num[e / EPB] += is_nan(p) ? (P)0 : p;
-                    }
-                }
-#pragma unroll
-                for (int m = 1; m < LPB; m <<= 1) num[0] += __shfl_xor(num[0], m);
-                if (active && (xv % LPB) == 0) {
-                    P *dst = static_cast<P *>(fp.out[f]) + (o * nyo + Y) * (int64_t)nxo + (int64_t)(xv / LPB) * BPL;
-                    if (BPL == 1) {
-                        dst[0] = num[0] / den[0];
-                    } else {
-                        Vec<P, BPL> r;
-#pragma unroll
-                        for (int b = 0; b < BPL; ++b) r[b] = num[b] / den[b];
-                        *reinterpret_cast<Vec<P, BPL> *>(dst) = r;
-                    }
-                }
+                    for (int e = 0; e < VEC; ++e) p[e] = (P)ov[dy][e] * wreg[dy][e];
+                    return p;
+                });
+                store_means<P, F>(static_cast<P *>(fp.out[f]), o, ny, nx, s, num, den);
             }
         }
     }
 }
 
-template <typename Tf, typename Ta, int F>
-int launch_mass_wavg(const MassFieldPtrs &fp, int nf, const Tf *delp, const Ta *area, int64_t n_outer, int ny, int nx,
-                     int64_t a_repeat, hipStream_t stream)
+// Grid of the two kernels above.  Split the levels that share a weight slice until the grid fills the chip several
+// times over (256 CUs x 8 blocks of 256 threads), but keep chunks long enough to amortise the weight loads.
+struct BlockPlan {
+    dim3 grid;
+    int zsplit;
+    int64_t n_gy;
+};
+
+template <typename P, int F>
+BlockPlan plan_block_average(int ny, int nx, int64_t n_outer, int64_t repeat)
 {
-    using P = typename Promote<Tf, Ta>::type;
-    constexpr int VEC = 16 / sizeof(P);
-    const int64_t S = (int64_t)(ny / F) * (nx / VEC);
-    const int64_t n_groups = n_outer / a_repeat;
-    const int64_t gx = ceil_div(S, 256);
+    const int64_t gx = ceil_div((int64_t)(ny / F) * (nx / BlockTile<P, F>::VEC), 256);
+    const int64_t n_groups = n_outer / repeat;
     int zsplit = 1;
-    const int64_t want_blocks = 256 * 16;
-    while (gx * n_groups * zsplit < want_blocks && (a_repeat / (zsplit * 2)) >= 4) zsplit *= 2;
+    while (gx * n_groups * zsplit < 256 * 16 && (repeat / (zsplit * 2)) >= 4) zsplit *= 2;
     const int64_t n_gy = n_groups * zsplit;
-    dim3 grid((unsigned)gx, (unsigned)(n_gy < 65535 ? n_gy : 65535));
-    switch (nf) {
-        case 1: hipLaunchKernelGGL((mass_wavg_block_kernel<Tf, Ta, F, 1>), grid, dim3(256), 0, stream, fp, delp, area, n_outer, ny, nx, a_repeat, zsplit, n_gy); break;
-        case 2: hipLaunchKernelGGL((mass_wavg_block_kernel<Tf, Ta, F, 2>), grid, dim3(256), 0, stream, fp, delp, area, n_outer, ny, nx, a_repeat, zsplit, n_gy); break;
-        case 3: hipLaunchKernelGGL((mass_wavg_block_kernel<Tf, Ta, F, 3>), grid, dim3(256), 0, stream, fp, delp, area, n_outer, ny, nx, a_repeat, zsplit, n_gy); break;
-        default: hipLaunchKernelGGL((mass_wavg_block_kernel<Tf, Ta, F, 4>), grid, dim3(256), 0, stream, fp, delp, area, n_outer, ny, nx, a_repeat, zsplit, n_gy); break;
-    }
-    return check_launch("mass_wavg_block_kernel");
+    return {dim3((unsigned)gx, (unsigned)(n_gy < 65535 ? n_gy : 65535)), zsplit, n_gy};
+}
+
+// Rows are whole vectors and every pointer is aligned for VEC elements of its type.
+template <int VEC, typename... T>
+bool rows_vectorise(int nx, const T *...p)
+{
+    return nx % VEC == 0 && ((reinterpret_cast<uintptr_t>(p) % (sizeof(T) * VEC) == 0) && ...);
+}
+
+// rc = fn(std::integral_constant<int, N>) for the N of the list that equals n; false when there is none.
+template <int... Ns, typename Fn>
+bool with_constant(int n, int &rc, Fn fn)
+{
+    return ((n == Ns ? (rc = fn(std::integral_constant<int, Ns>{}), true) : false) || ...);
+}
+
+// fn(To{}, Tw{}) for two dtype codes, each F32 or F64
+template <typename Fn>
+int with_float_pair(int a_dtype, int b_dtype, Fn fn)
+{
+    return with_float(a_dtype, [&](auto a) { return with_float(b_dtype, [&](auto b) { return fn(a, b); }); });
 }
 
 template <typename Tf, typename Ta>
-int dispatch_mass_wavg(const void *const *fields, int n_fields, const void *delp_, const void *area_, int64_t n_outer, int ny,
+int dispatch_mass_wavg(const void *const *fields, int n_fields, const Tf *delp, const Ta *area, int64_t n_outer, int ny,
                        int nx, int64_t a_repeat, int factor, void *const *outs, hipStream_t stream)
 {
     using P = typename Promote<Tf, Ta>::type;
     constexpr int VEC = 16 / sizeof(P);
-    const Tf *delp = static_cast<const Tf *>(delp_);
-    const Ta *area = static_cast<const Ta *>(area_);
-    bool ok = (nx % VEC == 0) && (!delp || reinterpret_cast<uintptr_t>(delp) % (sizeof(Tf) * VEC) == 0) &&
-              (reinterpret_cast<uintptr_t>(area) % (sizeof(Ta) * VEC) == 0);
+    bool ok = rows_vectorise<VEC>(nx, delp, area);
     for (int f = 0; f < n_fields && ok; ++f)
-        ok = (reinterpret_cast<uintptr_t>(fields[f]) % (sizeof(Tf) * VEC) == 0) && (reinterpret_cast<uintptr_t>(outs[f]) % 16 == 0);
-    if (!ok || !(factor == 2 || factor == 4 || factor == 8 || factor == 16))
+        ok = rows_vectorise<VEC>(nx, static_cast<const Tf *>(fields[f]), static_cast<const P *>(outs[f]));
+    int rc = FV3HIP_OK;
+    const bool taken = ok && with_constant<2, 4, 8, 16>(factor, rc, [&](auto f_) {
+        constexpr int F = decltype(f_)::value;
+        const BlockPlan plan = plan_block_average<P, F>(ny, nx, n_outer, a_repeat);
+        for (int f0 = 0; f0 < n_fields && rc == FV3HIP_OK; f0 += kMassFields) {
+            const int nf = (n_fields - f0 < kMassFields) ? n_fields - f0 : kMassFields;
+            MassFieldPtrs fp;
+            for (int f = 0; f < kMassFields; ++f) {
+                fp.obj[f] = f < nf ? fields[f0 + f] : nullptr;
+                fp.out[f] = f < nf ? outs[f0 + f] : nullptr;
+            }
+            with_constant<1, 2, 3, 4>(nf, rc, [&](auto nf_) {
+                hipLaunchKernelGGL((mass_wavg_block_kernel<Tf, Ta, F, decltype(nf_)::value>), plan.grid, dim3(256), 0, stream, fp,
+                                   delp, area, n_outer, ny, nx, a_repeat, plan.zsplit, plan.n_gy);
+                return check_launch("mass_wavg_block_kernel");
+            });
+        }
+        return rc;
+    });
+    if (!taken)
         return fail(FV3HIP_EUNSUPPORTED, "fused mass-weighted average needs factor in {2, 4, 8, 16}, nx %% %d == 0 and 16-byte aligned arrays",
                     VEC);
-    for (int f0 = 0; f0 < n_fields; f0 += kMassFields) {
-        const int nf = (n_fields - f0 < kMassFields) ? n_fields - f0 : kMassFields;
-        MassFieldPtrs fp;
-        for (int f = 0; f < kMassFields; ++f) {
-            fp.obj[f] = f < nf ? fields[f0 + f] : nullptr;
-            fp.out[f] = f < nf ? outs[f0 + f] : nullptr;
-        }
-        int rc;
-        switch (factor) {
-            case 2: rc = launch_mass_wavg<Tf, Ta, 2>(fp, nf, delp, area, n_outer, ny, nx, a_repeat, stream); break;
-            case 4: rc = launch_mass_wavg<Tf, Ta, 4>(fp, nf, delp, area, n_outer, ny, nx, a_repeat, stream); break;
-            case 8: rc = launch_mass_wavg<Tf, Ta, 8>(fp, nf, delp, area, n_outer, ny, nx, a_repeat, stream); break;
-            default: rc = launch_mass_wavg<Tf, Ta, 16>(fp, nf, delp, area, n_outer, ny, nx, a_repeat, stream); break;
-        }
-        if (rc) return rc;
-    }
-    return FV3HIP_OK;
-}
-
-template <typename To, typename Tw, int F>
-int launch_wavg_block(const To *obj, const Tw *w, void *out, int64_t n_outer, int ny, int nx,
-                      int64_t w_repeat, hipStream_t stream)
-{
-    using P = typename Promote<To, Tw>::type;
-    constexpr int VEC = 16 / sizeof(P);
-    const int64_t S = (int64_t)(ny / F) * (nx / VEC);
-    const int64_t n_groups = n_outer / w_repeat;
-    const int64_t gx = ceil_div(S, 256);
-    // Split the levels that share a weight slice until the grid fills the chip several times
-    // over (256 CUs x 8 blocks of 256 threads), but keep chunks long enough to amortise the
-    // weight loads.
-    int zsplit = 1;
-    const int64_t want_blocks = 256 * 16;
-    while (gx * n_groups * zsplit < want_blocks && (w_repeat / (zsplit * 2)) >= 4) zsplit *= 2;
-    const int64_t n_gy = n_groups * zsplit;
-    dim3 grid((unsigned)gx, (unsigned)(n_gy < 65535 ? n_gy : 65535));
-    hipLaunchKernelGGL((wavg_block_kernel<To, Tw, F>), grid, dim3(256), 0, stream, obj, w,
-                       reinterpret_cast<P *>(out), n_outer, ny, nx, w_repeat, zsplit, n_gy);
-    return check_launch("wavg_block_kernel");
+    return rc;
 }
 
 template <typename To, typename Tw>
-int dispatch_wavg(const void *obj_, const void *w_, void *out, int64_t n_outer, int ny, int nx,
+int dispatch_wavg(const To *obj, const Tw *w, typename Promote<To, Tw>::type *out, int64_t n_outer, int ny, int nx,
                   int64_t w_repeat, int by, int bx, int sy, int sx, hipStream_t stream)
 {
     using P = typename Promote<To, Tw>::type;
-    constexpr int VEC = 16 / sizeof(P);
-    const To *obj = static_cast<const To *>(obj_);
-    const Tw *w = static_cast<const Tw *>(w_);
-    const bool full_blocks = (by == bx && sy == by && sx == bx);
-    const bool vec_ok = (nx % VEC == 0) && (nx % bx == 0) && (ny % by == 0) &&
-                        ((reinterpret_cast<uintptr_t>(obj) % (sizeof(To) * VEC)) == 0) &&
-                        ((reinterpret_cast<uintptr_t>(w) % (sizeof(Tw) * VEC)) == 0) &&
-                        ((reinterpret_cast<uintptr_t>(out) % 16) == 0);
-    if (full_blocks && vec_ok) {
-        switch (by) {
-            case 2: return launch_wavg_block<To, Tw, 2>(obj, w, out, n_outer, ny, nx, w_repeat, stream);
-            case 4: return launch_wavg_block<To, Tw, 4>(obj, w, out, n_outer, ny, nx, w_repeat, stream);
-            case 8: return launch_wavg_block<To, Tw, 8>(obj, w, out, n_outer, ny, nx, w_repeat, stream);
-            case 16: return launch_wavg_block<To, Tw, 16>(obj, w, out, n_outer, ny, nx, w_repeat, stream);
-            case 32: return launch_wavg_block<To, Tw, 32>(obj, w, out, n_outer, ny, nx, w_repeat, stream);
-            default: break;
-        }
-    }
+    const bool full_blocks = (by == bx && sy == by && sx == bx) && (nx % bx == 0) && (ny % by == 0);
+    int rc = FV3HIP_OK;
+    if (full_blocks && rows_vectorise<16 / sizeof(P)>(nx, obj, w, out) && with_constant<2, 4, 8, 16, 32>(by, rc, [&](auto f_) {
+            constexpr int F = decltype(f_)::value;
+            const BlockPlan plan = plan_block_average<P, F>(ny, nx, n_outer, w_repeat);
+            hipLaunchKernelGGL((wavg_block_kernel<To, Tw, F>), plan.grid, dim3(256), 0, stream, obj, w, out, n_outer, ny, nx,
+                               w_repeat, plan.zsplit, plan.n_gy);
+            return check_launch("wavg_block_kernel");
+        }))
+        return rc;
     const int nyo = (ny - by) / sy + 1, nxo = (nx - bx) / sx + 1;
     const int64_t total = n_outer * nyo * nxo;
     if (total == 0) return FV3HIP_OK;
-    int64_t blocks = ceil_div(total, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL((wavg_generic_kernel<To, Tw>), dim3((unsigned)blocks), dim3(256), 0, stream,
-                       obj, w, reinterpret_cast<P *>(out), n_outer, ny, nx, w_repeat, by, bx, sy,
-                       sx, nyo, nxo);
+    hipLaunchKernelGGL((wavg_generic_kernel<To, Tw>), dim3(grid_stride_blocks(total)), dim3(256), 0, stream, obj, w, out,
+                       n_outer, ny, nx, w_repeat, by, bx, sy, sx, nyo, nxo);
     return check_launch("wavg_generic_kernel");
 }
 
@@ -448,39 +404,18 @@ int wavg_entry(const void *obj, int obj_dtype, const void *w, int w_dtype, int64
                    (long long)n_outer, (long long)w_repeat);
     if (n_outer == 0 || ny == 0 || nx == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(obj && w && out, "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (obj_dtype == FV3HIP_F32 && w_dtype == FV3HIP_F32)
-        return dispatch_wavg<float, float>(obj, w, out, n_outer, ny, nx, w_repeat, by, bx, sy, sx, st);
-    if (obj_dtype == FV3HIP_F64 && w_dtype == FV3HIP_F64)
-        return dispatch_wavg<double, double>(obj, w, out, n_outer, ny, nx, w_repeat, by, bx, sy, sx, st);
-    if (obj_dtype == FV3HIP_F64 && w_dtype == FV3HIP_F32)
-        return dispatch_wavg<double, float>(obj, w, out, n_outer, ny, nx, w_repeat, by, bx, sy, sx, st);
-    return dispatch_wavg<float, double>(obj, w, out, n_outer, ny, nx, w_repeat, by, bx, sy, sx, st);
+    return with_float_pair(obj_dtype, w_dtype, [&](auto o, auto ww) {
+        using To = decltype(o);
+        using Tw = decltype(ww);
+        return dispatch_wavg(static_cast<const To *>(obj), static_cast<const Tw *>(w),
+                             static_cast<typename Promote<To, Tw>::type *>(out), n_outer, ny, nx, w_repeat, by, bx, sy, sx,
+                             as_stream(stream));
+    });
 }
 
 // ---------------------------------------------------------------------------------------
 // Generic block reductions (sum / mean / min / max / median / mode).
 // ---------------------------------------------------------------------------------------
-template <typename T>
-struct IsFloat {
-    static constexpr bool value = false;
-};
-template <>
-struct IsFloat<float> {
-    static constexpr bool value = true;
-};
-template <>
-struct IsFloat<double> {
-    static constexpr bool value = true;
-};
-
-template <typename T>
-__device__ __forceinline__ bool nan_of(T x)
-{
-    if constexpr (IsFloat<T>::value) return x != x;
-    return false;
-}
-
 template <typename T>
 __device__ __forceinline__ T quiet_nan()
 {
@@ -521,7 +456,7 @@ __global__ void block_reduce_kernel(const T *__restrict__ in, T *__restrict__ ou
                 }
             }
             if (op == FV3HIP_OP_MEAN) {
-                if constexpr (IsFloat<T>::value)
+                if constexpr (std::is_floating_point_v<T>)
                     result = acc / (T)cnt;  // 0/0 = NaN for an all-NaN block (numpy.nanmean)
                 else
                     result = acc;
@@ -537,7 +472,7 @@ __global__ void block_reduce_kernel(const T *__restrict__ in, T *__restrict__ ou
                 if (!have || (op == FV3HIP_OP_MIN ? v < best : v > best)) best = v;
                 have = true;
             }
-            if constexpr (IsFloat<T>::value)
+            if constexpr (std::is_floating_point_v<T>)
                 result = have ? best : quiet_nan<T>();
             else
                 result = best;
@@ -561,7 +496,7 @@ __global__ void block_reduce_kernel(const T *__restrict__ in, T *__restrict__ ou
                     if (less <= r1 && r1 < less + eq) m1 = v;
                     if (less <= r2 && r2 < less + eq) m2 = v;
                 }
-                if constexpr (IsFloat<T>::value)
+                if constexpr (std::is_floating_point_v<T>)
                     result = (r1 == r2) ? m1 : (m1 + m2) / (T)2;
                 else
                     result = m1;
@@ -580,7 +515,7 @@ __global__ void block_reduce_kernel(const T *__restrict__ in, T *__restrict__ ou
                     best = v;
                 }
             }
-            if constexpr (IsFloat<T>::value) {
+            if constexpr (std::is_floating_point_v<T>) {
                 // all-NaN block: "propagate" gives 0.0 in scipy 1.7.3 (count 0); for "omit"
                 // the masked result is reported as NaN here.
                 result = (best_cnt > 0) ? best
@@ -634,7 +569,7 @@ __global__ __launch_bounds__(256) void block_rank_wave_kernel(const T *__restric
             if (any_nan) {
                 result = quiet_nan<T>();
             } else {
-                if constexpr (IsFloat<T>::value)
+                if constexpr (std::is_floating_point_v<T>)
                     result = (r1 == r2) ? m1 : (m1 + m2) / (T)2;
                 else
                     result = m1;
@@ -656,7 +591,7 @@ __global__ __launch_bounds__(256) void block_rank_wave_kernel(const T *__restric
                     who = w2;
                 }
             }
-            if constexpr (IsFloat<T>::value)
+            if constexpr (std::is_floating_point_v<T>)
                 result = (cnt > 0) ? best : (nan_policy == FV3HIP_NAN_OMIT ? quiet_nan<T>() : (T)0);
             else
                 result = best;
@@ -673,16 +608,13 @@ int launch_block_reduce(const void *in, void *out, int64_t n_outer, int ny, int 
     const int64_t total = n_outer * nyo * nxo;
     if (total <= 0) return FV3HIP_OK;
     if ((op == FV3HIP_OP_MEDIAN || op == FV3HIP_OP_MODE) && by * bx <= 64) {
-        int64_t wblocks = ceil_div(total, 4);  // one wavefront per output block
-        if (wblocks > 256 * 64) wblocks = 256 * 64;
-        hipLaunchKernelGGL((block_rank_wave_kernel<T>), dim3((unsigned)wblocks), dim3(256), 0, stream,
+        // one wavefront per output block
+        hipLaunchKernelGGL((block_rank_wave_kernel<T>), dim3(grid_stride_blocks(total * kWave)), dim3(256), 0, stream,
                            static_cast<const T *>(in), static_cast<T *>(out), n_outer, ny, nx, by, bx, sy, sx, nyo, nxo, op,
                            nan_policy);
         return check_launch("block_rank_wave_kernel");
     }
-    int64_t blocks = ceil_div(total, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL((block_reduce_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, stream,
+    hipLaunchKernelGGL((block_reduce_kernel<T>), dim3(grid_stride_blocks(total)), dim3(256), 0, stream,
                        static_cast<const T *>(in), static_cast<T *>(out), n_outer, ny, nx, by, bx,
                        sy, sx, nyo, nxo, op, nan_policy);
     return check_launch("block_reduce_kernel");
@@ -736,21 +668,30 @@ __global__ __launch_bounds__(256) void upsample_rows_kernel(const U *__restrict_
     }
 }
 
-template <typename U>
-static void launch_upsample(const U *in, U *out, int64_t n_outer, int ny_in, int nx_in, int ny_out, int nx_out, int fy, int fx,
-                            hipStream_t st)
+// fv3hip_block_upsample and fv3hip_repeat behind their own check of the factors: every other check, then one launch
+int upsample_entry(const void *in_, int elem_size, int64_t n_outer, int ny_in, int nx_in, int ny_out, int nx_out, int fy, int fx,
+                   void *out_, void *stream)
 {
-    constexpr int VEC = 16 / sizeof(U);
+    FV3HIP_REQUIRE(elem_size == 4 || elem_size == 8, "elem_size must be 4 or 8, got %d", elem_size);
+    FV3HIP_REQUIRE(n_outer >= 0 && ny_in >= 0 && nx_in >= 0, "negative extent");
+    if (n_outer == 0 || ny_in == 0 || nx_in == 0) return FV3HIP_OK;
+    FV3HIP_REQUIRE(in_ && out_, "null pointer");
     const int64_t n_rows = n_outer * ny_out;
-    if (nx_out % VEC == 0 && nx_out >= 256 && reinterpret_cast<uintptr_t>(out) % 16 == 0) {
-        const dim3 grid((unsigned)ceil_div(nx_out, 256 * VEC), (unsigned)(n_rows < 65535 ? n_rows : 65535));
-        hipLaunchKernelGGL((upsample_rows_kernel<U, VEC>), grid, dim3(256), 0, st, in, out, n_rows, ny_in, nx_in, ny_out, nx_out, fy, fx);
-        return;
-    }
-    const int64_t total = n_rows * nx_out;
-    int64_t blocks = ceil_div(total, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL((upsample_kernel<U>), dim3((unsigned)blocks), dim3(256), 0, st, in, out, n_outer, ny_in, nx_in, ny_out, nx_out, fy, fx);
+    with_word(elem_size, [&](auto word) {
+        using U = decltype(word);
+        constexpr int VEC = 16 / sizeof(U);
+        const U *in = static_cast<const U *>(in_);
+        U *out = static_cast<U *>(out_);
+        if (nx_out % VEC == 0 && nx_out >= 256 && aligned16(out)) {
+            const dim3 grid((unsigned)ceil_div(nx_out, 256 * VEC), (unsigned)(n_rows < 65535 ? n_rows : 65535));
+            hipLaunchKernelGGL((upsample_rows_kernel<U, VEC>), grid, dim3(256), 0, as_stream(stream), in, out, n_rows, ny_in, nx_in,
+                               ny_out, nx_out, fy, fx);
+        } else {
+            hipLaunchKernelGGL((upsample_kernel<U>), dim3(grid_stride_blocks(n_rows * nx_out)), dim3(256), 0, as_stream(stream), in,
+                               out, n_outer, ny_in, nx_in, ny_out, nx_out, fy, fx);
+        }
+    });
+    return check_launch("upsample_kernel");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -876,7 +817,7 @@ __global__ void ew_kernel(int op, const T *__restrict__ a, const T *__restrict__
             case FV3HIP_EW_FILLNA_S: v = (x != x) ? s : x; break;
             case FV3HIP_EW_AND: v = (x != (T)0 && y != (T)0) ? (T)1 : (T)0; break;
             case FV3HIP_EW_MIN_S: v = (x < s) ? x : s; break;                  // a.where(a < s, other=s)
-            case FV3HIP_EW_BLEND: v = x * y + ((T)1 - x) * z; break;
+            case FV3HIP_EW_BLEND: v = x * y + ((T)1 - x) * z; break;           // blend(weights a, pressure-level b, model-level c)
             case FV3HIP_EW_WHERE_S: v = (y != (T)0) ? x : s; break;            // a.where(mask b, other=s)
             case FV3HIP_EW_ADD: v = x + y; break;
             case FV3HIP_EW_ADD_S: v = x + s; break;
@@ -904,12 +845,56 @@ __global__ void ew_kernel(int op, const T *__restrict__ a, const T *__restrict__
                 v = (x <= (T)1.0e-3) ? y : y * rectified;
                 break;
             }
-            case FV3HIP_EW_MUL_S: v = s * x; break;                            // scalar * a           // blend(weights a, pressure-level b, model-level c)
+            case FV3HIP_EW_MUL_S: v = s * x; break;                            // scalar * a
             default: v = x;
         }
         out[i] = v;
     }
 }
+
+// Which of the operands b and c the switch above reads, by op code; fv3hip_ew refuses a null one.
+struct EwOperands {
+    bool b, c;
+};
+constexpr EwOperands kEwOperands[] = {
+    {true, false},   // MUL
+    {true, false},   // ISCLOSE
+    {false, false},  // ISCLOSE_S
+    {true, false},   // WHERE_NAN
+    {true, true},    // SELECT
+    {true, false},   // SELECT_S
+    {false, false},  // GT_S
+    {false, false},  // LT_S
+    {false, false},  // FILLNA_S
+    {true, false},   // AND
+    {false, false},  // MIN_S
+    {true, true},    // BLEND
+    {false, false},  // MUL_S
+    {true, false},   // WHERE_S
+    {true, false},   // ADD
+    {false, false},  // ADD_S
+    {true, false},   // SUB
+    {false, false},  // LOG_FLOOR_S
+    {false, false},  // EXP
+    {false, false},  // RELU_THRESHOLD_S
+    {false, false},  // BELOW_S
+    {false, false},  // DIV_S
+    {true, false},   // INCLOUD_TO_GRIDCELL
+    {false, false},  // CLIP01
+    {false, false},  // POW_BASE_S
+    {false, false},  // MINIMUM_S
+    {true, false},   // DIV
+    {true, false},   // WHERE_POS_S
+    {false, false},  // SIGN
+    {false, false},  // ABS
+    {false, false},  // RSUB_S
+    {false, false},  // RDIV_S
+    {false, false},  // WHERE_GT_S
+    {false, false},  // LE_S
+    {false, false},  // SIN
+    {false, false},  // COS
+};
+static_assert(sizeof(kEwOperands) / sizeof(kEwOperands[0]) == FV3HIP_EW_COS + 1, "one row of kEwOperands per FV3HIP_EW_* op code");
 
 }  // namespace
 }  // namespace fv3hip
@@ -944,14 +929,10 @@ extern "C" int fv3hip_mass_weighted_block_average(const void *const *fields, int
     if (n_outer == 0 || ny == 0 || nx == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(fields && outs && area, "null pointer");  // (delp may be null: the weights are `area` alone)
     for (int f = 0; f < n_fields; ++f) FV3HIP_REQUIRE(fields[f] && outs[f], "null field pointer");
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F32 && area_dtype == FV3HIP_F32)
-        return dispatch_mass_wavg<float, float>(fields, n_fields, delp, area, n_outer, ny, nx, a_repeat, factor, outs, st);
-    if (dtype == FV3HIP_F64 && area_dtype == FV3HIP_F64)
-        return dispatch_mass_wavg<double, double>(fields, n_fields, delp, area, n_outer, ny, nx, a_repeat, factor, outs, st);
-    if (dtype == FV3HIP_F64 && area_dtype == FV3HIP_F32)
-        return dispatch_mass_wavg<double, float>(fields, n_fields, delp, area, n_outer, ny, nx, a_repeat, factor, outs, st);
-    return dispatch_mass_wavg<float, double>(fields, n_fields, delp, area, n_outer, ny, nx, a_repeat, factor, outs, st);
+    return with_float_pair(dtype, area_dtype, [&](auto f, auto ar) {
+        return dispatch_mass_wavg(fields, n_fields, static_cast<const decltype(f) *>(delp), static_cast<const decltype(ar) *>(area),
+                                  n_outer, ny, nx, a_repeat, factor, outs, as_stream(stream));
+    });
 }
 
 extern "C" int fv3hip_edge_weighted_block_average(const void *obj, int obj_dtype,
@@ -1008,36 +989,17 @@ extern "C" int fv3hip_block_upsample(const void *in, int elem_size, int64_t n_ou
                                      int nx_in, int factor, void *out, void *stream)
 {
     FV3HIP_REQUIRE(factor >= 1, "upsampling factor must be >= 1, got %d", factor);
-    FV3HIP_REQUIRE(elem_size == 4 || elem_size == 8, "elem_size must be 4 or 8, got %d", elem_size);
-    FV3HIP_REQUIRE(n_outer >= 0 && ny_in >= 0 && nx_in >= 0, "negative extent");
-    if (n_outer == 0 || ny_in == 0 || nx_in == 0) return FV3HIP_OK;
-    FV3HIP_REQUIRE(in && out, "null pointer");
     // odd size = staggered (interface) dimension: the last point is not repeated
     const int ny_out = (ny_in % 2 == 1) ? (ny_in - 1) * factor + 1 : ny_in * factor;
     const int nx_out = (nx_in % 2 == 1) ? (nx_in - 1) * factor + 1 : nx_in * factor;
-    hipStream_t st = as_stream(stream);
-    if (elem_size == 4)
-        launch_upsample(static_cast<const uint32_t *>(in), static_cast<uint32_t *>(out), n_outer, ny_in, nx_in, ny_out, nx_out, factor, factor, st);
-    else
-        launch_upsample(static_cast<const uint64_t *>(in), static_cast<uint64_t *>(out), n_outer, ny_in, nx_in, ny_out, nx_out, factor, factor, st);
-    return check_launch("upsample_kernel");
+    return upsample_entry(in, elem_size, n_outer, ny_in, nx_in, ny_out, nx_out, factor, factor, out, stream);
 }
 
 extern "C" int fv3hip_repeat(const void *in, int elem_size, int64_t n_outer, int ny_in, int nx_in, int fy, int fx, void *out,
                              void *stream)
 {
     FV3HIP_REQUIRE(fy >= 1 && fx >= 1, "repeat counts must be >= 1, got %d, %d", fy, fx);
-    FV3HIP_REQUIRE(elem_size == 4 || elem_size == 8, "elem_size must be 4 or 8, got %d", elem_size);
-    FV3HIP_REQUIRE(n_outer >= 0 && ny_in >= 0 && nx_in >= 0, "negative extent");
-    if (n_outer == 0 || ny_in == 0 || nx_in == 0) return FV3HIP_OK;
-    FV3HIP_REQUIRE(in && out, "null pointer");
-    const int ny_out = ny_in * fy, nx_out = nx_in * fx;
-    hipStream_t st = as_stream(stream);
-    if (elem_size == 4)
-        launch_upsample(static_cast<const uint32_t *>(in), static_cast<uint32_t *>(out), n_outer, ny_in, nx_in, ny_out, nx_out, fy, fx, st);
-    else
-        launch_upsample(static_cast<const uint64_t *>(in), static_cast<uint64_t *>(out), n_outer, ny_in, nx_in, ny_out, nx_out, fy, fx, st);
-    return check_launch("upsample_kernel");
+    return upsample_entry(in, elem_size, n_outer, ny_in, nx_in, ny_in * fy, nx_in * fx, fy, fx, out, stream);
 }
 
 extern "C" int fv3hip_cube_edge_rows(const void *in, int elem_size, int n_tiles, int64_t n_mid, int n, void *rows,
@@ -1048,15 +1010,11 @@ extern "C" int fv3hip_cube_edge_rows(const void *in, int elem_size, int n_tiles,
     if (n_tiles == 0 || n_mid == 0 || n == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(in && rows, "null pointer");
     const int64_t total = (int64_t)n_tiles * 4 * n_mid * n;
-    int64_t blocks = ceil_div(total, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipStream_t st = as_stream(stream);
-    if (elem_size == 4)
-        hipLaunchKernelGGL((cube_edge_rows_kernel<uint32_t>), dim3((unsigned)blocks), dim3(256), 0, st,
-                           static_cast<const uint32_t *>(in), static_cast<uint32_t *>(rows), n_tiles, n_mid, n);
-    else
-        hipLaunchKernelGGL((cube_edge_rows_kernel<uint64_t>), dim3((unsigned)blocks), dim3(256), 0, st,
-                           static_cast<const uint64_t *>(in), static_cast<uint64_t *>(rows), n_tiles, n_mid, n);
+    with_word(elem_size, [&](auto word) {
+        using U = decltype(word);
+        hipLaunchKernelGGL((cube_edge_rows_kernel<U>), dim3(grid_stride_blocks(total)), dim3(256), 0, as_stream(stream),
+                           static_cast<const U *>(in), static_cast<U *>(rows), n_tiles, n_mid, n);
+    });
     return check_launch("cube_edge_rows_kernel");
 }
 
@@ -1078,15 +1036,11 @@ extern "C" int fv3hip_halo_pick(const void *rows, int elem_size, int n_local, in
             hp.flip[side][i] = flip[k] ? 1 : 0;
         }
     const int64_t total = 2 * (int64_t)n_local * n_mid * n;
-    int64_t blocks = ceil_div(total, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipStream_t st = as_stream(stream);
-    if (elem_size == 4)
-        hipLaunchKernelGGL((halo_pick_kernel<uint32_t>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const uint32_t *>(rows),
-                           static_cast<uint32_t *>(out), hp, n_local, n_mid, n);
-    else
-        hipLaunchKernelGGL((halo_pick_kernel<uint64_t>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const uint64_t *>(rows),
-                           static_cast<uint64_t *>(out), hp, n_local, n_mid, n);
+    with_word(elem_size, [&](auto word) {
+        using U = decltype(word);
+        hipLaunchKernelGGL((halo_pick_kernel<U>), dim3(grid_stride_blocks(total)), dim3(256), 0, as_stream(stream),
+                           static_cast<const U *>(rows), static_cast<U *>(out), hp, n_local, n_mid, n);
+    });
     return check_launch("halo_pick_kernel");
 }
 
@@ -1143,10 +1097,7 @@ extern "C" int fv3hip_cast_many(const void *const *in, const int *in_dtype, void
         if (bx > 4096) bx = 4096;
         if (bx < 1) bx = 1;
         dim3 grid((unsigned)bx, (unsigned)m);
-        if (out_dtype == FV3HIP_F32)
-            hipLaunchKernelGGL((cast_many_kernel<float>), grid, dim3(256), 0, st, t);
-        else
-            hipLaunchKernelGGL((cast_many_kernel<double>), grid, dim3(256), 0, st, t);
+        with_float(out_dtype, [&](auto o) { hipLaunchKernelGGL((cast_many_kernel<decltype(o)>), grid, dim3(256), 0, st, t); });
         const int rc = check_launch("cast_many_kernel");
         if (rc) return rc;
     }
@@ -1157,12 +1108,10 @@ namespace {
 template <typename Tin>
 int launch_cast(const void *in, int out_dtype, void *out, int64_t n, hipStream_t st)
 {
-    int64_t blocks = ceil_div(n, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    if (out_dtype == FV3HIP_F32)
-        hipLaunchKernelGGL((cast_kernel<Tin, float>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const Tin *>(in), static_cast<float *>(out), n);
-    else
-        hipLaunchKernelGGL((cast_kernel<Tin, double>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const Tin *>(in), static_cast<double *>(out), n);
+    with_float(out_dtype, [&](auto o) {
+        hipLaunchKernelGGL((cast_kernel<Tin, decltype(o)>), dim3(grid_stride_blocks(n)), dim3(256), 0, st, static_cast<const Tin *>(in),
+                           static_cast<decltype(o) *>(out), n);
+    });
     return check_launch("cast_kernel");
 }
 }  // namespace
@@ -1193,17 +1142,12 @@ extern "C" int fv3hip_interp_center_to_outer_lines(const void *in, int dtype, in
     if (n_outer == 0 || ny == 0 || nx == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(in && lo && hi && out, "null pointer");
     const int64_t total = n_outer * ((axis == 1) ? ny / step + 1 : ny) * ((axis == 0) ? nx / step + 1 : nx);
-    int64_t blocks = ceil_div(total, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F32)
-        hipLaunchKernelGGL((interp_to_outer_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, st,
-                           static_cast<const float *>(in), static_cast<const float *>(lo), static_cast<const float *>(hi),
-                           static_cast<float *>(out), n_outer, ny, nx, axis, step);
-    else
-        hipLaunchKernelGGL((interp_to_outer_kernel<double>), dim3((unsigned)blocks), dim3(256), 0, st,
-                           static_cast<const double *>(in), static_cast<const double *>(lo), static_cast<const double *>(hi),
-                           static_cast<double *>(out), n_outer, ny, nx, axis, step);
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((interp_to_outer_kernel<T>), dim3(grid_stride_blocks(total)), dim3(256), 0, as_stream(stream),
+                           static_cast<const T *>(in), static_cast<const T *>(lo), static_cast<const T *>(hi), static_cast<T *>(out),
+                           n_outer, ny, nx, axis, step);
+    });
     return check_launch("interp_to_outer_kernel");
 }
 
@@ -1221,22 +1165,14 @@ extern "C" int fv3hip_ew(int op, const void *a, const void *b, const void *c, do
     FV3HIP_REQUIRE(n >= 0 && inner >= 1 && b_rep >= 1 && c_rep >= 1, "bad extents");
     if (n == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(a && out, "null pointer");
-    const bool needs_b = op == FV3HIP_EW_MUL || op == FV3HIP_EW_ISCLOSE || op == FV3HIP_EW_WHERE_NAN ||
-                         op == FV3HIP_EW_SELECT || op == FV3HIP_EW_SELECT_S || op == FV3HIP_EW_AND || op == FV3HIP_EW_BLEND ||
-                         op == FV3HIP_EW_WHERE_S || op == FV3HIP_EW_ADD || op == FV3HIP_EW_SUB;
-    FV3HIP_REQUIRE(!needs_b || b, "this op needs operand b");
-    FV3HIP_REQUIRE((op != FV3HIP_EW_SELECT && op != FV3HIP_EW_BLEND) || c, "this op needs operand c");
+    FV3HIP_REQUIRE(!kEwOperands[op].b || b, "this op needs operand b");
+    FV3HIP_REQUIRE(!kEwOperands[op].c || c, "this op needs operand c");
     FV3HIP_REQUIRE(n % inner == 0, "n must be a multiple of inner");
-    int64_t blocks = ceil_div(n, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((ew_kernel<double>), dim3((unsigned)blocks), dim3(256), 0, st, op, static_cast<const double *>(a),
-                           static_cast<const double *>(b), static_cast<const double *>(c), scalar, n, inner, b_rep, c_rep,
-                           static_cast<double *>(out));
-    else
-        hipLaunchKernelGGL((ew_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, st, op, static_cast<const float *>(a),
-                           static_cast<const float *>(b), static_cast<const float *>(c), (float)scalar, n, inner, b_rep, c_rep,
-                           static_cast<float *>(out));
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((ew_kernel<T>), dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), op, static_cast<const T *>(a),
+                           static_cast<const T *>(b), static_cast<const T *>(c), (T)scalar, n, inner, b_rep, c_rep,
+                           static_cast<T *>(out));
+    });
     return check_launch("ew_kernel");
 }

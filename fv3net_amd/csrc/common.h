@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fv3hip.h"
@@ -32,6 +33,27 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Blocks of 256 threads for a grid-stride loop over `total` elements: one pass while they fit 64 blocks per CU.
+inline unsigned grid_stride_blocks(int64_t total)
+{
+    const int64_t blocks = ceil_div(total, 256);
+    return (unsigned)(blocks < 256 * 64 ? blocks : 256 * 64);
+}
+
+// f(T{}) with T the unsigned word of elem_size bytes (4 or 8) / the float type of a dtype code (F32 or F64); the
+// caller has checked the code.
+template <typename Fn>
+auto with_word(int elem_size, Fn f)
+{
+    return elem_size == 4 ? f(uint32_t{}) : f(uint64_t{});
+}
+
+template <typename Fn>
+auto with_float(int dtype, Fn f)
+{
+    return dtype == FV3HIP_F64 ? f(double{}) : f(float{});
+}
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

@@ -112,6 +112,19 @@ def _promoted(a: torch.Tensor, b: torch.Tensor) -> torch.dtype:
     return torch.float64 if torch.float64 in (a.dtype, b.dtype) else torch.float32
 
 
+def _weighted_operands(obj: torch.Tensor, weights: torch.Tensor, factor: Optional[int] = None):
+    """What the weighted averages of a contiguous ``obj`` [.., ny, nx] hand to the library: (weights made contiguous,
+    w_repeat, n_outer, ny, nx) and, given a block ``factor`` (checked here), the shape of the block means as well."""
+    weights, w_repeat = _weights_repeat(obj, weights)
+    ny, nx = int(obj.shape[-2]), int(obj.shape[-1])
+    operands = (weights, w_repeat, _prod(obj.shape[:-2]), ny, nx)
+    if factor is None:
+        return operands
+    if factor < 1 or ny % factor or nx % factor:
+        raise ValueError(f"horizontal extents ({ny}, {nx}) are not multiples of the coarsening factor {factor}")
+    return operands + (tuple(obj.shape[:-2]) + (ny // factor, nx // factor),)
+
+
 def weighted_block_average(obj: torch.Tensor, weights: torch.Tensor, factor: int) -> torch.Tensor:
     """``nansum(obj*w)/nansum(w)`` over factor x factor blocks of the last two dims
     (vcm.cubedsphere.weighted_block_average, coarsen.py:183-218)."""
@@ -120,16 +133,8 @@ def weighted_block_average(obj: torch.Tensor, weights: torch.Tensor, factor: int
     if obj.dim() < 2:
         raise ValueError("field must have at least two (horizontal) dimensions")
     obj = obj.contiguous()
-    weights, w_repeat = _weights_repeat(obj, weights)
-    ny, nx = int(obj.shape[-2]), int(obj.shape[-1])
-    if factor < 1 or ny % factor or nx % factor:
-        raise ValueError(
-            f"horizontal extents ({ny}, {nx}) are not multiples of the coarsening factor {factor}"
-        )
-    n_outer = _prod(obj.shape[:-2])
-    out = torch.empty(
-        tuple(obj.shape[:-2]) + (ny // factor, nx // factor), dtype=_promoted(obj, weights), device=dev
-    )
+    weights, w_repeat, n_outer, ny, nx, oshape = _weighted_operands(obj, weights, factor)
+    out = torch.empty(oshape, dtype=_promoted(obj, weights), device=dev)
     _lib.call_on(dev,
         "fv3hip_weighted_block_average", _ptr(obj), _float_code(obj), _ptr(weights), _float_code(weights),
         n_outer, ny, nx, w_repeat, factor, _ptr(out), _stream(dev),
@@ -149,16 +154,11 @@ def weighted_block_average_multi(fields: Sequence[torch.Tensor], weights: torch.
         return [weighted_block_average(f, weights, factor) for f in fields]
     dev = _require_device(weights, *fields)
     factor = int(factor)
-    w, w_repeat = _weights_repeat(f0, weights)
-    ny, nx = int(f0.shape[-2]), int(f0.shape[-1])
-    if factor < 1 or ny % factor or nx % factor:
-        raise ValueError(f"horizontal extents ({ny}, {nx}) are not multiples of the coarsening factor {factor}")
-    outs = [torch.empty(tuple(f0.shape[:-2]) + (ny // factor, nx // factor), dtype=f0.dtype, device=dev) for _ in fields]
-    n = len(fields)
+    w, w_repeat, n_outer, ny, nx, oshape = _weighted_operands(f0, weights, factor)
+    outs = [torch.empty(oshape, dtype=f0.dtype, device=dev) for _ in fields]
     try:
-        _lib.call_on(dev, "fv3hip_mass_weighted_block_average", (ctypes.c_void_p * n)(*[f.data_ptr() for f in fields]), n,
-                     _float_code(f0), None, _ptr(w), _float_code(w), _prod(f0.shape[:-2]), ny, nx, w_repeat, factor,
-                     (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), _stream(dev))
+        _lib.call_on(dev, "fv3hip_mass_weighted_block_average", _ptr_array(fields), len(fields), _float_code(f0), None, _ptr(w),
+                     _float_code(w), n_outer, ny, nx, w_repeat, factor, _ptr_array(outs), _stream(dev))
     except _lib.Fv3HipError as err:
         if err.code != _lib.EUNSUPPORTED:
             raise
@@ -180,19 +180,12 @@ def mass_weighted_block_average(fields: Sequence[torch.Tensor], delp: torch.Tens
     if any(f.shape != f0.shape or f.dtype != f0.dtype for f in fields) or delp.shape != f0.shape:
         raise ValueError("fields and delp must share one shape and dtype")
     delp = cast(delp, f0.dtype).contiguous()
-    area_b, a_repeat = _weights_repeat(f0, area)
-    ny, nx = int(f0.shape[-2]), int(f0.shape[-1])
-    if factor < 1 or ny % factor or nx % factor:
-        raise ValueError(f"horizontal extents ({ny}, {nx}) are not multiples of the coarsening factor {factor}")
-    n_outer = _prod(f0.shape[:-2])
+    area_b, a_repeat, n_outer, ny, nx, oshape = _weighted_operands(f0, area, factor)
     out_dtype = _promoted(f0, area_b)
-    outs = [torch.empty(tuple(f0.shape[:-2]) + (ny // factor, nx // factor), dtype=out_dtype, device=dev) for _ in fields]
-    n = len(fields)
-    f_ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fields])
-    o_ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    outs = [torch.empty(oshape, dtype=out_dtype, device=dev) for _ in fields]
     try:
-        _lib.call_on(dev, "fv3hip_mass_weighted_block_average", f_ptrs, n, _float_code(f0), _ptr(delp), _ptr(area_b),
-                     _float_code(area_b), n_outer, ny, nx, a_repeat, factor, o_ptrs, _stream(dev))
+        _lib.call_on(dev, "fv3hip_mass_weighted_block_average", _ptr_array(fields), len(fields), _float_code(f0), _ptr(delp),
+                     _ptr(area_b), _float_code(area_b), n_outer, ny, nx, a_repeat, factor, _ptr_array(outs), _stream(dev))
     except _lib.Fv3HipError as err:
         if err.code != _lib.EUNSUPPORTED:
             raise
@@ -219,8 +212,7 @@ def edge_weighted_block_average(
     dev = _require_device(obj, spacing)
     factor = int(factor)
     obj = obj.contiguous()
-    spacing, w_repeat = _weights_repeat(obj, spacing)
-    ny, nx = int(obj.shape[-2]), int(obj.shape[-1])
+    spacing, w_repeat, n_outer, ny, nx = _weighted_operands(obj, spacing)
     if edge == "x":
         if nx % factor:
             raise ValueError(f"x extent {nx} is not a multiple of the coarsening factor {factor}")
@@ -232,7 +224,7 @@ def edge_weighted_block_average(
     out = torch.empty(tuple(obj.shape[:-2]) + oshape, dtype=_promoted(obj, spacing), device=dev)
     _lib.call_on(dev,
         "fv3hip_edge_weighted_block_average", _ptr(obj), _float_code(obj), _ptr(spacing),
-        _float_code(spacing), _prod(obj.shape[:-2]), ny, nx, w_repeat, factor, 0 if edge == "x" else 1,
+        _float_code(spacing), n_outer, ny, nx, w_repeat, factor, 0 if edge == "x" else 1,
         _ptr(out), _stream(dev),
     )
     return out
@@ -246,13 +238,12 @@ def weighted_window_average(obj: torch.Tensor, weights: torch.Tensor, window: Se
     by, bx = (int(v) for v in window)
     sy, sx = (int(v) for v in stride)
     obj = obj.contiguous()
-    weights, w_repeat = _weights_repeat(obj, weights)
-    ny, nx = int(obj.shape[-2]), int(obj.shape[-1])
+    weights, w_repeat, n_outer, ny, nx = _weighted_operands(obj, weights)
     if ny < by or nx < bx:
         raise ValueError(f"window ({by}, {bx}) is larger than the field ({ny}, {nx})")
     out = torch.empty(tuple(obj.shape[:-2]) + ((ny - by) // sy + 1, (nx - bx) // sx + 1), dtype=_promoted(obj, weights), device=dev)
     _lib.call_on(dev, "fv3hip_weighted_window_average", _ptr(obj), _float_code(obj), _ptr(weights), _float_code(weights),
-                 _prod(obj.shape[:-2]), ny, nx, w_repeat, by, bx, sy, sx, _ptr(out), _stream(dev))
+                 n_outer, ny, nx, w_repeat, by, bx, sy, sx, _ptr(out), _stream(dev))
     return out
 
 
@@ -266,13 +257,19 @@ def take_lines(x: torch.Tensor, step: int, axis: int) -> torch.Tensor:
 def repeat(x: torch.Tensor, fy: int, fx: int) -> torch.Tensor:
     """Repeat each value ``fy`` times along the second-to-last and ``fx`` times along the last dim
     (``xarray_utils.repeat``, vcm/xarray_utils.py:37-82, a count per horizontal dim)."""
+    fy, fx = int(fy), int(fx)
+    return _upsampled(x, "fv3hip_repeat", lambda ny, nx: (ny * fy, nx * fx), fy, fx)
+
+
+def _upsampled(x: torch.Tensor, entry: str, out_hw, *factors) -> torch.Tensor:
+    """``repeat`` and ``block_upsample``: words of 4 or 8 bytes copied by ``entry`` to a fresh [.., *out_hw(ny, nx)] tensor."""
     dev = _require_device(x)
     x = x.contiguous()
     if x.element_size() not in (4, 8):
         raise TypeError(f"unsupported dtype {x.dtype}")
     ny, nx = int(x.shape[-2]), int(x.shape[-1])
-    out = torch.empty(tuple(x.shape[:-2]) + (ny * int(fy), nx * int(fx)), dtype=x.dtype, device=dev)
-    _lib.call_on(dev, "fv3hip_repeat", _ptr(x), x.element_size(), _prod(x.shape[:-2]), ny, nx, int(fy), int(fx), _ptr(out), _stream(dev))
+    out = torch.empty(tuple(x.shape[:-2]) + out_hw(ny, nx), dtype=x.dtype, device=dev)
+    _lib.call_on(dev, entry, _ptr(x), x.element_size(), _prod(x.shape[:-2]), ny, nx, *factors, _ptr(out), _stream(dev))
     return out
 
 
@@ -308,20 +305,9 @@ def block_reduce(
 def block_upsample(x: torch.Tensor, factor: int) -> torch.Tensor:
     """Repeat each value ``factor`` times along the last two dims; a dim of odd size is treated
     as staggered and its last point is not repeated (coarsen.py:843-897)."""
-    dev = _require_device(x)
     factor = int(factor)
-    x = x.contiguous()
-    if x.element_size() not in (4, 8):
-        raise TypeError(f"unsupported dtype {x.dtype}")
-    ny, nx = int(x.shape[-2]), int(x.shape[-1])
-    nyo = (ny - 1) * factor + 1 if ny % 2 == 1 else ny * factor
-    nxo = (nx - 1) * factor + 1 if nx % 2 == 1 else nx * factor
-    out = torch.empty(tuple(x.shape[:-2]) + (nyo, nxo), dtype=x.dtype, device=dev)
-    _lib.call_on(dev,
-        "fv3hip_block_upsample", _ptr(x), x.element_size(), _prod(x.shape[:-2]), ny, nx, factor, _ptr(out),
-        _stream(dev),
-    )
-    return out
+    size = lambda n: (n - 1) * factor + 1 if n % 2 == 1 else n * factor
+    return _upsampled(x, "fv3hip_block_upsample", lambda ny, nx: (size(ny), size(nx)), factor)
 
 
 def _column_view(x: torch.Tensor, z_axis: int):

@@ -403,3 +403,218 @@ def test_sfc_data_complex_with_categorical_fields(device):
             np.testing.assert_array_equal(got, want, err_msg=name)
         else:
             np.testing.assert_allclose(got, want, rtol=2e-7, atol=0, err_msg=name)
+
+
+# ---------------------------------------------------------------------------------------
+# The fused mass-weighted block average (mass_wavg_block_kernel) on its own, and what it shares with wavg_block_kernel.
+# ---------------------------------------------------------------------------------------
+_PAIRS = {"ff": (np.float32, np.float32), "dd": (np.float64, np.float64), "df": (np.float64, np.float32), "fd": (np.float32, np.float64)}
+
+
+def _tol(*dtypes):
+    return 1e-13 if all(dt == np.float64 for dt in dtypes) else 1e-5
+
+
+def _same(a, b):
+    # (as in tests/test_gpu_block_mean.py)
+    a, b = a.cpu().numpy(), b.cpu().numpy()
+    assert a.shape == b.shape and a.dtype == b.dtype
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) or np.array_equal(a, b, equal_nan=True), \
+        f"{np.sum(a.view(np.uint32) != b.view(np.uint32))} of {a.size} values differ, max {np.nanmax(np.abs(a - b))}"
+
+
+def _mass_raw(device, fields, delp, area, factor, override=()):
+    """fv3hip_mass_weighted_block_average itself on device tensors: it raises on EUNSUPPORTED where the ops wrappers would
+    fall back, so a result from here came from mass_wavg_block_kernel.  ``override`` replaces arguments by name."""
+    import ctypes
+
+    from fv3net_amd import _lib, ops
+
+    f0 = fields[0]
+    ny, nx = int(f0.shape[-2]), int(f0.shape[-1])
+    n_outer = int(np.prod(f0.shape[:-2]))
+    promoted = torch.float64 if torch.float64 in (f0.dtype, area.dtype) else torch.float32
+    outs = [torch.empty(tuple(f0.shape[:-2]) + (ny // factor, nx // factor), dtype=promoted, device=device) for _ in fields]
+    n = len(fields)
+    args = dict(fields=(ctypes.c_void_p * n)(*[f.data_ptr() for f in fields]), n_fields=n, dtype=ops._float_code(f0),
+                delp=ops._ptr(delp), area=ops._ptr(area), area_dtype=ops._float_code(area), n_outer=n_outer, ny=ny, nx=nx,
+                a_repeat=n_outer // max(int(np.prod(area.shape[:-2])), 1), factor=factor,
+                outs=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), stream=ops._stream(device))
+    args.update(override)
+    assert len(args) == 13
+    _lib.call_on(device, "fv3hip_mass_weighted_block_average", *args.values())
+    return outs
+
+
+def _mass_case(seed, shape, fdt, adt, n_fields, area_shape=None):
+    rng = np.random.default_rng(seed)
+    fields = [rng.uniform(-1000, 1000, shape).astype(fdt) for _ in range(n_fields)]
+    delp = rng.uniform(300, 1500, shape).astype(fdt)
+    area = rng.uniform(0.5, 1, area_shape or (shape[0],) + tuple(shape[-2:])).astype(adt)
+    promoted = np.float64 if np.float64 in (fdt, adt) else np.float32
+    a = area.astype(promoted)
+    w = delp.astype(promoted) * (a if a.shape == delp.shape else a[:, None])   # the product in the promoted dtype
+    return fields, delp, area, w
+
+
+@pytest.mark.parametrize("factor", [2, 4, 8, 16])
+@pytest.mark.parametrize("pair", ["ff", "dd", "df", "fd"])
+def test_mass_weighted_block_average_matches_oracle(device, factor, pair):
+    """[2, 9, 3F, 4F]: nine levels per area slice are walked as two z-chunks (5 + 4), the slab fills a fraction of one
+    workgroup (idle lanes join the shuffles), and five fields take a launch of four and a launch of one."""
+    fdt, adt = _PAIRS[pair]
+    fields, delp, area, w = _mass_case(factor, (2, 9, 3 * factor, 4 * factor), fdt, adt, 5)
+    d_fields, d_delp, d_area = [_dev(f, device) for f in fields], _dev(delp, device), _dev(area, device)
+    for n in (1, 3, 4, 5):
+        outs = _mass_raw(device, d_fields[:n], d_delp, d_area, factor)
+        assert len(outs) == n
+        for f, out in zip(fields, outs):
+            res = out.cpu().numpy()
+            assert res.dtype == w.dtype
+            _check_wavg(res, f, w, factor, _tol(fdt, adt))
+
+
+@pytest.mark.parametrize("factor", [2, 4, 8, 16])
+@pytest.mark.parametrize("pair", ["ff", "dd"])
+def test_mass_weighted_block_average_is_its_unfused_route_bit_for_bit(device, factor, pair):
+    """Same products, same order of additions: the fused kernel against the product kernel followed by the single-field
+    average."""
+    from fv3net_amd import ops
+
+    fdt, adt = _PAIRS[pair]
+    fields, delp, area, _ = _mass_case(factor, (2, 9, 3 * factor, 4 * factor), fdt, adt, 5)
+    d_fields, d_delp, d_area = [_dev(f, device) for f in fields], _dev(delp, device), _dev(area, device)
+    want = [ops.weighted_block_average(f, ops.ew("mul", d_delp, d_area), factor) for f in d_fields]
+    got = ops.mass_weighted_block_average(d_fields, d_delp, d_area, factor)
+    raw = _mass_raw(device, d_fields, d_delp, d_area, factor)
+    for g, r, w in zip(got, raw, want):
+        _same(g, w)
+        _same(r, w)
+
+
+@pytest.mark.parametrize("factor", [2, 8, 16, 32])
+@pytest.mark.parametrize("pair", ["ff", "dd"])
+@pytest.mark.parametrize("full_weights", [False, True])
+def test_weighted_block_average_multi_is_the_single_field_call_bit_for_bit(device, factor, pair, full_weights):
+    """Weights without delp (the surface-data means), 2-D per tile or of the fields' shape; factor 32 goes through the
+    wrapper's fallback."""
+    from fv3net_amd import ops
+
+    fdt, _ = _PAIRS[pair]
+    shape = (2, 9, 3 * factor, 4 * factor)
+    rng = np.random.default_rng(100 + factor)
+    d_fields = [_dev(rng.uniform(-1000, 1000, shape).astype(fdt), device) for _ in range(5)]
+    d_w = _dev(rng.uniform(0.5, 1, shape if full_weights else (2,) + shape[-2:]).astype(fdt), device)
+    want = [ops.weighted_block_average(f, d_w, factor) for f in d_fields]
+    for n in (2, 4, 5):
+        got = ops.weighted_block_average_multi(d_fields[:n], d_w, factor)
+        assert len(got) == n
+        for g, w in zip(got, want):
+            _same(g, w)
+        if factor != 32:   # (and the fused kernel did run)
+            for r, w in zip(_mass_raw(device, d_fields[:n], None, d_w, factor), want):
+                _same(r, w)
+
+
+def test_block_average_kernels_with_several_workgroups_and_a_ragged_last_one(device):
+    """[1, 4, 66, 64] float32 by 2: 33 * 16 = 528 = 2 * 256 + 16 threads of work."""
+    from fv3net_amd import ops
+
+    fields, delp, area, w = _mass_case(7, (1, 4, 66, 64), np.float32, np.float32, 1)
+    d_f, d_delp, d_area = _dev(fields[0], device), _dev(delp, device), _dev(area, device)
+    _check_wavg(ops.as_numpy(ops.weighted_block_average(d_f, d_area, 2)), fields[0], area[:, None], 2, 1e-5)
+    _check_wavg(_mass_raw(device, [d_f], d_delp, d_area, 2)[0].cpu().numpy(), fields[0], w, 2, 1e-5)
+
+
+def test_block_average_kernels_walk_more_weight_slices_than_grid_rows(device):
+    """[70000, 2, 4] float32 with weights of the same shape: 70000 (weight slice, z-chunk) pairs on at most 65535 grid
+    rows."""
+    from fv3net_amd import ops
+
+    shape = (70000, 2, 4)
+    fields, delp, area, w = _mass_case(8, shape, np.float32, np.float32, 1, area_shape=shape)
+    d_f, d_delp, d_area = _dev(fields[0], device), _dev(delp, device), _dev(area, device)
+    _check_wavg(ops.as_numpy(ops.weighted_block_average(d_f, d_area, 2)), fields[0], area, 2, 1e-5)
+    _check_wavg(_mass_raw(device, [d_f], d_delp, d_area, 2)[0].cpu().numpy(), fields[0], w, 2, 1e-5)
+
+
+@pytest.mark.parametrize("factor", [2, 4])
+def test_mass_weighted_block_average_non_finite_inputs(device, factor):
+    fields, delp, area, _ = _mass_case(9, (2, 3, 16, 16), np.float32, np.float32, 3)
+    fields[0][0, 1, 3, 5] = np.nan            # one NaN in a field
+    fields[1][1, 0, :4, :4] = np.nan          # fully-NaN blocks: numerator 0
+    delp[0, 2, 9, 9] = np.nan                 # a NaN weight is skipped in both sums
+    area[1, 12, 2] = np.nan
+    area[0, 4:8, 4:8] = 0.0                   # zero denominator: 0/0 = NaN
+    w = delp * area[:, None]
+    d_fields, d_delp, d_area = [_dev(f, device) for f in fields], _dev(delp, device), _dev(area, device)
+    outs = _mass_raw(device, d_fields, d_delp, d_area, factor)
+    with np.errstate(all="ignore"):
+        for f, out in zip(fields, outs):
+            _check_wavg(out.cpu().numpy(), f, w, factor, 1e-5)   # (the NaN map must be the oracle's)
+    # the NaNs of the first two fields stay out of the third
+    _same(outs[2], _mass_raw(device, d_fields[2:], d_delp, d_area, factor)[0])
+
+
+def _expect_code(code, fn, *args):
+    from fv3net_amd import _lib
+
+    with pytest.raises(_lib.Fv3HipError) as err:
+        fn(*args)
+    assert err.value.code == code, err.value
+
+
+def test_mass_weighted_block_average_refusals(device):
+    from fv3net_amd import _lib, ops
+
+    def case(shape, factor, shift=False):
+        fields, delp, area, w = _mass_case(10, shape, np.float32, np.float32, 1)
+        d_f = _dev(fields[0], device)
+        if shift:   # the same values 4 bytes off 16-byte alignment
+            big = torch.zeros(d_f.numel() + 4, dtype=d_f.dtype, device=device)
+            big[1:d_f.numel() + 1] = d_f.flatten()
+            d_f = big[1:d_f.numel() + 1].view(shape)
+            assert d_f.data_ptr() % 16 == 4
+        d_delp, d_area = _dev(delp, device), _dev(area, device)
+        _expect_code(_lib.EUNSUPPORTED, _mass_raw, device, [d_f], d_delp, d_area, factor)
+        res = ops.mass_weighted_block_average([d_f], d_delp, d_area, factor)[0]   # the fallback
+        _check_wavg(res.cpu().numpy(), fields[0], w, factor, 1e-5)
+
+    case((2, 3, 8, 8), 2, shift=True)
+    case((2, 3, 4, 6), 2)       # rows are not whole vectors
+    case((2, 3, 6, 12), 3)
+    case((2, 3, 32, 64), 32)
+
+    fields, delp, area, _ = _mass_case(11, (2, 3, 8, 8), np.float32, np.float32, 1)
+    d_f, d_delp, d_area = [_dev(fields[0], device)], _dev(delp, device), _dev(area, device)
+    _expect_code(_lib.EINVAL, _mass_raw, device, d_f, d_delp, d_area, 2, {"n_fields": -1})
+    _expect_code(_lib.EINVAL, _mass_raw, device, d_f, d_delp, d_area, 2, {"a_repeat": 0})
+    _expect_code(_lib.EINVAL, _mass_raw, device, d_f, d_delp, d_area, 2, {"a_repeat": 4})   # n_outer = 6
+    _expect_code(_lib.EINVAL, _mass_raw, device, d_f, d_delp, d_area, 2, {"area": None})
+
+
+# from the comments of include/fv3hip.h: the ops whose formula names b, and those that name c
+_EW_READS_B = {0: "MUL", 1: "ISCLOSE", 3: "WHERE_NAN", 4: "SELECT", 5: "SELECT_S", 9: "AND", 11: "BLEND", 13: "WHERE_S", 14: "ADD",
+               16: "SUB", 22: "INCLOUD_TO_GRIDCELL", 26: "DIV", 27: "WHERE_POS_S"}
+_EW_READS_C = {4: "SELECT", 11: "BLEND"}
+
+
+@pytest.mark.parametrize("op", range(36))
+def test_ew_refuses_a_missing_operand(device, op):
+    from fv3net_amd import _lib, ops
+
+    for dt in (torch.float32, torch.float64):
+        a = torch.rand((2, 3, 4), dtype=dt, device=device) + 0.5
+        out = torch.empty_like(a)
+
+        def ew(b, c):
+            _lib.call_on(device, "fv3hip_ew", op, ops._ptr(a), ops._ptr(b), ops._ptr(c), 0.5, ops._float_code(a), a.numel(), 12, 1, 1,
+                         ops._ptr(out), ops._stream(device))
+
+        if op in _EW_READS_B:
+            _expect_code(_lib.EINVAL, ew, None, a)
+            if op in _EW_READS_C:
+                _expect_code(_lib.EINVAL, ew, a, None)
+            ew(a, a)
+        else:
+            ew(None, None)
