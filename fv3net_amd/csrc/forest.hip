@@ -285,7 +285,7 @@ int check_call(fv3hip_forest_t f, const void *const *sources, const int *src_dty
     FV3HIP_REQUIRE(sources && src_dtype && fs && ss, "null pointer");
     for (int i = 0; i < kMaxForestSources; ++i) src[i] = Src{nullptr, 0, 0, 0};
     for (int i = 0; i < f->n_sources; ++i) {
-        FV3HIP_REQUIRE(sources[i], "source %d is null", i);
+        FV3HIP_REQUIRE(sources[i] || n == 0, "source %d is null", i);  // (an empty array has no address)
         FV3HIP_REQUIRE(src_dtype[i] == FV3HIP_F32 || src_dtype[i] == FV3HIP_F64, "source %d: dtype must be F32 or F64", i);
         src[i] = Src{sources[i], fs[i], ss[i], src_dtype[i] == FV3HIP_F64 ? 1 : 0};
     }

@@ -3,6 +3,7 @@
 artifact round-trips, and a directory in the reference's own layout converts to the same arrays."""
 import io
 import os
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -15,56 +16,8 @@ from fv3net_amd import _lib  # noqa: E402
 from fv3net_amd.fit import RandomForest, load  # noqa: E402
 from fv3net_amd.forest import ForestInput, ForestOutput, ForestSpec, create_handle, float32_floor, tree_arrays  # noqa: E402
 
-
-def walk(trees, X32, threshold=None):
-    """The device walk restated: leaf node id [tree, sample] (tree-local) for float32 inputs [sample, feature]."""
-    off = trees["node_offset"]
-    thr = trees["threshold"] if threshold is None else threshold
-    n = X32.shape[0]
-    leaves = np.empty((off.shape[0] - 1, n), np.int64)
-    rows = np.arange(n)
-    for t in range(off.shape[0] - 1):
-        o = off[t]
-        node = np.zeros(n, np.int64)
-        while True:
-            internal = trees["children_left"][o + node] != -1
-            if not internal.any():
-                break
-            g = o + node[internal]
-            x = X32[rows[internal], trees["feature"][g]]
-            left = np.where(np.isnan(x), trees["missing_go_to_left"][g] == 1, x <= thr[g])
-            node[internal] = np.where(left, trees["children_left"][g], trees["children_right"][g])
-        leaves[t] = node
-    return leaves
-
-
-def forest_sum(trees, leaves):
-    """y = 0; y += value_t[leaf_t] in tree order; y /= T (float64)."""
-    off = trees["node_offset"]
-    y = np.zeros((leaves.shape[1], trees["leaf_values"].shape[1]))
-    for t in range(leaves.shape[0]):
-        y += trees["leaf_values"][trees["leaf_row"][off[t] + leaves[t]]]
-    return y / leaves.shape[0]
-
-
-def probe_inputs(forest, X_train, rng):
-    """Training values, the float32 neighbours on both sides of every threshold (in rows otherwise from the training
-    set), random values, and NaNs."""
-    X = [X_train.astype(np.float32)]
-    for est in forest.estimators_:
-        t = est.tree_
-        internal = np.flatnonzero(t.children_left != -1)
-        base = X_train[rng.integers(0, X_train.shape[0], internal.shape[0])].astype(np.float32)
-        lo = float32_floor(t.threshold[internal])
-        hi = np.nextafter(lo, np.float32(np.inf))
-        for v in (lo, hi, t.threshold[internal].astype(np.float32)):
-            b = base.copy()
-            b[np.arange(internal.shape[0]), t.feature[internal]] = v
-            X.append(b)
-    r = rng.normal(0, 2, (200, X_train.shape[1])).astype(np.float32)
-    r[rng.uniform(size=r.shape) < 0.2] = np.nan
-    X.append(r)
-    return np.concatenate(X)
+import forest_np  # noqa: E402
+from forest_np import forest_sum, probe_inputs, walk  # noqa: E402
 
 
 def _train(n_out, max_depth, n_trees=5, seed=0, n=300, k=6, cls=None):
@@ -242,3 +195,152 @@ def test_non_forest_estimators_are_refused():
     for est in (LinearRegression().fit(X, y), DecisionTreeRegressor().fit(X, y)):
         with pytest.raises(NotImplementedError, match=type(est).__name__):
             RandomForest.from_sklearn(est, ["x"], ["y"], [1], np.zeros(1), np.ones(1))
+
+
+# ---- the reference and the inputs of tests/test_gpu_forest_edges.py, proved here before any kernel is involved -----
+def _apply_and_predict_equal_sklearn(forest, X):
+    trees = tree_arrays(forest)
+    leaves = walk(trees, X)
+    np.testing.assert_array_equal(leaves.T, forest.apply(X))
+    forest_np.assert_same_bits(forest_sum(trees, leaves), forest_np.sklearn_predict(forest, X))
+    return trees, leaves
+
+
+@pytest.mark.parametrize("kind", forest_np.SKLEARN_KINDS)
+def test_reference_equals_sklearn_on_every_kind_of_forest(kind):
+    forest, X_train = forest_np.sklearn_forest(kind)
+    thresholds = np.concatenate([e.tree_.threshold[e.tree_.children_left != -1] for e in forest.estimators_])
+    counts = [e.tree_.node_count for e in forest.estimators_]
+    if kind == "rf_nan_depth8":
+        assert np.isposinf(thresholds).any()  # what sklearn gives a node that only splits off the missing values
+    if kind == "constant_target":
+        assert counts == [1] * 7
+    if kind == "rf_nan_best_first":
+        assert max(e.tree_.n_leaves for e in forest.estimators_) == 40 and forest.n_outputs_ == 1
+    X = probe_inputs(forest, X_train, np.random.default_rng(1))
+    assert np.isnan(X).any() and not np.isinf(X).any()
+    trees, _ = _apply_and_predict_equal_sklearn(forest, X)
+    assert trees["node_offset"].tolist() == np.concatenate([[0], np.cumsum(counts)]).tolist()
+
+
+@pytest.mark.parametrize("kind", forest_np.SKLEARN_KINDS)
+def test_float64_probes_equal_sklearn_when_cast(kind):
+    forest, X_train = forest_np.sklearn_forest(kind)
+    X = forest_np.float64_probes(forest, np.nan_to_num(X_train), np.random.default_rng(2))
+    assert X.dtype == np.float64
+    if kind == "constant_target":
+        assert X.shape[0] == 0
+        return
+    trees = tree_arrays(forest)
+    leaves = walk(trees, X)  # rounds to float32 itself, like the kernel
+    np.testing.assert_array_equal(leaves.T, forest.apply(X))  # sklearn casts float64 to float32 too
+    np.testing.assert_array_equal(leaves, walk(trees, X.astype(np.float32)))
+    forest_np.assert_same_bits(forest_sum(trees, leaves), forest_np.sklearn_predict(forest, X))
+
+
+def test_probes_tell_each_walk_mutation_from_the_contract():
+    """Every switch of ``forest_np.walk`` changes a leaf id on the inputs the GPU tests feed the kernel."""
+    forest, X_train = forest_np.sklearn_forest("rf_nan_depth8")
+    trees = tree_arrays(forest)
+    X32 = probe_inputs(forest, X_train, np.random.default_rng(1))
+    right = walk(trees, X32)
+    assert (walk(trees, X32, strict=True) != right).any()
+    assert (walk(trees, X32, nan_left=True) != right).any()
+    assert (walk(trees, X32, nan_left=False) != right).any()
+    naive = np.concatenate([est.tree_.threshold.astype(np.float32) for est in forest.estimators_])
+    assert (walk(trees, X32, threshold=naive) != right).any()
+    X64 = forest_np.float64_probes(forest, np.nan_to_num(X_train), np.random.default_rng(2))
+    assert (walk(trees, X64, cast=False) != walk(trees, X64)).any()
+    np.testing.assert_array_equal(walk(trees, X32, cast=False), right)  # (nothing to round in a float32)
+    # the inputs sklearn refuses, so that forest_np is the only reference there
+    for dtype in (np.float32, np.float64):
+        Xu = forest_np.unrepresentable_inputs(forest, X_train, np.random.default_rng(3), dtype)
+        with pytest.raises(ValueError), np.errstate(over="ignore", invalid="ignore"):
+            forest.apply(Xu)
+        right = walk(trees, Xu)
+        assert (walk(trees, Xu, strict=True) != right).any()
+        assert (walk(trees, Xu, nan_left=True) != right).any() and (walk(trees, Xu, nan_left=False) != right).any()
+
+
+def test_hand_made_cases_tell_each_mutation_from_the_contract():
+    # special values: <= against <, and the rounding of a float64, at zero, the subnormals and the largest float32
+    assert F32_TINY_IS_KEPT
+    for dtype in (np.float32, np.float64):
+        trees, X = forest_np.special_value_case(dtype)
+        right = walk(trees, X)
+        np.testing.assert_array_equal(forest_np.walk_stumps(trees, X), right)
+        assert (walk(trees, X, strict=True) != right).any()
+        assert (walk(trees, X, nan_left=True) != right).any() and (walk(trees, X, nan_left=False) != right).any()
+        # restated once more in Python's own floats (every float32 is one exactly)
+        with np.errstate(over="ignore"):
+            x32 = X.astype(np.float32)
+        for t in range(right.shape[0]):
+            thr, k, mgl = float(trees["threshold"][3 * t]), trees["feature"][3 * t], trees["missing_go_to_left"][3 * t]
+            want = [1 if (mgl if x != x else x <= thr) else 2 for x in map(float, x32[:, k])]
+            assert right[t].tolist() == want
+    trees, X = forest_np.special_value_case(np.float64)
+    changed = walk(trees, X, cast=False) != walk(trees, X)
+    assert changed.any()
+    # code packing: the missing-left bit of sources 0 and 31
+    trees, X, _ = forest_np.packing_case()
+    right = walk(trees, X)
+    for t in range(4):
+        assert (walk(trees, X, nan_left=not trees["missing_go_to_left"][3 * t])[t] != right[t]).any()
+    assert not np.isnan(X[:, 1:31]).any()
+    # the order of the sum
+    for T in forest_np.SUM_T:
+        for n_out in forest_np.SUM_N_OUT:
+            trees, X, mean, std = forest_np.sum_case(T, n_out)
+            leaves = forest_np.walk_stumps(trees, X)
+            np.testing.assert_array_equal(leaves, walk(trees, X))
+            a, b = forest_sum(trees, leaves), forest_sum(trees, leaves, reverse=True)
+            assert np.isfinite(a).all()
+            if T >= 7:
+                assert (a != b).any(), (T, n_out)
+    # y * std + mean in two roundings, not one: a contracted multiply-add would show on these values
+    trees, X, mean, std = forest_np.sum_case(8, 3)
+    y = forest_sum(trees, forest_np.walk_stumps(trees, X))
+    fused = [[float(Fraction(v) * Fraction(s_) + Fraction(m)) for v, s_, m in zip(row, std, mean)] for row in y]
+    assert (forest_np.denormalize(y, mean, std) != np.asarray(fused)).any()
+
+
+F32_TINY_IS_KEPT = bool(np.float32(1e-45) > 0 and np.float32(1e-45) / np.float32(2) == 0)  # numpy does not flush subnormals
+
+
+@pytest.mark.parametrize("side", ["left", "right"])
+def test_chain_stops_at_every_depth(side):
+    depth = 200
+    rng = np.random.default_rng(4)
+    trees = forest_np.chain(depth, side, 3, 2, rng)
+    assert trees["node_offset"].tolist() == [0, 2 * depth + 1]
+    X = forest_np.chain_inputs(depth, 3, rng)
+    leaves = walk(trees, X)
+    assert set(leaves[0].tolist()) == set(np.flatnonzero(trees["children_left"] == -1).tolist())  # every leaf, the deepest two too
+    assert {2 * depth - 1, 2 * depth} <= set(leaves[0, :X.shape[0] // 2].tolist())
+
+
+def test_concat_forests_renumbers():
+    rng = np.random.default_rng(5)
+    a = forest_np.stumps(3, 4, 2, rng)
+    b = forest_np.single_leaf(2)
+    c = forest_np.chain(5, "right", 4, 2, rng)
+    f = forest_np.concat_forests(a, b, c, b)
+    assert f["node_offset"].tolist() == [0, 3, 6, 9, 10, 21, 22]
+    rows = f["leaf_row"][f["children_left"] == -1]
+    assert rows.tolist() == list(range(f["leaf_values"].shape[0]))  # one row per leaf, in node order
+    X = rng.normal(size=(50, 4)).astype(np.float32) * 3
+    leaves = walk(f, X)
+    parts = [walk(p, X) for p in (a, b, c, b)]
+    np.testing.assert_array_equal(leaves, np.concatenate(parts))
+    want = sum(forest_sum(p, l) * l.shape[0] for p, l in zip((a, b, c, b), parts))
+    np.testing.assert_allclose(forest_sum(f, leaves) * 6, want, rtol=1e-12)
+
+
+def test_stump_reference_equals_the_generic_walk():
+    rng = np.random.default_rng(6)
+    trees = forest_np.stumps(50, 4, 3, rng)
+    X = rng.normal(size=(80, 4))
+    X[rng.uniform(size=X.shape) < 0.2] = np.nan
+    for dtype in (np.float32, np.float64):
+        np.testing.assert_array_equal(forest_np.walk_stumps(trees, X.astype(dtype)), walk(trees, X.astype(dtype)))
+    assert not forest_np.is_stumps(forest_np.concat_forests(trees, forest_np.single_leaf(3)))
