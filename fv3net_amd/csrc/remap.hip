@@ -133,9 +133,27 @@ __device__ __forceinline__ float ld(const char *base, unsigned int boff)
     return (float)*reinterpret_cast<const Tin *>(base + boff);
 }
 
-// Dynamic LDS of a wave: [target interfaces: kRing rows x 64 lanes, or (TGT) the whole (kn + 1) x 8 table][result ring]
+// The mean of a layer's parabola (al, ar, a6) over the piece [PL, PR] of it (mappm.f90:85-97): sp = PR + PL,
+// TT = (PR^2 + PR PL + PL^2) / 3; the fast mode is handed a6pd = a6 + (ar - al) instead of ar.
+template <bool FAST, typename V>
+__device__ __forceinline__ V piece_mean(const V &al, const V &ar, const V &a6, const V &a6pd, float sp, float TT)
+{
+    if constexpr (FAST)
+        return v_fma(-a6, v_splat(a6, TT), v_fma(a6pd, v_splat(a6, 0.5f * sp), al));
+    else
+        return al + 0.5f * (a6 + ar - al) * sp - a6 * TT;
+}
+
 extern __shared__ float sweep_lds[];
 constexpr int kSweepRing = 16;
+// Dynamic LDS of a sweep wave, in floats: [target interfaces: kSweepRing rows x 64 lanes, or (TGT) the whole (kn + 1) x 8
+// table][result ring: a column of `rows` slots per field and lane]
+struct SweepLds {
+    bool tgt;
+    int kn;
+    __host__ __device__ constexpr int results() const { return tgt ? (kn + 1) * 8 : kSweepRing * 64; }
+    __host__ __device__ constexpr size_t bytes(int nf, int rows) const { return (size_t)(results() + nf * rows * 64) * sizeof(float); }
+};
 // Result rows held per field (see the result ring below).  8 everywhere but in the instantiation the float64 restart pipelines
 // launch in the fast arithmetic: on BASELINE configs[2]'s iid data (lanes up to 16 rows apart) 12 rows cut its partial
 // stores enough to win 11 % (1.16 -> 1.04 ms) although a wave then holds 14.5 KB of LDS; every other instantiation lost
@@ -158,17 +176,54 @@ template <typename Tin, int NF, bool FAST> constexpr int sweep_out_rows() { retu
 // brings it back -- same value, same sum.  A block with an ill-formed column is listed and redone (mean_redo_kernel).
 constexpr int kMeanStride = 68;
 constexpr int kMeanGroup = 4;   // rows per flush
-#ifndef MEAN_KOUT
-#define MEAN_KOUT 8
-#endif
-template <typename Tin, int NF, bool FAST> constexpr int mean_out_rows() { return MEAN_KOUT; }   // a multiple of kMeanGroup
-__host__ __device__ constexpr int mean_n1(int kn) { return (kn + 2 + 3) & ~3; }   // kn + 1 interfaces and one spare word (the spill flag)
-__host__ __device__ constexpr int mean_nl(int kn, int esz) { return ((kn * esz + 15) & ~15) / 4; }
-// LDS of a MEAN wave, in floats: [target interfaces: n1][compared levels: kn of Tin][row weight sums: n1][ring]
-__host__ __device__ constexpr int mean_tab_floats(int kn, int esz) { return 2 * mean_n1(kn) + mean_nl(kn, esz); }
+constexpr int kMeanOut = 8;     // rows of the ring (12 and 16 were measured: DESIGN 4.3c)
+static_assert(kMeanOut % kMeanGroup == 0, "a group of rows never wraps around the ring");
+// Dynamic LDS of a fused wave, and of the two passes that finish its blocks, in floats: [target interfaces: kn + 1, padded to
+// n1; the last word is the wave's spill flag][compared levels: kn of the input type][row weight sums: n1][ring: lines x kMeanStride]
+struct MeanLds {
+    int kn, esz;
+    __host__ __device__ constexpr int n1() const { return (kn + 2 + 3) & ~3; }   // kn + 1 interfaces and one spare word at least
+    __host__ __device__ constexpr int nl() const { return ((kn * esz + 15) & ~15) / 4; }
+    __host__ __device__ constexpr int tables() const { return 2 * n1() + nl(); }
+    __device__ float *flag(float *lds) const { return lds + n1() - 1; }
+    template <typename Tin> __device__ Tin *levels(float *lds) const { return reinterpret_cast<Tin *>(lds + n1()); }
+    __device__ float *sums(float *lds) const { return lds + n1() + nl(); }
+    __device__ float *ring(float *lds) const { return lds + tables(); }
+    __host__ __device__ constexpr size_t bytes(int lines) const { return (size_t)(tables() + lines * kMeanStride) * sizeof(float); }
+};
+// mean_tables' temporary (64 floats + 64 values of the input type) lies in the ring, whose smallest is mean_redo_kernel's
+static_assert(kMeanGroup * kMeanStride >= 64 + 64 * (int)(sizeof(double) / sizeof(float)), "the ring holds mean_tables' temporary");
 
 __device__ __forceinline__ int mean_pos(int lane) { return ((lane & 4) << 3) | ((lane >> 3) << 2) | (lane & 3); }
 __device__ __forceinline__ bool f_isnan(float x) { return x != x; }
+
+// One 8 x 8 block of the fused route -- its lanes are the block's 64 fine columns -- and where its wave reads and writes.
+// Blocks are counted over the whole array, [batch][coarse plane]: so the launch counts them and so the lists name them.
+// (The accessors take the fields of SweepArgs they need, not the struct: a helper that is handed the kernel's argument struct
+// by reference moves the sweep kernel's argument loads and, with them, its register allocation.)
+struct MeanBlock {
+    int64_t gw, b, blk, c0;   // uniform: the block, its batch, the block inside the coarse plane, its first column inside the fine one
+    unsigned int lcol;        // the lane's column, counted from c0
+    MeanBlock() = default;
+    __device__ __forceinline__ MeanBlock(int64_t gw_, int64_t pe2_plane, int pe2_nx, int nx, int lane) : gw(gw_)
+    {
+        b = gw / pe2_plane;
+        blk = gw - b * pe2_plane;
+        const int64_t Y = blk / pe2_nx, X = blk - Y * pe2_nx;
+        c0 = Y * 8 * nx + X * 8;
+        lcol = (unsigned int)(lane >> 3) * (unsigned int)nx + (unsigned int)(lane & 7);
+    }
+    // the lane's area weight ([n_batch / repeat][plane]) and its surface pressure (pe1 is [batch][km + 1][plane], compared in its own type)
+    __device__ __forceinline__ float area(const float *area, int64_t repeat, int64_t plane) const { return area[(b / repeat) * plane + c0 + lcol]; }
+    template <typename Tin>
+    __device__ __forceinline__ Tin surface(const void *pe1, int km, int64_t plane) const { return static_cast<const Tin *>(pe1)[(b * (km + 1) + km) * plane + c0 + lcol]; }
+    // the block's column of a coarse array of `levels` levels ([batch][levels][plane2]): the compared pressures, a field's means
+    template <typename T>
+    __device__ __forceinline__ T *column(T *base, int levels, int64_t plane2) const { return base + b * levels * plane2 + blk; }
+    // (spilled rows lie BLOCK-major in the scratch -- [block][row][lane], a row of the wave = 256 contiguous bytes -- so they
+    // leave and come back as whole rows; the fine layout would cut them into the block's eight 32-byte pieces)
+    __device__ __forceinline__ float *spilled(float *q2, int kn) const { return q2 + gw * (int64_t)kn * 64; }
+};
 
 // The tables of one block: compared levels -> lvl[0..kn), the block's row weight sums -> den[0..kn).  `tmp` (64 floats + 64 Tin,
 // the ring's first bytes) holds the lanes' areas and surface pressures in half-major order while the sums are formed.
@@ -212,17 +267,15 @@ __device__ __forceinline__ void mean_reduce(const float *ring, int slot0, int ro
     const bool act = ri < nrows;   // (ri < kMeanGroup follows: nrows <= kMeanGroup)
     const float *src = ring + ((slot0 + (act ? ri : 0)) * NF + f) * kMeanStride + half * 32;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-#ifndef MEAN_RBATCH
-#define MEAN_RBATCH 4
-#endif
+    constexpr int kBatch = 4;
     float s = 0.f;
 #pragma unroll
-    for (int h = 0; h < 8 / MEAN_RBATCH; ++h) {  // (batches of reads: 16 registers in flight, not 32 -- the call sits inside the sweep's loop)
-        f32x4 v[MEAN_RBATCH];
+    for (int h = 0; h < 8 / kBatch; ++h) {  // (batches of reads: 16 registers in flight, not 32 -- the call sits inside the sweep's loop)
+        f32x4 v[kBatch];
 #pragma unroll
-        for (int t = 0; t < MEAN_RBATCH; ++t) v[t] = *reinterpret_cast<const f32x4 *>(src + 4 * MEAN_RBATCH * h + 4 * t);
+        for (int t = 0; t < kBatch; ++t) v[t] = *reinterpret_cast<const f32x4 *>(src + 4 * kBatch * h + 4 * t);
 #pragma unroll
-        for (int t = 0; t < MEAN_RBATCH; ++t) {
+        for (int t = 0; t < kBatch; ++t) {
             s += v[t][0];
             s += v[t][1];
             s += v[t][2];
@@ -254,13 +307,13 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
     int64_t b, c0;          // batch and first column (inside the batch plane) of the wave, uniform
     unsigned int lcol;      // the lane's column, counted from c0
     int64_t blk = 0;        // (MEAN) the wave's block inside the coarse plane
+    std::conditional_t<MEAN, MeanBlock, std::nullptr_t> mb{};   // (MEAN) the wave's block
     if constexpr (MEAN) {
-        const int64_t gw = a.col0 / 64 + wid;
-        b = gw / a.pe2_plane;
-        blk = gw - b * a.pe2_plane;
-        const int64_t Y = blk / a.pe2_nx, X = blk - Y * a.pe2_nx;
-        c0 = Y * 8 * a.nx + X * 8;
-        lcol = (unsigned int)(lane >> 3) * (unsigned int)a.nx + (unsigned int)(lane & 7);
+        mb = MeanBlock(a.col0 / 64 + wid, a.pe2_plane, a.pe2_nx, a.nx, lane);
+        b = mb.b;
+        blk = mb.blk;
+        c0 = mb.c0;
+        lcol = mb.lcol;
     } else {
         const int64_t wcol = a.col0 + (int64_t)wid * 64;
         b = wcol / a.n_inner;
@@ -512,7 +565,7 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
     float dpsum = 0.f;
 #pragma unroll
     for (int v = 0; v < NV; ++v) qsum[v] = v_splat(q0[v], 0.f);
-    constexpr int kOut = MEAN ? mean_out_rows<Tin, NF, FAST>() : sweep_out_rows<Tin, NF, FAST>();  // rows of the result ring (below)
+    constexpr int kOut = MEAN ? kMeanOut : sweep_out_rows<Tin, NF, FAST>();  // rows of the result ring (below)
     int oslot = 0, fslot = 0;  // ring slot of this lane's row k - 1 / of the wave's row rf, counted along (kOut need not be a power of two)
     auto advance = [&]() {
         ++k;
@@ -533,7 +586,7 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
     // that runs kOut rows ahead of the slowest one writes its own oldest row out first.  Ill-formed lanes count as past
     // every row; whatever the flush writes for them is overwritten by the fallback pass.  (kOut = 16 and 32 were slower:
     // the ring's LDS footprint costs occupancy.)
-    float *oring = sweep_lds + (TGT ? (kn + 1) * 8 : kRing * 64) + lane;
+    float *oring = sweep_lds + SweepLds{TGT, kn}.results() + lane;
     int rf = 0;  // uniform: rows [0, rf) are in memory for every lane
     int rl = 0;  // per lane (>= rf where it matters)
     V out_v[NV];
@@ -545,15 +598,16 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
     float *m_mean[4] = {nullptr, nullptr, nullptr, nullptr};
     const int mpos = mean_pos(lane);
     if constexpr (MEAN) {
-        m_lvl = reinterpret_cast<Tin *>(sweep_lds + mean_n1(kn));
-        m_den = sweep_lds + mean_n1(kn) + mean_nl(kn, ESZ);
-        m_ring = sweep_lds + mean_tab_floats(kn, ESZ);
-        area_l = a.area[(b / a.area_repeat) * plane + c0 + lcol];
-        const char *lvl_col = static_cast<const char *>(a.lvl) + (b * a.cmp_levels * plane2 + blk) * ESZ;
+        const MeanLds lds{kn, (int)ESZ};
+        m_lvl = lds.levels<Tin>(sweep_lds);
+        m_den = lds.sums(sweep_lds);
+        m_ring = lds.ring(sweep_lds);
+        area_l = mb.area(a.area, a.area_repeat, plane);
+        const char *lvl_col = reinterpret_cast<const char *>(mb.column(static_cast<const Tin *>(a.lvl), a.cmp_levels, plane2));
         mean_tables<Tin>(lvl_col, row_p2, a.cmp_offset, kn, lane, area_l, ps_raw, m_lvl, m_den, m_ring);
 #pragma unroll
-        for (int f = 0; f < NF; ++f) m_mean[f] = a.mean[f] + b * kn * plane2 + blk;
-        if (lane == 0) sweep_lds[mean_n1(kn) - 1] = 0.f;   // the wave's spill flag (see below)
+        for (int f = 0; f < NF; ++f) m_mean[f] = mb.column(a.mean[f], kn, plane2);
+        if (lane == 0) *lds.flag(sweep_lds) = 0.f;   // the wave's spill flag (see below)
     }
     // A ring of kOut rows holds the block while its lanes stay within kOut target rows of each other -- smooth thicknesses, i.e.
     // most of a real restart file.  Where they do not (steep terrain inside the block; BASELINE configs[2]'s iid thicknesses
@@ -564,7 +618,7 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
     // values, same order, same means.  (Bringing evicted rows back into the ring instead -- at the flush, or asynchronously a
     // row per iteration -- was measured: every variant ends with most of the wave's rows making a round trip through memory
     // on which the flush then waits; 1.2 - 2.7 ms against 0.95 for the plain sweep on the iid data.)
-    float *m_flag = sweep_lds + mean_n1(kn) - 1;   // (the spare word behind the kn + 1 interfaces)
+    float *m_flag = MeanLds{kn, (int)ESZ}.flag(sweep_lds);   // (the spare word behind the kn + 1 interfaces)
     bool spill = false;   // uniform
     int spill_row = 0;    // uniform: first row that was not summed here
     // (spilled rows lie BLOCK-major in the scratch -- [block][row][lane], a row of the wave = 256 contiguous bytes -- so they
@@ -574,7 +628,7 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
     for (int f = 0; f < NF; ++f) s_b[f] = nullptr;
     if constexpr (MEAN) {
 #pragma unroll
-        for (int f = 0; f < NF; ++f) s_b[f] = reinterpret_cast<char *>(a.q2[f] + (a.col0 / 64 + wid) * (int64_t)kn * 64);
+        for (int f = 0; f < NF; ++f) s_b[f] = reinterpret_cast<char *>(mb.spilled(a.q2[f], kn));
     }
     const unsigned int lane4 = (unsigned int)lane * 4u;
     auto out_end_mean = [&]() {
@@ -599,9 +653,7 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
             const int nrows = (kn - rf < kMeanGroup) ? kn - rf : kMeanGroup;
             const bool past = bad | (k > rf + nrows);
             if (__builtin_amdgcn_ballot_w64(past) != __builtin_amdgcn_ballot_w64(true)) break;
-#ifndef MEAN_NO_REDUCE  // (timing experiment: wrong results)
             mean_reduce<NF>(m_ring, fslot, rf, nrows, m_den, m_mean, plane2, lane);
-#endif
             rf += nrows;
             fslot = (fslot + nrows >= kOut) ? fslot + nrows - kOut : fslot + nrows;
         }
@@ -769,12 +821,7 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
             const float PL = rd0.under(p2k - pL);
             const float sp = PR + PL, TT = FAST ? r3 * __builtin_fmaf(PR, sp, PL * PL) : r3 * (PR * (PR + PL) + PL * PL);
 #pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                if constexpr (FAST)
-                    OUT(v, v_fma(-a6[v], v_splat(a6[v], TT), v_fma(a6pd[v], v_splat(a6[v], 0.5f * sp), al[v])));
-                else
-                    OUT(v, al[v] + 0.5f * (a6[v] + ar[v] - al[v]) * sp - a6[v] * TT);
-            }
+            for (int v = 0; v < NV; ++v) OUT(v, piece_mean<FAST>(al[v], ar[v], a6[v], a6pd[v], sp, TT));
             out_end();
             advance();
             live = (k <= kn) && !bad && !(p2k >= pe1_bot);
@@ -789,12 +836,7 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
                 const float delp = pL1 - p2k;
                 const float sp = 1.f + PL, TT = FAST ? r3 * __builtin_fmaf(PL, sp, 1.f) : r3 * (1.f + PL * (1.f + PL));
 #pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    if constexpr (FAST)
-                        qsum[v] = delp * v_fma(-a6[v], v_splat(a6[v], TT), v_fma(a6pd[v], v_splat(a6[v], 0.5f * sp), al[v]));
-                    else
-                        qsum[v] = delp * (al[v] + 0.5f * (a6[v] + ar[v] - al[v]) * sp - a6[v] * TT);
-                }
+                for (int v = 0; v < NV; ++v) qsum[v] = delp * piece_mean<FAST>(al[v], ar[v], a6[v], a6pd[v], sp, TT);
                 dpsum = delp;
                 accum = true;
             }
@@ -913,28 +955,22 @@ __global__ __launch_bounds__(64) SWEEP_KERNEL_ATTR void mappm_sweep_kernel(const
 template <typename Tin>
 __global__ __launch_bounds__(64) void mean_redo_kernel(const SweepArgs a, int nf)
 {
-    constexpr unsigned int ESZ = sizeof(Tin);
-    const int lane = threadIdx.x, kn = a.kn, km = a.km;
+    const int lane = threadIdx.x, kn = a.kn;
     const unsigned int count = a.n_bad[1];
     const int64_t plane = a.n_inner, plane2 = a.pe2_plane;
-    float *tgt_unused = sweep_lds;
-    (void)tgt_unused;
-    Tin *m_lvl = reinterpret_cast<Tin *>(sweep_lds + mean_n1(kn));
-    float *m_den = sweep_lds + mean_n1(kn) + mean_nl(kn, ESZ);
-    float *m_ring = sweep_lds + mean_tab_floats(kn, ESZ);
+    const MeanLds lds{kn, (int)sizeof(Tin)};
+    Tin *m_lvl = lds.levels<Tin>(sweep_lds);
+    float *m_den = lds.sums(sweep_lds), *m_ring = lds.ring(sweep_lds);
     const int mpos = mean_pos(lane);
     for (unsigned int i = blockIdx.x; i < count; i += gridDim.x) {
-        const int64_t gw = a.bad_blocks[i];
-        const int64_t b = gw / plane2, blk = gw - b * plane2, Y = blk / a.pe2_nx, X = blk - Y * a.pe2_nx;
-        const int64_t c0 = Y * 8 * a.nx + X * 8;
-        const unsigned int lcol = (unsigned int)(lane >> 3) * (unsigned int)a.nx + (unsigned int)(lane & 7);
-        const float area_l = a.area[(b / a.area_repeat) * plane + c0 + lcol];
-        const Tin ps_raw = static_cast<const Tin *>(a.pe1)[(b * (km + 1) + km) * plane + c0 + lcol];
-        const char *lvl_col = static_cast<const char *>(a.lvl) + (b * a.cmp_levels * plane2 + blk) * ESZ;
-        mean_tables<Tin>(lvl_col, (unsigned int)plane2 * ESZ, a.cmp_offset, kn, lane, area_l, ps_raw, m_lvl, m_den, m_ring);
+        const MeanBlock blk(a.bad_blocks[i], plane2, a.pe2_nx, a.nx, lane);
+        const float area_l = blk.area(a.area, a.area_repeat, plane);
+        const Tin ps_raw = blk.surface<Tin>(a.pe1, a.km, plane);
+        const char *lvl_col = reinterpret_cast<const char *>(blk.column(static_cast<const Tin *>(a.lvl), a.cmp_levels, plane2));
+        mean_tables<Tin>(lvl_col, (unsigned int)plane2 * (unsigned int)sizeof(Tin), a.cmp_offset, kn, lane, area_l, ps_raw, m_lvl, m_den, m_ring);
         for (int f = 0; f < nf; ++f) {
-            const float *q = a.q2[f] + b * kn * plane + c0 + lcol;
-            float *mean[4] = {a.mean[f] + b * kn * plane2 + blk, nullptr, nullptr, nullptr};
+            const float *q = a.q2[f] + blk.b * kn * plane + blk.c0 + blk.lcol;
+            float *mean[4] = {blk.column(a.mean[f], kn, plane2), nullptr, nullptr, nullptr};
             for (int row0 = 0; row0 < kn; row0 += kMeanGroup) {
                 const int nrows = (kn - row0 < kMeanGroup) ? kn - row0 : kMeanGroup;
                 for (int j = 0; j < nrows; ++j) {
@@ -949,70 +985,30 @@ __global__ __launch_bounds__(64) void mean_redo_kernel(const SweepArgs a, int nf
     }
 }
 
-// (the file is compiled twice -- remap.o: the sweep launches, remap_mean.o: the fused block-mean launches -- so that the two
-// sets of instantiations build side by side; see the Makefile)
-#ifndef FV3HIP_REMAP_PART_MEAN
-template <typename Tin, int NV, int W>
-void launch_sweep2(const SweepArgs &a, int64_t n_waves, bool fast, bool tgt, hipStream_t st)
-{
-#define SWEEP_(F, T)                                                                                                                \
-    hipLaunchKernelGGL((mappm_sweep_kernel<Tin, NV, W, F, T>), dim3((unsigned)n_waves), dim3(64),                                   \
-                       (size_t)((tgt ? (a.kn + 1) * 8 : kSweepRing * 64) + NV * W * sweep_out_rows<Tin, NV * W, F>() * 64) * sizeof(float), st, a)
-    if (fast) {
-        if (tgt) SWEEP_(true, true); else SWEEP_(true, false);
-    } else {
-        if (tgt) SWEEP_(false, true); else SWEEP_(false, false);
-    }
-#undef SWEEP_
-}
-
-// fields per launch -> (register slots, fields per slot): pairs of fields share packed-math instructions
-template <typename Tin>
-void launch_sweep1(const SweepArgs &a, int nf, int64_t n_waves, bool fast, bool tgt, hipStream_t st)
-{
-#ifdef FV3HIP_REMAP_SUBSET  // (experiment builds: the float64 four-field instantiations only)
-    if constexpr (sizeof(Tin) == 8) launch_sweep2<Tin, 2, 2>(a, n_waves, fast, tgt, st);
-#else
-    switch (nf) {
-        case 1: launch_sweep2<Tin, 1, 1>(a, n_waves, fast, tgt, st); break;
-        case 2: launch_sweep2<Tin, 1, 2>(a, n_waves, fast, tgt, st); break;
-        case 3: launch_sweep2<Tin, 3, 1>(a, n_waves, fast, tgt, st); break;
-        default: launch_sweep2<Tin, 2, 2>(a, n_waves, fast, tgt, st); break;
-    }
-#endif
-}
-
-#endif  // sweep part
-#ifndef FV3HIP_REMAP_PART_SWEEP
 // The blocks whose waves went into spill mode: rows [row0, kn) of their NF fields lie in the scratch, block-major, as parked
 // (p = q2 * w, NaN -> 0); their means from there -- mean_reduce again, so the same sums.  One wave per listed block, the loads of a group of
 // rows in flight while the previous group is summed.
 template <typename Tin, int NF>
 __global__ __launch_bounds__(64) void mean_rest_kernel(const SweepArgs a)
 {
-    constexpr unsigned int ESZ = sizeof(Tin);
-    const int lane = threadIdx.x, kn = a.kn, km = a.km;
+    const int lane = threadIdx.x, kn = a.kn;
     const unsigned int count = a.n_bad[2];
     const int64_t plane = a.n_inner, plane2 = a.pe2_plane;
-    Tin *m_lvl = reinterpret_cast<Tin *>(sweep_lds + mean_n1(kn));
-    float *m_den = sweep_lds + mean_n1(kn) + mean_nl(kn, ESZ);
-    float *m_ring = sweep_lds + mean_tab_floats(kn, ESZ);
+    const MeanLds lds{kn, (int)sizeof(Tin)};
+    Tin *m_lvl = lds.levels<Tin>(sweep_lds);
+    float *m_den = lds.sums(sweep_lds), *m_ring = lds.ring(sweep_lds);
     const int mpos = mean_pos(lane);
-    const unsigned int lcol = (unsigned int)(lane >> 3) * (unsigned int)a.nx + (unsigned int)(lane & 7);
     for (unsigned int i = blockIdx.x; i < count; i += gridDim.x) {
-        const int64_t gw = a.rest_blocks[2 * i];
+        const MeanBlock blk(a.rest_blocks[2 * i], plane2, a.pe2_nx, a.nx, lane);
         const int row0 = (int)a.rest_blocks[2 * i + 1];
-        const int64_t b = gw / plane2, blk = gw - b * plane2, Y = blk / a.pe2_nx, X = blk - Y * a.pe2_nx;
-        const int64_t c0 = Y * 8 * a.nx + X * 8;
-        const float area_l = a.area[(b / a.area_repeat) * plane + c0 + lcol];
-        const Tin ps_raw = static_cast<const Tin *>(a.pe1)[(b * (km + 1) + km) * plane + c0 + lcol];
-        const char *lvl_col = static_cast<const char *>(a.lvl) + (b * a.cmp_levels * plane2 + blk) * ESZ;
+        const float area_l = blk.area(a.area, a.area_repeat, plane);
+        const Tin ps_raw = blk.surface<Tin>(a.pe1, a.km, plane);
         const float *q[NF];
         float *mean[4] = {nullptr, nullptr, nullptr, nullptr};
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
-            q[f] = a.q2[f] + gw * (int64_t)kn * 64 + lane;
-            mean[f] = a.mean[f] + b * kn * plane2 + blk;
+            q[f] = blk.spilled(a.q2[f], kn) + lane;
+            mean[f] = blk.column(a.mean[f], kn, plane2);
         }
         float cur[kMeanGroup][NF], nxt[kMeanGroup][NF];
         auto request = [&](float (&v)[kMeanGroup][NF], int r0) {
@@ -1024,7 +1020,8 @@ __global__ __launch_bounds__(64) void mean_rest_kernel(const SweepArgs a)
             }
         };
         request(cur, row0 < kn ? row0 : kn - 1);
-        mean_tables<Tin>(lvl_col, (unsigned int)plane2 * ESZ, a.cmp_offset, kn, lane, area_l, ps_raw, m_lvl, m_den, m_ring);
+        const char *lvl_col = reinterpret_cast<const char *>(blk.column(static_cast<const Tin *>(a.lvl), a.cmp_levels, plane2));
+        mean_tables<Tin>(lvl_col, (unsigned int)plane2 * (unsigned int)sizeof(Tin), a.cmp_offset, kn, lane, area_l, ps_raw, m_lvl, m_den, m_ring);
         for (int r0 = row0; r0 < kn; r0 += kMeanGroup) {
             const int nrows = (kn - r0 < kMeanGroup) ? kn - r0 : kMeanGroup;
             if (r0 + kMeanGroup < kn) request(nxt, r0 + kMeanGroup);
@@ -1041,34 +1038,36 @@ __global__ __launch_bounds__(64) void mean_rest_kernel(const SweepArgs a)
     }
 }
 
-template <typename Tin, int NV, int W>
-void launch_mean2(const SweepArgs &a, int64_t n_waves, bool fast, hipStream_t st)
+// ---- launches: one dispatch over the input type, one over the fields of a launch, one over a flag ----
+template <typename F>
+void for_input_type(int in_dtype, F &&f)
 {
-#define MEAN_(F)                                                                                                                    \
-    hipLaunchKernelGGL((mappm_sweep_kernel<Tin, NV, W, F, true, true>), dim3((unsigned)n_waves), dim3(64),                          \
-                       (size_t)(mean_tab_floats(a.kn, (int)sizeof(Tin)) + NV * W * mean_out_rows<Tin, NV * W, F>() * kMeanStride) * sizeof(float), st, a)
-    if (fast) MEAN_(true); else MEAN_(false);
-#undef MEAN_
+    if (in_dtype == FV3HIP_F32) f(float{}); else f(double{});
 }
 
-template <typename Tin>
-void launch_mean1(const SweepArgs &a, int nf, int64_t n_waves, bool fast, hipStream_t st)
+// fields per launch -> (register slots, fields per slot): pairs of fields share packed-math instructions
+template <typename F>
+void for_field_slots(int nf, F &&f)
 {
-#ifdef FV3HIP_REMAP_SUBSET
-    if constexpr (sizeof(Tin) == 8) launch_mean2<Tin, 2, 2>(a, n_waves, fast, st);
-#else
+    using std::integral_constant;
     switch (nf) {
-        case 1: launch_mean2<Tin, 1, 1>(a, n_waves, fast, st); break;
-        case 2: launch_mean2<Tin, 1, 2>(a, n_waves, fast, st); break;
-        case 3: launch_mean2<Tin, 3, 1>(a, n_waves, fast, st); break;
-        default: launch_mean2<Tin, 2, 2>(a, n_waves, fast, st); break;
+        case 1: f(integral_constant<int, 1>{}, integral_constant<int, 1>{}); break;
+        case 2: f(integral_constant<int, 1>{}, integral_constant<int, 2>{}); break;
+        case 3: f(integral_constant<int, 3>{}, integral_constant<int, 1>{}); break;
+        default: f(integral_constant<int, 2>{}, integral_constant<int, 2>{}); break;
     }
-#endif
 }
 
-#endif  // mean part
+template <typename F>
+void for_flag(bool x, F &&f)
+{
+    if (x) f(std::true_type{}); else f(std::false_type{});
+}
+
 }  // namespace
 
+// (the file is compiled twice -- remap.o: the sweep launches, remap_mean.o: the fused block-mean launches -- so that the two
+// sets of instantiations build side by side; see the Makefile)
 #ifndef FV3HIP_REMAP_PART_SWEEP
 bool mappm_mean_eligible(int ny, int nx, int factor, int km, int kn, int kord, int in_dtype)
 {
@@ -1082,38 +1081,30 @@ bool mappm_mean_eligible(int ny, int nx, int factor, int km, int kn, int kord, i
 void mappm_mean_launch(const SweepArgs &a, int nf, int in_dtype, int64_t col_end, bool fast, hipStream_t st)
 {
     const int64_t n_waves = (col_end - a.col0) / 64;
-    if (in_dtype == FV3HIP_F32)
-        launch_mean1<float>(a, nf, n_waves, fast, st);
-    else
-        launch_mean1<double>(a, nf, n_waves, fast, st);
+    for_input_type(in_dtype, [&](auto t) { for_field_slots(nf, [&](auto nv, auto w) { for_flag(fast, [&](auto f) {
+        using Tin = decltype(t);
+        constexpr int NV = decltype(nv)::value, W = decltype(w)::value;
+        hipLaunchKernelGGL((mappm_sweep_kernel<Tin, NV, W, decltype(f)::value, true, true>), dim3((unsigned)n_waves), dim3(64),
+                           (MeanLds{a.kn, (int)sizeof(Tin)}.bytes(NV * W * kMeanOut)), st, a);
+    }); }); });
 }
 
 void mappm_mean_rest_launch(const SweepArgs &a, int nf, int in_dtype, int64_t n_blocks, hipStream_t st)
 {
-    const int esz = (in_dtype == FV3HIP_F64) ? 8 : 4;
-    const size_t lds = (size_t)(mean_tab_floats(a.kn, esz) + kMeanGroup * 4 * kMeanStride) * sizeof(float);
     const unsigned grid = (unsigned)(n_blocks < 8192 ? (n_blocks < 1 ? 1 : n_blocks) : 8192);
-#define REST_(T, N) hipLaunchKernelGGL((mean_rest_kernel<T, N>), dim3(grid), dim3(64), lds, st, a)
-#define REST_T(T)                                                                                                                   \
-    switch (nf) {                                                                                                                   \
-        case 1: REST_(T, 1); break;                                                                                                 \
-        case 2: REST_(T, 2); break;                                                                                                 \
-        case 3: REST_(T, 3); break;                                                                                                 \
-        default: REST_(T, 4); break;                                                                                                \
-    }
-    if (in_dtype == FV3HIP_F32) { REST_T(float) } else { REST_T(double) }
-#undef REST_T
-#undef REST_
+    for_input_type(in_dtype, [&](auto t) { for_field_slots(nf, [&](auto nv, auto w) {
+        using Tin = decltype(t);
+        constexpr int NF = decltype(nv)::value * decltype(w)::value;
+        hipLaunchKernelGGL((mean_rest_kernel<Tin, NF>), dim3(grid), dim3(64), (MeanLds{a.kn, (int)sizeof(Tin)}.bytes(kMeanGroup * kSweepMaxFields)), st, a);
+    }); });
 }
 
 void mappm_mean_redo_launch(const SweepArgs &a, int nf, int in_dtype, hipStream_t st)
 {
-    const int esz = (in_dtype == FV3HIP_F64) ? 8 : 4;
-    const size_t lds = (size_t)(mean_tab_floats(a.kn, esz) + kMeanGroup * kMeanStride + 64 * 3) * sizeof(float);
-    if (in_dtype == FV3HIP_F32)
-        hipLaunchKernelGGL((mean_redo_kernel<float>), dim3(256), dim3(64), lds, st, a, nf);
-    else
-        hipLaunchKernelGGL((mean_redo_kernel<double>), dim3(256), dim3(64), lds, st, a, nf);
+    for_input_type(in_dtype, [&](auto t) {
+        using Tin = decltype(t);
+        hipLaunchKernelGGL((mean_redo_kernel<Tin>), dim3(256), dim3(64), (MeanLds{a.kn, (int)sizeof(Tin)}.bytes(kMeanGroup)), st, a, nf);
+    });
 }
 
 #endif  // mean part
@@ -1137,10 +1128,13 @@ void mappm_sweep_launch(const SweepArgs &a, int nf, int in_dtype, int64_t col_en
     const int64_t n_waves = (col_end - a.col0) / 64;
     // the whole target table in LDS: coarser by a power of two >= 8, waves inside one fine row, (kn + 1) * 8 <= 1024 floats
     const bool tgt = a.pe2_f >= 8 && a.pe2_f <= 64 && (a.pe2_f & (a.pe2_f - 1)) == 0 && a.nx % 64 == 0 && a.kn + 1 <= 128;
-    if (in_dtype == FV3HIP_F32)
-        launch_sweep1<float>(a, nf, n_waves, fast, tgt, st);
-    else
-        launch_sweep1<double>(a, nf, n_waves, fast, tgt, st);
+    for_input_type(in_dtype, [&](auto t) { for_field_slots(nf, [&](auto nv, auto w) { for_flag(fast, [&](auto f) { for_flag(tgt, [&](auto g) {
+        using Tin = decltype(t);
+        constexpr int NV = decltype(nv)::value, W = decltype(w)::value;
+        constexpr bool FAST = decltype(f)::value, TGT = decltype(g)::value;
+        hipLaunchKernelGGL((mappm_sweep_kernel<Tin, NV, W, FAST, TGT>), dim3((unsigned)n_waves), dim3(64),
+                           (SweepLds{TGT, a.kn}.bytes(NV * W, sweep_out_rows<Tin, NV * W, FAST>())), st, a);
+    }); }); }); });
 }
 
 #endif  // sweep part

@@ -71,12 +71,15 @@ def test_block_mean_is_the_unfused_route_bit_for_bit(arith, dtype, n_fields):
 
 
 @pytest.mark.parametrize("arith", ["exact", "fast"])
-def test_block_mean_with_lanes_far_apart(arith):
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("n_fields", [1, 2, 3, 4, 5])
+def test_block_mean_with_lanes_far_apart(arith, dtype, n_fields):
     """BASELINE configs[2]'s iid thicknesses and stronger: the lanes of a block end up more rows apart than the LDS ring
-    holds (16), so values take the detour through the scratch rows -- the means must not notice."""
+    holds (16), so values take the detour through the scratch rows -- the means must not notice.  Every field count and both
+    input types: each has its own instantiation of the spill flush and of mean_rest_kernel."""
     rng = np.random.default_rng(7)
     for spread, km in ((1.0, 79), (2.5, 79), (1.0, 127)):
-        pe1, fields, pe2c, pfull, area = _case(rng, (1,), km, 16, 16, spread, np.float64, 4)
+        pe1, fields, pe2c, pfull, area = _case(rng, (1,), km, 16, 16, spread, dtype, n_fields)
         got = ops.mappm_block_mean(pe1, fields, pe2c, area, arith=arith)
         for g, w in zip(got, _unfused(pe1, fields, pe2c, pfull, area, False, arith)):
             _same(g, w)

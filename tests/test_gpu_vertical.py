@@ -608,7 +608,7 @@ def test_mappm_sweep_kernel_exact_mode_is_bit_identical(device, km, kn, n_fields
 
 @pytest.mark.parametrize("km,kn", [(79, 79), (33, 29), (20, 45)])
 @pytest.mark.parametrize("n_fields,iv,kord,cast", [(1, 1, 1, np.float32), (2, 0, 2, np.float64), (4, 1, 1, np.float32),
-                                                   (7, -1, 3, np.float32)])
+                                                   (7, -1, 3, np.float32), (4, 1, 1, np.float64)])
 def test_mappm_sweep_kernel_fast_mode_within_tolerance(device, km, kn, n_fields, iv, kord, cast):
     """FV3HIP_ARITH_FAST (reciprocal-multiply, shared reciprocals): |fast - reference| <= 1e-5 x the column's value range
     on every level (the north star's 1e-5 relative; a result near zero has no relative accuracy in the reference
@@ -732,11 +732,13 @@ def test_fast_mode_outliers_stay_within_the_source_layers_bounds(device):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 @pytest.mark.parametrize("ny,nx,nfields", [(64, 64, 1), (64, 128, 4), (65, 64, 3), (64, 65, 2), (65, 16, 2)])
-def test_coarse_target_remap_equals_the_upsampled_one(device, dtype, ny, nx, nfields):
+@pytest.mark.parametrize("arith", [pytest.param("exact", id=pytest.HIDDEN_PARAM), "fast"])  # (the exact cases keep their ids)
+def test_coarse_target_remap_equals_the_upsampled_one(device, dtype, ny, nx, nfields, arith):
     """``mappm_multi_coarse_target`` (target interfaces read through (y // f, x // f)) gives bit for bit what the reference's
     route gives -- upsample the coarse interfaces, then remap (regridz.py:119-185) -- for centred and staggered (odd) dims,
     1..4 fields, both input dtypes, shapes the sweep kernel takes and one it does not (65 x 16 columns are not whole waves: the fallback inside the op);
-    so does ``mask_weights`` with the coarse pressures."""
+    so does ``mask_weights`` with the coarse pressures.  In both arithmetic modes: the arithmetic does not depend on where an
+    interface is read from (the fast mode's target table in LDS against its interface ring)."""
     from fv3net_amd import ops
 
     f, nb, km = 8, 3, 19
@@ -747,8 +749,8 @@ def test_coarse_target_remap_equals_the_upsampled_one(device, dtype, ny, nx, nfi
     pe1 = ops.pressure_at_interface(delp, 300.0, 1)
     pe2_c = ops.pressure_at_interface(delp_c, 300.0, 1)
     qs = [torch.rand((nb, km, ny, nx), device=device, generator=g, dtype=dtype) * 200 - 100 for _ in range(nfields)]
-    want = ops.mappm_multi(pe1, qs, ops.block_upsample(pe2_c, f), z_axis=1)
-    got = ops.mappm_multi_coarse_target(pe1, qs, pe2_c, f, z_axis=1)
+    want = ops.mappm_multi(pe1, qs, ops.block_upsample(pe2_c, f), z_axis=1, arith=arith)
+    got = ops.mappm_multi_coarse_target(pe1, qs, pe2_c, f, z_axis=1, arith=arith)
     for a, b in zip(got, want):
         assert torch.equal(a, b)
     w = torch.rand((nb, ny, nx), device=device, generator=g, dtype=torch.float32)
