@@ -797,15 +797,15 @@ __global__ void ew_kernel(int op, const T *__restrict__ a, const T *__restrict__
         T v;
         switch (op) {
             case FV3HIP_EW_MUL: v = x * y; break;
-            case FV3HIP_EW_ISCLOSE: {  // np.isclose(a, b): |a - b| <= atol + rtol |b|, equal infinities close, NaN never
-                const T d = x - y;
-                v = ((x == y) || ((d < 0 ? -d : d) <= (T)1e-8 + (T)1e-5 * (y < 0 ? -y : y))) ? (T)1 : (T)0;
+            case FV3HIP_EW_ISCLOSE: {  // np.isclose(a, b): (|a - b| <= atol + rtol |b| and b finite) or a == b; NaN never
+                const T d = x - y;     // (an infinite b makes the tolerance infinite: only an equal infinity is close to it)
+                v = ((x == y) || ((y - y == (T)0) && (d < 0 ? -d : d) <= (T)1e-8 + (T)1e-5 * (y < 0 ? -y : y))) ? (T)1 : (T)0;
                 if (x != x || y != y) v = (T)0;
                 break;
             }
             case FV3HIP_EW_ISCLOSE_S: {
                 const T d = x - s;
-                v = ((x == s) || ((d < 0 ? -d : d) <= (T)1e-8 + (T)1e-5 * (s < 0 ? -s : s))) ? (T)1 : (T)0;
+                v = ((x == s) || ((s - s == (T)0) && (d < 0 ? -d : d) <= (T)1e-8 + (T)1e-5 * (s < 0 ? -s : s))) ? (T)1 : (T)0;
                 if (x != x) v = (T)0;
                 break;
             }
@@ -824,8 +824,9 @@ __global__ void ew_kernel(int op, const T *__restrict__ a, const T *__restrict__
             case FV3HIP_EW_SUB: v = x - y; break;
             case FV3HIP_EW_LOG_FLOOR_S: v = log(x < s ? s : x); break;         // tf.math.log(tf.maximum(a, s)); a NaN stays a NaN 
             case FV3HIP_EW_EXP: v = exp(x); break;
-            case FV3HIP_EW_RELU_THRESHOLD_S: v = (x > s) ? x : (T)0; break;    // tf.keras.activations.relu(a, threshold=s)
-            case FV3HIP_EW_BELOW_S: v = (x < s) ? x : (T)0; break;             // tf.cast(a < s, a.dtype) * a
+            // LimitValueTransform.backward's two steps; the truth table is in oracle/mlp_np.py:limit_value_backward
+            case FV3HIP_EW_RELU_THRESHOLD_S: v = (x > s) ? x : ((x != x) ? x : (T)0); break;  // tf.keras.activations.relu(a, threshold=s): a NaN stays a NaN
+            case FV3HIP_EW_BELOW_S: v = (x < s) ? x : (T)0 * x; break;                        // tf.cast(a < s, a.dtype) * a: 0 * a where a >= s (NaN for NaN, +inf)
             case FV3HIP_EW_DIV_S: v = x / s; break;
             case FV3HIP_EW_CLIP01: v = (x != x) ? x : (x < (T)0 ? (T)0 : (x > (T)1 ? (T)1 : x)); break;  // np.clip(a, 0, 1)
             case FV3HIP_EW_POW_BASE_S: v = (T)pow((double)s, (double)x); break;                            // scalar ** a

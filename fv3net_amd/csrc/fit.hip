@@ -54,8 +54,8 @@ __global__ void member_reduce_kernel(MemberPtrs m, int n_members, int op, int64_
         if (cnt == 0) {
             r = (T)NAN;
         } else if (op == FV3HIP_OP_MEAN) {
-            T s = 0;
-            for (int k = 0; k < cnt; ++k) s += v[k];
+            T s = v[0];  // (from the first kept value, not from +0: members that are all -0 average to -0)
+            for (int k = 1; k < cnt; ++k) s += v[k];
             r = s / (T)cnt;
         } else {  // median: insertion sort of at most 32 values, mean of the two middle ones
             for (int a = 1; a < cnt; ++a) {

@@ -57,12 +57,13 @@ __device__ __forceinline__ int bin_of(const float *__restrict__ edges, int n, fl
     return lo > 0 ? lo - 1 : 0;
 }
 
-// LimitValueTransform.backward (transforms.py:148-158): keras relu(x, threshold=lower), then (x < upper) * x;
-// NaN stays NaN
+// LimitValueTransform.backward (transforms.py:151-159): keras relu(x, threshold=lower) -- x where x > lower (strict),
+// 0 elsewhere, a NaN stays a NaN -- then cast(x < upper) * x -- x where x < upper, else 0 * x (0 for a finite x, NaN for
+// NaN and +inf).  The truth table is in oracle/mlp_np.py:limit_value_backward.
 __device__ __forceinline__ float limit_value(float v, int flags, float lo, float hi)
 {
-    if ((flags & 1) && v < lo) v = 0.f;
-    if ((flags & 2) && !(v < hi) && v == v) v = 0.f;
+    if (flags & 1) v = (v > lo) ? v : ((v != v) ? v : 0.f);
+    if (flags & 2) v = (v < hi) ? v : 0.f * v;
     return v;
 }
 

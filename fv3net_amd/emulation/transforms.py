@@ -38,10 +38,11 @@ def _ew(op: str, a, b=None, scalar: float = 0.0):
         return np.log(np.where(a < scalar, a.dtype.type(scalar), a))
     if op == "exp":
         return np.exp(a)
-    if op == "relu_threshold_s":
-        return np.where(a > scalar, a, a.dtype.type(0))
-    if op == "below_s":
-        return np.where(a < scalar, a, a.dtype.type(0))
+    if op == "relu_threshold_s":  # (a NaN stays a NaN)
+        return np.where((a > scalar) | np.isnan(a), a, a.dtype.type(0))
+    if op == "below_s":  # (0 * a: NaN for a NaN and for +inf)
+        with np.errstate(invalid="ignore"):
+            return np.where(a < scalar, a, a.dtype.type(0) * a)
     raise ValueError(op)
 
 
@@ -102,7 +103,8 @@ class LogTransform:
 
 @dataclasses.dataclass
 class LimitValueTransform:
-    """forward: identity; backward: the value where ``lower < y < upper``, 0 elsewhere (transforms.py:131-158)."""
+    """forward: identity; backward: the value where ``lower < y < upper``, 0 elsewhere (transforms.py:131-158); what a NaN, an
+    infinity and a value on a limit become is tabulated in ``oracle/mlp_np.py:limit_value_backward``."""
 
     lower: Optional[float] = 0.0
     upper: Optional[float] = None

@@ -422,6 +422,10 @@ def flux_to_tendency(net_flux: torch.Tensor, surface_downward_flux: torch.Tensor
 def minmax_score(variables: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], offsets: Sequence[torch.Tensor]) -> torch.Tensor:
     """MinMaxNoveltyDetector's score (fv3fit/sklearn/_min_max_novelty_detector.py:94-121) of ``[feature, sample]`` arrays
     (any strides) scaled as ``MinMaxScaler.transform`` does: ``max(max_f - 1, 0) + max(-min_f, 0)``, float64 ``[sample]``."""
+    if len(variables) == 0:  # (no launch would ever write the score)
+        raise ValueError("minmax_score needs at least one variable")
+    if not len(variables) == len(scales) == len(offsets):
+        raise ValueError("minmax_score needs one scale and one offset array per variable")
     dev = _require_device(*variables)
     n = int(variables[0].shape[1])
     run_max = torch.empty(n, dtype=torch.float64, device=dev)

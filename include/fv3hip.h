@@ -191,8 +191,8 @@ int fv3hip_block_upsample(const void *in, int elem_size, int64_t n_outer, int ny
 #define FV3HIP_EW_SUB 16               /* a - b                                (Difference.forward)               */
 #define FV3HIP_EW_LOG_FLOOR_S 17       /* log(max(a, scalar))                  (LogTransform.forward)             */
 #define FV3HIP_EW_EXP 18               /* exp(a)                               (LogTransform.backward)            */
-#define FV3HIP_EW_RELU_THRESHOLD_S 19  /* a where a > scalar else 0            (LimitValueTransform, lower bound) */
-#define FV3HIP_EW_BELOW_S 20           /* a where a < scalar else 0            (LimitValueTransform, upper bound) */
+#define FV3HIP_EW_RELU_THRESHOLD_S 19  /* a where a > scalar (strict) else 0, NaN stays  (LimitValueTransform, lower bound) */
+#define FV3HIP_EW_BELOW_S 20           /* a where a < scalar else 0 * a (NaN for NaN, +inf) (LimitValueTransform, upper bound) */
 #define FV3HIP_EW_DIV_S 21             /* a / scalar                           (vcm temperature_tendency, thermo/local.py:340-358) */
 #define FV3HIP_EW_INCLOUD_TO_GRIDCELL 22 /* b where a <= 1e-3 else b * max-like(a, 5e-2): in-cloud -> gridcell condensate by cloud
                                           fraction a (vcm/calc/clouds.py:40-66) */
@@ -710,7 +710,8 @@ int fv3hip_hydrostatic_balance(const void *dz, const void *phis, const void *t, 
  *                                       b = max(upper_bound(edges[0..n_bins), cond_on) - 1, 0)
  *                                       (keras/math.py:5-23 piecewise)          (cond_on NULL = skipped)
  *                            LimitValueTransform.backward (transforms.py:131-158) on the last of these:
- *                                       x < value_lower -> 0 (limit_flags bit 0), x >= value_upper -> 0 (bit 1)
+ *                                       x <= value_lower -> 0, a NaN stays (limit_flags bit 0); x >= value_upper -> 0 * x,
+ *                                       NaN for NaN and +inf (bit 1); the table: oracle/mlp_np.py:limit_value_backward
  *                            after    = before + that value, limited likewise with after_lower / after_upper
  *                                       (bits 2, 3)                             (before NULL = skipped)
  *                          level z of yhat starts at yhat + z * yhat_level_stride; any of out_direct /

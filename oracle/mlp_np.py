@@ -127,12 +127,36 @@ def conditionally_scaled_backward(y, on, edges, scale, center, min_scale=0.0):
 
 
 def limit_value_backward(x, lower=None, upper=None):
-    """LimitValueTransform.backward (transforms/transforms.py:148-158): ``relu(x, threshold=lower)`` (x where
-    x >= lower, else 0), then ``cast(x < upper) * x``."""
+    """LimitValueTransform.backward (transforms/transforms.py:151-159): ``tf.keras.activations.relu(x, threshold=lower)``,
+    then ``tf.cast(x < upper, x.dtype) * x``.  The reference's own test (fv3fit/tests/emulation/test_transform.py:338-361)
+    expects ``[0, -1, 0, 1, 0, 0]`` of ``[-2, -1, 0, 1, 2, 3]`` with ``lower=-2, upper=2``: both limits are strict.  This is
+    the one statement of the rule; the device kernels (``limit_value`` in csrc/local.hip, the two ``fv3hip_ew`` steps) and
+    the host fallback of ``fv3net_amd.emulation.transforms`` implement the same table:
+
+        ===========  ===============================  ==================================
+        x            after ``lower`` (relu threshold)  after ``upper`` (mask * x)
+        ===========  ===============================  ==================================
+        x > lower    x                                .
+        x == lower   0                                .
+        x < lower    0                                .
+        -inf         0  (*)                           .
+        NaN          NaN                              NaN   (0 * NaN)
+        x < upper    .                                x     (-inf stays -inf)
+        x == upper   .                                0 * x (0 with x's sign)
+        x > upper    .                                0 * x (0 with x's sign)
+        +inf         +inf (when lower < +inf)         NaN   (0 * inf)
+        ===========  ===============================  ==================================
+
+    (*) unverified: for a non-zero threshold Keras multiplies by the mask ``x > threshold`` and may give NaN for -inf;
+    Keras was not available to check this one cell, and 0 is what ``tf.nn.relu`` gives for ``lower == 0``.  The sign of
+    the lower step's zero is +0 for every ``x <= lower``; a mask product would give -0 for a negative ``x``.  The two
+    compare equal, the reference's test cannot tell them apart, and this sign is as unverified as (*).  The upper
+    step's zero is the product ``0 * x`` and carries ``x``'s sign."""
     if lower is not None:
-        x = np.where(x < np.asarray(lower, x.dtype), np.zeros((), x.dtype), x)
+        x = np.where((x > np.asarray(lower, x.dtype)) | np.isnan(x), x, np.zeros((), x.dtype))
     if upper is not None:
-        x = np.where(~(x < np.asarray(upper, x.dtype)) & ~np.isnan(x), np.zeros((), x.dtype), x)
+        with np.errstate(invalid="ignore"):
+            x = np.where(x < np.asarray(upper, x.dtype), x, np.zeros((), x.dtype) * x)
     return x
 
 

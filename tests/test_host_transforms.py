@@ -33,6 +33,30 @@ def test_limit_value_transform(lower, upper, expected):  # test_transform.py:338
     np.testing.assert_array_equal(t.backward(x), np.array(expected, np.float64))
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("lower,upper,expected", [
+    # x:          nan      -inf     +inf    -1.5  nextafter(-1.5, +inf)  2.5  nextafter(2.5, -inf)  -3   3   0
+    (-1.5, None, [np.nan,  0,       np.inf,  0,   "above_lower",         2.5, "below_upper",         0,  3,  0]),
+    (None, 2.5,  [np.nan, -np.inf,  np.nan, -1.5, "above_lower",         0,   "below_upper",        -3,  0,  0]),
+    (-1.5, 2.5,  [np.nan,  0,       np.nan,  0,   "above_lower",         0,   "below_upper",         0,  0,  0]),
+])
+def test_limit_value_transform_nonfinite_and_on_the_limits(lower, upper, expected, dtype):
+    """The rows the reference's test does not have (the table in oracle/mlp_np.py:limit_value_backward): a NaN stays a NaN,
+    +inf times the zero of the upper mask is NaN, -inf under the lower limit is 0, a value equal to a non-zero lower limit is
+    0 and its upward neighbour survives; the host fallback and the oracle agree bit for bit."""
+    from oracle import mlp_np
+
+    above_lower, below_upper = np.nextafter(dtype(-1.5), dtype(np.inf)), np.nextafter(dtype(2.5), dtype(-np.inf))
+    x = np.array([np.nan, -np.inf, np.inf, -1.5, above_lower, 2.5, below_upper, -3, 3, 0], dtype)
+    want = np.array([{"above_lower": above_lower, "below_upper": below_upper}.get(e, e) for e in expected], dtype)
+    got = LimitValueTransform(lower=lower, upper=upper).backward(x)
+    assert got.dtype == dtype
+    np.testing.assert_array_equal(got, want)
+    oracle = mlp_np.limit_value_backward(x, lower, upper)
+    np.testing.assert_array_equal(got, oracle)
+    np.testing.assert_array_equal(np.signbit(got), np.signbit(oracle))
+
+
 def test_composed_transform_skips_what_it_cannot_apply_and_runs_backward_in_reverse():
     class Rename:  # test_transform.py:125-143
         def __init__(self, a, b):

@@ -147,11 +147,25 @@ def test_forward_local_against_torch_cpu(dtype, tol):
 
 
 def test_limit_value_backward_known_answers():
-    # external/fv3fit/fv3fit/emulation/transforms/transforms.py:131-158 (keras relu with a threshold, then the upper mask)
+    # external/fv3fit/fv3fit/emulation/transforms/transforms.py:151-159 (keras relu with a threshold, then the upper mask):
+    # both limits are strict, a NaN stays a NaN
     x = np.array([-2.0, -1.0, 0.0, 1.0, 2.0, np.nan], np.float32)
     np.testing.assert_array_equal(mlp_np.limit_value_backward(x, 0.0, None), [0, 0, 0, 1, 2, np.nan])
     np.testing.assert_array_equal(mlp_np.limit_value_backward(x, None, 0.0), [-2, -1, 0, 0, 0, np.nan])
-    np.testing.assert_array_equal(mlp_np.limit_value_backward(x, -1.0, 2.0), [0, -1, 0, 1, 0, np.nan])
+    np.testing.assert_array_equal(mlp_np.limit_value_backward(x, -1.0, 2.0), [0, 0, 0, 1, 0, np.nan])
+    # the reference's own five cases (external/fv3fit/tests/emulation/test_transform.py:338-361)
+    for dtype in (np.float32, np.float64):
+        t = np.array([-2, -1, 0, 1, 2, 3], dtype)
+        for lower, upper, expected in [(None, None, [-2, -1, 0, 1, 2, 3]), (0, None, [0, 0, 0, 1, 2, 3]), (None, 0, [-2, -1, 0, 0, 0, 0]),
+                                       (-2, 2, [0, -1, 0, 1, 0, 0]), (1, 1, [0, 0, 0, 0, 0, 0])]:
+            got = mlp_np.limit_value_backward(t, lower, upper)
+            assert got.dtype == dtype
+            np.testing.assert_array_equal(got, np.array(expected, dtype), err_msg=f"lower={lower}, upper={upper}")
+    # the rest of the table in the docstring: infinities (0 * inf is NaN; -inf under the lower limit gives 0)
+    e = np.array([-np.inf, np.inf, np.nan], np.float32)
+    np.testing.assert_array_equal(mlp_np.limit_value_backward(e, -1.0, None), [0, np.inf, np.nan])
+    np.testing.assert_array_equal(mlp_np.limit_value_backward(e, None, 2.0), [-np.inf, np.nan, np.nan])
+    np.testing.assert_array_equal(mlp_np.limit_value_backward(e, -1.0, 2.0), [0, np.nan, np.nan])
 
 
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-12), (np.float32, 5e-5)])
