@@ -327,13 +327,6 @@ bool with_constant(int n, int &rc, Fn fn)
     return ((n == Ns ? (rc = fn(std::integral_constant<int, Ns>{}), true) : false) || ...);
 }
 
-// fn(To{}, Tw{}) for two dtype codes, each F32 or F64
-template <typename Fn>
-int with_float_pair(int a_dtype, int b_dtype, Fn fn)
-{
-    return with_float(a_dtype, [&](auto a) { return with_float(b_dtype, [&](auto b) { return fn(a, b); }); });
-}
-
 template <typename Tf, typename Ta>
 int dispatch_mass_wavg(const void *const *fields, int n_fields, const Tf *delp, const Ta *area, int64_t n_outer, int ny,
                        int nx, int64_t a_repeat, int factor, void *const *outs, hipStream_t stream)

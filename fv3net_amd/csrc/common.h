@@ -41,8 +41,8 @@ inline unsigned grid_stride_blocks(int64_t total)
     return (unsigned)(blocks < 256 * 64 ? blocks : 256 * 64);
 }
 
-// f(T{}) with T the unsigned word of elem_size bytes (4 or 8) / the float type of a dtype code (F32 or F64); the
-// caller has checked the code.
+// f(T{}) with T the unsigned word of elem_size bytes (4 or 8) / the float type of a dtype code (F32 or F64) /
+// f(Ta{}, Tb{}) for two dtype codes; the caller has checked the code (is_float).
 template <typename Fn>
 auto with_word(int elem_size, Fn f)
 {
@@ -53,6 +53,26 @@ template <typename Fn>
 auto with_float(int dtype, Fn f)
 {
     return dtype == FV3HIP_F64 ? f(double{}) : f(float{});
+}
+
+template <typename Fn>
+auto with_float_pair(int a_dtype, int b_dtype, Fn f)
+{
+    return with_float(a_dtype, [&](auto a) { return with_float(b_dtype, [&](auto b) { return f(a, b); }); });
+}
+
+inline bool is_float(int dtype) { return dtype == FV3HIP_F32 || dtype == FV3HIP_F64; }
+
+// An untyped array argument as the T array that a dispatch lambda launches on (const stays const).
+template <typename T>
+T *as(void *p)
+{
+    return static_cast<T *>(p);
+}
+template <typename T>
+const T *as(const void *p)
+{
+    return static_cast<const T *>(p);
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -85,6 +105,22 @@ template <typename T>
 __device__ __forceinline__ T running_max(T mx, T v)
 {
     return (v > mx || v != v) ? v : mx;
+}
+
+// Element i of an F32 or F64 array as T: (float) of a float64 is the Keras cast to the layer dtype, (double) holds either
+// dtype exactly.
+template <typename T>
+__device__ __forceinline__ T load_as(const void *p, int dtype, int64_t i)
+{
+    return dtype == FV3HIP_F64 ? (T) static_cast<const double *>(p)[i] : (T) static_cast<const float *>(p)[i];
+}
+
+// np.max over the classes of column i of logits [n_class][n]; class c is hot where load_as<double>(its logit) equals it.
+__device__ __forceinline__ double class_max(const void *logits, int dtype, int n_class, int64_t n, int64_t i)
+{
+    double mx = load_as<double>(logits, dtype, i);
+    for (int c = 1; c < n_class; ++c) mx = running_max(mx, load_as<double>(logits, dtype, (int64_t)c * n + i));
+    return mx;
 }
 
 }  // namespace fv3hip

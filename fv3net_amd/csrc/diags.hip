@@ -217,8 +217,8 @@ extern "C" int fv3hip_group_sums(const void *a, const void *b, int dtype, const 
                                  int64_t n_groups, const int32_t *item_group, const int32_t *item_chunk, int64_t n_items,
                                  const int64_t *group_item, double *sums, void *workspace, size_t workspace_bytes, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "unsupported dtype %d", dtype);
-    FV3HIP_REQUIRE(!weights || w_dtype == FV3HIP_F32 || w_dtype == FV3HIP_F64, "unsupported weight dtype %d", w_dtype);
+    FV3HIP_REQUIRE(is_float(dtype), "unsupported dtype %d", dtype);
+    FV3HIP_REQUIRE(!weights || is_float(w_dtype), "unsupported weight dtype %d", w_dtype);
     FV3HIP_REQUIRE(n_batch >= 0 && nz >= 0 && n_inner >= 0 && n_order >= 0 && n_groups >= 0 && n_items >= 0, "negative extent");
     FV3HIP_REQUIRE(nz <= 65535, "at most 65535 levels, got %d", nz);
     FV3HIP_REQUIRE(n_inner == 0 || n_batch <= (int64_t)0x7fffffff / n_inner, "cell ids are int32: %lld x %lld cells do not fit",
@@ -234,26 +234,22 @@ extern "C" int fv3hip_group_sums(const void *a, const void *b, int dtype, const 
                        fv3hip_group_sums_workspace_bytes(n_items, nz));
         const dim3 grid((unsigned)n_items, (unsigned)nz);
         double *partial = static_cast<double *>(workspace);
-#define LAUNCH_(TA, TW, HB, HW)                                                                                              \
-    hipLaunchKernelGGL((group_sums_items_kernel<TA, TW, HB, HW>), grid, dim3(kGsThreads), 0, st, static_cast<const TA *>(a), \
-                       static_cast<const TA *>(b), static_cast<const TW *>(weights), n_batch, nz, n_inner, order, n_order,   \
-                       start, n_groups, item_group, item_chunk, partial)
-#define LAUNCH_B_(TA, TW, HW)          \
-    do {                               \
-        if (b) LAUNCH_(TA, TW, true, HW); \
-        else LAUNCH_(TA, TW, false, HW);  \
-    } while (0)
-#define LAUNCH_W_(TA)                                            \
-    do {                                                         \
-        if (!weights) LAUNCH_B_(TA, float, false);               \
-        else if (w_dtype == FV3HIP_F32) LAUNCH_B_(TA, float, true); \
-        else LAUNCH_B_(TA, double, true);                        \
-    } while (0)
-        if (dtype == FV3HIP_F32) LAUNCH_W_(float);
-        else LAUNCH_W_(double);
-#undef LAUNCH_W_
-#undef LAUNCH_B_
-#undef LAUNCH_
+        // the kernel for the operand types and for which of b and weights are there (without weights their type is float)
+        auto launch = [&](auto ta, auto tw, auto has_w) {
+            using TA = decltype(ta);
+            using TW = decltype(tw);
+            auto items = [&](auto has_b) {
+                hipLaunchKernelGGL((group_sums_items_kernel<TA, TW, decltype(has_b)::value, decltype(has_w)::value>), grid,
+                                   dim3(kGsThreads), 0, st, as<TA>(a), as<TA>(b), as<TW>(weights), n_batch, nz, n_inner, order,
+                                   n_order, start, n_groups, item_group, item_chunk, partial);
+            };
+            if (b) items(std::true_type{});
+            else items(std::false_type{});
+        };
+        with_float(dtype, [&](auto ta) {
+            if (weights) with_float(w_dtype, [&](auto tw) { launch(ta, tw, std::true_type{}); });
+            else launch(ta, float{}, std::false_type{});
+        });
         int rc = check_launch("group_sums_items_kernel");
         if (rc != FV3HIP_OK) return rc;
     }
@@ -266,27 +262,25 @@ extern "C" int fv3hip_group_sums(const void *a, const void *b, int dtype, const 
 
 extern "C" int fv3hip_histogram(const void *x, int dtype, int64_t n, const double *edges, int n_bins, int64_t *counts, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "unsupported dtype %d", dtype);
+    FV3HIP_REQUIRE(is_float(dtype), "unsupported dtype %d", dtype);
     FV3HIP_REQUIRE(n_bins >= 1 && n_bins <= kHistMaxBins, "1 to %d bins, got %d", kHistMaxBins, n_bins);
     FV3HIP_REQUIRE(n >= 0, "negative extent");
     FV3HIP_REQUIRE(edges && counts && (x || n == 0), "null pointer");
     hipStream_t st = as_stream(stream);
     FV3HIP_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)n_bins * sizeof(int64_t), st));
     if (n == 0) return FV3HIP_OK;
-    unsigned long long *out = reinterpret_cast<unsigned long long *>(counts);
-    if (dtype == FV3HIP_F32)
-        hipLaunchKernelGGL((histogram_kernel<float>), dim3(hist_blocks(n)), dim3(kHistThreads), 0, st, static_cast<const float *>(x), n,
-                           edges, n_bins, out);
-    else
-        hipLaunchKernelGGL((histogram_kernel<double>), dim3(hist_blocks(n)), dim3(kHistThreads), 0, st, static_cast<const double *>(x),
-                           n, edges, n_bins, out);
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((histogram_kernel<T>), dim3(hist_blocks(n)), dim3(kHistThreads), 0, st, as<T>(x), n, edges, n_bins,
+                           reinterpret_cast<unsigned long long *>(counts));
+    });
     return check_launch("histogram_kernel");
 }
 
 extern "C" int fv3hip_histogram2d(const void *x, const void *y, int dtype, int64_t n, const double *xedges, int nx_bins,
                                   const double *yedges, int ny_bins, int64_t *counts, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "unsupported dtype %d", dtype);
+    FV3HIP_REQUIRE(is_float(dtype), "unsupported dtype %d", dtype);
     FV3HIP_REQUIRE(nx_bins >= 1 && nx_bins <= kHist2dMaxBins && ny_bins >= 1 && ny_bins <= kHist2dMaxBins,
                    "1 to %d bins per axis, got %d x %d", kHist2dMaxBins, nx_bins, ny_bins);
     FV3HIP_REQUIRE(n >= 0, "negative extent");
@@ -294,12 +288,10 @@ extern "C" int fv3hip_histogram2d(const void *x, const void *y, int dtype, int64
     hipStream_t st = as_stream(stream);
     FV3HIP_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)nx_bins * ny_bins * sizeof(int64_t), st));
     if (n == 0) return FV3HIP_OK;
-    unsigned long long *out = reinterpret_cast<unsigned long long *>(counts);
-    if (dtype == FV3HIP_F32)
-        hipLaunchKernelGGL((histogram2d_kernel<float>), dim3(hist_blocks(n)), dim3(kHistThreads), 0, st, static_cast<const float *>(x),
-                           static_cast<const float *>(y), n, xedges, nx_bins, yedges, ny_bins, out);
-    else
-        hipLaunchKernelGGL((histogram2d_kernel<double>), dim3(hist_blocks(n)), dim3(kHistThreads), 0, st, static_cast<const double *>(x),
-                           static_cast<const double *>(y), n, xedges, nx_bins, yedges, ny_bins, out);
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((histogram2d_kernel<T>), dim3(hist_blocks(n)), dim3(kHistThreads), 0, st, as<T>(x), as<T>(y), n, xedges,
+                           nx_bins, yedges, ny_bins, reinterpret_cast<unsigned long long *>(counts));
+    });
     return check_launch("histogram2d_kernel");
 }

@@ -23,17 +23,6 @@
 namespace fv3hip {
 namespace {
 
-template <typename T>
-__device__ __forceinline__ T ld(const void *p, int dt, int64_t i)
-{
-    return dt == FV3HIP_F64 ? (T) static_cast<const double *>(p)[i] : (T) static_cast<const float *>(p)[i];
-}
-template <typename T>
-__device__ __forceinline__ void st(void *p, int64_t i, T v)
-{
-    static_cast<T *>(p)[i] = v;
-}
-
 // np.maximum / np.minimum: a NaN in either operand comes out (a ? b : c selects drop it)
 template <typename T>
 __device__ __forceinline__ T nan_max(T a, T b)
@@ -61,12 +50,12 @@ __global__ void squash_kernel(const void *cloud, int cdt, const void *hum, int h
                               int cloud_out_dt, T *qv_out)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const T c = ld<T>(cloud, cdt, i);
+        const T c = load_as<T>(cloud, cdt, i);
         const T co = less_in_dtype<T>(c, cdt, (double)bound) ? (T)0 : c;
         // (the squashed cloud keeps the cloud's own dtype, as np.where(cloud < bound, 0, cloud) does)
         if (cloud_out_dt == FV3HIP_F64) static_cast<double *>(cloud_out)[i] = (double)co;
         else static_cast<float *>(cloud_out)[i] = (float)co;
-        qv_out[i] = ld<T>(hum, hdt, i) + (c - co);
+        qv_out[i] = load_as<T>(hum, hdt, i) + (c - co);
     }
 }
 
@@ -75,7 +64,7 @@ __global__ void infer_cloud_kernel(const void *cloud_in, const void *qv_in, int 
                                    T *cloud_out)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        cloud_out[i] = ld<T>(cloud_in, sdt, i) - (ld<T>(qv_emul, edt, i) - ld<T>(qv_in, sdt, i));
+        cloud_out[i] = load_as<T>(cloud_in, sdt, i) - (load_as<T>(qv_emul, edt, i) - load_as<T>(qv_in, sdt, i));
 }
 
 // which cloud goes into the conservation step (zhao_carr.py:180-246).  The auxiliary array only decides (its dtype is
@@ -85,17 +74,13 @@ __device__ __forceinline__ T choose_cloud(int mode, T c_emul, T c_in, const void
                                           int n_class, int cls)
 {
     switch (mode) {
-        case FV3HIP_ZC_FORTRAN_VANISHES: return less_in_dtype<double>(ld<double>(aux, adt, i), adt, 1e-15) ? (T)0 : c_emul;
-        case FV3HIP_ZC_FORTRAN_IDENTICAL: return ld<double>(aux, adt, i) == (double)c_in ? c_in : c_emul;
+        case FV3HIP_ZC_FORTRAN_VANISHES: return less_in_dtype<double>(load_as<double>(aux, adt, i), adt, 1e-15) ? (T)0 : c_emul;
+        case FV3HIP_ZC_FORTRAN_IDENTICAL: return load_as<double>(aux, adt, i) == (double)c_in ? c_in : c_emul;
         case FV3HIP_ZC_CLASS_ZERO_CLOUD:
         case FV3HIP_ZC_CLASS_ZERO_TEND: {
             // one-hot by arg-max with ties all hot: logit[cls] == max over classes (zhao_carr.py:193-198)
-            double mx = ld<double>(aux, adt, i);
-            for (int c = 1; c < n_class; ++c) {
-                const double v = ld<double>(aux, adt, (int64_t)c * n + i);
-                mx = running_max(mx, v);
-            }
-            const bool hot = ld<double>(aux, adt, (int64_t)cls * n + i) == mx;
+            const double mx = class_max(aux, adt, n_class, n, i);
+            const bool hot = load_as<double>(aux, adt, (int64_t)cls * n + i) == mx;
             return hot ? (mode == FV3HIP_ZC_CLASS_ZERO_CLOUD ? (T)0 : c_in) : c_emul;
         }
         default: return c_emul;
@@ -123,9 +108,9 @@ __global__ void gscond_conserve_kernel(const void *cloud_in, const void *qv_in, 
                                        int cls, int64_t n, T *cloud_out, T *qv_out, T *t_out)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const T c_in = ld<T>(cloud_in, sdt, i);
-        const T choice = choose_cloud<T>(mode, ld<T>(cloud_emul, edt, i), c_in, aux, adt, i, n, n_class, cls);
-        conserve_one<T>(c_in, ld<T>(qv_in, sdt, i), ld<T>(t_in, sdt, i), choice, (T)kLv, i, cloud_out, qv_out, t_out);
+        const T c_in = load_as<T>(cloud_in, sdt, i);
+        const T choice = choose_cloud<T>(mode, load_as<T>(cloud_emul, edt, i), c_in, aux, adt, i, n, n_class, cls);
+        conserve_one<T>(c_in, load_as<T>(qv_in, sdt, i), load_as<T>(t_in, sdt, i), choice, (T)kLv, i, cloud_out, qv_out, t_out);
     }
 }
 
@@ -188,10 +173,10 @@ __global__ __launch_bounds__(256) void gscond_conserve_phase_kernel(const void *
     for (int64_t k = hi - 1; k >= lo && hi > 0; --k) {
         state = (elem_map(k) >> state) & 1u;
         const int64_t i = row * n1 + k;
-        const T c_in = ld<T>(cloud_in, sdt, i);
-        const T choice = choose_cloud<T>(mode, ld<T>(cloud_emul, edt, i), c_in, aux, adt, i, n, n_class, cls);
+        const T c_in = load_as<T>(cloud_in, sdt, i);
+        const T choice = choose_cloud<T>(mode, load_as<T>(cloud_emul, edt, i), c_in, aux, adt, i, n, n_class, cls);
         const T lv = (T)kLv + (T)state * (T)kHfus;
-        conserve_one<T>(c_in, ld<T>(qv_in, sdt, i), ld<T>(t_in, sdt, i), choice, lv, i, cloud_out, qv_out, t_out);
+        conserve_one<T>(c_in, load_as<T>(qv_in, sdt, i), load_as<T>(t_in, sdt, i), choice, lv, i, cloud_out, qv_out, t_out);
     }
 }
 
@@ -205,9 +190,9 @@ __global__ void precpd_conserve_kernel(const void *cloud_g, const void *qv_g, co
         T total = 0;
         for (int64_t k = n0 - 1; k >= 0; --k) {
             const int64_t i = k * n1 + s;
-            const T dp = ld<T>(delp, sdt, i), cg = ld<T>(cloud_g, sdt, i), qg = ld<T>(qv_g, sdt, i);
-            T src = (T)-1 * (ld<T>(cloud_p, edt, i) - cg) * dp / (T)kGravity;
-            T sink = (ld<T>(qv_p, edt, i) - qg) * dp / (T)kGravity;
+            const T dp = load_as<T>(delp, sdt, i), cg = load_as<T>(cloud_g, sdt, i), qg = load_as<T>(qv_g, sdt, i);
+            T src = (T)-1 * (load_as<T>(cloud_p, edt, i) - cg) * dp / (T)kGravity;
+            T sink = (load_as<T>(qv_p, edt, i) - qg) * dp / (T)kGravity;
             src = nan_max(src, (T)0);    // np.maximum(x, 0), np.minimum(total, evaporation): a NaN from the emulator
             sink = nan_max(sink, (T)0);  // stays a NaN, in this level and, through `total`, in all below it
             total = total + src;
@@ -216,7 +201,7 @@ __global__ void precpd_conserve_kernel(const void *cloud_g, const void *qv_g, co
             const T evap = ev / dp * (T)kGravity;
             cloud_out[i] = cg + ((T)-1 * src) / dp * (T)kGravity;
             qv_out[i] = qg + evap;
-            t_out[i] = ld<T>(t_g, sdt, i) + (T)(kLv / kCp) * (T)-1 * evap;
+            t_out[i] = load_as<T>(t_g, sdt, i) + (T)(kLv / kCp) * (T)-1 * evap;
         }
         precip_out[s] = total / (T)kRhoWater;
     }
@@ -235,12 +220,12 @@ __global__ void precip_simple_kernel(const void *cloud_g, const void *qv_g, cons
         for (int64_t k = 0; k < n0; ++k) {  // np.sum over axis 0: sequential in k
             const int64_t i = k * n1 + s;
             if (sdt == FV3HIP_F64)
-                before_d += (ld<double>(qv_g, sdt, i) + ld<double>(cloud_g, sdt, i)) * ld<double>(delp, sdt, i) / kGravity;
+                before_d += (load_as<double>(qv_g, sdt, i) + load_as<double>(cloud_g, sdt, i)) * load_as<double>(delp, sdt, i) / kGravity;
             else
-                before_f += (ld<float>(qv_g, sdt, i) + ld<float>(cloud_g, sdt, i)) * ld<float>(delp, sdt, i) / (float)kGravity;
-            const T wa = edt == FV3HIP_F64 ? (T)(ld<double>(qv_p, edt, i) + ld<double>(cloud_p, edt, i))
-                                           : (T)(ld<float>(qv_p, edt, i) + ld<float>(cloud_p, edt, i));
-            after += wa * ld<T>(delp, sdt, i) / (T)kGravity;
+                before_f += (load_as<float>(qv_g, sdt, i) + load_as<float>(cloud_g, sdt, i)) * load_as<float>(delp, sdt, i) / (float)kGravity;
+            const T wa = edt == FV3HIP_F64 ? (T)(load_as<double>(qv_p, edt, i) + load_as<double>(cloud_p, edt, i))
+                                           : (T)(load_as<float>(qv_p, edt, i) + load_as<float>(cloud_p, edt, i));
+            after += wa * load_as<T>(delp, sdt, i) / (T)kGravity;
         }
         const T before = sdt == FV3HIP_F64 ? (T)before_d : (T)before_f;
         precip_out[s] = (before - after) / (T)kRhoWater;
@@ -266,9 +251,9 @@ __global__ void level_fill_kernel(const void *emul, int edt, const void *src, in
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t k = i / n1;
         if (k >= start && k < stop)
-            out[i] = src ? ld<double>(src, sdt, i) : fill;
+            out[i] = src ? load_as<double>(src, sdt, i) : fill;
         else
-            out[i] = ld<double>(emul, edt, i);
+            out[i] = load_as<double>(emul, edt, i);
     }
 }
 
@@ -276,12 +261,8 @@ template <typename T>
 __global__ void class_zero_kernel(const T *x, const void *logits, int ldt, int n_class, int cls, int64_t n, T *out)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double mx = ld<double>(logits, ldt, i);
-        for (int c = 1; c < n_class; ++c) {
-            const double v = ld<double>(logits, ldt, (int64_t)c * n + i);
-            mx = running_max(mx, v);
-        }
-        out[i] = (ld<double>(logits, ldt, (int64_t)cls * n + i) == mx) ? (T)0 : x[i];
+        const double mx = class_max(logits, ldt, n_class, n, i);
+        out[i] = (load_as<double>(logits, ldt, (int64_t)cls * n + i) == mx) ? (T)0 : x[i];
     }
 }
 
@@ -316,52 +297,40 @@ __global__ void non_negative_sphum_kernel(const T *sphum, const T *q1, const T *
     }
 }
 
-inline unsigned grid_for(int64_t n)
-{
-    int64_t b = ceil_div(n, 256);
-    return (unsigned)(b > 256 * 64 ? 256 * 64 : (b < 1 ? 1 : b));
-}
-inline bool float_code(int dt) { return dt == FV3HIP_F32 || dt == FV3HIP_F64; }
-
 }  // namespace
 }  // namespace fv3hip
 
 using namespace fv3hip;
 
-#define ZC_COMMON_CHECKS(n)                                                                        \
-    FV3HIP_REQUIRE(out_dtype == FV3HIP_F32 || out_dtype == FV3HIP_F64, "out_dtype must be F32 or F64"); \
-    FV3HIP_REQUIRE((n) >= 0, "negative extent");                                                   \
-    if ((n) == 0) return FV3HIP_OK
-
 extern "C" int fv3hip_zc_squash(const void *cloud, int cloud_dtype, const void *humidity, int hum_dtype, int64_t n,
                                 double bound, int out_dtype, void *cloud_out, void *qv_out, void *stream)
 {
-    ZC_COMMON_CHECKS(n);
-    FV3HIP_REQUIRE(float_code(cloud_dtype) && float_code(hum_dtype), "arrays must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(out_dtype), "out_dtype must be F32 or F64");
+    FV3HIP_REQUIRE(n >= 0, "negative extent");
+    if (n == 0) return FV3HIP_OK;
+    FV3HIP_REQUIRE(is_float(cloud_dtype) && is_float(hum_dtype), "arrays must be F32 or F64");
     FV3HIP_REQUIRE(cloud && humidity && cloud_out && qv_out, "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (out_dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((squash_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, cloud, cloud_dtype, humidity,
-                           hum_dtype, n, bound, cloud_out, cloud_dtype, static_cast<double *>(qv_out));
-    else
-        hipLaunchKernelGGL((squash_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, cloud, cloud_dtype, humidity,
-                           hum_dtype, n, (float)bound, cloud_out, cloud_dtype, static_cast<float *>(qv_out));
+    with_float(out_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((squash_kernel<T>), dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), cloud, cloud_dtype,
+                           humidity, hum_dtype, n, (T)bound, cloud_out, cloud_dtype, as<T>(qv_out));
+    });
     return check_launch("squash_kernel");
 }
 
 extern "C" int fv3hip_zc_infer_cloud(const void *cloud_in, const void *qv_in, int state_dtype, const void *qv_emul,
                                      int emul_dtype, int64_t n, int out_dtype, void *cloud_out, void *stream)
 {
-    ZC_COMMON_CHECKS(n);
-    FV3HIP_REQUIRE(float_code(state_dtype) && float_code(emul_dtype), "arrays must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(out_dtype), "out_dtype must be F32 or F64");
+    FV3HIP_REQUIRE(n >= 0, "negative extent");
+    if (n == 0) return FV3HIP_OK;
+    FV3HIP_REQUIRE(is_float(state_dtype) && is_float(emul_dtype), "arrays must be F32 or F64");
     FV3HIP_REQUIRE(cloud_in && qv_in && qv_emul && cloud_out, "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (out_dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((infer_cloud_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, cloud_in, qv_in, state_dtype,
-                           qv_emul, emul_dtype, n, static_cast<double *>(cloud_out));
-    else
-        hipLaunchKernelGGL((infer_cloud_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, cloud_in, qv_in, state_dtype,
-                           qv_emul, emul_dtype, n, static_cast<float *>(cloud_out));
+    with_float(out_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((infer_cloud_kernel<T>), dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), cloud_in, qv_in,
+                           state_dtype, qv_emul, emul_dtype, n, as<T>(cloud_out));
+    });
     return check_launch("infer_cloud_kernel");
 }
 
@@ -372,32 +341,29 @@ extern "C" int fv3hip_zc_gscond_conserve(const void *cloud_in, const void *qv_in
 {
     const int64_t n = n0 * n1;
     FV3HIP_REQUIRE(n0 >= 0 && n1 >= 0, "negative extent");
-    ZC_COMMON_CHECKS(n);
-    FV3HIP_REQUIRE(float_code(state_dtype) && float_code(emul_dtype), "arrays must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(out_dtype), "out_dtype must be F32 or F64");
+    FV3HIP_REQUIRE(n >= 0, "negative extent");
+    if (n == 0) return FV3HIP_OK;
+    FV3HIP_REQUIRE(is_float(state_dtype) && is_float(emul_dtype), "arrays must be F32 or F64");
     FV3HIP_REQUIRE(mode >= FV3HIP_ZC_NO_MASK && mode <= FV3HIP_ZC_CLASS_ZERO_TEND, "unknown gscond mask mode %d", mode);
     FV3HIP_REQUIRE(cloud_in && qv_in && t_in && cloud_emul && cloud_out && qv_out && t_out, "null pointer");
     if (mode != FV3HIP_ZC_NO_MASK) {
-        FV3HIP_REQUIRE(aux && float_code(aux_dtype), "this mask mode needs its auxiliary array (F32 or F64)");
+        FV3HIP_REQUIRE(aux && is_float(aux_dtype), "this mask mode needs its auxiliary array (F32 or F64)");
         if (mode >= FV3HIP_ZC_CLASS_ZERO_CLOUD)
             FV3HIP_REQUIRE(n_class >= 1 && cls >= 0 && cls < n_class, "class index %d out of range [0, %d)", cls, n_class);
     }
-    hipStream_t st = as_stream(stream);
-#define ZC_LAUNCH_(T)                                                                                              \
-    if (phase_dependent)                                                                                           \
-        hipLaunchKernelGGL((gscond_conserve_phase_kernel<T>), dim3((unsigned)n0), dim3(256), 0, st, cloud_in, qv_in, t_in, \
-                           state_dtype, cloud_emul, emul_dtype, mode, aux, aux_dtype, n_class, cls, n0, n1,        \
-                           static_cast<T *>(cloud_out), static_cast<T *>(qv_out), static_cast<T *>(t_out));        \
-    else                                                                                                           \
-        hipLaunchKernelGGL((gscond_conserve_kernel<T>), dim3(grid_for(n)), dim3(256), 0, st, cloud_in, qv_in, t_in, \
-                           state_dtype, cloud_emul, emul_dtype, mode, aux, aux_dtype, n_class, cls, n,             \
-                           static_cast<T *>(cloud_out), static_cast<T *>(qv_out), static_cast<T *>(t_out))
-    if (out_dtype == FV3HIP_F64) {
-        ZC_LAUNCH_(double);
-    } else {
-        ZC_LAUNCH_(float);
-    }
-#undef ZC_LAUNCH_
-    return check_launch("gscond_conserve_kernel");
+    with_float(out_dtype, [&](auto t) {
+        using T = decltype(t);
+        if (phase_dependent)
+            hipLaunchKernelGGL((gscond_conserve_phase_kernel<T>), dim3((unsigned)n0), dim3(256), 0, as_stream(stream), cloud_in, qv_in,
+                               t_in, state_dtype, cloud_emul, emul_dtype, mode, aux, aux_dtype, n_class, cls, n0, n1,
+                               as<T>(cloud_out), as<T>(qv_out), as<T>(t_out));
+        else
+            hipLaunchKernelGGL((gscond_conserve_kernel<T>), dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), cloud_in,
+                               qv_in, t_in, state_dtype, cloud_emul, emul_dtype, mode, aux, aux_dtype, n_class, cls, n,
+                               as<T>(cloud_out), as<T>(qv_out), as<T>(t_out));
+    });
+    return check_launch(phase_dependent ? "gscond_conserve_phase_kernel" : "gscond_conserve_kernel");
 }
 
 extern "C" int fv3hip_zc_precpd_conserve(const void *cloud_g, const void *qv_g, const void *t_g, const void *delp,
@@ -406,20 +372,18 @@ extern "C" int fv3hip_zc_precpd_conserve(const void *cloud_g, const void *qv_g, 
                                          void *precip_out, void *stream)
 {
     FV3HIP_REQUIRE(n0 >= 0 && n1 >= 0, "negative extent");
-    ZC_COMMON_CHECKS(n1);
-    FV3HIP_REQUIRE(float_code(state_dtype) && float_code(emul_dtype), "arrays must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(out_dtype), "out_dtype must be F32 or F64");
+    if (n1 == 0) return FV3HIP_OK;
+    FV3HIP_REQUIRE(is_float(state_dtype) && is_float(emul_dtype), "arrays must be F32 or F64");
     // (no levels: the arrays are empty and may be null; the column totals are still written, as numpy's zeros)
     FV3HIP_REQUIRE(precip_out && (n0 == 0 || (cloud_g && qv_g && t_g && delp && cloud_p && qv_p && cloud_out && qv_out && t_out)),
                    "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (out_dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((precpd_conserve_kernel<double>), dim3(grid_for(n1)), dim3(256), 0, st, cloud_g, qv_g, t_g, delp,
-                           state_dtype, cloud_p, qv_p, emul_dtype, n0, n1, static_cast<double *>(cloud_out),
-                           static_cast<double *>(qv_out), static_cast<double *>(t_out), static_cast<double *>(precip_out));
-    else
-        hipLaunchKernelGGL((precpd_conserve_kernel<float>), dim3(grid_for(n1)), dim3(256), 0, st, cloud_g, qv_g, t_g, delp,
-                           state_dtype, cloud_p, qv_p, emul_dtype, n0, n1, static_cast<float *>(cloud_out),
-                           static_cast<float *>(qv_out), static_cast<float *>(t_out), static_cast<float *>(precip_out));
+    with_float(out_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((precpd_conserve_kernel<T>), dim3(grid_stride_blocks(n1)), dim3(256), 0, as_stream(stream), cloud_g, qv_g,
+                           t_g, delp, state_dtype, cloud_p, qv_p, emul_dtype, n0, n1, as<T>(cloud_out), as<T>(qv_out),
+                           as<T>(t_out), as<T>(precip_out));
+    });
     return check_launch("precpd_conserve_kernel");
 }
 
@@ -428,82 +392,73 @@ extern "C" int fv3hip_zc_precip_simple(const void *cloud_g, const void *qv_g, co
                                        int out_dtype, void *precip_out, void *stream)
 {
     FV3HIP_REQUIRE(n0 >= 0 && n1 >= 0, "negative extent");
-    ZC_COMMON_CHECKS(n1);
-    FV3HIP_REQUIRE(float_code(state_dtype) && float_code(emul_dtype), "arrays must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(out_dtype), "out_dtype must be F32 or F64");
+    if (n1 == 0) return FV3HIP_OK;
+    FV3HIP_REQUIRE(is_float(state_dtype) && is_float(emul_dtype), "arrays must be F32 or F64");
     FV3HIP_REQUIRE(precip_out && (n0 == 0 || (cloud_g && qv_g && delp && cloud_p && qv_p)), "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (out_dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((precip_simple_kernel<double>), dim3(grid_for(n1)), dim3(256), 0, st, cloud_g, qv_g, delp,
-                           state_dtype, cloud_p, qv_p, emul_dtype, n0, n1, static_cast<double *>(precip_out));
-    else
-        hipLaunchKernelGGL((precip_simple_kernel<float>), dim3(grid_for(n1)), dim3(256), 0, st, cloud_g, qv_g, delp,
-                           state_dtype, cloud_p, qv_p, emul_dtype, n0, n1, static_cast<float *>(precip_out));
+    with_float(out_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((precip_simple_kernel<T>), dim3(grid_stride_blocks(n1)), dim3(256), 0, as_stream(stream), cloud_g, qv_g,
+                           delp, state_dtype, cloud_p, qv_p, emul_dtype, n0, n1, as<T>(precip_out));
+    });
     return check_launch("precip_simple_kernel");
 }
 
 extern "C" int fv3hip_clamp(const void *x, int dtype, int64_t n, double lo, double hi, int has_lo, int has_hi, void *out,
                             void *stream)
 {
-    FV3HIP_REQUIRE(float_code(dtype), "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n >= 0, "negative extent");
     if (n == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(x && out, "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((clamp_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, static_cast<const double *>(x), n, lo,
-                           hi, has_lo, has_hi, static_cast<double *>(out));
-    else
-        hipLaunchKernelGGL((clamp_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, static_cast<const float *>(x), n,
-                           (float)lo, (float)hi, has_lo, has_hi, static_cast<float *>(out));
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((clamp_kernel<T>), dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), as<T>(x), n, (T)lo, (T)hi,
+                           has_lo, has_hi, as<T>(out));
+    });
     return check_launch("clamp_kernel");
 }
 
 extern "C" int fv3hip_level_fill(const void *emul, int emul_dtype, const void *src, int src_dtype, double fill_value,
                                  int64_t n0, int64_t n1, int64_t start, int64_t stop, void *out, void *stream)
 {
-    FV3HIP_REQUIRE(float_code(emul_dtype), "emul_dtype must be F32 or F64");
-    FV3HIP_REQUIRE(!src || float_code(src_dtype), "src_dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(emul_dtype), "emul_dtype must be F32 or F64");
+    FV3HIP_REQUIRE(!src || is_float(src_dtype), "src_dtype must be F32 or F64");
     FV3HIP_REQUIRE(n0 >= 0 && n1 >= 0, "negative extent");
     if (n0 * n1 == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(emul && out, "null pointer");
-    hipLaunchKernelGGL(level_fill_kernel, dim3(grid_for(n0 * n1)), dim3(256), 0, as_stream(stream), emul, emul_dtype, src,
-                       src_dtype, fill_value, n0, n1, start, stop, static_cast<double *>(out));
+    hipLaunchKernelGGL(level_fill_kernel, dim3(grid_stride_blocks(n0 * n1)), dim3(256), 0, as_stream(stream), emul, emul_dtype, src,
+                       src_dtype, fill_value, n0, n1, start, stop, as<double>(out));
     return check_launch("level_fill_kernel");
 }
 
 extern "C" int fv3hip_zc_class_zero(const void *x, int dtype, const void *logits, int logits_dtype, int n_class, int cls,
                                     int64_t n, void *out, void *stream)
 {
-    FV3HIP_REQUIRE(float_code(dtype) && float_code(logits_dtype), "arrays must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype) && is_float(logits_dtype), "arrays must be F32 or F64");
     FV3HIP_REQUIRE(n_class >= 1 && cls >= 0 && cls < n_class, "class index %d out of range [0, %d)", cls, n_class);
     FV3HIP_REQUIRE(n >= 0, "negative extent");
     if (n == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(x && logits && out, "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((class_zero_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st, static_cast<const double *>(x),
-                           logits, logits_dtype, n_class, cls, n, static_cast<double *>(out));
-    else
-        hipLaunchKernelGGL((class_zero_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st, static_cast<const float *>(x),
-                           logits, logits_dtype, n_class, cls, n, static_cast<float *>(out));
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((class_zero_kernel<T>), dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), as<T>(x), logits,
+                           logits_dtype, n_class, cls, n, as<T>(out));
+    });
     return check_launch("class_zero_kernel");
 }
 
 extern "C" int fv3hip_non_negative_sphum(const void *sphum, const void *q1, const void *q2, int dtype, int64_t n, double dt,
                                          int mse_conserving, void *q1_out, void *q2_out, void *stream)
 {
-    FV3HIP_REQUIRE(float_code(dtype), "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n >= 0, "negative extent");
     if (n == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(sphum && q2 && q2_out && (!q1 || q1_out), "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((non_negative_sphum_kernel<double>), dim3(grid_for(n)), dim3(256), 0, st,
-                           static_cast<const double *>(sphum), static_cast<const double *>(q1), static_cast<const double *>(q2),
-                           n, dt, mse_conserving, static_cast<double *>(q1_out), static_cast<double *>(q2_out));
-    else
-        hipLaunchKernelGGL((non_negative_sphum_kernel<float>), dim3(grid_for(n)), dim3(256), 0, st,
-                           static_cast<const float *>(sphum), static_cast<const float *>(q1), static_cast<const float *>(q2), n,
-                           (float)dt, mse_conserving, static_cast<float *>(q1_out), static_cast<float *>(q2_out));
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((non_negative_sphum_kernel<T>), dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), as<T>(sphum),
+                           as<T>(q1), as<T>(q2), n, (T)dt, mse_conserving, as<T>(q1_out), as<T>(q2_out));
+    });
     return check_launch("non_negative_sphum_kernel");
 }

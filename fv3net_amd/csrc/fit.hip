@@ -184,12 +184,6 @@ __global__ __launch_bounds__(kSvmSamples) void ocsvm_score_kernel(const double *
     if (i < n) score[i] = -1.0 * total;
 }
 
-inline unsigned flat_grid(int64_t n)
-{
-    int64_t b = ceil_div(n, 256);
-    return (unsigned)(b > 256 * 64 ? 256 * 64 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 }  // namespace fv3hip
 
@@ -198,24 +192,23 @@ using namespace fv3hip;
 extern "C" int fv3hip_level_scale(const void *x, int dtype, const double *scale, int64_t n_outer, int nz, int64_t n_inner,
                                   double *out, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_outer >= 0 && nz >= 0 && n_inner >= 0, "negative extent");
     const int64_t total = n_outer * nz * n_inner;
     if (total == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(x && scale && out, "null pointer");
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((level_scale_kernel<double>), dim3(flat_grid(total)), dim3(256), 0, as_stream(stream),
-                           static_cast<const double *>(x), scale, n_outer, nz, n_inner, out);
-    else
-        hipLaunchKernelGGL((level_scale_kernel<float>), dim3(flat_grid(total)), dim3(256), 0, as_stream(stream),
-                           static_cast<const float *>(x), scale, n_outer, nz, n_inner, out);
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((level_scale_kernel<T>), dim3(grid_stride_blocks(total)), dim3(256), 0, as_stream(stream), as<T>(x), scale,
+                           n_outer, nz, n_inner, out);
+    });
     return check_launch("level_scale_kernel");
 }
 
 extern "C" int fv3hip_member_reduce(const void *const *members, int n_members, int dtype, int op, int64_t n, void *out,
                                     void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(op == FV3HIP_OP_MEAN || op == FV3HIP_OP_MEDIAN, "op must be FV3HIP_OP_MEAN or FV3HIP_OP_MEDIAN");
     FV3HIP_REQUIRE(n_members >= 1 && n_members <= kMaxMembers, "between 1 and %d members", kMaxMembers);
     FV3HIP_REQUIRE(n >= 0, "negative extent");
@@ -227,12 +220,11 @@ extern "C" int fv3hip_member_reduce(const void *const *members, int n_members, i
         FV3HIP_REQUIRE(members[k], "null member pointer");
         m.p[k] = members[k];
     }
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((member_reduce_kernel<double>), dim3(flat_grid(n)), dim3(256), 0, as_stream(stream), m, n_members, op, n,
-                           static_cast<double *>(out));
-    else
-        hipLaunchKernelGGL((member_reduce_kernel<float>), dim3(flat_grid(n)), dim3(256), 0, as_stream(stream), m, n_members, op, n,
-                           static_cast<float *>(out));
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((member_reduce_kernel<T>), dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), m, n_members, op,
+                           n, as<T>(out));
+    });
     return check_launch("member_reduce_kernel");
 }
 
@@ -240,22 +232,17 @@ extern "C" int fv3hip_tendency_to_flux(const void *tendency, const void *delp, c
                                        const void *surface_upward_flux, int dtype, int64_t n_outer, int nz, int64_t n_inner,
                                        int rectify, int closure, void *net_flux, void *surface_downward_flux, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_outer >= 0 && nz >= 1 && n_inner >= 0, "bad extents");
     const int64_t cols = n_outer * n_inner;
     if (cols == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(tendency && delp && surface_upward_flux && surface_downward_flux && (closure || net_flux), "null pointer");
-    const dim3 grid((unsigned)ceil_div(cols, (int64_t)256));
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((tendency_to_flux_kernel<double>), grid, dim3(256), 0, as_stream(stream), static_cast<const double *>(tendency),
-                           static_cast<const double *>(delp), static_cast<const double *>(toa_net_flux),
-                           static_cast<const double *>(surface_upward_flux), n_outer, nz, n_inner, rectify, closure,
-                           static_cast<double *>(net_flux), static_cast<double *>(surface_downward_flux));
-    else
-        hipLaunchKernelGGL((tendency_to_flux_kernel<float>), grid, dim3(256), 0, as_stream(stream), static_cast<const float *>(tendency),
-                           static_cast<const float *>(delp), static_cast<const float *>(toa_net_flux),
-                           static_cast<const float *>(surface_upward_flux), n_outer, nz, n_inner, rectify, closure,
-                           static_cast<float *>(net_flux), static_cast<float *>(surface_downward_flux));
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((tendency_to_flux_kernel<T>), dim3((unsigned)ceil_div(cols, 256)), dim3(256), 0, as_stream(stream),
+                           as<T>(tendency), as<T>(delp), as<T>(toa_net_flux), as<T>(surface_upward_flux), n_outer, nz, n_inner,
+                           rectify, closure, as<T>(net_flux), as<T>(surface_downward_flux));
+    });
     return check_launch("tendency_to_flux_kernel");
 }
 
@@ -263,20 +250,17 @@ extern "C" int fv3hip_flux_to_tendency(const void *net_flux, const void *surface
                                        const void *delp, int dtype, int64_t n_outer, int nz, int64_t n_inner, void *tendency,
                                        void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_outer >= 0 && nz >= 1 && n_inner >= 0, "bad extents");
     const int64_t cols = n_outer * n_inner;
     if (cols == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(net_flux && surface_downward_flux && surface_upward_flux && delp && tendency, "null pointer");
-    const dim3 grid((unsigned)ceil_div(cols, (int64_t)256));
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((flux_to_tendency_kernel<double>), grid, dim3(256), 0, as_stream(stream), static_cast<const double *>(net_flux),
-                           static_cast<const double *>(surface_downward_flux), static_cast<const double *>(surface_upward_flux),
-                           static_cast<const double *>(delp), n_outer, nz, n_inner, static_cast<double *>(tendency));
-    else
-        hipLaunchKernelGGL((flux_to_tendency_kernel<float>), grid, dim3(256), 0, as_stream(stream), static_cast<const float *>(net_flux),
-                           static_cast<const float *>(surface_downward_flux), static_cast<const float *>(surface_upward_flux),
-                           static_cast<const float *>(delp), n_outer, nz, n_inner, static_cast<float *>(tendency));
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((flux_to_tendency_kernel<T>), dim3((unsigned)ceil_div(cols, 256)), dim3(256), 0, as_stream(stream),
+                           as<T>(net_flux), as<T>(surface_downward_flux), as<T>(surface_upward_flux), as<T>(delp), n_outer, nz,
+                           n_inner, as<T>(tendency));
+    });
     return check_launch("flux_to_tendency_kernel");
 }
 
@@ -284,17 +268,15 @@ extern "C" int fv3hip_minmax_score(const void *x, int dtype, int64_t feat_stride
                                    const double *scale, const double *offset, int64_t n, int first, int finish, double *run_max,
                                    double *run_min, double *score, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n >= 0 && n_feat >= 1, "bad extents");
     if (n == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(x && scale && offset && run_max && run_min && (score || !finish), "null pointer");
-    const dim3 grid((unsigned)ceil_div(n, (int64_t)256));
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((minmax_score_kernel<double>), grid, dim3(256), 0, as_stream(stream), static_cast<const double *>(x),
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((minmax_score_kernel<T>), dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, as_stream(stream), as<T>(x),
                            feat_stride, sample_stride, n_feat, scale, offset, n, first, finish, run_max, run_min, score);
-    else
-        hipLaunchKernelGGL((minmax_score_kernel<float>), grid, dim3(256), 0, as_stream(stream), static_cast<const float *>(x),
-                           feat_stride, sample_stride, n_feat, scale, offset, n, first, finish, run_max, run_min, score);
+    });
     return check_launch("minmax_score_kernel");
 }
 

@@ -24,13 +24,8 @@
 namespace fv3hip {
 namespace {
 
-__device__ __forceinline__ float ldf(const void *p, int dt, int64_t i)
-{
-    // Keras casts float64 inputs to the layer dtype first
-    return dt == FV3HIP_F64 ? (float)static_cast<const double *>(p)[i] : static_cast<const float *>(p)[i];
-}
-
-// one network input: out[z][c] = (t(x[z or 0][c]) - center[z]) / scale[z]
+// one network input: out[z][c] = (t(x[z or 0][c]) - center[z]) / scale[z]; Keras casts float64 inputs to the layer dtype
+// first (load_as<float>, here and in local_unpack_kernel)
 __global__ void local_pack_kernel(const void *__restrict__ x, int dtype, int has_levels, int transform, float eps,
                                   const float *__restrict__ center, const float *__restrict__ scale, int nz, int64_t ncol,
                                   float *__restrict__ out)
@@ -39,7 +34,7 @@ __global__ void local_pack_kernel(const void *__restrict__ x, int dtype, int has
     const float c = center[z], s = scale[z];
     const int64_t row_in = has_levels ? (int64_t)z * ncol : 0, row_out = (int64_t)z * ncol;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < ncol; i += (int64_t)gridDim.x * blockDim.x) {
-        float v = ldf(x, dtype, row_in + i);
+        float v = load_as<float>(x, dtype, row_in + i);
         if (transform == FV3HIP_TRANSFORM_LOG) v = logf(v > eps ? v : eps);  // log(max(x, epsilon))
         out[row_out + i] = (v - c) / s;
     }
@@ -87,7 +82,7 @@ __global__ void local_unpack_kernel(const float *__restrict__ yhat, int64_t yhat
         float v = yhat[yrow + i] * s + c;
         if (cond_on) {
             if (out_direct) out_direct[row + i] = v;
-            const int b = bin_of(edges, n_bins, ldf(cond_on, cond_dtype, row + i));
+            const int b = bin_of(edges, n_bins, load_as<float>(cond_on, cond_dtype, row + i));
             const float sc = cs_scale[b];
             v = v * (sc > min_scale ? sc : min_scale) + cs_center[b];
             v = limit_value(v, limit_flags, value_lo, value_hi);
@@ -96,7 +91,7 @@ __global__ void local_unpack_kernel(const float *__restrict__ yhat, int64_t yhat
             v = limit_value(v, limit_flags, value_lo, value_hi);
             if (out_direct) out_direct[row + i] = v;
         }
-        if (before) out_after[row + i] = limit_value(ldf(before, before_dtype, row + i) + v, limit_flags >> 2, after_lo, after_hi);
+        if (before) out_after[row + i] = limit_value(load_as<float>(before, before_dtype, row + i) + v, limit_flags >> 2, after_lo, after_hi);
     }
 }
 
@@ -105,17 +100,10 @@ __global__ void classify_onehot_kernel(const void *__restrict__ logits, int dtyp
                                        uint8_t *__restrict__ onehot, uint8_t *__restrict__ any_of, int cls_a, int cls_b)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double mx = dtype == FV3HIP_F64 ? static_cast<const double *>(logits)[i] : (double)static_cast<const float *>(logits)[i];
-        for (int c = 1; c < n_class; ++c) {
-            const double v = dtype == FV3HIP_F64 ? static_cast<const double *>(logits)[(int64_t)c * n + i]
-                                                 : (double)static_cast<const float *>(logits)[(int64_t)c * n + i];
-            mx = running_max(mx, v);
-        }
+        const double mx = class_max(logits, dtype, n_class, n, i);
         uint8_t both = 0;
         for (int c = 0; c < n_class; ++c) {
-            const double v = dtype == FV3HIP_F64 ? static_cast<const double *>(logits)[(int64_t)c * n + i]
-                                                 : (double)static_cast<const float *>(logits)[(int64_t)c * n + i];
-            const uint8_t hot = (v == mx) ? 1 : 0;
+            const uint8_t hot = (load_as<double>(logits, dtype, (int64_t)c * n + i) == mx) ? 1 : 0;
             onehot[(int64_t)c * n + i] = hot;
             if (c == cls_a || c == cls_b) both |= hot;
         }
@@ -139,7 +127,7 @@ using namespace fv3hip;
 extern "C" int fv3hip_local_pack(const void *x, int dtype, int has_levels, int transform, double eps, const float *center,
                                  const float *scale, int nz, int64_t ncol, float *out, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(transform == FV3HIP_TRANSFORM_NONE || transform == FV3HIP_TRANSFORM_LOG, "unknown transform");
     FV3HIP_REQUIRE(nz >= 0 && nz <= 65535 && ncol >= 0, "bad extent");
     if (nz == 0 || ncol == 0) return FV3HIP_OK;
@@ -162,11 +150,11 @@ extern "C" int fv3hip_local_unpack(const float *yhat, int64_t yhat_level_stride,
     if (nz == 0 || ncol == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(yhat, "null pointer");
     if (cond_on) {
-        FV3HIP_REQUIRE(cond_dtype == FV3HIP_F32 || cond_dtype == FV3HIP_F64, "cond_dtype must be F32 or F64");
+        FV3HIP_REQUIRE(is_float(cond_dtype), "cond_dtype must be F32 or F64");
         FV3HIP_REQUIRE(edges && cs_scale && cs_center && n_bins >= 1, "conditional scaling needs edges, scale and center tables");
     }
     if (before) {
-        FV3HIP_REQUIRE(before_dtype == FV3HIP_F32 || before_dtype == FV3HIP_F64, "before_dtype must be F32 or F64");
+        FV3HIP_REQUIRE(is_float(before_dtype), "before_dtype must be F32 or F64");
         FV3HIP_REQUIRE(out_after, "a Difference needs its output array");
     }
     FV3HIP_REQUIRE(out_direct || out_unscaled || out_after, "no output requested");
@@ -180,13 +168,11 @@ extern "C" int fv3hip_local_unpack(const float *yhat, int64_t yhat_level_stride,
 extern "C" int fv3hip_classify_onehot(const void *logits, int dtype, int n_class, int64_t n, uint8_t *onehot, uint8_t *any_of,
                                       int cls_a, int cls_b, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_class >= 1 && n >= 0, "bad extent");
     if (n == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(logits && onehot, "null pointer");
-    int64_t blocks = ceil_div(n, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL(classify_onehot_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), logits, dtype, n_class, n,
-                       onehot, any_of, cls_a, cls_b);
+    hipLaunchKernelGGL(classify_onehot_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), logits, dtype, n_class,
+                       n, onehot, any_of, cls_a, cls_b);
     return check_launch("classify_onehot_kernel");
 }

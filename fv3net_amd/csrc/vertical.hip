@@ -1157,22 +1157,16 @@ extern "C" int fv3hip_pressure_at_interface(const void *delp, int dtype, int64_t
                                             int64_t n_inner, double toa_pressure, void *out,
                                             void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64, got %d", dtype);
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64, got %d", dtype);
     FV3HIP_REQUIRE(n_batch >= 0 && nz >= 0 && n_inner >= 0, "negative extent");
     const int64_t ncol = n_batch * n_inner;
     if (ncol == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(delp && out, "null pointer");
-    int64_t blocks = ceil_div(ncol, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F32)
-        hipLaunchKernelGGL((pressure_at_interface_kernel<float>), dim3((unsigned)blocks), dim3(256), 0,
-                           st, static_cast<const float *>(delp), static_cast<float *>(out), n_batch,
-                           nz, n_inner, (float)toa_pressure);
-    else
-        hipLaunchKernelGGL((pressure_at_interface_kernel<double>), dim3((unsigned)blocks), dim3(256),
-                           0, st, static_cast<const double *>(delp), static_cast<double *>(out),
-                           n_batch, nz, n_inner, toa_pressure);
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pressure_at_interface_kernel<T>), dim3(grid_stride_blocks(ncol)), dim3(256), 0, as_stream(stream),
+                           as<T>(delp), as<T>(out), n_batch, nz, n_inner, (T)toa_pressure);
+    });
     return check_launch("pressure_at_interface_kernel");
 }
 
@@ -1180,22 +1174,16 @@ extern "C" int fv3hip_pressure_at_midpoint_log(const void *delp, int dtype, int6
                                                int64_t n_inner, double toa_pressure, void *out,
                                                void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64, got %d", dtype);
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64, got %d", dtype);
     FV3HIP_REQUIRE(n_batch >= 0 && nz >= 0 && n_inner >= 0, "negative extent");
     const int64_t ncol = n_batch * n_inner;
     if (ncol == 0 || nz == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(delp && out, "null pointer");
-    int64_t blocks = ceil_div(ncol, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F32)
-        hipLaunchKernelGGL((pressure_at_midpoint_log_kernel<float>), dim3((unsigned)blocks), dim3(256),
-                           0, st, static_cast<const float *>(delp), static_cast<float *>(out), n_batch,
-                           nz, n_inner, (float)toa_pressure);
-    else
-        hipLaunchKernelGGL((pressure_at_midpoint_log_kernel<double>), dim3((unsigned)blocks), dim3(256),
-                           0, st, static_cast<const double *>(delp), static_cast<double *>(out),
-                           n_batch, nz, n_inner, toa_pressure);
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pressure_at_midpoint_log_kernel<T>), dim3(grid_stride_blocks(ncol)), dim3(256), 0, as_stream(stream),
+                           as<T>(delp), as<T>(out), n_batch, nz, n_inner, (T)toa_pressure);
+    });
     return check_launch("pressure_at_midpoint_log_kernel");
 }
 
@@ -1203,36 +1191,30 @@ extern "C" int fv3hip_mask_weights(const void *weights, int w_dtype, const void 
                                    int cmp_offset, const void *p_fine, int p_dtype, int64_t n_batch,
                                    int nz, int64_t n_inner, int64_t w_repeat, void *out, void *stream)
 {
-    FV3HIP_REQUIRE(w_dtype == FV3HIP_F32 || w_dtype == FV3HIP_F64, "weights dtype must be F32 or F64");
-    FV3HIP_REQUIRE(p_dtype == FV3HIP_F32 || p_dtype == FV3HIP_F64, "pressure dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(w_dtype), "weights dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(p_dtype), "pressure dtype must be F32 or F64");
     FV3HIP_REQUIRE(w_repeat >= 1 && n_batch % w_repeat == 0, "bad w_repeat %lld", (long long)w_repeat);
     FV3HIP_REQUIRE(cmp_offset >= 0 && cmp_levels >= nz + cmp_offset,
                    "p_cmp has %d levels, need at least nz + cmp_offset = %d", cmp_levels, nz + cmp_offset);
     const int64_t total = n_batch * nz * n_inner;
     if (total <= 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(weights && p_cmp && p_fine && out, "null pointer");
-    int64_t blocks = ceil_div(total, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
     hipStream_t st = as_stream(stream);
     // rows grid (no per-element division) when a row is whole quads of 16-byte aligned columns and the grid fits
     const bool rows = n_inner % 4 == 0 && n_batch * nz <= 65535 && reinterpret_cast<uintptr_t>(weights) % 16 == 0 &&
                       reinterpret_cast<uintptr_t>(p_cmp) % 16 == 0 && reinterpret_cast<uintptr_t>(p_fine) % 16 == 0 &&
                       reinterpret_cast<uintptr_t>(out) % 16 == 0;
-#define LAUNCH_(TW, TP)                                                                              \
-    if (rows)                                                                                        \
-        hipLaunchKernelGGL((mask_weights_rows_kernel<TW, TP>), dim3((unsigned)ceil_div(n_inner, 1024), (unsigned)(n_batch * nz)), dim3(256), 0, st, \
-                           static_cast<const TW *>(weights), static_cast<const TP *>(p_cmp), static_cast<const TP *>(p_fine),                      \
-                           static_cast<TW *>(out), nz, n_inner, w_repeat, cmp_levels, cmp_offset);                                                 \
-    else                                                                                             \
-        hipLaunchKernelGGL((mask_weights_kernel<TW, TP>), dim3((unsigned)blocks), dim3(256), 0, st,  \
-                           static_cast<const TW *>(weights), static_cast<const TP *>(p_cmp),         \
-                           static_cast<const TP *>(p_fine), static_cast<TW *>(out), n_batch, nz, n_inner, \
-                           w_repeat, cmp_levels, cmp_offset)
-    if (w_dtype == FV3HIP_F32 && p_dtype == FV3HIP_F32) LAUNCH_(float, float);
-    else if (w_dtype == FV3HIP_F32) LAUNCH_(float, double);
-    else if (p_dtype == FV3HIP_F32) LAUNCH_(double, float);
-    else LAUNCH_(double, double);
-#undef LAUNCH_
+    with_float_pair(w_dtype, p_dtype, [&](auto w, auto p) {
+        using TW = decltype(w);
+        using TP = decltype(p);
+        if (rows)
+            hipLaunchKernelGGL((mask_weights_rows_kernel<TW, TP>), dim3((unsigned)ceil_div(n_inner, 1024), (unsigned)(n_batch * nz)),
+                               dim3(256), 0, st, as<TW>(weights), as<TP>(p_cmp), as<TP>(p_fine), as<TW>(out), nz, n_inner, w_repeat,
+                               cmp_levels, cmp_offset);
+        else
+            hipLaunchKernelGGL((mask_weights_kernel<TW, TP>), dim3(grid_stride_blocks(total)), dim3(256), 0, st, as<TW>(weights),
+                               as<TP>(p_cmp), as<TP>(p_fine), as<TW>(out), n_batch, nz, n_inner, w_repeat, cmp_levels, cmp_offset);
+    });
     return check_launch("mask_weights_kernel");
 }
 
@@ -1246,8 +1228,8 @@ extern "C" int fv3hip_mask_weights_coarse(const void *weights, int w_dtype, cons
                                           const void *p_fine, int p_dtype, int64_t n_batch, int nz, int ny, int nx, int factor,
                                           int64_t w_repeat, void *out, void *stream)
 {
-    FV3HIP_REQUIRE(w_dtype == FV3HIP_F32 || w_dtype == FV3HIP_F64, "weights dtype must be F32 or F64");
-    FV3HIP_REQUIRE(p_dtype == FV3HIP_F32 || p_dtype == FV3HIP_F64, "pressure dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(w_dtype), "weights dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(p_dtype), "pressure dtype must be F32 or F64");
     FV3HIP_REQUIRE(w_repeat >= 1 && n_batch % w_repeat == 0, "bad w_repeat %lld", (long long)w_repeat);
     FV3HIP_REQUIRE(cmp_offset >= 0 && cmp_levels >= nz + cmp_offset, "p_cmp has %d levels, need at least nz + cmp_offset = %d", cmp_levels,
                    nz + cmp_offset);
@@ -1266,20 +1248,16 @@ extern "C" int fv3hip_mask_weights_coarse(const void *weights, int w_dtype, cons
     const bool quads = nx % 4 == 0 && factor >= 4 && reinterpret_cast<uintptr_t>(weights) % 16 == 0 &&
                        reinterpret_cast<uintptr_t>(p_fine) % 32 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
     const dim3 grid4((unsigned)ceil_div(n_inner, 1024), (unsigned)(n_batch * nz));
-#define LAUNCH_(TW, TP)                                                                                                            \
-    if (quads)                                                                                                                     \
-        hipLaunchKernelGGL((mask_weights_coarse4_kernel<TW, TP>), grid4, dim3(256), 0, st, static_cast<const TW *>(weights),      \
-                           static_cast<const TP *>(p_cmp_coarse), static_cast<const TP *>(p_fine), static_cast<TW *>(out), nz, n_inner, nx, \
-                           factor, nxc, plane2, w_repeat, cmp_levels, cmp_offset);                                                 \
-    else                                                                                                                           \
-        hipLaunchKernelGGL((mask_weights_coarse_kernel<TW, TP>), grid, dim3(256), 0, st, static_cast<const TW *>(weights),        \
-                           static_cast<const TP *>(p_cmp_coarse), static_cast<const TP *>(p_fine), static_cast<TW *>(out), nz, n_inner, nx, factor, \
-                           nxc, plane2, w_repeat, cmp_levels, cmp_offset)
-    if (w_dtype == FV3HIP_F32 && p_dtype == FV3HIP_F32) LAUNCH_(float, float);
-    else if (w_dtype == FV3HIP_F32) LAUNCH_(float, double);
-    else if (p_dtype == FV3HIP_F32) LAUNCH_(double, float);
-    else LAUNCH_(double, double);
-#undef LAUNCH_
+    with_float_pair(w_dtype, p_dtype, [&](auto w, auto p) {
+        using TW = decltype(w);
+        using TP = decltype(p);
+        if (quads)
+            hipLaunchKernelGGL((mask_weights_coarse4_kernel<TW, TP>), grid4, dim3(256), 0, st, as<TW>(weights), as<TP>(p_cmp_coarse),
+                               as<TP>(p_fine), as<TW>(out), nz, n_inner, nx, factor, nxc, plane2, w_repeat, cmp_levels, cmp_offset);
+        else
+            hipLaunchKernelGGL((mask_weights_coarse_kernel<TW, TP>), grid, dim3(256), 0, st, as<TW>(weights), as<TP>(p_cmp_coarse),
+                               as<TP>(p_fine), as<TW>(out), nz, n_inner, nx, factor, nxc, plane2, w_repeat, cmp_levels, cmp_offset);
+    });
     return check_launch("mask_weights_coarse_kernel");
 }
 
@@ -1573,56 +1551,39 @@ extern "C" int fv3hip_interpolate_2d(const void *xp, const void *x, const void *
     const int64_t total = n_batch * n_inner * n_out;
     if (total == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(xp && x && y && out, "null pointer");
-    int64_t blocks = ceil_div(total, 256);
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL(interpolate_2d_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
-                       static_cast<const double *>(xp), static_cast<const double *>(x), static_cast<const double *>(y),
-                       static_cast<double *>(out), fill_value, n_batch, n_inner, n_in, n_out, layout);
+    hipLaunchKernelGGL(interpolate_2d_kernel, dim3(grid_stride_blocks(total)), dim3(256), 0, as_stream(stream), as<double>(xp),
+                       as<double>(x), as<double>(y), as<double>(out), fill_value, n_batch, n_inner, n_in, n_out, layout);
     return check_launch("interpolate_2d_kernel");
 }
-
-namespace {
-inline unsigned col_grid(int64_t n)
-{
-    int64_t b = ceil_div(n, 256);
-    return (unsigned)(b > 256 * 64 ? 256 * 64 : (b < 1 ? 1 : b));
-}
-}  // namespace
 
 extern "C" int fv3hip_column_sum(const void *x, int dtype, int64_t n_batch, int nz, int64_t n_inner, double addend, void *out,
                                  void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_batch >= 0 && nz >= 0 && n_inner >= 0, "negative extent");
     if (n_batch * n_inner == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(x && out, "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((column_sum_kernel<double>), dim3(col_grid(n_batch * n_inner)), dim3(256), 0, st,
-                           static_cast<const double *>(x), static_cast<double *>(out), n_batch, nz, n_inner, addend);
-    else
-        hipLaunchKernelGGL((column_sum_kernel<float>), dim3(col_grid(n_batch * n_inner)), dim3(256), 0, st,
-                           static_cast<const float *>(x), static_cast<float *>(out), n_batch, nz, n_inner, (float)addend);
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((column_sum_kernel<T>), dim3(grid_stride_blocks(n_batch * n_inner)), dim3(256), 0, as_stream(stream),
+                           as<T>(x), as<T>(out), n_batch, nz, n_inner, (T)addend);
+    });
     return check_launch("column_sum_kernel");
 }
 
 extern "C" int fv3hip_blend_weights(const void *blending_pressure, const void *ps_coarse, const void *pfull_coarse, int dtype,
                                     int64_t n_batch, int nz, int64_t n_inner, void *out, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_batch >= 0 && nz >= 0 && n_inner >= 0, "negative extent");
     const int64_t total = n_batch * nz * n_inner;
     if (total == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(blending_pressure && ps_coarse && pfull_coarse && out, "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((blend_weights_kernel<double>), dim3(col_grid(total)), dim3(256), 0, st,
-                           static_cast<const double *>(blending_pressure), static_cast<const double *>(ps_coarse),
-                           static_cast<const double *>(pfull_coarse), static_cast<double *>(out), n_batch, nz, n_inner);
-    else
-        hipLaunchKernelGGL((blend_weights_kernel<float>), dim3(col_grid(total)), dim3(256), 0, st,
-                           static_cast<const float *>(blending_pressure), static_cast<const float *>(ps_coarse),
-                           static_cast<const float *>(pfull_coarse), static_cast<float *>(out), n_batch, nz, n_inner);
+    with_float(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((blend_weights_kernel<T>), dim3(grid_stride_blocks(total)), dim3(256), 0, as_stream(stream),
+                           as<T>(blending_pressure), as<T>(ps_coarse), as<T>(pfull_coarse), as<T>(out), n_batch, nz, n_inner);
+    });
     return check_launch("blend_weights_kernel");
 }
 
@@ -1630,20 +1591,15 @@ extern "C" int fv3hip_hydrostatic_balance(const void *dz, const void *phis, cons
                                           int dtype, int64_t n_batch, int nz, int64_t n_inner, double toa_pressure,
                                           void *dz_out, void *phis_out, void *stream)
 {
-    FV3HIP_REQUIRE(dtype == FV3HIP_F32 || dtype == FV3HIP_F64, "dtype must be F32 or F64");
+    FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_batch >= 0 && nz >= 0 && n_inner >= 0, "negative extent");
     if (n_batch * n_inner == 0) return FV3HIP_OK;
     FV3HIP_REQUIRE(dz && phis && t && q && delp && dz_out && phis_out, "null pointer");
-    hipStream_t st = as_stream(stream);
-    if (dtype == FV3HIP_F64)
-        hipLaunchKernelGGL((hydrostatic_kernel<double>), dim3(col_grid(n_batch * n_inner)), dim3(256), 0, st,
-                           static_cast<const double *>(dz), static_cast<const double *>(phis), static_cast<const double *>(t),
-                           static_cast<const double *>(q), static_cast<const double *>(delp), static_cast<double *>(dz_out),
-                           static_cast<double *>(phis_out), n_batch, nz, n_inner, toa_pressure);
-    else
-        hipLaunchKernelGGL((hydrostatic_kernel<float>), dim3(col_grid(n_batch * n_inner)), dim3(256), 0, st,
-                           static_cast<const float *>(dz), static_cast<const float *>(phis), static_cast<const float *>(t),
-                           static_cast<const float *>(q), static_cast<const float *>(delp), static_cast<float *>(dz_out),
-                           static_cast<float *>(phis_out), n_batch, nz, n_inner, (float)toa_pressure);
+    with_float(dtype, [&](auto v) {
+        using T = decltype(v);
+        hipLaunchKernelGGL((hydrostatic_kernel<T>), dim3(grid_stride_blocks(n_batch * n_inner)), dim3(256), 0, as_stream(stream),
+                           as<T>(dz), as<T>(phis), as<T>(t), as<T>(q), as<T>(delp), as<T>(dz_out), as<T>(phis_out), n_batch, nz,
+                           n_inner, (T)toa_pressure);
+    });
     return check_launch("hydrostatic_kernel");
 }
