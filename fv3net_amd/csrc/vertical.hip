@@ -1123,7 +1123,9 @@ __global__ void hydrostatic_kernel(const T *__restrict__ dz, const T *__restrict
                                    const T *__restrict__ q, const T *__restrict__ delp, T *__restrict__ dz_out,
                                    T *__restrict__ phis_out, int64_t n_batch, int nz, int64_t n_inner, T toa)
 {
-    const T g = (T)9.80665, rd = (T)287.05, rv = (T)461.5;
+    // rv / rd - 1 is formed in double and rounded once, as numpy rounds the reference's Python float
+    // (vertically_dependent.py:233); the quotient of the two float32 constants lies two ulps away
+    const T g = (T)9.80665, rd = (T)287.05, eps_v = (T)(461.5 / 287.05 - 1.0);
     const int64_t ncol = n_batch * n_inner;
     for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < ncol; c += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = c / n_inner, i = c - b * n_inner;
@@ -1137,7 +1139,7 @@ __global__ void hydrostatic_kernel(const T *__restrict__ dz, const T *__restrict
             const int64_t o = base + (int64_t)k * n_inner;
             const T p_lo = p_hi + delp[o];
             const T lp_lo = log(p_lo);
-            const T tv = t[o] * ((T)1 + (rv / rd - (T)1) * q[o]);
+            const T tv = t[o] * ((T)1 + eps_v * q[o]);
             const T d = -(lp_lo - lp_hi) * rd * tv / g;
             dz_out[o] = d;
             sum += d;
@@ -1161,7 +1163,7 @@ extern "C" int fv3hip_pressure_at_interface(const void *delp, int dtype, int64_t
     FV3HIP_REQUIRE(n_batch >= 0 && nz >= 0 && n_inner >= 0, "negative extent");
     const int64_t ncol = n_batch * n_inner;
     if (ncol == 0) return FV3HIP_OK;
-    FV3HIP_REQUIRE(delp && out, "null pointer");
+    FV3HIP_REQUIRE((delp || nz == 0) && out, "null pointer");  // (columns without levels: an empty delp, the toa plane)
     with_float(dtype, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((pressure_at_interface_kernel<T>), dim3(grid_stride_blocks(ncol)), dim3(256), 0, as_stream(stream),
@@ -1562,7 +1564,7 @@ extern "C" int fv3hip_column_sum(const void *x, int dtype, int64_t n_batch, int 
     FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_batch >= 0 && nz >= 0 && n_inner >= 0, "negative extent");
     if (n_batch * n_inner == 0) return FV3HIP_OK;
-    FV3HIP_REQUIRE(x && out, "null pointer");
+    FV3HIP_REQUIRE((x || nz == 0) && out, "null pointer");  // (columns without levels: an empty x, the addend)
     with_float(dtype, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((column_sum_kernel<T>), dim3(grid_stride_blocks(n_batch * n_inner)), dim3(256), 0, as_stream(stream),
@@ -1594,7 +1596,8 @@ extern "C" int fv3hip_hydrostatic_balance(const void *dz, const void *phis, cons
     FV3HIP_REQUIRE(is_float(dtype), "dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_batch >= 0 && nz >= 0 && n_inner >= 0, "negative extent");
     if (n_batch * n_inner == 0) return FV3HIP_OK;
-    FV3HIP_REQUIRE(dz && phis && t && q && delp && dz_out && phis_out, "null pointer");
+    // (columns without levels: the five [n_batch][nz][n_inner] arrays are empty, phis_out = g * (phis / g))
+    FV3HIP_REQUIRE(((dz && t && q && delp && dz_out) || nz == 0) && phis && phis_out, "null pointer");
     with_float(dtype, [&](auto v) {
         using T = decltype(v);
         hipLaunchKernelGGL((hydrostatic_kernel<T>), dim3(grid_stride_blocks(n_batch * n_inner)), dim3(256), 0, as_stream(stream),

@@ -268,6 +268,7 @@ int fv3hip_interp_center_to_outer_lines(const void *in, int dtype, int64_t n_out
  * p[k+1] = p[k] + delp[k], accumulated sequentially in the array's own dtype (as
  * numpy.cumsum does).  delp: [n_batch][nz][n_inner] -> out: [n_batch][nz+1][n_inner]
  * (LEVEL_COL) or [ncol][nz] -> [ncol][nz+1] (COL_LEVEL, n_batch = ncol, n_inner = 1).
+ * nz == 0: out is the toa plane and delp, an empty array, may be null.
  */
 int fv3hip_pressure_at_interface(const void *delp, int dtype, int64_t n_batch, int nz,
                                  int64_t n_inner, double toa_pressure, void *out, void *stream);
@@ -295,7 +296,8 @@ int fv3hip_mask_weights(const void *weights, int w_dtype, const void *p_cmp, int
 
 /* fv3hip_mask_weights with p_cmp on a horizontally coarser grid, [n_batch][cmp_levels][ny / factor][nx / factor]: column (y, x)
  * compares the level of coarse column (y / factor, x / factor) -- regridz.py:119-121 upsamples it first; this does not.
- * FV3HIP_EUNSUPPORTED unless nx % 4 == 0 and n_batch * nz <= 65535 (upsample and call fv3hip_mask_weights then). */
+ * Any nx (an odd, staggered extent keeps its last point).  FV3HIP_EUNSUPPORTED only where n_batch * nz > 65535 (the grid's row
+ * limit) or ny * nx >= 2^31 (upsample and call fv3hip_mask_weights then). */
 int fv3hip_mask_weights_coarse(const void *weights, int w_dtype, const void *p_cmp_coarse, int cmp_levels, int cmp_offset,
                                const void *p_fine, int p_dtype, int64_t n_batch, int nz, int ny, int nx, int factor,
                                int64_t w_repeat, void *out, void *stream);
@@ -683,6 +685,8 @@ int fv3hip_timer_destroy(fv3hip_timer_t t);
  *   fv3hip_hydrostatic_balance _impose_hydrostatic_balance (coarsen_restarts.py:990-1017 with
  *                              height_at_interface, hydrostatic_dz, dz_and_top_to_phis,
  *                              vertically_dependent.py:69-99, 182-186, 211-235)
+ * Columns without levels (nz == 0) still get their per-column result -- the addend, g * (phis / g) -- and the
+ * [n_batch][nz][n_inner] arrays, being empty, may be null.
  */
 int fv3hip_column_sum(const void *x, int dtype, int64_t n_batch, int nz, int64_t n_inner,
                       double addend, void *out, void *stream);
