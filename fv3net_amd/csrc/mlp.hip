@@ -75,6 +75,7 @@ constexpr int kMaxOutputs = 32;
 constexpr int kMaxK = 2048;       // network inputs whose per-feature table still fits LDS
 constexpr int kThreads = 256;     // 4 waves, one per SIMD
 constexpr int kTileSamples = 128; // 32 per wave
+constexpr int kZeroPadFloats = 8; // zero words ahead of the device bias block: what the input table's padding rows read
 
 struct XAddr {  // per call: where network input k is read from (16 bytes)
     int64_t row;       // byte address of (feature, sample 0)
@@ -118,7 +119,7 @@ struct MlpLaunch {
     const f32x4 *w;     // packed weight stream
     const KEntry *ktab; // [2 * 16 * n_chunks1]
     const OEntry *otab; // [32 * n_otiles]
-    const float *bias;  // packed biases
+    const float *bias;  // packed biases (kZeroPadFloats zero words sit right ahead of them in the same allocation)
     int n_chunks1;      // layer-1 chunks of 16 k-pairs
     int n_hidden;
     int n_otiles;       // 32-feature output tiles (= output-type chunks per sample tile)
@@ -219,8 +220,10 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
             const int sidx = e.src < 0 ? 0 : e.src;
             const int64_t esz = SRC64 ? 8 : 4;
             XAddr a;
-            // padding reads a finite constant (the first bias) and is multiplied by rscale = 0
-            a.row = e.src < 0 ? reinterpret_cast<int64_t>(p.bias)
+            // padding reads zeros that the model owns -- the kZeroPadFloats words ahead of the bias block, valid as float
+            // and as double, for the widest load (32 bytes) -- and meets a zero weight row: 1 / std lives in the
+            // layer-1 weights, the value itself enters the MFMA, so it must be finite under either element type
+            a.row = e.src < 0 ? reinterpret_cast<int64_t>(p.bias) - (int64_t)(kZeroPadFloats * sizeof(float))
                               : ksrc[sidx] + (int64_t)e.feat * ksrc[kMaxSources + sidx] * esz;
             a.ss = e.src < 0 ? 0u : (unsigned int)(ksrc[2 * kMaxSources + sidx] * esz);
             a.pad = 0;
@@ -375,7 +378,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
         // one v_mad_u64_u32: samples and strides are below 2^32
         xraw[s] = *(GRawPtr)(a.row + (int64_t)((uint64_t)(unsigned int)nc * (uint64_t)a.ss));
     };
-    // padding entries need no special case: their row points at a finite constant, center = rscale = 0
+    // padding entries need no special case: their row points at zeros, center = 0 and their weight row is zero
     auto finish_x1 = [&](const XNorm e, int s) {  // generic: log transform where flagged
         const float raw = (float)xraw[s];
         const float lg = logf(raw < e.eps ? e.eps : raw);
@@ -1900,6 +1903,9 @@ int fill_model(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m)
     build_output_table(d, m->n_otab, 32 * m->n_hout_tiles, dm.hout ? m->width : 0, otab);
     std::vector<float> w, bias;
     if (!m->layered && (rc = pack_fused(d, dm, m, it, w, bias))) return rc;
+    // (the device copy starts with the zero words the padding rows of the fused kernels' input table read; 32 bytes keep
+    // the biases 16-byte aligned)
+    if (!m->layered) bias.insert(bias.begin(), (size_t)kZeroPadFloats, 0.f);
     // the layered path's matrices / the plain copies for mlp_small_kernel
     PlainWeights pw;
     build_plain_weights(d, dm.F, m->n_ktab, m->Wp, m->Fp, it, pw);
@@ -2060,7 +2066,7 @@ extern "C" int fv3hip_mlp_predict(fv3hip_mlp_t m, const void *const *sources, co
     lp.w_bytes = m->w_bytes;
     lp.ktab = static_cast<const KEntry *>(m->d_ktab);
     lp.otab = static_cast<const OEntry *>(m->d_otab);
-    lp.bias = static_cast<const float *>(m->d_bias);
+    lp.bias = static_cast<const float *>(m->d_bias) + kZeroPadFloats;
     lp.n_chunks1 = m->n_chunks1;
     lp.n_hidden = m->n_hidden;
     lp.n_otiles = m->n_otiles;

@@ -12,6 +12,7 @@ import torch
 
 from oracle import mlp_np
 
+from mlp_cases import expected_variant
 from tolerances import assert_close_per_level, decades
 
 pytestmark = pytest.mark.gpu
@@ -197,10 +198,12 @@ def test_nan_input_propagates_only_to_its_sample(device):
 
     a = rng.normal(0, 1, (n, 20)).astype(np.float32)
     a[17, 3] = np.nan
-    model = MlpModel(spec, device=device)
-    out = model.predict({"a": torch.from_numpy(a).to(device)}, layout="sample_feature")["y"].cpu().numpy()
-    assert np.all(np.isnan(out[17]))
-    assert not np.isnan(np.delete(out, 17, axis=0)).any()
+    for which, limit in (("mlp_fused_kernel<1,false,false,false,false,false> epilogue=general", 0), ("mlp_small_kernel<false>", 1 << 40)):
+        model = MlpModel(spec, device=device, small_limit=limit)
+        out = model.predict({"a": torch.from_numpy(a).to(device)}, layout="sample_feature")["y"].cpu().numpy()
+        assert model.last_variant.startswith(which), model.last_variant
+        assert np.all(np.isnan(out[17]))
+        assert not np.isnan(np.delete(out, 17, axis=0)).any()
 
 
 def test_predict_does_not_mutate_inputs_and_is_deterministic(device):
@@ -562,22 +565,31 @@ def test_hidden_output_models(device, width, n_samples, with_outputs):
     spec = _random_spec(rng, {"a": ("a", 21, 0), "b": ("b", 40, 0)}, width, 2, {"y": 7, "z": 33} if with_outputs else {})
     spec.hidden_output = "h"
     src = {"a": rng.normal(0, 1, (n_samples, 21)).astype(np.float32), "b": rng.normal(0, 1, (n_samples, 40)).astype(np.float32)}
-    model = MlpModel(spec, device=device)
-    got = model.predict({k: torch.from_numpy(np.ascontiguousarray(v.T)).to(device) for k, v in src.items()})
     truth = mlp_np.forward(spec, src, dtype=np.float64)
-    assert list(got) == (["y", "z"] if with_outputs else []) + ["h"]
-    assert got["h"].shape == (width, n_samples)
-    assert (got["h"] >= 0).all()
-    for name in got:
-        t = truth[name].T
-        assert np.max(np.abs(got[name].cpu().numpy() - t)) <= 1e-5 * np.max(np.abs(t)), name
-    # strided outputs (a level's slice of a larger array, as the RNN sweep passes them) and reuse of the handle
-    big = torch.zeros((width, 3, n_samples), device=device)
-    outs = {"h": big[:, 1]}
-    if with_outputs:
-        outs.update({"y": torch.empty((7, n_samples), device=device), "z": torch.empty((33, n_samples), device=device)})
-    model.predict({k: torch.from_numpy(np.ascontiguousarray(v.T)).to(device) for k, v in src.items()}, out=outs)
-    assert torch.equal(big[:, 1], got["h"]) and not big[:, 0].any() and not big[:, 2].any()
+    n_cu = torch.cuda.get_device_properties(device).multi_processor_count
+    # both kernels: the HOUT instantiation of the hidden tiling (fast I/O when the sample count is a multiple of 32, else
+    # the general one) and the feature-split kernel, which the library's rule would pick for these sample counts
+    for limit in (0, 1 << 40):
+        model = MlpModel(spec, device=device, small_limit=limit)
+        got = model.predict({k: torch.from_numpy(np.ascontiguousarray(v.T)).to(device) for k, v in src.items()})
+        if limit == 0:
+            ht = next(v for v in (1, 2, 4, 8) if 32 * v >= width)
+            fast = "true" if n_samples % 32 == 0 else "false"
+            assert model.last_variant.startswith(f"mlp_fused_kernel<{ht},false,{fast},true,false,false> epilogue="), model.last_variant
+        assert model.last_variant == expected_variant(spec, n_samples, "float32", "float32", True, n_cu, limit), model.last_variant
+        assert list(got) == (["y", "z"] if with_outputs else []) + ["h"]
+        assert got["h"].shape == (width, n_samples)
+        assert (got["h"] >= 0).all()
+        for name in got:
+            t = truth[name].T
+            assert np.max(np.abs(got[name].cpu().numpy() - t)) <= 1e-5 * np.max(np.abs(t)), name
+        # strided outputs (a level's slice of a larger array, as the RNN sweep passes them) and reuse of the handle
+        big = torch.zeros((width, 3, n_samples), device=device)
+        outs = {"h": big[:, 1]}
+        if with_outputs:
+            outs.update({"y": torch.empty((7, n_samples), device=device), "z": torch.empty((33, n_samples), device=device)})
+        model.predict({k: torch.from_numpy(np.ascontiguousarray(v.T)).to(device) for k, v in src.items()}, out=outs)
+        assert torch.equal(big[:, 1], got["h"]) and not big[:, 0].any() and not big[:, 2].any()
 
 
 @pytest.mark.parametrize("width", [16, 64, 100, 128, 256])
@@ -592,13 +604,26 @@ def test_small_output_and_short_first_chunk_variants(device, width, k_in, n_out,
     outs = {f"y{i}": 1 for i in range(n_out)}
     src = {"a": rng.normal(0, 1, (n_samples, k_in)).astype(np.float32)}
     dev_src = {"a": torch.from_numpy(np.ascontiguousarray(src["a"].T)).to(device)}
+    n_cu = torch.cuda.get_device_properties(device).multi_processor_count
+    ht = next(v for v in (1, 2, 4, 8) if 32 * v >= width)
     for hidden_output in (None, "h"):
         spec = _random_spec(rng, {"a": ("a", k_in, 0)}, width, 2, outs)
         spec.hidden_output = hidden_output
-        got = MlpModel(spec, device=device).predict(dev_src)
         truth = mlp_np.forward(spec, src, dtype=np.float64)
-        assert list(got) == list(outs) + ([hidden_output] if hidden_output else [])
-        for name in got:
-            t = truth[name].T
-            assert got[name].shape == t.shape
-            assert np.max(np.abs(got[name].cpu().numpy() - t)) <= 1e-5 * max(np.max(np.abs(t)), 1e-30), (name, hidden_output)
+        for limit in (0, 1 << 40):  # the fused kernel's instantiation, then the feature-split kernel
+            model = MlpModel(spec, device=device, small_limit=limit)
+            got = model.predict(dev_src)
+            if limit == 0:
+                hout = "true" if hidden_output else "false"
+                if n_samples % 32 == 0:  # fast I/O: the small-output path, with the 8-slot first chunk for <= 16 inputs
+                    short = "true" if (k_in <= 16 and not hidden_output) else "false"
+                    want = f"mlp_fused_kernel<{ht},false,true,{hout},true,{short}> epilogue=small-output"
+                else:  # a ragged count: the general instantiation of the same handle
+                    want = f"mlp_fused_kernel<{ht},false,false,{hout},false,false> epilogue=general"
+                assert model.last_variant == want, model.last_variant
+            assert model.last_variant == expected_variant(spec, n_samples, "float32", "float32", True, n_cu, limit), model.last_variant
+            assert list(got) == list(outs) + ([hidden_output] if hidden_output else [])
+            for name in got:
+                t = truth[name].T
+                assert got[name].shape == t.shape
+                assert np.max(np.abs(got[name].cpu().numpy() - t)) <= 1e-5 * max(np.max(np.abs(t)), 1e-30), (name, hidden_output)
