@@ -97,6 +97,20 @@ int upload(const std::vector<T> &v, void **dptr)
     return FV3HIP_OK;
 }
 
+// A scratch buffer kept with a handle and grown on demand: a first call, or one that needs more than any before, allocates
+// -- so warm a model up before capturing a graph.  After a failed hipMalloc the handle holds a null pointer and size 0
+// (its destroy frees whatever it holds).
+inline int grow(void **p, size_t *have, size_t need)
+{
+    if (*have >= need) return FV3HIP_OK;
+    if (*p) FV3HIP_CHECK_HIP(hipFree(*p));
+    *p = nullptr;
+    *have = 0;
+    FV3HIP_CHECK_HIP(hipMalloc(p, need));
+    *have = need;
+    return FV3HIP_OK;
+}
+
 constexpr int kWave = 64;  // gfx950 wavefront
 
 // Running maximum of np.max: NaN once any value is NaN, so that `logit == max` is hot nowhere in a column of class logits

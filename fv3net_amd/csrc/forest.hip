@@ -390,18 +390,12 @@ extern "C" int fv3hip_forest_predict(fv3hip_forest_t f, const void *const *sourc
         b.out_fs[j] = out_feat_stride[j];
         b.out_ss[j] = out_sample_stride[j];
     }
-    // slabs of samples whose [tree][sample] leaf rows fit the scratch (grown on demand: warm up before capturing a graph)
+    // slabs of samples whose [tree][sample] leaf rows fit the scratch
     int64_t slab = (int64_t)(kLeafScratchBytes / ((size_t)f->T * sizeof(int32_t)));
     slab = slab < kWalkBlock ? kWalkBlock : slab;
     slab = slab > n_samples ? n_samples : slab;
     const size_t need = (size_t)f->T * slab * sizeof(int32_t);
-    if (f->leaf_bytes < need) {
-        if (f->d_leaf) FV3HIP_CHECK_HIP(hipFree(f->d_leaf));
-        f->d_leaf = nullptr;
-        f->leaf_bytes = 0;
-        FV3HIP_CHECK_HIP(hipMalloc(&f->d_leaf, need));
-        f->leaf_bytes = need;
-    }
+    if ((rc = grow(reinterpret_cast<void **>(&f->d_leaf), &f->leaf_bytes, need))) return rc;
     const hipStream_t st = as_stream(stream);
     const int vec = f->n_out == 1 ? 1 : 2;
     b.table = f->d_table;

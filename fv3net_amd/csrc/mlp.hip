@@ -170,6 +170,17 @@ struct MlpLaunch {
 // (32 features x 128 samples) are brought in by the whole workgroup with 16-byte loads, normalised
 // four at a time and parked in LDS; a k-pair slot then needs one ds_read for its B operand
 // instead of a table lookup, an address computation, a 4-byte load and the normalisation.
+//
+// Which epilogue an instantiation compiles (the kernel defines EPI_SIDE / RES_SIDE by these, and fv3hip_mlp_predict names
+// the flavour of a launch by the same two).  epi_side: the epilogue of output tile t rides under the MFMAs of tile t+1,
+// which needs 12 or more slots per output-type chunk (KC_O below) -- of the compiled tilings, HT = 8 has them.  res_side:
+// so does the residual epilogue, in the plain float32 instantiations.
+constexpr bool epi_side(int HT, bool xbulk) { return xbulk && HT * 16 / (HT == 1 ? 4 : 8) >= 12; }
+constexpr bool res_side(int HT, bool src64, bool xbulk, bool hout, bool smallf)
+{
+    return epi_side(HT, xbulk) && !src64 && !hout && !smallf;
+}
+
 template <int HT, bool SRC64, bool XBULK, bool HOUT, bool SMALLF, bool L1SHORT>
 __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch p)
 {
@@ -190,7 +201,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
     constexpr int NV_MAX = (NV_H > NV_O) ? NV_H : NV_O;
     constexpr int CH_MAX = (CH_H > CH_O) ? CH_H : CH_O;
     // the epilogue of output tile t rides under the MFMAs of tile t+1 (needs enough slots per chunk)
-    constexpr bool EPI_SIDE = XBULK && KC_O >= 12;
+    constexpr bool EPI_SIDE = epi_side(HT, XBULK);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4 *wbuf = reinterpret_cast<f32x4 *>(smem);                       // [2][CH_MAX]
@@ -794,7 +805,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
             // slots 11, 12 of its own chunk -- branch-free, every other chunk reading an all-scratch table tile -- cost
             // 900 cycles per chunk in slot 12.)
             // Rows without a residual (total_precipitation, padding) read and write the scratch row.
-            constexpr bool RES_SIDE = EPI_SIDE && !SRC64 && !HOUT && !SMALLF;
+            constexpr bool RES_SIDE = res_side(HT, SRC64, XBULK, HOUT, SMALLF);
             int64_t e_src[RES_SIDE ? 4 : 1], e_out[2];
             f32x4 e_before[RES_SIDE ? 4 : 1];
             const int64_t e_loff = (n0t + e_wcol) * 4;
@@ -1608,30 +1619,26 @@ using namespace fv3hip;
 // Model object
 // ---------------------------------------------------------------------------------------------
 struct fv3hip_mlp {
-    int device = 0;
-    int HT = 0;
-    int n_sources = 0, n_inputs = 0, K = 0, width = 0, n_hidden = 0, n_outputs = 0, F = 0, n_residual = 0;
-    int n_chunks1 = 0, n_otiles = 0, n_hout_tiles = 0, n_ktab = 0, n_otab = 0, n_bias = 0;
+    int device = 0, n_cu = 256, HT = 0, has_limits = 0;
+    int n_sources = 0, K = 0, width = 0, n_hidden = 0, n_outputs = 0, F = 0, n_residual = 0;
+    int n_otiles = 0, n_hout_tiles = 0, n_ktab = 0, n_otab = 0, n_slots = 0;  // (n_slots: output arrays of a call)
     int smallf_off = 0, smallf_n = 0;  // small-output path: where its [HT*32][4] weights sit in the bias block; 0 = not eligible
     int64_t flops = 0;
-    int has_limits = 0;
-    int n_log_chunks = 0, n_logfast_chunks = 0;
-    int l1_short_log = 0;  // see MlpLaunch
-    unsigned int w_bytes = 0;
-    void *d_sink = nullptr;
-    size_t sink_bytes = 0;
+    // scratch grown on demand: the fast-I/O kernels' row for padded output rows, the layered path's two activation buffers
+    void *d_sink = nullptr, *d_scr[2] = {nullptr, nullptr};
+    size_t sink_bytes = 0, scr_bytes[2] = {0, 0};
     void *d_w = nullptr, *d_ktab = nullptr, *d_otab = nullptr, *d_bias = nullptr;
     // plain (operand-layout) copies of the weights for mlp_small_kernel
     void *d_w1 = nullptr, *d_wh = nullptr, *d_wo = nullptr, *d_bh = nullptr, *d_bo = nullptr;
     int Wp = 0, Fp = 0;
     int64_t small_limit = -1;  // fv3hip_mlp_set_small_limit: -1 = default rule, 0 = never, n = calls of at most n samples
     // layered path (networks the fused kernels do not hold): d_w1 / d_wh / d_wo / d_bh / d_bo are its matrices
-    // ([n_ktab][Wp], [Wp][Wp] each, [Wp or n_ktab][Fp]; Wp and Fp multiples of 64), d_scr its two activation buffers
+    // ([n_ktab][Wp], [Wp][Wp] each, [Wp or n_ktab][Fp]; Wp and Fp multiples of 64)
     int layered = 0, relu = 1;
-    void *d_scr[2] = {nullptr, nullptr};
-    size_t scr_bytes = 0;
-    int n_cu = 256;
-    size_t lds_bytes = 0;
+    size_t lds_bytes = 0, lds_small = 0;  // dynamic LDS of mlp_fused_kernel (without the fast-I/O input tiles) / mlp_small_kernel
+    // launch templates, filled once (the fused kernels' chunk counts, n_bias and w_bytes live here alone); a call copies one
+    MlpLaunch fused = {};
+    SmallLaunch small = {};
     char last_variant[160] = {0};  // what the last fv3hip_mlp_predict launched (fv3hip_mlp_last_variant)
 };
 
@@ -1639,23 +1646,19 @@ namespace {
 
 const int kHiddenTilings[] = {1, 2, 4, 8};  // compiled kernel variants: hidden width <= 32 * HT
 
-template <int HT, bool SRC64, bool XBULK, bool HOUT = false, bool SMALLF = false, bool L1SHORT = false>
-int launch_one(const MlpLaunch &lp, int grid, size_t lds, hipStream_t st)
+// a fused or small kernel with its `lds` bytes of dynamic LDS
+template <typename P>
+int launch_lds(void (*kern)(const P), const char *what, const P &p, int grid, int threads, size_t lds, hipStream_t st)
 {
-    auto kern = mlp_fused_kernel<HT, SRC64, XBULK, HOUT, SMALLF, L1SHORT>;
-    FV3HIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, st, lp);
-    return check_launch("mlp_fused_kernel");
+    FV3HIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, p);
+    return check_launch(what);
 }
 
-template <bool SRC64>
-int launch_small(const SmallLaunch &sp, int grid, size_t lds, hipStream_t st)
+template <int HT, bool SRC64, bool XBULK, bool HOUT, bool SMALLF, bool L1SHORT>
+int launch_one(const MlpLaunch &lp, int grid, size_t lds, hipStream_t st)
 {
-    auto kern = mlp_small_kernel<SRC64>;
-    FV3HIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSmallWaves * 64), lds, st, sp);
-    return check_launch("mlp_small_kernel");
+    return launch_lds(mlp_fused_kernel<HT, SRC64, XBULK, HOUT, SMALLF, L1SHORT>, "mlp_fused_kernel", lp, grid, kThreads, lds, st);
 }
 
 // the layered path's gather (grid.y = table rows) or scatter (grid.y = output features) of one slab
@@ -1674,16 +1677,8 @@ int predict_layered(fv3hip_mlp *m, const MlpIo &mio, bool src64, int out_dtype, 
     const int rows = std::max(m->n_ktab, std::max(m->Wp, m->Fp));
     const int64_t np_max = (std::min(n_samples, kLayeredSlab) + 255) / 256 * 256;
     const size_t need = (size_t)rows * np_max * sizeof(float);
-    if (m->scr_bytes < need) {  // (grown on demand, like the fused kernels' scratch row: warm up before capturing a graph)
-        for (void *&q : m->d_scr) {
-            if (q) FV3HIP_CHECK_HIP(hipFree(q));
-            q = nullptr;
-        }
-        m->scr_bytes = 0;
-        FV3HIP_CHECK_HIP(hipMalloc(&m->d_scr[0], need));
-        FV3HIP_CHECK_HIP(hipMalloc(&m->d_scr[1], need));
-        m->scr_bytes = need;
-    }
+    int rc;
+    if ((rc = grow(&m->d_scr[0], &m->scr_bytes[0], need)) || (rc = grow(&m->d_scr[1], &m->scr_bytes[1], need))) return rc;
     LayeredIo io;
     memset(&io, 0, sizeof(io));
     io.ktab = static_cast<const KEntry *>(m->d_ktab);
@@ -1701,8 +1696,8 @@ int predict_layered(fv3hip_mlp *m, const MlpIo &mio, bool src64, int out_dtype, 
         io.np = np;
         io.x = cur;
         const dim3 gg((unsigned)(np / 256), (unsigned)m->n_ktab);
-        int rc = launch_layered_io(src64 ? layered_gather_kernel<true> : layered_gather_kernel<false>, "layered_gather_kernel", io, gg, st);
-        if (rc) return rc;
+        if ((rc = launch_layered_io(src64 ? layered_gather_kernel<true> : layered_gather_kernel<false>, "layered_gather_kernel", io, gg, st)))
+            return rc;
         auto dense = [&](const void *w, const void *b, int kp, int fp, int relu) {
             LayeredDense dp;
             dp.w = static_cast<const float *>(w);
@@ -1730,10 +1725,6 @@ int predict_layered(fv3hip_mlp *m, const MlpIo &mio, bool src64, int out_dtype, 
     return FV3HIP_OK;
 }
 
-}  // namespace
-
-namespace {
-
 // ---- create: what is specific to each path; fv3hip_mlp_create below is the skeleton ----
 
 // Layered path (what the fused kernels do not hold goes layer by layer, see layered_dense_kernel): tables and matrices
@@ -1757,16 +1748,16 @@ int fused_geometry(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m)
         if (!HT && v * 32 >= m->width) HT = v;
     FV3HIP_REQUIRE(HT > 0, "no kernel variant for width %d", m->width);
     m->HT = HT;
-    m->n_chunks1 = ((dm.K + 1) / 2 + 15) / 16;
+    m->fused.n_chunks1 = ((dm.K + 1) / 2 + 15) / 16;
     m->n_otiles = nt_out;
-    m->n_ktab = 2 * 16 * m->n_chunks1;
+    m->n_ktab = 2 * 16 * m->fused.n_chunks1;
     m->n_hout_tiles = dm.hout ? HT : 0;
     m->n_otab = 32 * (m->n_hout_tiles + nt_out);
-    m->n_bias = d->n_hidden * HT * 32 + nt_out * 32;
+    m->fused.n_bias = d->n_hidden * HT * 32 + nt_out * 32;
     if (F >= 1 && F <= 4 && !m->has_limits && d->n_residual == 0) {  // eligible for the small-output path (see the kernel)
         m->smallf_n = F;
-        m->smallf_off = m->n_bias;
-        m->n_bias += HT * 32 * 4;
+        m->smallf_off = m->fused.n_bias;
+        m->fused.n_bias += HT * 32 * 4;
     }
     m->Wp = HT * 32;  // (mlp_small_kernel's plain copies)
     m->Fp = (nt_out > 0 ? nt_out : 1) * 32;
@@ -1782,17 +1773,17 @@ int pack_fused(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m, con
     const int HG = (HT + 3) / 4;
     const int GS = (HT == 1) ? 4 : 8, NGO = GS / 4, KC_O = HT * 16 / GS;  // as in the kernel
     const int64_t CH_H = 16 * HG * 64, CH_O = (int64_t)KC_O * NGO * 64;  // float4 per chunk
-    const int n_hid_chunks = m->n_chunks1 + (d->n_hidden - 1) * HT;
+    const int n_hid_chunks = m->fused.n_chunks1 + (d->n_hidden - 1) * HT;
     const int n_out_chunks = nt_out;
-    m->n_log_chunks = (it.n_log_padded + 31) / 32;
-    m->n_logfast_chunks = it.eps_normal ? it.n_log_padded / 32 : 0;
+    m->fused.n_log_chunks = (it.n_log_padded + 31) / 32;
+    m->fused.n_logfast_chunks = it.eps_normal ? it.n_log_padded / 32 : 0;
     // the log block was padded to whole chunks, the real rows of its last chunk fit 8 k-pair slots and a plain chunk follows
-    m->l1_short_log = (it.n_log_padded % 32 == 0 && it.n_log % 32 >= 1 && it.n_log % 32 <= 16 && m->n_log_chunks < m->n_chunks1) ? 1 : 0;
+    m->fused.l1_short_log = (it.n_log_padded % 32 == 0 && it.n_log % 32 >= 1 && it.n_log % 32 <= 16 && m->fused.n_log_chunks < m->fused.n_chunks1) ? 1 : 0;
     // ---- packed weight stream ----
     // (+ one maximal chunk of zero padding: the two-half staging may read past a short last chunk)
     const size_t n_w = (size_t)(n_hid_chunks * CH_H + n_out_chunks * CH_O + (CH_H > CH_O ? CH_H : CH_O)) * 4;
     FV3HIP_REQUIRE(n_w * sizeof(float) < (1ull << 31), "model too large: the packed weight stream exceeds 2 GiB");
-    m->w_bytes = (unsigned int)(n_w * sizeof(float));
+    m->fused.w_bytes = (unsigned int)(n_w * sizeof(float));
     w.assign(n_w, 0.f);
     auto hid_slot = [&](int g, int s, int j, int lane, int e) -> float & {
         return w[(size_t)((g * CH_H + ((int64_t)(s * HG + j) * 64 + lane)) * 4 + e)];
@@ -1800,7 +1791,7 @@ int pack_fused(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m, con
     // layer 1: k = 2 * kpair + half, the row scaled by the input's folded 1 / (std + eps) (ktab[k].scale)
     {
         const float *W = d->hidden_kernels[0];
-        for (int g = 0; g < m->n_chunks1; ++g)
+        for (int g = 0; g < m->fused.n_chunks1; ++g)
             for (int s = 0; s < 16; ++s)
                 for (int j = 0; j < HG; ++j)
                     for (int lane = 0; lane < 64; ++lane)
@@ -1815,7 +1806,7 @@ int pack_fused(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m, con
     for (int l = 1; l < d->n_hidden; ++l) {
         const float *W = d->hidden_kernels[l];
         for (int kt = 0; kt < HT; ++kt) {
-            const int g = m->n_chunks1 + (l - 1) * HT + kt;
+            const int g = m->fused.n_chunks1 + (l - 1) * HT + kt;
             for (int s = 0; s < 16; ++s)
                 for (int j = 0; j < HG; ++j)
                     for (int lane = 0; lane < 64; ++lane)
@@ -1845,7 +1836,7 @@ int pack_fused(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m, con
                         }
     }
     // ---- biases: [layer][tile][reg][half] ----
-    bias.assign(m->n_bias, 0.f);
+    bias.assign(m->fused.n_bias, 0.f);
     for (int l = 0; l < d->n_hidden; ++l)
         for (int t = 0; t < HT; ++t)
             for (int r = 0; r < 16; ++r)
@@ -1872,7 +1863,7 @@ int pack_fused(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m, con
     // (the fast-I/O kernels add the 32 KB input tiles at launch)
     m->lds_bytes = wb + (size_t)m->n_ktab * sizeof(KEntry) +
                    (size_t)m->n_otab * (sizeof(OFast) + sizeof(OSlow) + (d->n_residual ? sizeof(ORes) : 0)) +
-                   (size_t)((m->n_bias + 3) & ~3) * sizeof(float) + (size_t)(3 * kMaxSources + 3 * kMaxOutputs) * 8;
+                   (size_t)((m->fused.n_bias + 3) & ~3) * sizeof(float) + (size_t)(3 * kMaxSources + 3 * kMaxOutputs) * 8;
     if (m->lds_bytes > 160 * 1024) return fail(FV3HIP_EUNSUPPORTED, "model tables need %zu bytes of LDS (> 160 KiB)", m->lds_bytes);
     return FV3HIP_OK;
 }
@@ -1885,7 +1876,6 @@ int fill_model(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m)
     if (hipGetDeviceProperties(&prop, m->device) == hipSuccess) m->n_cu = prop.multiProcessorCount;
     m->relu = d->hidden_activation == FV3HIP_ACT_RELU;
     m->n_sources = d->n_sources;
-    m->n_inputs = d->n_inputs;
     m->K = dm.K;
     m->width = d->n_hidden ? d->width : dm.K;  // (no hidden layer: the output layer reads the inputs)
     m->n_hidden = d->n_hidden;
@@ -1896,6 +1886,7 @@ int fill_model(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m)
     m->flops = mlp_flops(dm.K, m->width, d->n_hidden, dm.F);
     int rc;
     if ((rc = m->layered ? layered_geometry(dm, m) : fused_geometry(d, dm, m))) return rc;
+    m->n_slots = m->n_outputs + m->n_residual + (m->n_hout_tiles ? 1 : 0);
     // the tables (hidden-output models: the output table starts with the last hidden layer's features)
     InputTable it;
     build_input_table(d, dm.K, m->n_ktab, it);
@@ -1913,6 +1904,33 @@ int fill_model(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m)
         (rc = upload(pw.bh, &m->d_bh)) || (rc = upload(pw.bo, &m->d_bo)) || (rc = upload(w, &m->d_w)) ||
         (rc = upload(it.ktab, &m->d_ktab)) || (rc = upload(otab, &m->d_otab)) || (rc = upload(bias, &m->d_bias)))
         return rc;
+    if (m->layered) return FV3HIP_OK;
+    // the launch templates of the fused and the small kernel (what stays zero belongs to the call: predict_fused, predict_small)
+    auto shared = [m](auto &p) {
+        p.ktab = static_cast<const KEntry *>(m->d_ktab);
+        p.otab = static_cast<const OEntry *>(m->d_otab);
+        p.n_ktab = m->n_ktab;
+        p.n_hidden = m->n_hidden;
+        p.n_otiles = m->n_otiles;
+        p.n_hout_tiles = m->n_hout_tiles;
+        p.has_limits = m->has_limits;
+    };
+    shared(m->fused);
+    m->fused.w = static_cast<const f32x4 *>(m->d_w);
+    m->fused.bias = static_cast<const float *>(m->d_bias) + kZeroPadFloats;
+    m->fused.n_otab = m->n_otab;
+    m->fused.n_residual = m->n_residual;
+    shared(m->small);
+    m->small.w1 = static_cast<const float *>(m->d_w1);
+    m->small.wh = static_cast<const float *>(m->d_wh);
+    m->small.wo = static_cast<const float *>(m->d_wo);
+    m->small.bh = static_cast<const float *>(m->d_bh);
+    m->small.bo = static_cast<const float *>(m->d_bo);
+    m->small.Wp = m->Wp;
+    m->small.HT = m->HT;
+    m->small.Fp = m->Fp;
+    m->lds_small = (size_t)(2 * kSmallChunk * 32 + 2 * m->Wp * 32) * sizeof(float) + (size_t)m->n_ktab * 32 +
+                   (size_t)3 * (kMaxOutputs + kMaxSources) * sizeof(int64_t);
     return FV3HIP_OK;
 }
 
@@ -1950,12 +1968,7 @@ extern "C" void fv3hip_diag_set_mlp_stamps(void *p) { g_mlp_stamps = static_cast
 extern "C" int fv3hip_mlp_destroy(fv3hip_mlp_t m)
 {
     if (!m) return FV3HIP_OK;
-    if (m->d_sink) hipFree(m->d_sink);
-    if (m->d_w) hipFree(m->d_w);
-    if (m->d_ktab) hipFree(m->d_ktab);
-    if (m->d_otab) hipFree(m->d_otab);
-    if (m->d_bias) hipFree(m->d_bias);
-    for (void *q : {m->d_w1, m->d_wh, m->d_wo, m->d_bh, m->d_bo, m->d_scr[0], m->d_scr[1]})
+    for (void *q : {m->d_sink, m->d_w, m->d_ktab, m->d_otab, m->d_bias, m->d_w1, m->d_wh, m->d_wo, m->d_bh, m->d_bo, m->d_scr[0], m->d_scr[1]})
         if (q) hipFree(q);
     delete m;
     return FV3HIP_OK;
@@ -1972,33 +1985,31 @@ extern "C" int fv3hip_mlp_set_small_limit(fv3hip_mlp_t m, int64_t max_samples)
 
 extern "C" const char *fv3hip_mlp_last_variant(fv3hip_mlp_t m) { return m ? m->last_variant : ""; }
 
-extern "C" int fv3hip_mlp_predict(fv3hip_mlp_t m, const void *const *sources, const int *src_dtype,
-                                  const int64_t *src_feat_stride, const int64_t *src_sample_stride,
-                                  int64_t n_samples, void *const *outputs, int out_dtype,
-                                  const int64_t *out_feat_stride, const int64_t *out_sample_stride,
-                                  void *stream)
+namespace {
+
+// ---- predict: what is specific to each path; fv3hip_mlp_predict below is the skeleton ----
+
+constexpr size_t kLdsMax = 160 * 1024, kXsBytes = 2 * 32 * kTileSamples * sizeof(float);
+
+// The arguments of a call of n_samples > 0, checked and gathered into `io`.
+int check_call(const fv3hip_mlp *m, const void *const *sources, const int *src_dtype, const int64_t *src_feat_stride,
+               const int64_t *src_sample_stride, int64_t n_samples, void *const *outputs, int out_dtype,
+               const int64_t *out_feat_stride, const int64_t *out_sample_stride, MlpIo &io, bool &src64)
 {
-    FV3HIP_REQUIRE(m, "null model handle");
-    FV3HIP_REQUIRE(n_samples >= 0, "negative n_samples");
-    if (n_samples == 0) return FV3HIP_OK;
-    {   // the model's tables (and the scratch row this call may grow) live on the device it was created on
-        int cur = -1;
-        FV3HIP_CHECK_HIP(hipGetDevice(&cur));
-        FV3HIP_REQUIRE(cur == m->device, "the model lives on device %d but the current device is %d: make the model's "
-                       "device current around fv3hip_mlp_predict", m->device, cur);
-    }
-    FV3HIP_REQUIRE(sources && src_dtype && src_feat_stride && src_sample_stride && outputs &&
-                       out_feat_stride && out_sample_stride, "null pointer");
+    int cur = -1;  // the model's tables (and the scratch row this call may grow) live on the device it was created on
+    FV3HIP_CHECK_HIP(hipGetDevice(&cur));
+    FV3HIP_REQUIRE(cur == m->device, "the model lives on device %d but the current device is %d: make the model's "
+                   "device current around fv3hip_mlp_predict", m->device, cur);
+    FV3HIP_REQUIRE(sources && src_dtype && src_feat_stride && src_sample_stride && outputs && out_feat_stride && out_sample_stride, "null pointer");
     FV3HIP_REQUIRE(out_dtype == FV3HIP_F32 || out_dtype == FV3HIP_F64, "out_dtype must be F32 or F64");
-    MlpIo io;
     memset(&io, 0, sizeof(io));
     const int dt0 = src_dtype[0];
-    const bool src64 = (dt0 == FV3HIP_F64);
+    src64 = (dt0 == FV3HIP_F64);
     FV3HIP_REQUIRE(dt0 == FV3HIP_F32 || dt0 == FV3HIP_F64, "source dtype must be F32 or F64");
     FV3HIP_REQUIRE(n_samples < ((int64_t)1 << 32), "n_samples must be below 2^32");
     for (int i = 0; i < m->n_sources; ++i) {
         FV3HIP_REQUIRE(sources[i], "source %d is null", i);
-        FV3HIP_REQUIRE(src_sample_stride[i] >= 0 && src_sample_stride[i] * (dt0 == FV3HIP_F64 ? 8 : 4) < ((int64_t)1 << 32),
+        FV3HIP_REQUIRE(src_sample_stride[i] >= 0 && src_sample_stride[i] * (src64 ? 8 : 4) < ((int64_t)1 << 32),
                        "sample stride of source %d must be in [0, 4 GiB)", i);
         if (src_dtype[i] != dt0)
             return fail(FV3HIP_EUNSUPPORTED, "all sources must share one dtype (source 0 is %d, source %d is %d)", dt0, i, src_dtype[i]);
@@ -2007,8 +2018,7 @@ extern "C" int fv3hip_mlp_predict(fv3hip_mlp_t m, const void *const *sources, co
         io.src_ss[i] = src_sample_stride[i];
     }
     for (int i = m->n_sources; i < kMaxSources; ++i) io.src[i] = sources[0];
-    const int n_slots = m->n_outputs + m->n_residual + (m->n_hout_tiles ? 1 : 0);
-    for (int j = 0; j < n_slots; ++j) {
+    for (int j = 0; j < m->n_slots; ++j) {
         FV3HIP_REQUIRE(outputs[j], "output %d is null", j);
         FV3HIP_REQUIRE(out_sample_stride[j] >= 0 && out_sample_stride[j] * (out_dtype == FV3HIP_F64 ? 8 : 4) < ((int64_t)1 << 32),
                        "sample stride of output %d must be in [0, 4 GiB)", j);
@@ -2016,150 +2026,149 @@ extern "C" int fv3hip_mlp_predict(fv3hip_mlp_t m, const void *const *sources, co
         io.out_fs[j] = out_feat_stride[j];
         io.out_ss[j] = out_sample_stride[j];
     }
-    if (m->layered) return predict_layered(m, io, src64, out_dtype, n_samples, as_stream(stream));
-    // ---- few samples: the feature-split kernel while the big one would leave CUs without a tile (see mlp_small_kernel) ----
-    {
-        static const int64_t small_max = [] {
-            const char *e = getenv("FV3HIP_MLP_SMALL_MAX_SAMPLES");  // 0 disables; default: one round of 32-sample workgroups over the CUs
-            return e ? (int64_t)atoll(e) : (int64_t)-1;
-        }();
-        // (measured, profiles/r03_bench.json: a 32-sample workgroup takes 0.5-0.7 of the time of a 128-sample tile of the
-        // big kernel, so a second round of workgroups -- 9 216 columns on 256 CUs -- already loses to the big kernel's one)
-        const int64_t limit = m->small_limit >= 0 ? m->small_limit : small_max >= 0 ? small_max : (int64_t)32 * m->n_cu;
-        const size_t lds_small = (size_t)(2 * kSmallChunk * 32 + 2 * m->Wp * 32) * sizeof(float) + (size_t)m->n_ktab * 32 +
-                                 (size_t)3 * (kMaxOutputs + kMaxSources) * sizeof(int64_t);
-        if (n_samples <= limit && m->n_otiles + m->n_hout_tiles > 0 && lds_small <= 160 * 1024) {
-            SmallLaunch sp;
-            memset(&sp, 0, sizeof(sp));
-            sp.w1 = static_cast<const float *>(m->d_w1);
-            sp.wh = static_cast<const float *>(m->d_wh);
-            sp.wo = static_cast<const float *>(m->d_wo);
-            sp.bh = static_cast<const float *>(m->d_bh);
-            sp.bo = static_cast<const float *>(m->d_bo);
-            sp.ktab = static_cast<const KEntry *>(m->d_ktab);
-            sp.otab = static_cast<const OEntry *>(m->d_otab);
-            sp.n_ktab = m->n_ktab;
-            sp.Wp = m->Wp;
-            sp.HT = m->HT;
-            sp.n_hidden = m->n_hidden;
-            sp.Fp = m->Fp;
-            sp.n_otiles = m->n_otiles;
-            sp.n_hout_tiles = m->n_hout_tiles;
-            sp.out64 = (out_dtype == FV3HIP_F64);
-            sp.has_limits = m->has_limits;
-            sp.n_samples = n_samples;
+    return FV3HIP_OK;
+}
+
+// Calls of at most this many samples take mlp_small_kernel: the handle's value (fv3hip_mlp_set_small_limit), then the
+// environment's (0 disables), then one round of 32-sample workgroups over the CUs.
+// (measured, profiles/r03_bench.json: a 32-sample workgroup takes 0.5-0.7 of the time of a 128-sample tile of the
+// big kernel, so a second round of workgroups -- 9 216 columns on 256 CUs -- already loses to the big kernel's one)
+int64_t small_limit(const fv3hip_mlp *m)
+{
+    static const char *const env = getenv("FV3HIP_MLP_SMALL_MAX_SAMPLES");
+    static const int64_t small_max = env ? (int64_t)atoll(env) : (int64_t)-1;
+    return m->small_limit >= 0 ? m->small_limit : small_max >= 0 ? small_max : (int64_t)32 * m->n_cu;
+}
+
+// Few samples: the feature-split kernel while the big one would leave CUs without a tile (see mlp_small_kernel).
+int predict_small(fv3hip_mlp *m, const MlpIo &io, bool src64, int out_dtype, int64_t n_samples, hipStream_t st)
+{
+    SmallLaunch sp = m->small;
+    sp.out64 = (out_dtype == FV3HIP_F64);
+    sp.n_samples = n_samples;
 #ifdef SMALL_STAMPS
-            sp.stamps = g_small_stamps;
+    sp.stamps = g_small_stamps;
 #endif
-            sp.io = io;
-            const int grid_s = (int)ceil_div(n_samples, (int64_t)32);
-            hipStream_t st_s = as_stream(stream);
-            snprintf(m->last_variant, sizeof(m->last_variant), "mlp_small_kernel<%s> (32-sample workgroups, features split over %d waves)",
-                     src64 ? "true" : "false", kSmallWaves);
-            return src64 ? launch_small<true>(sp, grid_s, lds_small, st_s) : launch_small<false>(sp, grid_s, lds_small, st_s);
-        }
-    }
-    MlpLaunch lp;
-    memset(&lp, 0, sizeof(lp));
+    sp.io = io;
+    snprintf(m->last_variant, sizeof(m->last_variant), "mlp_small_kernel<%s> (32-sample workgroups, features split over %d waves)",
+             src64 ? "true" : "false", kSmallWaves);
+    return launch_lds(src64 ? mlp_small_kernel<true> : mlp_small_kernel<false>, "mlp_small_kernel", sp,
+                      (int)ceil_div(n_samples, (int64_t)32), kSmallWaves * 64, m->lds_small, st);
+}
+
+// What the fast-I/O kernels need: every source and output sample-contiguous and 16-byte aligned at every feature, n_samples % 32 == 0.
+bool fast_layout(const fv3hip_mlp *m, const MlpIo &io, bool src64, bool out64, int64_t n_samples)
+{
+    const int oal = out64 ? 2 : 4, sal = src64 ? 2 : 4;  // elements per 16 bytes
+    bool fast = (n_samples % 32 == 0);
+    for (int j = 0; j < m->n_slots && fast; ++j) fast = io.out_ss[j] == 1 && aligned16(io.out[j]) && io.out_fs[j] % oal == 0;
+    for (int i = 0; i < m->n_sources && fast; ++i) fast = io.src_ss[i] == 1 && aligned16(io.src[i]) && io.src_fs[i] % sal == 0;
+    return fast;
+}
+
+// One instantiation mlp_fused_kernel<HT, SRC64, XBULK, HOUT, SMALLF, L1SHORT>, and the one a call runs.
+struct FusedVariant { int HT; bool src64, xbulk, hout, smallf, l1short; };
+
+int select_variant(const fv3hip_mlp *m, bool src64, bool out64, bool fast, FusedVariant &v)
+{
+    // hidden-output models (recurrent cells) have their own instantiations, so that the plain ones keep their
+    // register allocation and schedule; they take float32 sources only (packed inputs and states)
+    const bool hout = m->n_hout_tiles != 0;
+    if (hout && src64) return fail(FV3HIP_EUNSUPPORTED, "hidden-output models take float32 sources only");
+    // fast-I/O kernels where the layout allows them and their input tiles fit (large tables: the general kernels still fit)
+    const bool xbulk = fast && m->lds_bytes + kXsBytes <= kLdsMax;
+    // small-output launches (<= 4 outputs, fast I/O, float32 in and out): no output chunk in the stream
+    const bool smallf = m->smallf_n && xbulk && !src64 && !out64;
+    // ... and, with one layer-1 chunk of at most 16 untransformed inputs, an 8-slot first chunk (the dense-local models)
+    const bool l1short = smallf && !hout && m->K <= 16 && m->fused.n_log_chunks == 0;
+    v = FusedVariant{m->HT, src64, xbulk, hout, smallf, l1short};
+    return FV3HIP_OK;
+}
+
+// The compiled instantiations, each with the launcher of its kernel: nine kinds per hidden tiling, in the order of the
+// kernels in the code object.  Nothing else instantiates mlp_fused_kernel.
+struct FusedRow { FusedVariant v; int (*launch)(const MlpLaunch &, int grid, size_t lds, hipStream_t); };
+template <int HT, bool S, bool X, bool H, bool F, bool L>
+constexpr FusedRow fused_row() { return {{HT, S, X, H, F, L}, launch_one<HT, S, X, H, F, L>}; }
+constexpr int kFusedKinds = 9;
+template <int HT>
+constexpr FusedRow kFusedRows[kFusedKinds] = {
+    fused_row<HT, false, true, false, true, true>(),   fused_row<HT, false, true, true, true, false>(),
+    fused_row<HT, false, true, false, true, false>(),  fused_row<HT, false, true, true, false, false>(),
+    fused_row<HT, false, false, true, false, false>(), fused_row<HT, true, true, false, false, false>(),
+    fused_row<HT, false, true, false, false, false>(), fused_row<HT, true, false, false, false, false>(),
+    fused_row<HT, false, false, false, false, false>()};
+const FusedRow *const kFusedTable[] = {
+#ifndef MLP_FAST_BUILD  // (experiments compile the flagship tiling only)
+    kFusedRows<1>, kFusedRows<2>, kFusedRows<4>,
+#endif
+    kFusedRows<8>};
+
+const FusedRow *find_variant(const FusedVariant &v)
+{
+    const auto flags = [](const FusedVariant &a) { return a.src64 | a.xbulk << 1 | a.hout << 2 | a.smallf << 3 | a.l1short << 4; };
+    for (const FusedRow *rows : kFusedTable)
+        for (int i = 0; i < kFusedKinds && rows[0].v.HT == v.HT; ++i)
+            if (flags(rows[i].v) == flags(v)) return &rows[i];
+    return nullptr;
+}
+
+int predict_fused(fv3hip_mlp *m, const MlpIo &io, bool src64, int out_dtype, int64_t n_samples, hipStream_t st)
+{
+    const bool out64 = (out_dtype == FV3HIP_F64), fast = fast_layout(m, io, src64, out64, n_samples);
+    FusedVariant want;
+    int rc = select_variant(m, src64, out64, fast, want);
+    if (rc) return rc;
+    const FusedRow *row = find_variant(want);
+    if (!row) return fail(FV3HIP_EUNSUPPORTED, "no compiled kernel variant for HT=%d", m->HT);
+    const FusedVariant &v = row->v;
+    MlpLaunch lp = m->fused;
     lp.io = io;
-    lp.w = static_cast<const f32x4 *>(m->d_w);
-    lp.w_bytes = m->w_bytes;
-    lp.ktab = static_cast<const KEntry *>(m->d_ktab);
-    lp.otab = static_cast<const OEntry *>(m->d_otab);
-    lp.bias = static_cast<const float *>(m->d_bias) + kZeroPadFloats;
-    lp.n_chunks1 = m->n_chunks1;
-    lp.n_hidden = m->n_hidden;
-    lp.n_otiles = m->n_otiles;
-    lp.n_hout_tiles = m->n_hout_tiles;
-    lp.n_ktab = m->n_ktab;
-    lp.n_otab = m->n_otab;
-    lp.n_bias = m->n_bias;
-    lp.out64 = (out_dtype == FV3HIP_F64);
-    lp.has_limits = m->has_limits;
-    {
-        const int oal = (out_dtype == FV3HIP_F64) ? 2 : 4, sal = src64 ? 2 : 4;  // elements per 16 bytes
-        bool fast = (n_samples % 32 == 0);
-        for (int j = 0; j < n_slots && fast; ++j)
-            fast = out_sample_stride[j] == 1 && (reinterpret_cast<uintptr_t>(outputs[j]) % 16 == 0) &&
-                   (out_feat_stride[j] % oal == 0);
-        for (int i = 0; i < m->n_sources && fast; ++i)
-            fast = src_sample_stride[i] == 1 && (reinterpret_cast<uintptr_t>(sources[i]) % 16 == 0) &&
-                   (src_feat_stride[i] % sal == 0);
-        lp.epi_fast = fast ? 1 : 0;
-    }
-    lp.n_log_chunks = m->n_log_chunks;
-    lp.n_logfast_chunks = m->n_logfast_chunks;
-    lp.l1_short_log = m->l1_short_log;
-    lp.n_residual = m->n_residual;
+    lp.out64 = out64;
+    lp.epi_fast = fast ? 1 : 0;
     lp.n_samples = n_samples;
     lp.n_tiles = ceil_div(n_samples, kTileSamples);
 #ifdef MLP_STAMPS
     lp.stamps = g_mlp_stamps;
 #endif
-    const int grid = (int)(lp.n_tiles < m->n_cu ? lp.n_tiles : m->n_cu);
-    // fast-I/O kernels when every source and output is sample-contiguous and aligned (see the kernel)
-    bool xbulk = lp.epi_fast != 0;
-    hipStream_t st = as_stream(stream);
-    constexpr size_t kLdsMax = 160 * 1024, kXsBytes = 2 * 32 * kTileSamples * sizeof(float);
-    if (m->lds_bytes + kXsBytes > kLdsMax) xbulk = false;  // (large tables: the general kernels still fit)
-    const size_t lds = m->lds_bytes + (xbulk ? kXsBytes : 0);
-    lp.sink = 0;
-    if (xbulk) {
-        // scratch row for the padded output rows (kept with the model; grown on demand -- a first
-        // call or a larger n_samples allocates, so warm the model up before capturing a graph)
-        const size_t need = (size_t)n_samples * 8;
-        if (m->sink_bytes < need) {
-            if (m->d_sink) FV3HIP_CHECK_HIP(hipFree(m->d_sink));
-            m->d_sink = nullptr;
-            m->sink_bytes = 0;
-            FV3HIP_CHECK_HIP(hipMalloc(&m->d_sink, need));
-            m->sink_bytes = need;
-        }
+    if (v.xbulk) {  // scratch row for the padded output rows, kept with the model
+        if ((rc = grow(&m->d_sink, &m->sink_bytes, (size_t)n_samples * 8))) return rc;
         lp.sink = reinterpret_cast<int64_t>(m->d_sink);
     }
-    // hidden-output models (recurrent cells) have their own instantiations, so that the plain ones keep their
-    // register allocation and schedule; they take float32 sources only (packed inputs and states)
-    if (m->n_hout_tiles && src64)
-        return fail(FV3HIP_EUNSUPPORTED, "hidden-output models take float32 sources only");
-    // small-output launches (<= 4 outputs, fast I/O, float32 in and out): no output chunk in the stream
-    const bool smallf = m->smallf_n && xbulk && !src64 && out_dtype == FV3HIP_F32;
-    if (smallf) {
+    if (v.smallf) {
         lp.n_otiles = 0;
         lp.smallf_off = m->smallf_off;
         lp.smallf_n = m->smallf_n;
     }
-    // ... and, with one layer-1 chunk of at most 16 untransformed inputs, an 8-slot first chunk (the dense-local models)
-    const bool l1short = smallf && !m->n_hout_tiles && m->K <= 16 && m->n_log_chunks == 0;
-    // the instantiation and the epilogue flavour of this launch, for fv3hip_mlp_last_variant: full sample tiles of a
-    // fast-I/O float32 launch of the 8-tile kernel take the branch-free side epilogue ("plain", or "residual" when the
-    // model has residual outputs), everything else the general one
-    {
-        const bool hout_v = m->n_hout_tiles != 0;
-        const bool src64_v = src64 && !smallf && !hout_v;
-        const bool side = xbulk && !smallf && m->HT == 8 && !m->has_limits && out_dtype == FV3HIP_F32 && n_samples >= kTileSamples;
-        const char *epi = smallf ? "small-output" : (side && !m->n_residual) ? "plain"
-                          : (side && !src64_v && !hout_v) ? "residual" : "general";
-        snprintf(m->last_variant, sizeof(m->last_variant), "mlp_fused_kernel<%d,%s,%s,%s,%s,%s> epilogue=%s", m->HT,
-                 src64_v ? "true" : "false", xbulk ? "true" : "false", hout_v ? "true" : "false",
-                 smallf ? "true" : "false", l1short ? "true" : "false", epi);
-    }
-#define VARIANT_(H)                                                                                \
-    if (m->HT == H && l1short) return launch_one<H, false, true, false, true, true>(lp, grid, lds, st); \
-    if (m->HT == H && smallf)                                                                      \
-        return m->n_hout_tiles ? launch_one<H, false, true, true, true>(lp, grid, lds, st)         \
-                               : launch_one<H, false, true, false, true>(lp, grid, lds, st);       \
-    if (m->HT == H && m->n_hout_tiles)                                                             \
-        return xbulk ? launch_one<H, false, true, true>(lp, grid, lds, st) : launch_one<H, false, false, true>(lp, grid, lds, st); \
-    if (m->HT == H) {                                                                              \
-        if (xbulk) return src64 ? launch_one<H, true, true>(lp, grid, lds, st) : launch_one<H, false, true>(lp, grid, lds, st); \
-        return src64 ? launch_one<H, true, false>(lp, grid, lds, st) : launch_one<H, false, false>(lp, grid, lds, st);          \
-    }
-#ifndef MLP_FAST_BUILD  // (experiments compile the flagship variant only)
-    VARIANT_(1)
-    VARIANT_(2)
-    VARIANT_(4)
-#endif
-    VARIANT_(8)
-#undef VARIANT_
-    return fail(FV3HIP_EUNSUPPORTED, "no compiled kernel variant for HT=%d", m->HT);
+    // the row and the epilogue flavour of this launch, for fv3hip_mlp_last_variant: "small-output", or what the kernel's tile loop
+    // takes on a full sample tile -- the branch-free side epilogue where the instantiation compiles one ("plain", "residual" for a model
+    // with residual outputs), else the general one.  side_plain: the run-time half of the kernel's `side_plain`, for a call with a full tile.
+    const bool side_plain = epi_side(v.HT, v.xbulk) && !m->has_limits && !out64 && n_samples >= kTileSamples;
+    const char *epi = v.smallf ? "small-output" : (side_plain && !m->n_residual) ? "plain"
+                      : (side_plain && res_side(v.HT, v.src64, v.xbulk, v.hout, v.smallf)) ? "residual" : "general";
+    const auto tf = [](bool b) { return b ? "true" : "false"; };
+    snprintf(m->last_variant, sizeof(m->last_variant), "mlp_fused_kernel<%d,%s,%s,%s,%s,%s> epilogue=%s", v.HT, tf(v.src64),
+             tf(v.xbulk), tf(v.hout), tf(v.smallf), tf(v.l1short), epi);
+    const int grid = (int)(lp.n_tiles < m->n_cu ? lp.n_tiles : m->n_cu);
+    return row->launch(lp, grid, m->lds_bytes + (v.xbulk ? kXsBytes : 0), st);
+}
+
+}  // namespace
+
+extern "C" int fv3hip_mlp_predict(fv3hip_mlp_t m, const void *const *sources, const int *src_dtype, const int64_t *src_feat_stride,
+                                  const int64_t *src_sample_stride, int64_t n_samples, void *const *outputs, int out_dtype,
+                                  const int64_t *out_feat_stride, const int64_t *out_sample_stride, void *stream)
+{
+    FV3HIP_REQUIRE(m, "null model handle");
+    FV3HIP_REQUIRE(n_samples >= 0, "negative n_samples");
+    if (n_samples == 0) return FV3HIP_OK;
+    MlpIo io;
+    bool src64;
+    int rc = check_call(m, sources, src_dtype, src_feat_stride, src_sample_stride, n_samples, outputs, out_dtype,
+                        out_feat_stride, out_sample_stride, io, src64);
+    if (rc) return rc;
+    if (m->layered) return predict_layered(m, io, src64, out_dtype, n_samples, as_stream(stream));
+    if (n_samples <= small_limit(m) && m->n_otiles + m->n_hout_tiles > 0 && m->lds_small <= kLdsMax)
+        return predict_small(m, io, src64, out_dtype, n_samples, as_stream(stream));
+    return predict_fused(m, io, src64, out_dtype, n_samples, as_stream(stream));
 }

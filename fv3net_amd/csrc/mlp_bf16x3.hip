@@ -789,16 +789,52 @@ using namespace fv3hip;
 
 struct fv3hip_mlp3 {
     int device = 0, n_cu = 256;
-    int n_sources = 0, n_outputs = 0, n_residual = 0, n_hidden = 0, n_ks1 = 0, n_log_ks = 0, n_ot = 0, has_out = 1, hout = 0, small_out = 0;
+    int n_sources = 0, n_outputs = 0, hout = 0;
+    Mlp3Launch tmpl = {};  // what a launch takes from the model (the layer and tile counts live here alone); a call copies it
     void *d_wsmall = nullptr;
     int64_t flops = 0;
     void *d_w = nullptr, *d_bias = nullptr, *d_center = nullptr, *d_eps = nullptr, *d_ofeat = nullptr, *d_ores = nullptr;
-    size_t lds_bytes = 0, lds_fast = 0, w_bytes = 0;
+    size_t lds_bytes = 0, lds_fast = 0;
     void *d_sink = nullptr;
-    int64_t sink_samples = 0;
+    size_t sink_bytes = 0;
     // per layer-1 k-step: the source it reads, its first feature row there and how many real rows follow (<= 16)
     std::vector<int> ks_src, ks_feat0, ks_rows, res_source;
 };
+
+namespace {
+
+// The compiled instantiations: 1, 3, 5 or 13 output tiles x residual outputs x the 16-byte epilogue.
+struct Mlp3Row { int OT; bool res, fast; void (*kern)(const Mlp3Launch); };
+template <int OT, bool RES, bool FAST>
+constexpr Mlp3Row row3() { return {OT, RES, FAST, mlp3_kernel<OT, RES, FAST>}; }
+constexpr Mlp3Row kMlp3Table[] = {
+    row3<13, true, true>(), row3<13, true, false>(), row3<13, false, true>(), row3<13, false, false>(),
+    row3<5, true, true>(),  row3<5, true, false>(),  row3<5, false, true>(),  row3<5, false, false>(),
+    row3<3, true, true>(),  row3<3, true, false>(),  row3<3, false, true>(),  row3<3, false, false>(),
+    row3<1, true, true>(),  row3<1, true, false>(),  row3<1, false, true>(),  row3<1, false, false>()};
+
+const Mlp3Row *mlp3_row(int n_ot, bool res, bool fast)
+{
+    for (const Mlp3Row &r : kMlp3Table)
+        if (r.OT == n_ot && r.res == res && r.fast == fast) return &r;
+    return nullptr;
+}
+
+// The kernel's chunk waits count memory operations (s_waitcnt vmcnt(N)); a register spill is a memory operation the
+// count does not know -- an instantiation that needs scratch memory must not run.
+int launch3(const Mlp3Row &row, const Mlp3Launch &lp, int grid, size_t lds, hipStream_t st)
+{
+    hipFuncAttributes attr;
+    FV3HIP_CHECK_HIP(hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(row.kern)));
+    if (attr.localSizeBytes != 0)
+        return fail(FV3HIP_EUNSUPPORTED, "mlp3_kernel<%d,%d,%d> was built with %zu bytes of scratch per lane (register spills)", row.OT,
+                    (int)row.res, (int)row.fast, (size_t)attr.localSizeBytes);
+    FV3HIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(row.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(row.kern, dim3(grid), dim3(256), lds, st, lp);
+    return check_launch("mlp3_kernel");
+}
+
+}  // namespace
 
 #ifdef MLP3_STAMPS
 static unsigned long long *g_mlp3_stamps = nullptr;
@@ -831,7 +867,7 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
     const int small_out = (F >= 1 && F <= 4 && d->n_residual == 0) ? F : 0;   // (output layer on the vector ALU, see the kernel)
     const int has_out = (F > 0 && !small_out) ? 1 : 0;
     const int n_ot = has_out ? (F + 31) / 32 : 1;   // (no output layer on the matrix cores: the one-tile instantiation, that phase skipped)
-    if (n_ot != 13 && n_ot != 3 && n_ot != 5 && n_ot != 1)
+    if (!mlp3_row(n_ot, d->n_residual != 0, false))
         return fail(FV3HIP_EUNSUPPORTED, "the split-bf16 kernel is compiled for 1, 3, 5 or 13 output tiles of 32 (got %d outputs)", F);
     // k-slots of layer 1: every input padded to whole k-steps of 16 (a k-step reads 16 consecutive rows of one source), the
     // log-transformed inputs first
@@ -876,13 +912,13 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
     if (hipGetDeviceProperties(&prop, m->device) == hipSuccess) m->n_cu = prop.multiProcessorCount;
     m->n_sources = d->n_sources;
     m->n_outputs = d->n_outputs;
-    m->n_residual = d->n_residual;
-    m->n_hidden = d->n_hidden;
-    m->n_ks1 = n_ks1;
-    m->n_log_ks = n_log_slots / 16;
-    m->n_ot = n_ot;
-    m->has_out = has_out;
-    m->small_out = small_out;
+    m->tmpl.n_residual = d->n_residual;
+    m->tmpl.n_hidden = d->n_hidden;
+    m->tmpl.n_ks1 = n_ks1;
+    m->tmpl.n_log_ks = n_log_slots / 16;
+    m->tmpl.n_ot = n_ot;
+    m->tmpl.has_out = has_out;
+    m->tmpl.small_out = small_out;
     m->hout = dm.hout;
     m->flops = mlp_flops(dm.K, W, d->n_hidden, F);
     m->ks_src = ks_src;
@@ -970,7 +1006,14 @@ extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out
         return rc;
     }
     const size_t ch_max = (size_t)((CH_H > CH_O) ? CH_H : CH_O);
-    m->w_bytes = w.size() * sizeof(unsigned short);
+    m->tmpl.w = static_cast<const f32x4 *>(m->d_w);
+    m->tmpl.w_bytes = (uint32_t)(w.size() * sizeof(unsigned short));
+    m->tmpl.bias = static_cast<const float *>(m->d_bias);
+    m->tmpl.center = static_cast<const float *>(m->d_center);
+    m->tmpl.eps = static_cast<const float *>(m->d_eps);
+    m->tmpl.ofeat = static_cast<const int *>(m->d_ofeat);
+    m->tmpl.ores = static_cast<const int *>(m->d_ores);
+    m->tmpl.wsmall = static_cast<const float *>(m->d_wsmall);
     m->lds_bytes = 3 * ch_max * 16 + (size_t)(d->n_hidden * kHT + n_ot) * 128 + (size_t)slots.size() * 8 + (size_t)n_ot * 32 * 24;
     m->lds_fast = m->lds_bytes + 4 * 32 * 36 * 4 + (size_t)n_ot * 128;   // + a transposition patch per wave and the output biases by feature
     if (small_out) {   // + the small output layer's table (behind everything else in both layouts)
@@ -998,45 +1041,30 @@ extern "C" int fv3hip_mlp3_predict(fv3hip_mlp3_t m, const void *const *sources, 
         FV3HIP_CHECK_HIP(hipGetDevice(&cur));
         FV3HIP_REQUIRE(cur == m->device, "the model lives on device %d but the current device is %d", m->device, cur);
     }
-    Mlp3Launch lp;
-    memset(&lp, 0, sizeof(lp));
+    Mlp3Launch lp = m->tmpl;
     for (int i = 0; i < m->n_sources; ++i) {
         FV3HIP_REQUIRE(sources[i], "source %d is null", i);
         lp.src[i] = static_cast<const float *>(sources[i]);
         lp.src_fs[i] = src_feat_stride[i];
     }
-    for (int j = 0; j < m->n_outputs + m->n_residual; ++j) {
+    for (int j = 0; j < m->n_outputs + m->tmpl.n_residual; ++j) {
         FV3HIP_REQUIRE(outputs[j], "output %d is null", j);
         lp.out[j] = static_cast<float *>(outputs[j]);
         lp.out_fs[j] = out_feat_stride[j];
     }
-    lp.has_out = m->has_out;
-    lp.small_out = m->small_out;
-    lp.wsmall = static_cast<const float *>(m->d_wsmall);
     if (m->hout) {   // (the hidden output is the last entry of `outputs`, as for fv3hip_mlp_predict)
-        const int j = m->n_outputs + m->n_residual;
+        const int j = m->n_outputs + m->tmpl.n_residual;
         FV3HIP_REQUIRE(outputs[j], "the hidden output (output %d) is null", j);
         FV3HIP_REQUIRE(out_feat_stride[j] >= n_samples, "hidden output: feature stride %lld < n_samples", (long long)out_feat_stride[j]);
         lp.hout = static_cast<float *>(outputs[j]);
         lp.hout_fs = out_feat_stride[j];
     }
-    lp.w = static_cast<const f32x4 *>(m->d_w);
-    lp.bias = static_cast<const float *>(m->d_bias);
-    lp.center = static_cast<const float *>(m->d_center);
-    lp.eps = static_cast<const float *>(m->d_eps);
-    if (n_samples > m->sink_samples) {   // (grow-only; a first call or a larger batch than any before)
-        if (m->d_sink) FV3HIP_CHECK_HIP(hipFree(m->d_sink));
-        m->d_sink = nullptr;
-        m->sink_samples = 0;
-        FV3HIP_CHECK_HIP(hipMalloc(&m->d_sink, (size_t)n_samples * 4));
-        m->sink_samples = n_samples;
-    }
+    if (int rc = grow(&m->d_sink, &m->sink_bytes, (size_t)n_samples * 4)) return rc;
     lp.sink = static_cast<float *>(m->d_sink);
-    lp.w_bytes = (uint32_t)m->w_bytes;
 #ifdef MLP3_STAMPS
     lp.stamps = g_mlp3_stamps;
 #endif
-    for (int ks = 0; ks < m->n_ks1; ++ks) {
+    for (int ks = 0; ks < m->tmpl.n_ks1; ++ks) {
         const int sidx = m->ks_src[ks];
         const int64_t fs4 = src_feat_stride[sidx] * 4;
         FV3HIP_REQUIRE(fs4 >= n_samples * 4, "source %d: feature stride %lld < n_samples", sidx, (long long)src_feat_stride[sidx]);
@@ -1048,46 +1076,16 @@ extern "C" int fv3hip_mlp3_predict(fv3hip_mlp3_t m, const void *const *sources, 
         lp.xk[ks].rows = (uint32_t)m->ks_rows[ks];
         lp.xk[ks].fs4 = (uint32_t)fs4;
     }
-    lp.ofeat = static_cast<const int *>(m->d_ofeat);
-    lp.ores = static_cast<const int *>(m->d_ores);
-    lp.n_ks1 = m->n_ks1;
-    lp.n_log_ks = m->n_log_ks;
-    lp.n_hidden = m->n_hidden;
-    lp.n_ot = m->n_ot;
-    lp.n_residual = m->n_residual;
     lp.n_samples = n_samples;
     lp.n_tiles = ceil_div(n_samples, 128);
     const int grid = (int)(lp.n_tiles < m->n_cu ? lp.n_tiles : m->n_cu);
-    hipStream_t st = as_stream(stream);
     // the 16-byte epilogue: every output row and every residual `before` row 16-byte aligned at every feature, whole quads
     bool fast = n_samples % 4 == 0 && m->lds_fast <= 160 * 1024;
-    for (int j = 0; j < m->n_outputs + m->n_residual && fast; ++j)
+    for (int j = 0; j < m->n_outputs + m->tmpl.n_residual && fast; ++j)
         fast = reinterpret_cast<uintptr_t>(outputs[j]) % 16 == 0 && out_feat_stride[j] % 4 == 0;
-    for (int r = 0; r < m->n_residual && fast; ++r)
+    for (int r = 0; r < m->tmpl.n_residual && fast; ++r)
         fast = reinterpret_cast<uintptr_t>(sources[m->res_source[r]]) % 16 == 0 && src_feat_stride[m->res_source[r]] % 4 == 0;
     if (fast && lp.hout) fast = reinterpret_cast<uintptr_t>(lp.hout) % 16 == 0 && lp.hout_fs % 4 == 0;
     const size_t lds = fast ? m->lds_fast : m->lds_bytes;
-#define LAUNCH3_(OT)                                                                                                     \
-    if (m->n_residual) {                                                                                                 \
-        if (fast) LAUNCH3R_(OT, true, true) else LAUNCH3R_(OT, true, false)                                              \
-    } else {                                                                                                             \
-        if (fast) LAUNCH3R_(OT, false, true) else LAUNCH3R_(OT, false, false)                                            \
-    }
-    // The kernel's chunk waits count memory operations (s_waitcnt vmcnt(N)); a register spill is a memory operation the
-    // count does not know -- an instantiation that needs scratch memory must not run.
-#define LAUNCH3R_(OT, RES, FAST)                                                                                         \
-    {                                                                                                                    \
-        auto kern = mlp3_kernel<OT, RES, FAST>;                                                                          \
-        hipFuncAttributes attr;                                                                                          \
-        FV3HIP_CHECK_HIP(hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kern)));                              \
-        if (attr.localSizeBytes != 0)                                                                                    \
-            return fail(FV3HIP_EUNSUPPORTED, "mlp3_kernel<%d,%d,%d> was built with %zu bytes of scratch per lane (register spills)", OT, \
-                        (int)RES, (int)FAST, (size_t)attr.localSizeBytes);                                               \
-        FV3HIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, lp);                                                    \
-    }
-    if (m->n_ot == 13) LAUNCH3_(13) else if (m->n_ot == 5) LAUNCH3_(5) else if (m->n_ot == 3) LAUNCH3_(3) else LAUNCH3_(1)
-#undef LAUNCH3_
-#undef LAUNCH3R_
-    return check_launch("mlp3_kernel");
+    return launch3(*mlp3_row(m->tmpl.n_ot, m->tmpl.n_residual != 0, fast), lp, grid, lds, as_stream(stream));
 }

@@ -100,7 +100,7 @@ def expected_variant(spec, n, src_dtype, out_dtype, fast_layout, n_cu, small_lim
             f" epilogue={epi}")
 
 
-# the nine instantiation kinds VARIANT_ compiles per hidden tiling: template flags <SRC64, XBULK, HOUT, SMALLF, L1SHORT>
+# the nine instantiation kinds mlp.hip's kFusedRows compiles per hidden tiling: template flags <SRC64, XBULK, HOUT, SMALLF, L1SHORT>
 KINDS = {
     "general": "false,false,false,false,false",
     "fast": "false,true,false,false,false",
