@@ -18,8 +18,48 @@ import yaml
 
 from ..cubedsphere._device import compute_device, on_device
 from ..local_mlp import HybridRnnModel, HybridRnnSpec, LocalMlpModel, LocalMlpSpec, RnnModel, RnnSpec
-from ..mlp import MlpModel, MlpModelSplitBf16, MlpSpec
+from .. import mlp
+from ..mlp import MlpSpec, _dtype_code
 from . import zhao_carr
+
+_SPEC_FILENAME = "spec.yaml"
+_WEIGHTS_FILENAME = "weights.npz"
+
+
+def _dump(emulator, path: str) -> None:
+    """``emulator.spec`` as a saved emulator directory (the ``dump`` of both emulator classes)."""
+    os.makedirs(path, exist_ok=True)
+    meta, arrays = emulator.spec.to_arrays()
+    np.savez(os.path.join(path, _WEIGHTS_FILENAME), **arrays)
+    with open(os.path.join(path, _SPEC_FILENAME), "w") as f:
+        yaml.safe_dump(meta, f)
+
+
+def _read(path: str):
+    """(meta, arrays) of a saved emulator directory."""
+    with open(os.path.join(path, _SPEC_FILENAME)) as f:
+        meta = yaml.safe_load(f)
+    with np.load(os.path.join(path, _WEIGHTS_FILENAME), allow_pickle=False) as z:
+        return meta, {k: z[k] for k in z.files}
+
+
+def _to_device(names: Sequence[str], state: Mapping[str, np.ndarray]):
+    """The entries ``names`` of a state of ``[sample, feature]`` (or ``[sample]``) arrays as ``[feature, sample]`` device
+    views, and whether any of them was on the device already."""
+    sources, on_gpu = {}, False
+    for name in names:
+        a = state[name]
+        if isinstance(a, torch.Tensor):
+            on_gpu = on_gpu or a.is_cuda
+        else:
+            a = np.asarray(a)
+            if a.ndim == 2 and a.T.flags.c_contiguous:
+                # a transposed view of call_py_fort's [feature, sample] array: upload it as it is
+                sources[name] = on_device(a.T)
+                continue
+        t = on_device(a)
+        sources[name] = t.t() if t.dim() == 2 else t
+    return sources, on_gpu
 
 
 class HipEmulator:
@@ -28,25 +68,21 @@ class HipEmulator:
     ``model_time``, unused fields) are ignored."""
 
     device_resident = True  # MicrophysicsHook keeps the state and the masks on the device around this model
-    _SPEC_FILENAME = "spec.yaml"
-    _WEIGHTS_FILENAME = "weights.npz"
     # "fp32": the product kernel (fp32 MFMA).  "split-bf16": OPT-IN, experimental -- the same graph with the contraction on
     # the bf16 matrix cores, every operand split into three bf16 pieces (fp32-level accuracy, ~1.4x faster on the Zhao-Carr
     # network; DESIGN.md section 10.1).  A network that kernel does not implement raises at construction, nothing falls back.
-    ARITHMETIC_ENV = "FV3NET_AMD_EMULATOR_ARITHMETIC"
+    ARITHMETIC_ENV = mlp.ARITHMETIC_ENV
 
     def __init__(self, spec: MlpSpec, inputs_to_ignore: Sequence[str] = ("rank", "model_time"), arithmetic: str = None):
         self.spec = spec
         self.inputs_to_ignore = tuple(inputs_to_ignore)
-        self.arithmetic = arithmetic or os.environ.get(self.ARITHMETIC_ENV, "fp32")
-        if self.arithmetic not in ("fp32", "split-bf16"):
-            raise ValueError(f"arithmetic must be 'fp32' or 'split-bf16', got {self.arithmetic!r}")
+        self.arithmetic, _ = mlp.resolve_arithmetic(arithmetic)
         self._model = None
 
     @property
     def model(self):
         if self._model is None:
-            cls = MlpModelSplitBf16 if self.arithmetic == "split-bf16" else MlpModel
+            _, cls = mlp.resolve_arithmetic(self.arithmetic)
             self._model = cls(self.spec, device=compute_device())
         return self._model
 
@@ -59,23 +95,7 @@ class HipEmulator:
         return self.spec.output_names
 
     def __call__(self, state: Mapping[str, np.ndarray]) -> Dict[str, np.ndarray]:
-        sources = {}
-        on_gpu = False
-        for name in self.spec.sources:
-            a = state[name]
-            if isinstance(a, torch.Tensor):
-                on_gpu = on_gpu or a.is_cuda
-                t = on_device(a)
-                sources[name] = t.t() if t.dim() == 2 else t
-                continue
-            a = np.asarray(a)
-            if a.ndim == 2 and a.T.flags.c_contiguous:
-                # a transposed view of call_py_fort's [feature, sample] array: upload it as it is
-                sources[name] = on_device(a.T)
-            elif a.ndim == 2:
-                sources[name] = on_device(np.ascontiguousarray(a)).t()
-            else:
-                sources[name] = on_device(a)
+        sources, on_gpu = _to_device(self.spec.sources, state)
         if self.arithmetic == "split-bf16":  # (that kernel reads float32 [feature, sample] rows with unit sample stride only)
             from .. import ops
 
@@ -95,20 +115,11 @@ class HipEmulator:
                 result[name] = t.cpu().numpy().T  # [sample, feature] view of the [feature, sample] buffer
         return result
 
-    def dump(self, path: str) -> None:
-        os.makedirs(path, exist_ok=True)
-        meta, arrays = self.spec.to_arrays()
-        np.savez(os.path.join(path, self._WEIGHTS_FILENAME), **arrays)
-        with open(os.path.join(path, self._SPEC_FILENAME), "w") as f:
-            yaml.safe_dump(meta, f)
+    dump = _dump
 
     @classmethod
     def load(cls, path: str) -> "HipEmulator":
-        with open(os.path.join(path, cls._SPEC_FILENAME)) as f:
-            meta = yaml.safe_load(f)
-        with np.load(os.path.join(path, cls._WEIGHTS_FILENAME), allow_pickle=False) as z:
-            arrays = {k: z[k] for k in z.files}
-        return cls(MlpSpec.from_arrays(meta, arrays))
+        return cls(MlpSpec.from_arrays(*_read(path)))
 
 
 class HipLocalEmulator:
@@ -118,8 +129,6 @@ class HipLocalEmulator:
     like the Keras model's."""
 
     device_resident = True
-    _SPEC_FILENAME = HipEmulator._SPEC_FILENAME
-    _WEIGHTS_FILENAME = HipEmulator._WEIGHTS_FILENAME
 
     def __init__(self, spec, inputs_to_ignore: Sequence[str] = ("rank", "model_time")):
         self.spec = spec
@@ -129,7 +138,7 @@ class HipLocalEmulator:
     @property
     def model(self):
         if self._model is None:
-            # (both follow FV3NET_AMD_EMULATOR_ARITHMETIC, like HipEmulator)
+            # (the dense-local and the RNN model follow the environment's arithmetic, like HipEmulator)
             cls = RnnModel if isinstance(self.spec, RnnSpec) else HybridRnnModel if isinstance(self.spec, HybridRnnSpec) else LocalMlpModel
             self._model = cls(self.spec, device=compute_device())
         return self._model
@@ -143,18 +152,7 @@ class HipLocalEmulator:
         return self.spec.output_names
 
     def __call__(self, state: Mapping[str, np.ndarray]) -> Dict[str, np.ndarray]:
-        sources = {}
-        on_gpu = False
-        for name in self.spec.sources:
-            a = state[name]
-            if isinstance(a, torch.Tensor):
-                on_gpu = on_gpu or a.is_cuda
-                t = on_device(a)
-            else:
-                a = np.asarray(a)
-                # [sample, feature] views of call_py_fort's [feature, sample] arrays go up as they are
-                t = on_device(a.T).t() if a.ndim == 2 and a.T.flags.c_contiguous else on_device(a)
-            sources[name] = t.t() if t.dim() == 2 else t
+        sources, on_gpu = _to_device(self.spec.sources, state)
         outs = self.model.predict(sources)
         result = {}
         for name, t in outs.items():
@@ -162,12 +160,7 @@ class HipLocalEmulator:
             result[name] = t if on_gpu else t.cpu().numpy()
         return result
 
-    def dump(self, path: str) -> None:
-        os.makedirs(path, exist_ok=True)
-        meta, arrays = self.spec.to_arrays()
-        np.savez(os.path.join(path, self._WEIGHTS_FILENAME), **arrays)
-        with open(os.path.join(path, self._SPEC_FILENAME), "w") as f:
-            yaml.safe_dump(meta, f)
+    dump = _dump
 
     @classmethod
     def load(cls, path: str) -> "HipLocalEmulator":
@@ -178,10 +171,7 @@ def load_emulator(path: str, expect=None):
     """Load a saved emulator directory; ``spec.yaml``'s ``architecture`` key ("dense" when absent,
     "dense-local") selects the class -- the counterpart of ``tf.keras.models.load_model`` in
     external/emulation/emulation/config.py:39-44."""
-    with open(os.path.join(path, HipEmulator._SPEC_FILENAME)) as f:
-        meta = yaml.safe_load(f)
-    with np.load(os.path.join(path, HipEmulator._WEIGHTS_FILENAME), allow_pickle=False) as z:
-        arrays = {k: z[k] for k in z.files}
+    meta, arrays = _read(path)
     arch = meta.get("architecture", "dense")
     if arch == "dense-local":
         model = HipLocalEmulator(LocalMlpSpec.from_arrays(meta, arrays))
@@ -220,7 +210,7 @@ def _get_classify_output(logit_classes, one_hot_axis: int = 0) -> Dict[str, obje
         dev = _require_device(logits)
         onehot = torch.empty(logits.shape, dtype=torch.uint8, device=dev)
         both = torch.empty(logits.shape[1:], dtype=torch.uint8, device=dev)
-        _lib.call_on(dev, "fv3hip_classify_onehot", _ptr(logits), _lib.F64 if logits.dtype == torch.float64 else _lib.F32, n_class,
+        _lib.call_on(dev, "fv3hip_classify_onehot", _ptr(logits), _dtype_code(logits.dtype), n_class,
                   both.numel(), _ptr(onehot), _ptr(both), names.index(zhao_carr.POSITIVE_TENDENCY),
                   names.index(zhao_carr.NEGATIVE_TENDENCY), _stream(dev))
         inverse = [order.index(d) for d in range(1, moved.dim())]  # back to the plane's own dim order (views)

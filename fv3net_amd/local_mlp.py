@@ -12,15 +12,14 @@ three device steps: ``fv3hip_local_pack`` per input -> ``fv3hip_mlp_predict`` on
 ``[n_inputs][nz * ncol]`` array (a point is a sample) -> ``fv3hip_local_unpack`` per output channel.
 """
 import dataclasses
-import os
-from typing import Dict, List, Mapping, Optional, Tuple
+from typing import Callable, Dict, List, Mapping, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .mlp import InputSpec, MlpModel, MlpModelSplitBf16, MlpSpec, OutputSpec, ResidualSpec
-from .ops import _ptr, _require_device, _stream
+from .mlp import InputSpec, MlpModel, MlpSpec, OutputSpec, _dtype_code, _unique, resolve_arithmetic
+from .ops import _ptr, _require_device, _stream, device_info
 
 
 @dataclasses.dataclass
@@ -71,6 +70,64 @@ class LocalOutput:
     single_level: bool = False           # RNN architectures: a [1, ncol] output read off the last (surface) step
 
 
+# -- what the three spec classes share: the input-order rule and the flat (yaml meta, npz arrays) form of their lists ------
+
+def _check_input_order(inputs: List[LocalInput]) -> None:
+    if [i.name for i in inputs] != sorted(i.name for i in inputs):
+        raise ValueError("inputs must be listed sorted by their network name (combine_sequence_inputs)")
+
+
+def _tables_to_arrays(item, prefix: str, arrays: Dict[str, np.ndarray]) -> None:
+    for key in ("center", "scale"):
+        if getattr(item, key) is not None:
+            arrays[f"{prefix}_{key}"] = np.atleast_1d(np.asarray(getattr(item, key), np.float32))
+
+
+def _inputs_to_arrays(inputs: List[LocalInput], arrays: Dict[str, np.ndarray]) -> list:
+    """The meta's ``inputs`` list; the tables go into ``arrays`` (``in{n}_center``, ``in{n}_scale``)."""
+    for n, i in enumerate(inputs):
+        _tables_to_arrays(i, f"in{n}", arrays)
+    return [{"name": i.name, "source": i.source, "transform": i.transform, "eps": float(i.eps)} for i in inputs]
+
+
+def _inputs_from_arrays(meta: list, arrays: Mapping[str, np.ndarray]) -> List[LocalInput]:
+    return [LocalInput(name=m["name"], source=m["source"], transform=m.get("transform", "none"), eps=float(m.get("eps", 0.0)),
+                       center=arrays.get(f"in{n}_center"), scale=arrays.get(f"in{n}_scale")) for n, m in enumerate(meta)]
+
+
+def _outputs_to_arrays(outputs: List[LocalOutput], arrays: Dict[str, np.ndarray]) -> list:
+    """The meta's ``outputs`` list; the tables go into ``arrays`` (``out{n}_center``, ``out{n}_scale``, ``out{n}_cs_*``)."""
+    meta = []
+    for n, o in enumerate(outputs):
+        m = {"name": o.name, "channels": int(o.channels), "after": o.after, "before": o.before,
+             "value_limit": [None if v is None else float(v) for v in o.value_limit],
+             "after_limit": [None if v is None else float(v) for v in o.after_limit], "single_level": bool(o.single_level)}
+        _tables_to_arrays(o, f"out{n}", arrays)
+        if o.conditional is not None:
+            c = o.conditional
+            m["conditional"] = {"name": c.name, "on": c.on, "min_scale": float(c.min_scale)}
+            for key in ("edges", "scale", "center"):
+                arrays[f"out{n}_cs_{key}"] = np.asarray(getattr(c, key), np.float32)
+        meta.append(m)
+    return meta
+
+
+def _outputs_from_arrays(meta: list, arrays: Mapping[str, np.ndarray]) -> List[LocalOutput]:
+    outputs = []
+    for n, m in enumerate(meta):
+        cond = None
+        if m.get("conditional"):
+            c = m["conditional"]
+            cond = ConditionalScale(name=c["name"], on=c["on"], min_scale=float(c.get("min_scale", 0.0)),
+                                    **{key: np.asarray(arrays[f"out{n}_cs_{key}"]) for key in ("edges", "scale", "center")})
+        outputs.append(LocalOutput(name=m["name"], channels=int(m.get("channels", 1)), scale=arrays.get(f"out{n}_scale"),
+                                   center=arrays.get(f"out{n}_center"), conditional=cond, after=m.get("after"),
+                                   before=m.get("before"), value_limit=tuple(m.get("value_limit") or (None, None)),
+                                   after_limit=tuple(m.get("after_limit") or (None, None)),
+                                   single_level=bool(m.get("single_level", False))))
+    return outputs
+
+
 @dataclasses.dataclass
 class LocalMlpSpec:
     inputs: List[LocalInput]            # in the network's (sorted-by-name) order
@@ -83,17 +140,13 @@ class LocalMlpSpec:
 
     @property
     def sources(self) -> List[str]:
-        seen: List[str] = []
         names = [i.source for i in self.inputs]
         for o in self.outputs:
             if o.conditional is not None:
                 names.append(o.conditional.on)
             if o.before is not None:
                 names.append(o.before)
-        for n in names:
-            if n not in seen:
-                seen.append(n)
-        return seen
+        return _unique(names)
 
     @property
     def output_names(self) -> List[str]:
@@ -111,8 +164,7 @@ class LocalMlpSpec:
         return sum(o.channels for o in self.outputs)
 
     def validate(self):
-        if [i.name for i in self.inputs] != sorted(i.name for i in self.inputs):
-            raise ValueError("inputs must be listed sorted by their network name (combine_sequence_inputs)")
+        _check_input_order(self.inputs)
         if not self.hidden_kernels or len(self.hidden_kernels) != len(self.hidden_biases):
             raise ValueError("at least one hidden layer, one bias per kernel")
         if int(self.hidden_kernels[0].shape[0]) != len(self.inputs):
@@ -128,31 +180,9 @@ class LocalMlpSpec:
 
     # -- flat (yaml meta, npz arrays) serialisation ------------------------------------------
     def to_arrays(self) -> Tuple[dict, Dict[str, np.ndarray]]:
-        meta = {
-            "architecture": self.architecture,
-            "inputs": [{"name": i.name, "source": i.source, "transform": i.transform, "eps": float(i.eps)} for i in self.inputs],
-            "outputs": [],
-            "n_hidden": len(self.hidden_kernels),
-        }
         arrays: Dict[str, np.ndarray] = {}
-        for n, i in enumerate(self.inputs):
-            for key in ("center", "scale"):
-                if getattr(i, key) is not None:
-                    arrays[f"in{n}_{key}"] = np.atleast_1d(np.asarray(getattr(i, key), np.float32))
-        for n, o in enumerate(self.outputs):
-            m = {"name": o.name, "channels": int(o.channels), "after": o.after, "before": o.before,
-                 "value_limit": [None if v is None else float(v) for v in o.value_limit],
-                 "after_limit": [None if v is None else float(v) for v in o.after_limit], "single_level": bool(o.single_level)}
-            for key in ("center", "scale"):
-                if getattr(o, key) is not None:
-                    arrays[f"out{n}_{key}"] = np.atleast_1d(np.asarray(getattr(o, key), np.float32))
-            if o.conditional is not None:
-                c = o.conditional
-                m["conditional"] = {"name": c.name, "on": c.on, "min_scale": float(c.min_scale)}
-                arrays[f"out{n}_cs_edges"] = np.asarray(c.edges, np.float32)
-                arrays[f"out{n}_cs_scale"] = np.asarray(c.scale, np.float32)
-                arrays[f"out{n}_cs_center"] = np.asarray(c.center, np.float32)
-            meta["outputs"].append(m)
+        meta = {"architecture": self.architecture, "inputs": _inputs_to_arrays(self.inputs, arrays),
+                "outputs": _outputs_to_arrays(self.outputs, arrays), "n_hidden": len(self.hidden_kernels)}
         for n, (kern, b) in enumerate(zip(self.hidden_kernels, self.hidden_biases)):
             arrays[f"hidden{n}_kernel"] = np.asarray(kern, np.float32)
             arrays[f"hidden{n}_bias"] = np.asarray(b, np.float32)
@@ -162,25 +192,11 @@ class LocalMlpSpec:
 
     @classmethod
     def from_arrays(cls, meta: Mapping, arrays: Mapping[str, np.ndarray]) -> "LocalMlpSpec":
-        inputs = [LocalInput(name=m["name"], source=m["source"], transform=m.get("transform", "none"), eps=float(m.get("eps", 0.0)),
-                             center=arrays.get(f"in{n}_center"), scale=arrays.get(f"in{n}_scale"))
-                  for n, m in enumerate(meta["inputs"])]
-        outputs = []
-        for n, m in enumerate(meta["outputs"]):
-            cond = None
-            if m.get("conditional"):
-                c = m["conditional"]
-                cond = ConditionalScale(name=c["name"], on=c["on"], min_scale=float(c.get("min_scale", 0.0)),
-                                        edges=np.asarray(arrays[f"out{n}_cs_edges"]), scale=np.asarray(arrays[f"out{n}_cs_scale"]),
-                                        center=np.asarray(arrays[f"out{n}_cs_center"]))
-            outputs.append(LocalOutput(name=m["name"], channels=int(m.get("channels", 1)), scale=arrays.get(f"out{n}_scale"),
-                                       center=arrays.get(f"out{n}_center"), conditional=cond, after=m.get("after"),
-                                       before=m.get("before"), value_limit=tuple(m.get("value_limit") or (None, None)),
-                                       after_limit=tuple(m.get("after_limit") or (None, None)),
-                                       single_level=bool(m.get("single_level", False))))
         nh = int(meta["n_hidden"])
-        return cls(inputs=inputs, hidden_kernels=[np.asarray(arrays[f"hidden{n}_kernel"]) for n in range(nh)],
-                   hidden_biases=[np.asarray(arrays[f"hidden{n}_bias"]) for n in range(nh)], outputs=outputs,
+        return cls(inputs=_inputs_from_arrays(meta["inputs"], arrays),
+                   hidden_kernels=[np.asarray(arrays[f"hidden{n}_kernel"]) for n in range(nh)],
+                   hidden_biases=[np.asarray(arrays[f"hidden{n}_bias"]) for n in range(nh)],
+                   outputs=_outputs_from_arrays(meta["outputs"], arrays),
                    out_kernel=np.asarray(arrays["out_kernel"]), out_bias=np.asarray(arrays["out_bias"]))
 
 
@@ -192,6 +208,22 @@ class RnnLayer:
     kernel: np.ndarray            # [in, channels]
     recurrent_kernel: np.ndarray  # [channels, channels]
     bias: np.ndarray              # [channels]
+
+    def check(self, fan: int, what: str) -> int:
+        """Refuse shapes that do not fit ``fan`` inputs; returns the channel count (the fan-in of what follows)."""
+        ch = int(self.kernel.shape[1])
+        if tuple(self.kernel.shape) != (fan, ch) or tuple(self.recurrent_kernel.shape) != (ch, ch) or tuple(self.bias.shape) != (ch,):
+            raise ValueError(f"{what}: kernel {self.kernel.shape}, recurrent kernel {self.recurrent_kernel.shape}, "
+                             f"bias {self.bias.shape} do not fit {fan} inputs")
+        return ch
+
+    def to_arrays(self, prefix: str, arrays: Dict[str, np.ndarray]) -> None:
+        for key in ("kernel", "recurrent_kernel", "bias"):
+            arrays[f"{prefix}_{key}"] = np.asarray(getattr(self, key), np.float32)
+
+    @classmethod
+    def from_arrays(cls, prefix: str, arrays: Mapping[str, np.ndarray]) -> "RnnLayer":
+        return cls(*[np.asarray(arrays[f"{prefix}_{key}"]) for key in ("kernel", "recurrent_kernel", "bias")])
 
 
 @dataclasses.dataclass
@@ -214,17 +246,12 @@ class RnnSpec:
     n_channels = LocalMlpSpec.n_channels
 
     def validate(self):
-        if [i.name for i in self.inputs] != sorted(i.name for i in self.inputs):
-            raise ValueError("inputs must be listed sorted by their network name (combine_sequence_inputs)")
+        _check_input_order(self.inputs)
         if not self.layers:
             raise ValueError("at least one recurrent layer")
         fan = len(self.inputs)
         for n, layer in enumerate(self.layers):
-            ch = int(layer.kernel.shape[1])
-            if tuple(layer.kernel.shape) != (fan, ch) or tuple(layer.recurrent_kernel.shape) != (ch, ch) or tuple(layer.bias.shape) != (ch,):
-                raise ValueError(f"recurrent layer {n}: kernel {layer.kernel.shape}, recurrent kernel {layer.recurrent_kernel.shape}, "
-                                 f"bias {layer.bias.shape} do not fit {fan} inputs")
-            fan = ch
+            fan = layer.check(fan, f"recurrent layer {n}")
         if tuple(self.out_kernel.shape) != (fan, self.n_channels) or tuple(self.out_bias.shape) != (self.n_channels,):
             raise ValueError(f"output kernel has shape {self.out_kernel.shape}, expected {(fan, self.n_channels)}")
         for o in self.outputs:
@@ -236,26 +263,21 @@ class RnnSpec:
                 raise ValueError(f"single-level output {o.name!r} cannot carry level-wise transforms")
 
     def to_arrays(self) -> Tuple[dict, Dict[str, np.ndarray]]:
-        shell = LocalMlpSpec(self.inputs, [np.zeros((len(self.inputs), 1), np.float32)], [np.zeros(1, np.float32)], self.outputs,
-                             self.out_kernel, self.out_bias)
-        meta, arrays = shell.to_arrays()
-        for key in ("hidden0_kernel", "hidden0_bias"):
-            del arrays[key]
-        meta["architecture"] = self.architecture
-        meta["n_hidden"] = 0
-        meta["n_rnn"] = len(self.layers)
+        arrays: Dict[str, np.ndarray] = {}
+        meta = {"architecture": self.architecture, "inputs": _inputs_to_arrays(self.inputs, arrays),
+                "outputs": _outputs_to_arrays(self.outputs, arrays), "n_hidden": 0, "n_rnn": len(self.layers)}
+        arrays["out_kernel"] = np.asarray(self.out_kernel, np.float32)
+        arrays["out_bias"] = np.asarray(self.out_bias, np.float32)
         for n, layer in enumerate(self.layers):
-            arrays[f"rnn{n}_kernel"] = np.asarray(layer.kernel, np.float32)
-            arrays[f"rnn{n}_recurrent_kernel"] = np.asarray(layer.recurrent_kernel, np.float32)
-            arrays[f"rnn{n}_bias"] = np.asarray(layer.bias, np.float32)
+            layer.to_arrays(f"rnn{n}", arrays)
         return meta, arrays
 
     @classmethod
     def from_arrays(cls, meta: Mapping, arrays: Mapping[str, np.ndarray]) -> "RnnSpec":
-        shell = LocalMlpSpec.from_arrays({**meta, "n_hidden": 0}, arrays)
-        layers = [RnnLayer(np.asarray(arrays[f"rnn{n}_kernel"]), np.asarray(arrays[f"rnn{n}_recurrent_kernel"]),
-                           np.asarray(arrays[f"rnn{n}_bias"])) for n in range(int(meta["n_rnn"]))]
-        return cls(inputs=shell.inputs, layers=layers, outputs=shell.outputs, out_kernel=shell.out_kernel, out_bias=shell.out_bias)
+        return cls(inputs=_inputs_from_arrays(meta["inputs"], arrays),
+                   layers=[RnnLayer.from_arrays(f"rnn{n}", arrays) for n in range(int(meta["n_rnn"]))],
+                   outputs=_outputs_from_arrays(meta["outputs"], arrays),
+                   out_kernel=np.asarray(arrays["out_kernel"]), out_bias=np.asarray(arrays["out_bias"]))
 
 
 @dataclasses.dataclass
@@ -278,23 +300,15 @@ class HybridRnnSpec:
 
     @property
     def sources(self) -> List[str]:
-        seen: List[str] = []
-        for n in [i.source for i in self.inputs] + [r.source for r in self.head.residuals]:
-            if n not in seen:
-                seen.append(n)
-        return seen
+        return _unique([i.source for i in self.inputs] + [r.source for r in self.head.residuals])
 
     @property
     def output_names(self) -> List[str]:
         return self.head.output_names
 
     def validate(self):
-        if [i.name for i in self.inputs] != sorted(i.name for i in self.inputs):
-            raise ValueError("inputs must be listed sorted by their network name (combine_sequence_inputs)")
-        fan, ch = len(self.inputs), int(self.rnn.kernel.shape[1])
-        if tuple(self.rnn.kernel.shape) != (fan, ch) or tuple(self.rnn.recurrent_kernel.shape) != (ch, ch) or tuple(self.rnn.bias.shape) != (ch,):
-            raise ValueError(f"recurrent layer: kernel {self.rnn.kernel.shape}, recurrent kernel {self.rnn.recurrent_kernel.shape}, "
-                             f"bias {self.rnn.bias.shape} do not fit {fan} inputs")
+        _check_input_order(self.inputs)
+        ch = self.rnn.check(len(self.inputs), "recurrent layer")
         if [(i.source, i.nfeat, i.start) for i in self.head.inputs] != [(self.STATE, ch, 0)]:
             raise ValueError(f"the head's only input must be the {ch} features of {self.STATE!r}")
         if self.head.hidden_output:
@@ -305,27 +319,36 @@ class HybridRnnSpec:
 
     def to_arrays(self) -> Tuple[dict, Dict[str, np.ndarray]]:
         head_meta, head_arrays = self.head.to_arrays()
-        meta = {"architecture": self.architecture, "go_backwards": bool(self.go_backwards), "head": head_meta,
-                "inputs": [{"name": i.name, "source": i.source, "transform": i.transform, "eps": float(i.eps)} for i in self.inputs]}
         arrays = {f"head_{k}": v for k, v in head_arrays.items()}
-        for n, i in enumerate(self.inputs):
-            for key in ("center", "scale"):
-                if getattr(i, key) is not None:
-                    arrays[f"in{n}_{key}"] = np.atleast_1d(np.asarray(getattr(i, key), np.float32))
-        arrays["rnn_kernel"] = np.asarray(self.rnn.kernel, np.float32)
-        arrays["rnn_recurrent_kernel"] = np.asarray(self.rnn.recurrent_kernel, np.float32)
-        arrays["rnn_bias"] = np.asarray(self.rnn.bias, np.float32)
+        meta = {"architecture": self.architecture, "go_backwards": bool(self.go_backwards), "head": head_meta,
+                "inputs": _inputs_to_arrays(self.inputs, arrays)}
+        self.rnn.to_arrays("rnn", arrays)
         return meta, arrays
 
     @classmethod
     def from_arrays(cls, meta: Mapping, arrays: Mapping[str, np.ndarray]) -> "HybridRnnSpec":
-        inputs = [LocalInput(name=m["name"], source=m["source"], transform=m.get("transform", "none"), eps=float(m.get("eps", 0.0)),
-                             center=arrays.get(f"in{n}_center"), scale=arrays.get(f"in{n}_scale"))
-                  for n, m in enumerate(meta["inputs"])]
         head = MlpSpec.from_arrays(meta["head"], {k[len("head_"):]: v for k, v in arrays.items() if k.startswith("head_")})
-        return cls(inputs=inputs, rnn=RnnLayer(np.asarray(arrays["rnn_kernel"]), np.asarray(arrays["rnn_recurrent_kernel"]),
-                                               np.asarray(arrays["rnn_bias"])),
-                   head=head, go_backwards=bool(meta.get("go_backwards", True)))
+        return cls(inputs=_inputs_from_arrays(meta["inputs"], arrays), rnn=RnnLayer.from_arrays("rnn", arrays), head=head,
+                   go_backwards=bool(meta.get("go_backwards", True)))
+
+
+def _cell_spec(layer: RnnLayer, out_kernel: Optional[np.ndarray] = None, out_bias: Optional[np.ndarray] = None) -> MlpSpec:
+    """A SimpleRNN cell as a fused-MLP model: one hidden layer ``relu([in, rec] @ [kernel; recurrent_kernel] + bias)`` that
+    is returned as the hidden output "h" (the new state).  With ``out_kernel`` / ``out_bias`` the launch also applies that
+    output layer to the new state (output "y"); without, the model has no outputs."""
+    fan, ch = int(layer.kernel.shape[0]), int(layer.kernel.shape[1])
+    last = out_kernel is not None
+    return MlpSpec(
+        inputs=[InputSpec("in", fan), InputSpec("rec", ch)],
+        hidden_kernels=[np.concatenate([layer.kernel, layer.recurrent_kernel], axis=0).astype(np.float32)],
+        hidden_biases=[np.asarray(layer.bias, np.float32)], outputs=[OutputSpec("y", int(out_kernel.shape[1]))] if last else [],
+        out_kernel=np.asarray(out_kernel, np.float32) if last else np.zeros((ch, 0), np.float32),
+        out_bias=np.asarray(out_bias, np.float32) if last else np.zeros(0, np.float32), hidden_output="h")
+
+
+def _state_pair(width: int, ncol: int, dev) -> List[torch.Tensor]:
+    """The ping-pong buffers of one recurrent layer's state: [h_{-1} = 0, not yet written]."""
+    return [torch.zeros((width, ncol), dtype=torch.float32, device=dev), torch.empty((width, ncol), dtype=torch.float32, device=dev)]
 
 
 def _per_level(values, nz: int, default: float, what: str) -> np.ndarray:
@@ -339,18 +362,17 @@ def _per_level(values, nz: int, default: float, what: str) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
-def _dt(t: torch.Tensor) -> int:
-    return _lib.F64 if t.dtype == torch.float64 else _lib.F32
-
-
 class _PointModel:
-    """What the dense-local and the RNN models share: source checks, the pack pass, the unpack pass."""
+    """What the dense-local and the RNN models share: source checks, the pack pass, the unpack pass, and for the RNN models
+    the replay of their level sweep as a HIP graph."""
 
     def __init__(self, spec, device):
         spec.validate()
         self.spec = spec
         self.device = torch.device(device)
         self._tables: Dict[Tuple[str, int], torch.Tensor] = {}
+        self._graphs: Dict[Tuple[int, int], tuple] = {}  # (nz, ncol) -> (graph, its static buffers); one shape at a time
+        self._n_cu: Optional[int] = None
 
     def _table(self, key: str, values, nz: Optional[int], default: float = 0.0) -> torch.Tensor:
         """Small per-level / per-bin float tables, uploaded once per (table, nz)."""
@@ -396,7 +418,7 @@ class _PointModel:
     def _pack_into(self, arrs, nz: int, ncol: int, dev, x: torch.Tensor) -> None:
         for n, i in enumerate(self.spec.inputs):
             t = arrs[i.source]
-            _lib.call_on(dev, "fv3hip_local_pack", _ptr(t), _dt(t), int(t.shape[0] != 1),
+            _lib.call_on(dev, "fv3hip_local_pack", _ptr(t), _dtype_code(t.dtype), int(t.shape[0] != 1),
                       _lib.TRANSFORM_LOG if i.transform == "log" else _lib.TRANSFORM_NONE, float(i.eps),
                       _ptr(self._table(f"in{n}_center", i.center, nz, 0.0)), _ptr(self._table(f"in{n}_scale", i.scale, nz, 1.0)),
                       nz, ncol, _ptr(x[n]), _stream(dev))
@@ -410,13 +432,13 @@ class _PointModel:
         if cond is not None:
             unscaled = torch.empty_like(direct)
             on = arrs[cond.on]
-            cond_args = [_ptr(on), _dt(on), _ptr(self._table(f"out{n}_cs_edges", cond.edges, None)),
+            cond_args = [_ptr(on), _dtype_code(on.dtype), _ptr(self._table(f"out{n}_cs_edges", cond.edges, None)),
                          _ptr(self._table(f"out{n}_cs_scale", cond.scale, None)),
                          _ptr(self._table(f"out{n}_cs_center", cond.center, None)), int(len(cond.edges)), float(cond.min_scale)]
         before_args = [None, 0]
         if o.before is not None:
             after = torch.empty_like(direct)
-            before_args = [_ptr(arrs[o.before]), _dt(arrs[o.before])]
+            before_args = [_ptr(arrs[o.before]), _dtype_code(arrs[o.before].dtype)]
         bounds = list(o.value_limit) + list(o.after_limit)
         flags = sum(1 << b for b, v in enumerate(bounds) if v is not None)
         _lib.call_on(dev, "fv3hip_local_unpack", _ptr(rows), int(level_stride),
@@ -430,6 +452,40 @@ class _PointModel:
         if o.after is not None:
             out[o.after] = after
 
+    def _leaves_cus_idle(self, ncol: int) -> bool:
+        """Fewer than ~128 columns per CU: the launches of one recurrent layer leave most of the chip idle."""
+        if self._n_cu is None:
+            self._n_cu = int(device_info()["compute_units"])
+        return ncol < 128 * self._n_cu
+
+    def _graphed(self, key: Tuple[int, int], arrs, dev, buffers: Callable[[], tuple], sweep: Callable[..., object]) -> tuple:
+        """The level sweep of a call of shape ``key`` = (nz, ncol) as the replay of a HIP graph (bit-identical to the eager
+        launches).  ``buffers()`` allocates the graph's static buffers, ``(x, state pairs, ...)``: the packed input, one
+        ``_state_pair`` per recurrent layer, whatever else the sweep writes; ``sweep(*buffers)`` launches the recurrence.
+        The first call of a shape packs, sweeps once eagerly on the current stream (the kernels' one-time allocations happen
+        there; the side streams a pipelined sweep creates are the ones the capture then records as parallel branches),
+        synchronises, and captures the zeroing of the first state buffers followed by the sweep.  Every call packs into
+        ``x`` and replays.  Returns the static buffers: valid until the next call, the caller consumes them before it
+        returns."""
+        nz, ncol = key
+        entry = self._graphs.get(key)
+        if entry is None:
+            self._graphs.clear()  # one shape at a time: the static buffers of another shape are released
+            bufs = buffers()
+            self._pack_into(arrs, nz, ncol, dev, bufs[0])
+            sweep(*bufs)
+            torch.cuda.synchronize(dev)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for pair in bufs[1]:
+                    pair[0].zero_()
+                sweep(*bufs)
+            entry = self._graphs[key] = (graph, bufs)
+        graph, bufs = entry
+        self._pack_into(arrs, nz, ncol, dev, bufs[0])
+        graph.replay()
+        return bufs
+
 
 class LocalMlpModel(_PointModel):
     """Device handle of a dense-local emulator."""
@@ -437,13 +493,11 @@ class LocalMlpModel(_PointModel):
     def __init__(self, spec: LocalMlpSpec, device="cuda", arithmetic: Optional[str] = None):
         """``arithmetic``: "fp32" (the product kernel) or "split-bf16" (opt-in, experimental: the network on the bf16 matrix
         cores with every operand split into three bf16 pieces, csrc/mlp_bf16x3.hip); default: the environment variable
-        FV3NET_AMD_EMULATOR_ARITHMETIC, else "fp32".  A network the split kernel does not implement raises here."""
+        ``mlp.ARITHMETIC_ENV``, else "fp32" (``mlp.resolve_arithmetic``).  A network the split kernel does not implement
+        raises here."""
         super().__init__(spec, device)
         k, c = len(spec.inputs), spec.n_channels
-        self.arithmetic = arithmetic or os.environ.get("FV3NET_AMD_EMULATOR_ARITHMETIC", "fp32")
-        if self.arithmetic not in ("fp32", "split-bf16"):
-            raise ValueError(f"arithmetic must be 'fp32' or 'split-bf16', got {self.arithmetic!r}")
-        inner_cls = MlpModelSplitBf16 if self.arithmetic == "split-bf16" else MlpModel
+        self.arithmetic, inner_cls = resolve_arithmetic(arithmetic)
         self._inner = inner_cls(MlpSpec(
             inputs=[InputSpec("X", k)], hidden_kernels=spec.hidden_kernels, hidden_biases=spec.hidden_biases,
             outputs=[OutputSpec("Y", c)], out_kernel=spec.out_kernel, out_bias=spec.out_bias), device=self.device)
@@ -476,12 +530,9 @@ class RnnModel(_PointModel):
     per call, each with ``ncol`` samples; the states ping-pong between two buffers per layer."""
 
     def __init__(self, spec: RnnSpec, device="cuda", use_graph: Optional[bool] = None, arithmetic: Optional[str] = None):
-        """``arithmetic``: as for ``LocalMlpModel`` ("fp32" / opt-in "split-bf16"; default from FV3NET_AMD_EMULATOR_ARITHMETIC)."""
+        """``arithmetic``: as for ``LocalMlpModel`` ("fp32" / opt-in "split-bf16"; default from the environment)."""
         super().__init__(spec, device)
-        self.arithmetic = arithmetic or os.environ.get("FV3NET_AMD_EMULATOR_ARITHMETIC", "fp32")
-        if self.arithmetic not in ("fp32", "split-bf16"):
-            raise ValueError(f"arithmetic must be 'fp32' or 'split-bf16', got {self.arithmetic!r}")
-        cell_cls = MlpModelSplitBf16 if self.arithmetic == "split-bf16" else MlpModel
+        self.arithmetic, cell_cls = resolve_arithmetic(arithmetic)
         # ``use_graph``: capture the level sweep (nz x depth launches) once per (nz, ncol) into a HIP graph on static
         # buffers and replay it (bit-identical).  None = where it pays: the column counts of one model rank, whose launches
         # are ~20-40 us each on the feature-split kernel -- 158 of them cost more host time than device time when launched
@@ -489,34 +540,32 @@ class RnnModel(_PointModel):
         # launch lasts milliseconds.  (Round 2 measured no gain at all: a step was then bound by the ~60 us one 128-sample
         # tile needs on each of the 18 CUs it occupied.)
         self._use_graph = use_graph
-        self._graphs: Dict[Tuple[int, int], tuple] = {}
-        self._cells: List[MlpModel] = []
-        c = spec.n_channels
-        for n, layer in enumerate(spec.layers):
-            fan, ch = int(layer.kernel.shape[0]), int(layer.kernel.shape[1])
-            last = n == len(spec.layers) - 1
-            self._cells.append(cell_cls(MlpSpec(
-                inputs=[InputSpec("in", fan), InputSpec("rec", ch)],
-                hidden_kernels=[np.concatenate([layer.kernel, layer.recurrent_kernel], axis=0).astype(np.float32)],
-                hidden_biases=[np.asarray(layer.bias, np.float32)], outputs=[OutputSpec("y", c)] if last else [],
-                out_kernel=np.asarray(spec.out_kernel, np.float32) if last else np.zeros((ch, 0), np.float32),
-                out_bias=np.asarray(spec.out_bias, np.float32) if last else np.zeros(0, np.float32), hidden_output="h"),
-                device=self.device))
+        last = len(spec.layers) - 1
+        self._cells: List[MlpModel] = [
+            cell_cls(_cell_spec(layer, spec.out_kernel, spec.out_bias) if n == last else _cell_spec(layer), device=self.device)
+            for n, layer in enumerate(spec.layers)]
         self.flops_per_point = sum(m.flops_per_sample for m in self._cells)
 
     def predict(self, sources: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """As ``LocalMlpModel.predict``; single-level outputs come back as ``[1, ncol]``."""
         spec = self.spec
         arrs, nz, ncol, dev = self._gather(sources)
-        c = spec.n_channels
-        use_graph = self._use_graph if self._use_graph is not None else (self.arithmetic == "fp32" and ncol < 128 * self._inner_cus())
+        k, c = len(spec.inputs), spec.n_channels
+        # (column counts that leave most CUs idle: the layers on a stream each, layer n + 1 of level z beside layer n of
+        # level z - 1; a capture records the side streams' work as parallel branches of the graph)
+        idle = self._leaves_cus_idle(ncol)
+        use_graph = self._use_graph if self._use_graph is not None else (self.arithmetic == "fp32" and idle)
         if use_graph:
-            x, y = self._sweep_graphed(arrs, nz, ncol, dev)
+            def buffers():
+                x = torch.empty((k, nz, ncol), dtype=torch.float32, device=dev)
+                y = torch.empty((c, nz, ncol), dtype=torch.float32, device=dev)
+                return x, self._new_states(ncol, dev), y
+
+            x, _, y = self._graphed((nz, ncol), arrs, dev, buffers, lambda x, states, y: self._sweep(x, y, states, nz, pipelined=idle))
         else:
-            x = self._pack(arrs, nz, ncol, dev).view(len(spec.inputs), nz, ncol)
+            x = self._pack(arrs, nz, ncol, dev).view(k, nz, ncol)
             y = torch.empty((c, nz, ncol), dtype=torch.float32, device=dev)
-            # (below ~128 columns per CU the launches of one layer leave most of the chip idle)
-            self._sweep(x, y, self._new_states(ncol, dev), nz, pipelined=ncol < 128 * self._inner_cus())
+            self._sweep(x, y, self._new_states(ncol, dev), nz, pipelined=idle)
         del x
         out: Dict[str, torch.Tensor] = {}
         for n, o in enumerate(spec.outputs):
@@ -526,16 +575,8 @@ class RnnModel(_PointModel):
                 self._unpack_one(n, o, y[n], ncol, arrs, nz, ncol, dev, out)
         return out
 
-    def _inner_cus(self) -> int:
-        from .ops import device_info
-
-        if not hasattr(self, "_n_cu"):
-            self._n_cu = int(device_info()["compute_units"])
-        return self._n_cu
-
     def _new_states(self, ncol: int, dev):
-        return [[torch.zeros((m.spec.width, ncol), dtype=torch.float32, device=dev),
-                 torch.empty((m.spec.width, ncol), dtype=torch.float32, device=dev)] for m in self._cells]
+        return [_state_pair(m.spec.width, ncol, dev) for m in self._cells]
 
     def _sweep(self, x: torch.Tensor, y: torch.Tensor, states, nz: int, pipelined: bool = False) -> None:
         """The recurrence, from the model top (last index) to the surface.  ``pipelined`` (column counts that leave most
@@ -575,33 +616,6 @@ class RnnModel(_PointModel):
             for _, st in zip(side, self._streams):
                 main.wait_stream(st)
 
-    def _sweep_graphed(self, arrs, nz: int, ncol: int, dev):
-        """Pack into the graph's static input buffer, replay the captured sweep, hand back its static output buffer
-        (valid until the next call with the same shape; ``predict`` consumes it before returning)."""
-        key = (nz, ncol)
-        entry = self._graphs.get(key)
-        if entry is None:
-            self._graphs.clear()  # one shape at a time: the static buffers of another shape are released
-            x = torch.empty((len(self.spec.inputs), nz, ncol), dtype=torch.float32, device=dev)
-            y = torch.empty((self.spec.n_channels, nz, ncol), dtype=torch.float32, device=dev)
-            states = self._new_states(ncol, dev)
-            self._pack_into(arrs, nz, ncol, dev, x)
-            # (column counts that leave most CUs idle: the layers on a stream each, layer n + 1 of level z beside layer n of
-            # level z - 1; the capture records the side streams' work as parallel branches of the graph)
-            pipelined = ncol < 128 * self._inner_cus()
-            self._sweep(x, y, states, nz, pipelined=pipelined)  # eager warm-up: the kernels' one-time allocations happen here
-            torch.cuda.synchronize(dev)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                for st in states:
-                    st[0].zero_()
-                self._sweep(x, y, states, nz, pipelined=pipelined)
-            entry = self._graphs[key] = (graph, x, y, states)
-        graph, x, y, _ = entry
-        self._pack_into(arrs, nz, ncol, dev, x)
-        graph.replay()
-        return x, y
-
 
 class HybridRnnModel(_PointModel):
     """Device handle of a "rnn" (``HybridRnnSpec``) emulator: the pack pass, one fused-MLP launch per level for the
@@ -612,15 +626,9 @@ class HybridRnnModel(_PointModel):
 
     def __init__(self, spec: HybridRnnSpec, device="cuda", use_graph: Optional[bool] = None):
         super().__init__(spec, device)
-        fan, ch = int(spec.rnn.kernel.shape[0]), int(spec.rnn.kernel.shape[1])
-        self._cell = MlpModel(MlpSpec(
-            inputs=[InputSpec("in", fan), InputSpec("rec", ch)],
-            hidden_kernels=[np.concatenate([spec.rnn.kernel, spec.rnn.recurrent_kernel], axis=0).astype(np.float32)],
-            hidden_biases=[np.asarray(spec.rnn.bias, np.float32)], outputs=[], out_kernel=np.zeros((ch, 0), np.float32),
-            out_bias=np.zeros(0, np.float32), hidden_output="h"), device=self.device)
+        self._cell = MlpModel(_cell_spec(spec.rnn), device=self.device)
         self._head = MlpModel(spec.head, device=self.device)
         self._use_graph = use_graph
-        self._graphs: Dict[Tuple[int, int], tuple] = {}
         self.flops_per_column_level = self._cell.flops_per_sample
         self.flops_per_column_head = self._head.flops_per_sample
 
@@ -634,34 +642,18 @@ class HybridRnnModel(_PointModel):
     def predict(self, sources: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """``sources``: name -> device array ``[nz, ncol]`` (or ``[ncol]`` / ``[1, ncol]``); returns name -> float32
         ``[nfeat, ncol]``."""
-        from .ops import device_info
-
         spec = self.spec
         arrs, nz, ncol, dev = self._gather(sources)
-        ch = int(spec.rnn.kernel.shape[1])
-        use_graph = self._use_graph if self._use_graph is not None else ncol < 128 * int(device_info()["compute_units"])
-        if not use_graph:
-            x = self._pack(arrs, nz, ncol, dev).view(len(spec.inputs), nz, ncol)
-            states = [torch.zeros((ch, ncol), dtype=torch.float32, device=dev), torch.empty((ch, ncol), dtype=torch.float32, device=dev)]
-            final = self._sweep(x, states, nz)
-        else:
-            entry = self._graphs.get((nz, ncol))
-            if entry is None:
-                self._graphs.clear()  # one shape at a time
-                x = torch.empty((len(spec.inputs), nz, ncol), dtype=torch.float32, device=dev)
-                states = [torch.zeros((ch, ncol), dtype=torch.float32, device=dev), torch.empty((ch, ncol), dtype=torch.float32, device=dev)]
-                self._pack_into(arrs, nz, ncol, dev, x)
-                self._sweep(x, states, nz)  # eager warm-up
-                torch.cuda.synchronize(dev)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    states[0].zero_()
-                    self._sweep(x, states, nz)
-                entry = self._graphs[(nz, ncol)] = (graph, x, states)
-            graph, x, states = entry
-            self._pack_into(arrs, nz, ncol, dev, x)
-            graph.replay()
+        k, ch = len(spec.inputs), self._cell.spec.width
+        use_graph = self._use_graph if self._use_graph is not None else self._leaves_cus_idle(ncol)
+        if use_graph:
+            _, (states,) = self._graphed(
+                (nz, ncol), arrs, dev, lambda: (torch.empty((k, nz, ncol), dtype=torch.float32, device=dev), [_state_pair(ch, ncol, dev)]),
+                lambda x, pairs: self._sweep(x, pairs[0], nz))
             final = states[nz & 1]
+        else:
+            x = self._pack(arrs, nz, ncol, dev).view(k, nz, ncol)
+            final = self._sweep(x, _state_pair(ch, ncol, dev), nz)
         head_sources = {HybridRnnSpec.STATE: final}
         for r in spec.head.residuals:
             if arrs[r.source].dtype != torch.float32:  # (one source dtype per launch: the state is float32)

@@ -7,6 +7,7 @@ once (``fv3hip_mlp_create``) and runs ``fv3hip_mlp_predict`` on device arrays.
 """
 import ctypes
 import dataclasses
+import os
 from typing import Dict, List, Mapping, Optional, Tuple
 
 import numpy as np
@@ -52,6 +53,11 @@ class ResidualSpec:
     output: str
 
 
+def _unique(names) -> List[str]:
+    """``names`` in first-seen order, each once."""
+    return list(dict.fromkeys(names))
+
+
 @dataclasses.dataclass
 class MlpSpec:
     inputs: List[InputSpec]
@@ -68,11 +74,7 @@ class MlpSpec:
 
     @property
     def sources(self) -> List[str]:
-        seen: List[str] = []
-        for name in [i.source for i in self.inputs] + [r.source for r in self.residuals]:
-            if name not in seen:
-                seen.append(name)
-        return seen
+        return _unique([i.source for i in self.inputs] + [r.source for r in self.residuals])
 
     @property
     def n_in_features(self) -> int:
@@ -100,6 +102,15 @@ class MlpSpec:
         for r in self.residuals:
             need[r.source] = max(need.get(r.source, 0), outs[r.output])
         return need
+
+    def output_nfeat(self) -> Dict[str, int]:
+        """Number of features of every entry of ``output_names``."""
+        nfeat = {o.name: o.nfeat for o in self.outputs}
+        for r in self.residuals:
+            nfeat[r.name] = nfeat[r.output]
+        if self.hidden_output:
+            nfeat[self.hidden_output] = self.width
+        return nfeat
 
     def validate(self):
         k = self.n_in_features
@@ -209,32 +220,67 @@ def _iptr(a: np.ndarray):
 DEFAULT_SMALL_LIMIT: Optional[int] = None
 
 
-class MlpModel:
-    """Device handle of a fused MLP (``fv3hip_mlp_t``)."""
+def _dtype_code(dtype: torch.dtype) -> int:
+    """The library's code of an array's float type (float32 unless float64: the callers have checked)."""
+    return _lib.F64 if dtype == torch.float64 else _lib.F32
 
-    def __init__(self, spec: MlpSpec, device="cuda", small_limit: Optional[int] = None):
-        """``small_limit``: calls of at most that many samples run on the feature-split kernel for small sample counts
-        (``fv3hip_mlp_set_small_limit``); None = the library's rule (while the 128-sample tiles would leave CUs idle),
-        0 = never."""
+
+def _oriented_sources(need, sources: Mapping[str, torch.Tensor], layout: str, unit_stride_f32: bool = False):
+    """The 2-D view of every source ``need`` lists (name, least feature count) and their common sample count.  The C entry
+    points see pointers, strides and the sample count only: a short or mismatched source would be read past its end.
+    ``unit_stride_f32``: what the split-bf16 kernel reads."""
+    f_ax, s_ax = (0, 1) if layout == "feature_sample" else (1, 0)
+    tensors, n_samples = [], None
+    for name, nfeat in need:
+        t = sources[name]
+        if t.dim() == 1:
+            t = t.unsqueeze(f_ax)
+        if t.dim() != 2:
+            raise ValueError(f"source {name!r} must be 1-D or 2-D, got shape {tuple(t.shape)}")
+        nf, ns = int(t.shape[f_ax]), int(t.shape[s_ax])
+        if unit_stride_f32 and (t.dtype != torch.float32 or (ns > 1 and t.stride(s_ax) != 1)):
+            raise TypeError("the split-bf16 kernel takes float32 [feature, sample] sources with unit sample stride")
+        if nf < nfeat:
+            raise ValueError(f"source {name!r} has {nf} features, the model needs {nfeat}")
+        if n_samples is None:
+            n_samples = ns
+        elif ns != n_samples:
+            raise ValueError("sources differ in their number of samples")
+        tensors.append(t)
+    return tensors, n_samples
+
+
+class _MlpHandle:
+    """What the two device handles share: the upload of the network (``<ENTRY>_create``), its per-model constants and the
+    release (``<ENTRY>_destroy``)."""
+
+    ENTRY: str
+
+    def __init__(self, spec: MlpSpec, device="cuda"):
         spec.validate()
         self.spec = spec
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("MlpModel needs a 'cuda' (ROCm) device; there is no CPU fallback")
+            raise RuntimeError(f"{type(self).__name__} needs a 'cuda' (ROCm) device; there is no CPU fallback")
         with torch.cuda.device(self.device):
             _require_device(torch.empty(1, device=self.device))
-            self._handle = self._create(spec)
-        self.flops_per_sample = int(_lib.load().fv3hip_mlp_flops_per_sample(self._handle))
-        if small_limit is None:
-            small_limit = DEFAULT_SMALL_LIMIT
-        if small_limit is not None:
-            self.set_small_limit(small_limit)
+            self._handle = self._create(spec, self.ENTRY + "_create")
+        self.flops_per_sample = int(getattr(_lib.load(), self.ENTRY + "_flops_per_sample")(self._handle))
+        # what every predict checks its arrays against: (source, least feature count), (output, feature count)
+        need, nfeat = spec.source_nfeat(), spec.output_nfeat()
+        self._need = [(name, need[name]) for name in spec.sources]
+        self._out_nfeat = [(name, nfeat[name]) for name in spec.output_names]
 
-    def set_small_limit(self, max_samples: Optional[int]) -> None:
-        _lib.call("fv3hip_mlp_set_small_limit", self._handle, -1 if max_samples is None else int(max_samples))
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h:
+            try:
+                getattr(_lib.load(), self.ENTRY + "_destroy")(h)
+            except Exception:
+                pass
 
     @staticmethod
-    def _create(spec: MlpSpec, entry_point: str = "fv3hip_mlp_create"):
+    def _create(spec: MlpSpec, entry_point: str):
         sources = spec.sources
         keep = []  # keep numpy buffers alive during the call
 
@@ -248,30 +294,12 @@ class MlpModel:
             keep.append(a)
             return a
 
-        in_center = np.concatenate(
-            [np.zeros(i.nfeat, np.float32) if i.center is None else np.broadcast_to(_f32(i.center), (i.nfeat,))
-             for i in spec.inputs]
-        )
-        in_scale = np.concatenate(
-            [np.ones(i.nfeat, np.float32) if i.scale is None else np.broadcast_to(_f32(i.scale), (i.nfeat,))
-             for i in spec.inputs]
-        )
+        def per_feature(items, attr, default):
+            """``attr`` of every input / output, one value per feature (``default`` where it is None)."""
+            parts = [np.broadcast_to(_f32(default if getattr(x, attr) is None else getattr(x, attr)), (x.nfeat,)) for x in items]
+            return arr_f(np.concatenate(parts) if parts else np.zeros(0, np.float32))
+
         transforms = {"none": _lib.TRANSFORM_NONE, "log": _lib.TRANSFORM_LOG}
-        F = spec.n_out_features
-
-        def per_feature(attr, default):
-            parts = []
-            for o in spec.outputs:
-                v = getattr(o, attr)
-                parts.append(
-                    np.full(o.nfeat, default, np.float32) if v is None
-                    else np.broadcast_to(_f32(v), (o.nfeat,))
-                )
-            return np.concatenate(parts) if parts else np.zeros(0, np.float32)
-
-        any_min = any(o.min is not None for o in spec.outputs)
-        any_max = any(o.max is not None for o in spec.outputs)
-        any_mask = any(o.mask is not None for o in spec.outputs)
         hk = [arr_f(k) for k in spec.hidden_kernels]
         hb = [arr_f(b) for b in spec.hidden_biases]
         PF = ctypes.POINTER(ctypes.c_float)
@@ -287,8 +315,8 @@ class MlpModel:
         desc.in_nfeat = _iptr(arr_i([i.nfeat for i in spec.inputs]))
         desc.in_transform = _iptr(arr_i([transforms[i.transform] for i in spec.inputs]))
         desc.in_eps = _fptr(arr_f([i.eps for i in spec.inputs]))
-        desc.in_center = _fptr(arr_f(in_center))
-        desc.in_scale = _fptr(arr_f(in_scale))
+        desc.in_center = _fptr(per_feature(spec.inputs, "center", 0.0))
+        desc.in_scale = _fptr(per_feature(spec.inputs, "scale", 1.0))
         desc.n_hidden = len(hk)
         desc.width = spec.width
         desc.hidden_activation = {"relu": _lib.ACT_RELU, "linear": _lib.ACT_LINEAR}[spec.activation]
@@ -298,25 +326,38 @@ class MlpModel:
         desc.out_nfeat = _iptr(arr_i([o.nfeat for o in spec.outputs]))
         desc.out_kernel = _fptr(arr_f(spec.out_kernel))
         desc.out_bias = _fptr(arr_f(spec.out_bias))
-        desc.out_scale = _fptr(arr_f(per_feature("scale", 1.0)))
-        desc.out_center = _fptr(arr_f(per_feature("center", 0.0)))
-        if any_min:
-            desc.out_min = _fptr(arr_f(np.concatenate(
-                [np.full(o.nfeat, -np.inf if o.min is None else o.min, np.float32) for o in spec.outputs])))
-        if any_max:
-            desc.out_max = _fptr(arr_f(np.concatenate(
-                [np.full(o.nfeat, np.inf if o.max is None else o.max, np.float32) for o in spec.outputs])))
-        if any_mask:
-            desc.out_mask = _fptr(arr_f(per_feature("mask", 1.0)))
+        desc.out_scale = _fptr(per_feature(spec.outputs, "scale", 1.0))
+        desc.out_center = _fptr(per_feature(spec.outputs, "center", 0.0))
+        for attr, default in (("min", -np.inf), ("max", np.inf), ("mask", 1.0)):  # (a table only where an output has one)
+            if any(getattr(o, attr) is not None for o in spec.outputs):
+                setattr(desc, "out_" + attr, _fptr(per_feature(spec.outputs, attr, default)))
         desc.hidden_output = 1 if spec.hidden_output else 0
         desc.n_residual = len(spec.residuals)
         if spec.residuals:
             desc.res_source = _iptr(arr_i([sources.index(r.source) for r in spec.residuals]))
             desc.res_output = _iptr(arr_i([out_names.index(r.output) for r in spec.residuals]))
-        assert F == sum(o.nfeat for o in spec.outputs)
         handle = ctypes.c_void_p()
         _lib.call(entry_point, ctypes.byref(desc), ctypes.byref(handle))
         return handle
+
+
+class MlpModel(_MlpHandle):
+    """Device handle of a fused MLP (``fv3hip_mlp_t``)."""
+
+    ENTRY = "fv3hip_mlp"
+
+    def __init__(self, spec: MlpSpec, device="cuda", small_limit: Optional[int] = None):
+        """``small_limit``: calls of at most that many samples run on the feature-split kernel for small sample counts
+        (``fv3hip_mlp_set_small_limit``); None = the library's rule (while the 128-sample tiles would leave CUs idle),
+        0 = never."""
+        super().__init__(spec, device)
+        if small_limit is None:
+            small_limit = DEFAULT_SMALL_LIMIT
+        if small_limit is not None:
+            self.set_small_limit(small_limit)
+
+    def set_small_limit(self, max_samples: Optional[int]) -> None:
+        _lib.call("fv3hip_mlp_set_small_limit", self._handle, -1 if max_samples is None else int(max_samples))
 
     def predict(
         self,
@@ -334,43 +375,20 @@ class MlpModel:
         Arbitrary strides are honoured, nothing is copied.  ``out``: preallocated output arrays (all of
         ``spec.output_names``, float32 or float64 alike) to write into instead of allocating.
         """
-        spec = self.spec
-        names = spec.sources
-        need = spec.source_nfeat()
-        tensors = []
-        n_samples = None
-        for name in names:
-            t = sources[name]
-            if t.dim() == 1:
-                t = t.unsqueeze(0) if layout == "feature_sample" else t.unsqueeze(1)
-            if t.dim() != 2:
-                raise ValueError(f"source {name!r} must be 1-D or 2-D, got shape {tuple(t.shape)}")
-            nf, ns = (t.shape[0], t.shape[1]) if layout == "feature_sample" else (t.shape[1], t.shape[0])
-            if nf < need[name]:
-                raise ValueError(f"source {name!r} has {nf} features, the model needs {need[name]}")
-            if n_samples is None:
-                n_samples = int(ns)
-            elif int(ns) != n_samples:
-                raise ValueError("sources differ in their number of samples")
-            tensors.append(t)
+        tensors, n_samples = _oriented_sources(self._need, sources, layout)
         dev = _require_device(*tensors)
         dtypes = {t.dtype for t in tensors}
         if dtypes - {torch.float32, torch.float64}:
             raise TypeError(f"sources must be float32 or float64, got {dtypes}")
         if len(dtypes) > 1:  # the kernel wants one source dtype per call
             tensors = [t.to(torch.float64) for t in tensors]
-        src_code = _lib.F64 if tensors[0].dtype == torch.float64 else _lib.F32
+        src_code = _dtype_code(tensors[0].dtype)
         fs_ax, ss_ax = (0, 1) if layout == "feature_sample" else (1, 0)
 
         outs: Dict[str, torch.Tensor] = {}
-        nfeat = {o.name: o.nfeat for o in spec.outputs}
-        for r in spec.residuals:
-            nfeat[r.name] = nfeat[r.output]
-        if spec.hidden_output:
-            nfeat[spec.hidden_output] = spec.width
         out_list = []
-        for name in spec.output_names:
-            shape = (nfeat[name], n_samples) if layout == "feature_sample" else (n_samples, nfeat[name])
+        for name, nfeat in self._out_nfeat:
+            shape = (nfeat, n_samples) if layout == "feature_sample" else (n_samples, nfeat)
             if out is not None:
                 t = out[name]
                 if tuple(t.shape) != shape or t.device != dev:
@@ -393,7 +411,7 @@ class MlpModel:
         out_ss = (ctypes.c_int64 * n_out)(*[t.stride(ss_ax) for t in out_list])
         _lib.call_on(dev,
             "fv3hip_mlp_predict", self._handle, src_ptrs, src_dt, src_fs, src_ss, n_samples, out_ptrs,
-            _lib.F64 if out_dtype == torch.float64 else _lib.F32, out_fs, out_ss, _stream(dev),
+            _dtype_code(out_dtype), out_fs, out_ss, _stream(dev),
         )
         return outs
 
@@ -402,82 +420,46 @@ class MlpModel:
         """Kernel instantiation and epilogue flavour of the last ``predict`` (``fv3hip_mlp_last_variant``)."""
         return _lib.load().fv3hip_mlp_last_variant(self._handle).decode()
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h:
-            try:
-                _lib.load().fv3hip_mlp_destroy(h)
-            except Exception:
-                pass
 
-
-class MlpModelSplitBf16:
+class MlpModelSplitBf16(_MlpHandle):
     """EXPERIMENTAL: the same network through ``fv3hip_mlp3_*`` -- the contraction on the bf16 matrix cores with every fp32
     operand split into three bf16 pieces (csrc/mlp_bf16x3.hip).  float32 ``[feature, sample]`` sources
     with unit sample stride only; ``MlpModel`` (fp32 MFMA) is the product path."""
 
-    def __init__(self, spec: MlpSpec, device="cuda"):
-        spec.validate()
-        self.spec = spec
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("MlpModelSplitBf16 needs a 'cuda' (ROCm) device; there is no CPU fallback")
-        with torch.cuda.device(self.device):
-            _require_device(torch.empty(1, device=self.device))
-            self._handle = MlpModel._create(spec, "fv3hip_mlp3_create")
-        self.flops_per_sample = int(_lib.load().fv3hip_mlp3_flops_per_sample(self._handle))
-        self.last_variant = "mlp3_kernel"
+    ENTRY = "fv3hip_mlp3"
+    last_variant = "mlp3_kernel"
 
     def predict(self, sources: Mapping[str, torch.Tensor], out: Optional[Mapping[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """``sources``: name -> float32 ``[feature, sample]`` device array with unit sample stride.  ``out``: preallocated
         float32 ``[feature, sample]`` arrays (unit sample stride) for any of the outputs -- the hidden output included, as
         ``MlpModel.predict`` takes them; the others are allocated."""
-        spec = self.spec
-        need = spec.source_nfeat()
-        tensors = []
-        n = None
-        # the C entry point sees pointers, strides and n only: a short or mismatched source would be read past its end
-        for name in spec.sources:
-            t = sources[name]
-            t = t.unsqueeze(0) if t.dim() == 1 else t
-            if t.dim() != 2:
-                raise ValueError(f"source {name!r} must be 1-D or 2-D, got shape {tuple(t.shape)}")
-            if t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
-                raise TypeError("the split-bf16 kernel takes float32 [feature, sample] sources with unit sample stride")
-            if int(t.shape[0]) < need[name]:
-                raise ValueError(f"source {name!r} has {int(t.shape[0])} features, the model needs {need[name]}")
-            if n is None:
-                n = int(t.shape[1])
-            elif int(t.shape[1]) != n:
-                raise ValueError("sources differ in their number of samples")
-            tensors.append(t)
+        tensors, n = _oriented_sources(self._need, sources, "feature_sample", unit_stride_f32=True)
         dev = _require_device(*tensors)
-        nfeat = {o.name: o.nfeat for o in spec.outputs}
-        for r in spec.residuals:
-            nfeat[r.name] = nfeat[r.output]
-        if spec.hidden_output:
-            nfeat[spec.hidden_output] = spec.width
         outs = {}
-        for name in spec.output_names:
+        for name, nfeat in self._out_nfeat:
             given = None if out is None else out.get(name)
             if given is None:
-                outs[name] = torch.empty((nfeat[name], n), dtype=torch.float32, device=dev)
+                outs[name] = torch.empty((nfeat, n), dtype=torch.float32, device=dev)
                 continue
             g2 = given.unsqueeze(0) if given.dim() == 1 else given
-            if g2.dtype != torch.float32 or tuple(g2.shape) != (nfeat[name], n) or g2.stride(1) != 1 or g2.device != dev:
-                raise TypeError(f"out[{name!r}] must be a float32 [{nfeat[name]}, {n}] array with unit sample stride on {dev}")
+            if g2.dtype != torch.float32 or tuple(g2.shape) != (nfeat, n) or g2.stride(1) != 1 or g2.device != dev:
+                raise TypeError(f"out[{name!r}] must be a float32 [{nfeat}, {n}] array with unit sample stride on {dev}")
             outs[name] = g2
-        ol = [outs[name] for name in spec.output_names]
+        ol = [outs[name] for name, _ in self._out_nfeat]
         ns, no = len(tensors), len(ol)
         _lib.call_on(dev, "fv3hip_mlp3_predict", self._handle, (ctypes.c_void_p * ns)(*[t.data_ptr() for t in tensors]),
                      (ctypes.c_int64 * ns)(*[t.stride(0) for t in tensors]), n, (ctypes.c_void_p * no)(*[t.data_ptr() for t in ol]),
                      (ctypes.c_int64 * no)(*[t.stride(0) for t in ol]), _stream(dev))
         return outs
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h:
-            try:
-                _lib.load().fv3hip_mlp3_destroy(h)
-            except Exception:
-                pass
+
+ARITHMETIC_ENV = "FV3NET_AMD_EMULATOR_ARITHMETIC"
+
+
+def resolve_arithmetic(arithmetic: Optional[str]):
+    """(arithmetic, handle class) for an emulator's ``arithmetic=``: "fp32" -- ``MlpModel``, the product kernel -- or the
+    opt-in "split-bf16" (``MlpModelSplitBf16``); None: the environment variable ``ARITHMETIC_ENV``, else "fp32"."""
+    arithmetic = arithmetic or os.environ.get(ARITHMETIC_ENV, "fp32")
+    if arithmetic not in ("fp32", "split-bf16"):
+        raise ValueError(f"arithmetic must be 'fp32' or 'split-bf16', got {arithmetic!r}")
+    return arithmetic, (MlpModelSplitBf16 if arithmetic == "split-bf16" else MlpModel)

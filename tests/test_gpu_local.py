@@ -255,6 +255,53 @@ def test_rnn_emulator_matches_oracle(nz, ncol, dtype, channels, tmp_path):
         np.testing.assert_array_equal(out[name].T, got[name].cpu().numpy())
 
 
+def test_rnn_sequential_sweep_at_column_counts_that_fill_the_chip():
+    """From 128 columns per CU on, the layers of a multi-layer RNN run one after the other on one stream (the sweep is not
+    pipelined): eager launches and the graph replay give the same bits, and both match the oracle."""
+    from fv3net_amd.local_mlp import RnnModel
+    from fv3net_amd.ops import device_info
+
+    nz, ncol = 2, 128 * int(device_info()["compute_units"])
+    rng = np.random.default_rng(nz + ncol)
+    st = cases.state(rng, nz, ncol, np.float32)
+    spec = cases.precpd_rnn(rng, st, nz, channels=32, depth=2, make=cases.product_makers())
+    dev = _dev(st)
+    eager = RnnModel(spec, device="cuda", use_graph=False).predict(dev)
+    graphed = RnnModel(spec, device="cuda", use_graph=True).predict(dev)
+    src = {k: v.T for k, v in st.items()}
+    truth = mlp_np.forward_rnn(spec, src, dtype=np.float64)
+    f32 = mlp_np.forward_rnn(spec, src, dtype=np.float32)
+    assert list(eager) == list(graphed) == spec.output_names
+    for name in spec.output_names:
+        assert torch.equal(eager[name], graphed[name]), name
+        _check(eager[name].cpu().numpy(), truth[name].T, name, f32=f32[name].T, compounding=True)
+
+
+@pytest.mark.parametrize("kind", ["rnn", "hybrid"])
+def test_graph_cache_holds_one_shape_at_a_time(kind):
+    """A graphed model called with one shape, another, and the first again (fresh data each time): every result has the
+    bits of an eager model's, and the model keeps the graph and static buffers of the last shape only."""
+    from fv3net_amd.local_mlp import HybridRnnModel, RnnModel
+
+    nz = 3
+    rng = np.random.default_rng(41)
+    st = cases.state(rng, nz, 64)
+    if kind == "rnn":
+        spec = cases.precpd_rnn(rng, st, nz, channels=32, depth=2, make=cases.product_makers())
+        graphed, eager = RnnModel(spec, device="cuda", use_graph=True), RnnModel(spec, device="cuda", use_graph=False)
+    else:
+        spec = cases.hybrid_rnn(rng, st, nz, channels=32, dense_width=32, make=cases.product_makers())
+        graphed, eager = HybridRnnModel(spec, device="cuda", use_graph=True), HybridRnnModel(spec, device="cuda", use_graph=False)
+    for call, ncol in enumerate((64, 97, 64)):
+        data = _dev(cases.state(np.random.default_rng(100 + call), nz, ncol))
+        a, b = graphed.predict(data), eager.predict(data)
+        assert list(a) == spec.output_names
+        for name in spec.output_names:
+            assert torch.equal(a[name], b[name]), (ncol, name)
+        assert list(graphed._graphs) == [(nz, ncol)]
+    assert not eager._graphs
+
+
 def test_production_style_fv3config_both_hooks(tmp_path):
     """projects/microphysics/configs/gscond-and-precpd.yaml:268-287 in miniature, through ``get_hooks``: the gscond
     hook (dense-local regressor + classifier, conservation fixes, classifier masks, level masks filled from the
