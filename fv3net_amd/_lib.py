@@ -227,6 +227,8 @@ SIGNATURES = {
     "fv3hip_minmax_score": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
                                     c_void_p, c_void_p, c_void_p]),
     "fv3hip_ocsvm_score": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p]),
+    "fv3hip_precip_closure": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int64, c_int,
+                                      c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fv3hip_local_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "fv3hip_local_unpack": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                     c_double, c_void_p, c_int, c_int, c_double, c_double, c_double, c_double, c_int, c_int64,

@@ -10,6 +10,8 @@
 //   external/vcm/vcm/calc/flux_form.py:7-104 (+ thermo/vertically_dependent.py:18-38)
 //       the flux-form output transforms of TransformedPredictor (vcm/data_transform.py:140-300): tendencies <-> net
 //       fluxes at the cell interfaces, the surface flux that closes the column budget
+//   external/fv3fit/fv3fit/keras/_models/precipitative.py:35-66,239-253
+//       the column water budget of the precipitative model (TensorFlow layers in the reference's Keras graph)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -184,6 +186,57 @@ __global__ __launch_bounds__(kSvmSamples) void ocsvm_score_kernel(const double *
     if (i < n) score[i] = -1.0 * total;
 }
 
+// The budget closure of the precipitative model (fv3fit/keras/_models/precipitative.py:239-253, layers :35-66): one lane
+// per column of the [nz][n] heads, so that consecutive lanes read consecutive words of every row.  float32 throughout, as
+// in the Keras graph: every product is rounded (the library is built with -ffp-contract=off), and the integral is one
+// float32 accumulator from +0 over ascending levels.  The levels go in groups of kClosureLevels, loads before stores: dq1 /
+// dq2 may be t_res / q_res, so the compiler cannot move a load over a store by itself, and one level per round trip to
+// HBM would leave the lane waiting 79 times.
+constexpr int kClosureLevels = 8;
+
+template <typename Td, typename Tp>
+__global__ void precip_closure_kernel(const float *t_res, const float *q_res, const float *__restrict__ cp,
+                                      const Td *__restrict__ delp, int64_t delp_fs, int64_t delp_ss, const Tp *__restrict__ pp,
+                                      int64_t pp_stride, int nz, int64_t n, int couple, float *dq1, float *dq2,
+                                      float *__restrict__ precip)
+{
+    const float c_heat = (float)(-2.5e6 / 1004.6);  // -LV / CPD (precipitative.py:21-23,66)
+    const float c_g = (float)(-1.0 / kGravity);     // (:51)
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const Td *d = delp + i * delp_ss;
+        float acc = 0.0f;
+        for (int k0 = 0; k0 < nz; k0 += kClosureLevels) {
+            float c[kClosureLevels], w[kClosureLevels], t[kClosureLevels], q[kClosureLevels];
+#pragma unroll
+            for (int j = 0; j < kClosureLevels; ++j) {
+                const int k = k0 + j;
+                if (k < nz) {
+                    const int64_t at = (int64_t)k * n + i;
+                    c[j] = cp[at];
+                    w[j] = (float)d[k * delp_fs];
+                    if (couple) {
+                        t[j] = t_res[at];
+                        q[j] = q_res[at];
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < kClosureLevels; ++j) {
+                const int k = k0 + j;
+                if (k < nz) {
+                    const int64_t at = (int64_t)k * n + i;
+                    acc = acc + c[j] * w[j];
+                    if (couple) {
+                        dq1[at] = t[j] + c_heat * c[j];
+                        dq2[at] = q[j] + c[j];
+                    }
+                }
+            }
+        }
+        precip[i] = (float)pp[i * pp_stride] + c_g * acc;
+    }
+}
+
 }  // namespace
 }  // namespace fv3hip
 
@@ -293,4 +346,28 @@ extern "C" int fv3hip_ocsvm_score(const double *x, int n_feat, int64_t n, const 
     hipLaunchKernelGGL(ocsvm_score_kernel, dim3((unsigned)ceil_div(n, (int64_t)kSvmSamples)), dim3(kSvmSamples), lds, as_stream(stream), x,
                        n_feat, n, mean, scale, support_vectors, dual_coef, n_sv, gamma, score);
     return check_launch("ocsvm_score_kernel");
+}
+
+extern "C" int fv3hip_precip_closure(const float *t_res, const float *q_res, const float *col_precip, const void *delp,
+                                     int delp_dtype, int64_t delp_feat_stride, int64_t delp_sample_stride,
+                                     const void *physics_precip, int pp_dtype, int64_t pp_stride, int nz, int64_t n, int couple,
+                                     float *dq1, float *dq2, float *precip, void *stream)
+{
+    FV3HIP_REQUIRE(is_float(delp_dtype) && is_float(pp_dtype), "delp_dtype and pp_dtype must be F32 or F64");
+    FV3HIP_REQUIRE(nz >= 0 && n >= 0, "negative extent");
+    FV3HIP_REQUIRE(delp_feat_stride >= 0 && delp_sample_stride >= 0 && pp_stride >= 0, "negative stride");
+    if (n == 0) return FV3HIP_OK;
+    FV3HIP_REQUIRE(physics_precip && precip, "null pointer (physics_precip, precip)");
+    if (nz > 0) {  // (no levels: an empty sum, and no [nz][n] array is read or written)
+        FV3HIP_REQUIRE(col_precip && delp, "null pointer (col_precip, delp)");
+        FV3HIP_REQUIRE(!couple || (t_res && q_res && dq1 && dq2), "null pointer (t_res, q_res, dq1, dq2 with couple)");
+    }
+    with_float_pair(delp_dtype, pp_dtype, [&](auto d, auto p) {
+        using Td = decltype(d);
+        using Tp = decltype(p);
+        hipLaunchKernelGGL((precip_closure_kernel<Td, Tp>), dim3(grid_stride_blocks(n)), dim3(256), 0, as_stream(stream), t_res, q_res,
+                           col_precip, as<Td>(delp), delp_feat_stride, delp_sample_stride, as<Tp>(physics_precip), pp_stride, nz, n,
+                           couple, dq1, dq2, precip);
+    });
+    return check_launch("precip_closure_kernel");
 }

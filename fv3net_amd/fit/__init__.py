@@ -1,5 +1,6 @@
 """``fv3fit``-shaped model API for the column MLP: Predictor ABC, the name-file io registry,
-the dataset <-> array adapter, and the HIP dense predictor (registered as ``"hip-dense"``)."""
+the dataset <-> array adapter, and the HIP dense predictor (registered as ``"hip-dense"``; its sibling with the
+column water budget closed is ``"hip-precipitative"``)."""
 from . import io
 from .io import dump, load
 from .predictor import Predictor
@@ -15,6 +16,8 @@ from .novelty import (MinMaxNoveltyDetector, NoveltyDetector, OCSVMNoveltyDetect
 from .transformed import OutOfSampleModel, TransformedPredictor
 from .forest import RandomForest
 from .conv import HipConvolutionalModel, conv_spec_from_arrays
+from .precipitative import (HipPrecipitativeModel, PrecipitativeHyperparameters, precipitative_spec_from_arrays,
+                            train_precipitative_model)
 from .reservoir import (HybridReservoirComputingModel, HybridReservoirDatasetAdapter, ReservoirComputingModel,
                         ReservoirDatasetAdapter, split_multi_subdomain_model)
 
@@ -25,4 +28,5 @@ __all__ = [
     "CombinedOutputModel", "ConstantOutputPredictor", "DenseHyperparameters", "DerivedMapping", "DerivedModel", "EnsembleModel", "SquashedOutputConfig",
     "SquashedOutputModel", "TaperConfig", "TaperedModel", "vertical_tapering_scale_factors", "HipDenseModel", "Predictor", "SAMPLE_DIM_NAME", "dump", "io",
     "load", "match_prediction_to_input_coords", "spec_from_arrays", "stack", "train_dense_model",
+    "HipPrecipitativeModel", "PrecipitativeHyperparameters", "precipitative_spec_from_arrays", "train_precipitative_model",
 ]

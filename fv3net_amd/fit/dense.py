@@ -27,13 +27,40 @@ from .predictor import Predictor
 from .stacking import column_sources, match_prediction_to_input_coords
 
 
+CONFIG_FILENAME = "config.yaml"
+SPEC_FILENAME = "spec.yaml"
+WEIGHTS_FILENAME = "weights.npz"
+
+
+def write_artifact(path: str, spec: MlpSpec, config: Mapping) -> None:
+    """The files a column predictor's directory holds beside ``name``: ``config.yaml``, ``spec.yaml``, ``weights.npz``."""
+    os.makedirs(path, exist_ok=True)
+    meta, arrays = spec.to_arrays()
+    np.savez(os.path.join(path, WEIGHTS_FILENAME), **arrays)
+    with open(os.path.join(path, SPEC_FILENAME), "w") as f:
+        yaml.safe_dump(meta, f)
+    with open(os.path.join(path, CONFIG_FILENAME), "w") as f:
+        yaml.safe_dump(dict(config), f)
+
+
+def read_artifact(path: str):
+    """(config, spec) of a directory written by ``write_artifact``."""
+    with open(os.path.join(path, CONFIG_FILENAME)) as f:
+        config = yaml.safe_load(f)
+    with open(os.path.join(path, SPEC_FILENAME)) as f:
+        meta = yaml.safe_load(f)
+    with np.load(os.path.join(path, WEIGHTS_FILENAME), allow_pickle=False) as z:
+        arrays = {k: z[k] for k in z.files}
+    return config, MlpSpec.from_arrays(meta, arrays)
+
+
 @io.register("hip-dense")
 class HipDenseModel(Predictor):
     """Column MLP predictor running on the MI355X fused kernel."""
 
-    _CONFIG_FILENAME = "config.yaml"
-    _SPEC_FILENAME = "spec.yaml"
-    _WEIGHTS_FILENAME = "weights.npz"
+    _CONFIG_FILENAME = CONFIG_FILENAME
+    _SPEC_FILENAME = SPEC_FILENAME
+    _WEIGHTS_FILENAME = WEIGHTS_FILENAME
 
     def __init__(self, input_variables: Iterable[Hashable], output_variables: Iterable[Hashable], model: MlpSpec,
                  unstacked_dims: Sequence[str] = ("z",), n_halo: int = 0):
@@ -82,25 +109,13 @@ class HipDenseModel(Predictor):
 
     # -- serialisation ----------------------------------------------------------------------
     def dump(self, path: str) -> None:
-        os.makedirs(path, exist_ok=True)
-        meta, arrays = self.spec.to_arrays()
-        np.savez(os.path.join(path, self._WEIGHTS_FILENAME), **arrays)
-        with open(os.path.join(path, self._SPEC_FILENAME), "w") as f:
-            yaml.safe_dump(meta, f)
-        with open(os.path.join(path, self._CONFIG_FILENAME), "w") as f:
-            yaml.safe_dump(
-                {"input_variables": list(self.input_variables), "output_variables": list(self.output_variables),
-                 "unstacked_dims": list(self._unstacked_dims), "n_halo": self._n_halo}, f)
+        write_artifact(path, self.spec, {"input_variables": list(self.input_variables), "output_variables": list(self.output_variables),
+                                         "unstacked_dims": list(self._unstacked_dims), "n_halo": self._n_halo})
 
     @classmethod
     def load(cls, path: str) -> "HipDenseModel":
-        with open(os.path.join(path, cls._CONFIG_FILENAME)) as f:
-            config = yaml.safe_load(f)
-        with open(os.path.join(path, cls._SPEC_FILENAME)) as f:
-            meta = yaml.safe_load(f)
-        with np.load(os.path.join(path, cls._WEIGHTS_FILENAME), allow_pickle=False) as z:
-            arrays = {k: z[k] for k in z.files}
-        return cls(config["input_variables"], config["output_variables"], MlpSpec.from_arrays(meta, arrays),
+        config, spec = read_artifact(path)
+        return cls(config["input_variables"], config["output_variables"], spec,
                    unstacked_dims=config.get("unstacked_dims", None), n_halo=config.get("n_halo", 0))
 
 

@@ -456,6 +456,35 @@ def ocsvm_score(x: torch.Tensor, mean: torch.Tensor, scale: torch.Tensor, suppor
     return out
 
 
+def precip_closure(t_res: Optional[torch.Tensor], q_res: Optional[torch.Tensor], col_precip: torch.Tensor, delp: torch.Tensor,
+                   physics_precip: torch.Tensor, couple: bool = True, in_place: bool = False):
+    """The column water budget of fv3fit's precipitative model (keras/_models/precipitative.py:239-253) on the network's
+    three denormalised heads, contiguous float32 ``[nz, n]``: returns ``(dQ1, dQ2, total_precipitation_rate [n])``.
+    ``delp`` ``[nz, n]`` and ``physics_precip`` ``[n]`` (or ``[1, n]``) are read as they lie, float32 or float64, any strides.
+    ``couple``: ``dQ1 = t_res + c_heat * col_precip``, ``dQ2 = q_res + col_precip`` -- written over ``t_res`` / ``q_res``
+    when ``in_place``; without it the residual heads are returned as they are (and may be None)."""
+    nz, n = int(col_precip.shape[0]), int(col_precip.shape[1])
+    heads = [col_precip] + ([t_res, q_res] if couple else [])
+    dev = _require_device(*heads, delp, physics_precip)
+    for t in heads:
+        if t.dtype != torch.float32 or tuple(t.shape) != (nz, n) or not t.is_contiguous():
+            raise ValueError(f"the heads must be contiguous float32 [{nz}, {n}] arrays")
+    if tuple(delp.shape) != (nz, n):
+        raise ValueError(f"delp has shape {tuple(delp.shape)}, the heads have {(nz, n)}")
+    pp = physics_precip.reshape(-1) if physics_precip.dim() != 1 and physics_precip.shape[0] == 1 else physics_precip
+    if tuple(pp.shape) != (n,):
+        raise ValueError(f"physics_precip has shape {tuple(physics_precip.shape)}, expected ({n},)")
+    dq1, dq2 = t_res, q_res
+    if couple and not in_place:
+        dq1, dq2 = torch.empty_like(t_res), torch.empty_like(q_res)
+    precip = torch.empty(n, dtype=torch.float32, device=dev)
+    on = lambda t: _ptr(t if couple else None)
+    _lib.call_on(dev, "fv3hip_precip_closure", on(t_res), on(q_res), _ptr(col_precip), _ptr(delp), _float_code(delp),
+                 int(delp.stride(0)), int(delp.stride(1)), _ptr(pp), _float_code(pp), int(pp.stride(0)), nz, n, int(bool(couple)),
+                 on(dq1), on(dq2), _ptr(precip), _stream(dev))
+    return dq1, dq2, precip
+
+
 def member_reduce(members: Sequence[torch.Tensor], op: str) -> torch.Tensor:
     """NaN-skipping ``mean`` / ``median`` over same-shaped member arrays (EnsembleModel.predict, models.py:253-260)."""
     dev = _require_device(*members)

@@ -791,6 +791,29 @@ int fv3hip_ocsvm_score(const double *x, int n_feat, int64_t n, const double *mea
                        void *stream);
 
 /*
+ * The column water budget that closes fv3fit's "precipitative" model (external/fv3fit/fv3fit/keras/_models/
+ * precipitative.py:239-253 with the layers of :35-66), on the three denormalised heads right after the network:
+ *   fv3hip_precip_closure  t_res, q_res, col_precip [nz][n] float32 contiguous (what fv3hip_mlp_predict leaves in the
+ *                          feature_sample layout); delp level k of sample i at delp[k * delp_feat_stride + i *
+ *                          delp_sample_stride] (`delp_dtype`; the RAW thickness over all nz levels, :246, not the clipped
+ *                          network input), physics_precip sample i at physics_precip[i * pp_stride] (`pp_dtype`).  Strides
+ *                          count elements and are >= 0.  All arithmetic is float32 (Keras casts float64 inputs first), with
+ *                          c_heat = (float)(-2.5e6 / 1004.6) and c_g = (float)(-1.0 / 9.80665):
+ *                              precip[i] = (float)physics_precip[i] + c_g * sum_k(col_precip[k][i] * (float)delp[k][i])
+ *                              couple != 0:  dq1 = t_res + c_heat * col_precip,  dq2 = q_res + col_precip   ([nz][n])
+ *                          Every product is rounded before it is added; the sum runs in a float32 accumulator from +0.0f
+ *                          over ascending k (TensorFlow leaves reduce_sum's order open; this fixes it, so that a numpy
+ *                          float32 loop over the levels is bit-identical).  dq1 may be t_res and dq2 may be q_res (each
+ *                          element is read before it is written); no other two arrays may overlap.  couple == 0 writes
+ *                          precip only: t_res, q_res, dq1, dq2 are not read and may be null.  nz == 0: the sum is empty,
+ *                          the [nz][n] arrays may be null.
+ */
+int fv3hip_precip_closure(const float *t_res, const float *q_res, const float *col_precip, const void *delp, int delp_dtype,
+                          int64_t delp_feat_stride, int64_t delp_sample_stride, const void *physics_precip, int pp_dtype,
+                          int64_t pp_stride, int nz, int64_t n, int couple, float *dq1, float *dq2, float *precip,
+                          void *stream);
+
+/*
  * Replaces mappm.interpolate_2d (external/mappm/mappm/interpolate_2d.f90:1-28; called from
  * external/vcm/vcm/interpolate.py:165-169): per column, linear interpolation of y(x) (n_in points,
  * x increasing) onto xp (n_out points); outside the column's range the result is fill_value.
