@@ -282,6 +282,7 @@ SIGNATURES = {
     "fv3hip_mlp3_destroy": (c_int, [c_void_p]),
     "fv3hip_mlp3_flops_per_sample": (c_int64, [c_void_p]),
     "fv3hip_mlp3_predict": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), c_int64, POINTER(c_void_p), POINTER(c_int64), c_void_p]),
+    "fv3hip_mlp3_last_variant": (c_char_p, [c_void_p]),
     "fv3hip_forest_create": (c_int, [POINTER(ForestDesc), POINTER(c_void_p)]),
     "fv3hip_forest_destroy": (c_int, [c_void_p]),
     "fv3hip_forest_predict": (

@@ -6,6 +6,11 @@
 // the single-layer measurement that motivated this (same accuracy as fp32 arithmetic, above the fp32 matrix peak).
 // The fp32 kernel stays the product path and the headline; this one is reached only through fv3hip_mlp3_* and is
 // validated against the same float64 oracle (tests/test_gpu_mlp.py::test_split_bf16_kernel_against_oracle).
+// Tests: tests/test_gpu_mlp3_edges.py runs all 16 instantiations of kMlp3Table and the run-time paths inside them at their
+// edges (cases and the dispatch restated: tests/mlp3_cases.py; the coverage proof and the proof that the tracer bound of the
+// arithmetic test notices a dropped cross product, without a GPU: tests/test_host_mlp3_edges.py).  Every call there asserts
+// fv3hip_mlp3_last_variant, the string fv3hip_mlp3_predict writes from the table row it launches: a change to the
+// dispatch below that moves a case to another instantiation fails there -- restate it in tests/mlp3_cases.py.
 //
 // Same graph as mlp.hip (reference lines there): log / centre inputs (1/std folded into the layer-1 weights), Dense + ReLU
 // stack, output heads with scale / centre folded in, optional residual outputs `after = before + difference`, optionally the
@@ -678,7 +683,10 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(const Mlp3Launch p)
             B3 bn;
             if constexpr (KS + 1 < 16) x_of(h, std::integral_constant<int, (KS + 1 < 16 ? KS + 1 : 0)>{}, xn);
             kstep_mfma<OT, KS == 0, (KS + 1 < 16), (KS < 14)>(y, a_lane + b0, b, xn, bn, dsc);
-            if (KS == 0 && FAST && p.hout)   // (the 32 stores of the hidden output sit between the last chunk request and this one)
+            // (the 32 stores of the hidden output sit between the last chunk request and this one -- in a wave that has samples:
+            // a wave whose quads all lie past the batch branches around them (s_cbranch_execz) and has issued none, and a
+            // count that includes them would not wait for its share of the chunk at all)
+            if (KS == 0 && FAST && p.hout && tile * 128 + wave * 32 < p.n_samples)
                 fence(std::integral_constant<int, (PRE ? 4 : 0) + (KS == 0 ? 32 : 0)>{}, ah);
             else
                 fence(std::integral_constant<int, PRE ? (FAST ? 4 : 16) : 0>{}, ah);
@@ -799,6 +807,7 @@ struct fv3hip_mlp3 {
     size_t sink_bytes = 0;
     // per layer-1 k-step: the source it reads, its first feature row there and how many real rows follow (<= 16)
     std::vector<int> ks_src, ks_feat0, ks_rows, res_source;
+    char last_variant[192] = {0};  // what the last fv3hip_mlp3_predict launched (fv3hip_mlp3_last_variant)
 };
 
 namespace {
@@ -852,6 +861,8 @@ extern "C" int fv3hip_mlp3_destroy(fv3hip_mlp3_t m)
 }
 
 extern "C" int64_t fv3hip_mlp3_flops_per_sample(fv3hip_mlp3_t m) { return m ? m->flops : 0; }
+
+extern "C" const char *fv3hip_mlp3_last_variant(fv3hip_mlp3_t m) { return m ? m->last_variant : ""; }
 
 extern "C" int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *d, fv3hip_mlp3_t *out)
 {
@@ -1087,5 +1098,13 @@ extern "C" int fv3hip_mlp3_predict(fv3hip_mlp3_t m, const void *const *sources, 
         fast = reinterpret_cast<uintptr_t>(sources[m->res_source[r]]) % 16 == 0 && src_feat_stride[m->res_source[r]] % 4 == 0;
     if (fast && lp.hout) fast = reinterpret_cast<uintptr_t>(lp.hout) % 16 == 0 && lp.hout_fs % 4 == 0;
     const size_t lds = fast ? m->lds_fast : m->lds_bytes;
-    return launch3(*mlp3_row(m->tmpl.n_ot, m->tmpl.n_residual != 0, fast), lp, grid, lds, as_stream(stream));
+    const Mlp3Row &row = *mlp3_row(m->tmpl.n_ot, m->tmpl.n_residual != 0, fast);
+    // the row of this launch and the run-time facts that choose code inside it, for fv3hip_mlp3_last_variant
+    char out_path[16] = "none";
+    if (lp.has_out) snprintf(out_path, sizeof(out_path), "mfma");
+    if (lp.small_out) snprintf(out_path, sizeof(out_path), "valu%d", lp.small_out);
+    snprintf(m->last_variant, sizeof(m->last_variant), "mlp3_kernel<%d,%s,%s> out=%s hout=%d layer1=%s ks1=%d/%d hidden=%d xwrap=%d", row.OT,
+             row.res ? "true" : "false", row.fast ? "true" : "false", out_path, lp.hout ? 1 : 0,
+             (lp.n_hidden >= 2 || !lp.has_out) ? "block" : "builtin", lp.n_ks1, lp.n_log_ks, lp.n_hidden, lp.x_wrap);
+    return launch3(row, lp, grid, lds, as_stream(stream));
 }

@@ -427,7 +427,12 @@ class MlpModelSplitBf16(_MlpHandle):
     with unit sample stride only; ``MlpModel`` (fp32 MFMA) is the product path."""
 
     ENTRY = "fv3hip_mlp3"
-    last_variant = "mlp3_kernel"
+
+    @property
+    def last_variant(self) -> str:
+        """Instantiation of the last ``predict`` and the run-time facts that choose code inside it
+        (``fv3hip_mlp3_last_variant``)."""
+        return _lib.load().fv3hip_mlp3_last_variant(self._handle).decode()
 
     def predict(self, sources: Mapping[str, torch.Tensor], out: Optional[Mapping[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """``sources``: name -> float32 ``[feature, sample]`` device array with unit sample stride.  ``out``: preallocated
@@ -447,9 +452,15 @@ class MlpModelSplitBf16(_MlpHandle):
             outs[name] = g2
         ol = [outs[name] for name, _ in self._out_nfeat]
         ns, no = len(tensors), len(ol)
+
+        def feature_stride(t):
+            # (the stride of an array's only row means nothing -- a transposed [n, 1] array reports 1 --, but the library
+            # holds every feature stride to >= n and to the 16-byte rule of its epilogue: such a row is n apart from nothing)
+            return t.stride(0) if t.shape[0] > 1 else max(n, 1)
+
         _lib.call_on(dev, "fv3hip_mlp3_predict", self._handle, (ctypes.c_void_p * ns)(*[t.data_ptr() for t in tensors]),
-                     (ctypes.c_int64 * ns)(*[t.stride(0) for t in tensors]), n, (ctypes.c_void_p * no)(*[t.data_ptr() for t in ol]),
-                     (ctypes.c_int64 * no)(*[t.stride(0) for t in ol]), _stream(dev))
+                     (ctypes.c_int64 * ns)(*[feature_stride(t) for t in tensors]), n, (ctypes.c_void_p * no)(*[t.data_ptr() for t in ol]),
+                     (ctypes.c_int64 * no)(*[feature_stride(t) for t in ol]), _stream(dev))
         return outs
 
 

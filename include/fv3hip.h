@@ -469,9 +469,12 @@ const char *fv3hip_mlp_last_variant(fv3hip_mlp_t model);
 /*
  * EXPERIMENTAL: the same predict graph with the contraction on the bf16 matrix cores, every fp32 operand split into three
  * bf16 pieces and six cross products accumulated in fp32 (fv3net_amd/csrc/mlp_bf16x3.hip).  Same
- * descriptor as fv3hip_mlp_create; restrictions: hidden width 256, ReLU, no hidden output, no limits / masks, log epsilons
- * >= FLT_MIN, 3 / 5 / 13 output tiles of 32.  Sources and outputs are float32 [feature][sample] with unit sample stride
- * (element (f, n) at f * feat_stride + n).  Not a replacement of fv3hip_mlp_predict: the fp32 kernel is the product path.
+ * descriptor as fv3hip_mlp_create (hidden_output included: it is the last entry of `outputs`, and n_outputs may then be 0);
+ * restrictions: hidden width 256, ReLU, no limits / masks, log epsilons >= FLT_MIN, 1 / 3 / 5 / 13 output tiles of 32, at most
+ * 64 layer-1 k-steps of 16 input features (every input padded to 16), at least two k-steps per sample tile, tables within
+ * 160 KiB of LDS.  Sources and outputs are float32 [feature][sample] with unit sample stride (element (f, n) at
+ * f * feat_stride + n; feat_stride >= n_samples for every source an input reads and for the hidden output).  Not a
+ * replacement of fv3hip_mlp_predict: the fp32 kernel is the product path.
  */
 typedef struct fv3hip_mlp3 *fv3hip_mlp3_t;
 int fv3hip_mlp3_create(const fv3hip_mlp_desc_t *desc, fv3hip_mlp3_t *out);
@@ -479,6 +482,16 @@ int fv3hip_mlp3_destroy(fv3hip_mlp3_t model);
 int64_t fv3hip_mlp3_flops_per_sample(fv3hip_mlp3_t model);
 int fv3hip_mlp3_predict(fv3hip_mlp3_t model, const void *const *sources, const int64_t *src_feat_stride, int64_t n_samples,
                         void *const *outputs, const int64_t *out_feat_stride, void *stream);
+/* Diagnostic (additive to ABI v3): the instantiation the model's last fv3hip_mlp3_predict launched and the run-time facts
+ * that choose code inside it, e.g.
+ *   "mlp3_kernel<13,true,true> out=mfma hout=0 layer1=block ks1=16/5 hidden=2 xwrap=0"
+ * <output tiles, residual outputs, 16-byte epilogue>; out: the output layer on the matrix cores (mfma), on the vector ALU
+ * with F outputs (valu<F>) or absent (none); hout: a hidden output is stored; layer1: how layer 1 requests its weight chunks
+ * (block: inside the k-step's assembly block; builtin: a single hidden layer in front of an output layer on the matrix
+ * cores); ks1: layer-1 k-steps / those of log inputs; hidden: hidden layers; xwrap: 16 feature rows of a source span 4 GiB or
+ * more.  "" before the first call that launches (a call of 0 samples launches nothing and leaves the string).  The string
+ * lives in the model handle. */
+const char *fv3hip_mlp3_last_variant(fv3hip_mlp3_t model);
 
 /*
  * Random forest: fv3fit.sklearn.RandomForest (registered "sklearn", external/fv3fit/fv3fit/sklearn/_random_forest.py:65-377),

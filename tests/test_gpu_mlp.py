@@ -386,6 +386,7 @@ def test_split_bf16_kernel_against_oracle(device, n, residuals):
     src = bench.zc_inputs_numpy(np.random.default_rng(13), n)
     model = MlpModelSplitBf16(spec, device=device)
     out = model.predict({k: torch.from_numpy(np.ascontiguousarray(v.T)).to(device) for k, v in src.items()})
+    assert model.last_variant.startswith(f"mlp3_kernel<13,{'true' if residuals else 'false'},true> out=mfma hout=0 layer1=block"), model.last_variant
     truth = mlp_np.forward(spec, src, dtype=np.float64)
     cpu32 = mlp_np.forward(spec, src, dtype=np.float32)
     assert set(out) == set(truth)
@@ -416,6 +417,9 @@ def test_split_bf16_kernel_other_architectures(device, n_hidden, out_feats, n, p
     dev_src = {"state": torch.from_numpy(state).to(device)[:, :n], "ps": torch.from_numpy(ps).to(device)[:, :n]}
     model = MlpModelSplitBf16(spec, device=device)
     out = model.predict(dev_src)
+    tiles = (sum(out_feats.values()) + 31) // 32
+    assert model.last_variant.startswith(f"mlp3_kernel<{tiles},true,{'false' if pad else 'true'}> out=mfma hout=0 "
+                                         f"layer1={'builtin' if n_hidden == 1 else 'block'}"), model.last_variant
     host = {"state": np.ascontiguousarray(state[:, :n].T), "ps": np.ascontiguousarray(ps[:, :n].T)}
     truth = mlp_np.forward(spec, host, dtype=np.float64)
     cpu32 = mlp_np.forward(spec, host, dtype=np.float32)
