@@ -319,6 +319,15 @@ SIGNATURES = {
                                   c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fv3hip_histogram": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "fv3hip_histogram2d": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "fv3hip_graph_sage": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                  c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "fv3hip_graph_pool2": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
+    "fv3hip_graph_up2": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
+                                 c_int, c_void_p]),
+    "fv3hip_graph_pack": (c_int, [POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), c_int, POINTER(c_int), c_void_p, c_void_p,
+                                  c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fv3hip_graph_unpack": (c_int, [c_void_p, c_int64, c_int, c_int, POINTER(c_int), c_void_p, c_void_p, POINTER(c_void_p),
+                                    c_void_p]),
     "fv3hip_timer_create": (c_int, [POINTER(c_void_p)]),
     "fv3hip_timer_start": (c_int, [c_void_p, c_void_p]),
     "fv3hip_timer_stop": (c_int, [c_void_p, c_void_p]),

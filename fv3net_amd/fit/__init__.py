@@ -18,6 +18,8 @@ from .forest import RandomForest
 from .conv import HipConvolutionalModel, conv_spec_from_arrays
 from .precipitative import (HipPrecipitativeModel, PrecipitativeHyperparameters, precipitative_spec_from_arrays,
                             train_precipitative_model)
+from .graph import (GraphHyperparameters, GraphUNetTwin, HipGraphAutoregressor, graph_unet_spec_from_state_dict,
+                    state_dict_from_spec, train_graph_model, twin_from_spec)
 from .reservoir import (HybridReservoirComputingModel, HybridReservoirDatasetAdapter, ReservoirComputingModel,
                         ReservoirDatasetAdapter, split_multi_subdomain_model)
 
@@ -29,4 +31,6 @@ __all__ = [
     "SquashedOutputModel", "TaperConfig", "TaperedModel", "vertical_tapering_scale_factors", "HipDenseModel", "Predictor", "SAMPLE_DIM_NAME", "dump", "io",
     "load", "match_prediction_to_input_coords", "spec_from_arrays", "stack", "train_dense_model",
     "HipPrecipitativeModel", "PrecipitativeHyperparameters", "precipitative_spec_from_arrays", "train_precipitative_model",
+    "GraphHyperparameters", "GraphUNetTwin", "HipGraphAutoregressor", "graph_unet_spec_from_state_dict", "state_dict_from_spec",
+    "train_graph_model", "twin_from_spec",
 ]

@@ -951,6 +951,47 @@ int fv3hip_histogram2d(const void *x, const void *y, int dtype, int64_t n, const
                        int nx_bins, const double *yedges, int ny_bins, int64_t *counts,
                        void *stream);
 
+/*
+ * fv3fit's graph U-Net autoregressor (external/fv3fit/fv3fit/pytorch/graph/unet.py:216-261, pytorch/predict.py:136-250):
+ * stateless layer kernels on the resident six-tile cube.  Activations are float32, channel-last: cell (sample s, tile t, x, y)
+ * of an array with row length `ld` and channel offset `off` holds its channels at
+ *     base[s * sample_stride + ((t * n + x) * n + y) * ld + off + c],        x the first spatial axis,
+ * so a layer reads one channel slice and writes another (the U-Net's concatenation is two layers writing the halves of one
+ * buffer).  A sample stride of 0 means contiguous cubes (6 n n ld).  The caller owns every buffer; nothing is allocated or
+ * synchronised; all arguments are checked on the host before any HIP call.  A layer must not read what it writes: slices of
+ * one buffer (same base and ld) must be disjoint in channels, different buffers must not overlap (FV3HIP_EINVAL).
+ *
+ *   fv3hip_graph_sage   dgl's SAGEConv(c_in, c_out, "mean") on the graph of graph_builder.py:12-49 (every cell, its x-low,
+ *                       x-high, y-low, y-high neighbours, across the cube seams as the one-cell halo of append_halos shows
+ *                       them): dst = act(src W_self + mean5(src) W_neigh + bias), w_self / w_neigh [c_in][c_out] (the
+ *                       transpose of torch's Linear weight), bias [c_out] or null, act one of FV3HIP_ACT_* (another code:
+ *                       FV3HIP_EUNSUPPORTED).  mean5 = ((((self + x-low) + x-high) + y-low) + y-high) / 5 in float32, formed
+ *                       while the tile is staged: no gathered or averaged copy is written to memory.  Exact-f32 MFMA over
+ *                       K = 2 c_in in chunks of 8 channels (their 8 self rows, then their 8 mean rows).  ReLU keeps NaN.
+ *   fv3hip_graph_pool2  AvgPool2d(2, 2) per tile, n even: ((a[2i][2j] + a[2i][2j+1]) + a[2i+1][2j]) + a[2i+1][2j+1], times 0.25.
+ *   fv3hip_graph_up2    ConvTranspose2d(c_in, c_out, 2, stride 2) per tile: dst[2i+di][2j+dj][co] = bias[co] + sum over ci of
+ *                       src[i][j][ci] w[ci][di][dj][co]  (w: torch's [c_in][c_out][kx][ky] moved to [c_in][kx][ky][c_out]);
+ *                       dst has 2 n cells per edge.  The same MFMA kernel with K = c_in and N = 4 c_out.
+ *   fv3hip_graph_pack   state[w][t][tile][x][y][f] float32 = (float)((x - mean[f]) / std[f]) computed in float64, from time
+ *                       w * timesteps + t of variable v (f = its first feature + level): sources[v] of src_dtype[v] (F32 / F64),
+ *                       element strides src_strides + 5 v for (time, tile, x, y, level); nfeat[v] levels; mean / std DEVICE
+ *                       float64 [F], F = sum of nfeat; at most 16 variables.  sources / src_dtype / src_strides / nfeat are HOST arrays.
+ *   fv3hip_graph_unpack outputs[v][row][tile][x][y][level] float64 contiguous = (double)state * std[f] + mean[f], the product
+ *                       rounded before the sum; state [n_rows][6][n][n][F] contiguous.
+ */
+int fv3hip_graph_sage(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, const float *w_self,
+                      const float *w_neigh, const float *bias, float *dst, int64_t dst_ld, int64_t dst_off,
+                      int64_t dst_sample_stride, int64_t n_samples, int n, int c_in, int c_out, int act, void *stream);
+int fv3hip_graph_pool2(const float *src, int64_t src_ld, int64_t src_off, float *dst, int64_t dst_ld, int64_t dst_off,
+                       int64_t n_samples, int n, int c, void *stream);
+int fv3hip_graph_up2(const float *src, int64_t src_ld, int64_t src_off, const float *w, const float *bias, float *dst,
+                     int64_t dst_ld, int64_t dst_off, int64_t n_samples, int n, int c_in, int c_out, void *stream);
+int fv3hip_graph_pack(const void *const *sources, const int *src_dtype, const int64_t *src_strides, int n_vars, const int *nfeat,
+                      const double *mean, const double *std, int64_t n_windows, int n_times, int timesteps, int n, float *state,
+                      void *stream);
+int fv3hip_graph_unpack(const float *state, int64_t n_rows, int n, int n_vars, const int *nfeat, const double *mean,
+                        const double *std, double *const *outputs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
