@@ -4,11 +4,12 @@ usage: run.py PHASE [--lib-dir DIR] [--out FILE.json]
   PHASE is the per-slot phase the library was built for (MLP_STAMP_PHASE in mlp.hip):
     0 / 2  layer-1 chunks by the flavour of the input tile they prepare (plain / fast log)
     3      the 8-slot layer-1 chunk behind a log block whose last chunk is at most half full
+    4      the 13-slot first plain chunk, where the plain block's partial chunk is its first
     10     hidden chunks        20  output chunks
 One process per phase (the library is chosen when it is loaded); both epilogue flavours, plain and residual, run in it.
 Prints, and merges into FILE.json under "phase_<PHASE>", per flavour: the per-phase cycle sums per tile (st_acc[0..3]:
 layer 1, hidden, output, last epilogue) and the per-slot means sl_acc[0..15] / sl_acc[16] with the chunk count.
-A whole table:  for p in 0 2 3 10 20; do timeout -k 10 120 python benchmarks/mlp_stamps/run.py $p --out t.json || break; done
+A whole table:  for p in 0 2 3 4 10 20; do timeout -k 10 120 python benchmarks/mlp_stamps/run.py $p --out t.json || break; done
 """
 import argparse
 import ctypes

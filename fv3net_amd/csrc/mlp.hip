@@ -70,6 +70,12 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// max(x, lo) in one instruction (v_maximum3_f32, the IEEE-754-2019 maximum) where `x < lo ? lo : x` is a compare, a wait for
+// vcc and a select.  A NaN in x stays a NaN (quieted), as in the select form; for any other x the value is the same.  The
+// one difference is the sign of a zero: ReLU of -0 is +0 here and was -0, which can only change the sign of an exact
+// zero further down -- results stay equal by value.  (The log floor's eps is > 0, so nothing changes there.)
+__device__ __forceinline__ float max_keep_nan(float x, float lo) { return __builtin_elementwise_maximum(x, lo); }
+
 constexpr int kMaxSources = 16;
 constexpr int kMaxOutputs = 32;
 constexpr int kMaxK = 2048;       // network inputs whose per-feature table still fits LDS
@@ -135,6 +141,8 @@ struct MlpLaunch {
     int n_logfast_chunks;  // the leading ones of them that are all-log with every eps >= FLT_MIN
     int l1_short_log;      // the last log chunk's real rows fill at most 8 of its 16 k-pair slots, the rest is zero padding, and
                            // plain chunks follow: the fast-I/O kernels run that chunk with 8 slots
+    int l1_short_plain;    // kShortPlainSlots: the first plain chunk is the partial one (the host put it there, InputTable::short_plain_slots)
+                           // and its real rows fill at most that many k-pair slots: the fast-I/O kernels run it with as many; 0: not
     int epi_fast;      // sources and outputs are sample-contiguous and 16-byte aligned, n_samples % 32 == 0: fast-I/O kernel
     int has_limits;    // any output limit or zero mask
     int n_residual;
@@ -145,7 +153,7 @@ struct MlpLaunch {
 };
 
 #ifndef MLP_STAMP_PHASE
-#define MLP_STAMP_PHASE 0  // per-slot stamps: 0/1/2 layer-1 XBULK chunks by log mode, 3 the 8-slot last log chunk, 10 hidden, 20 output
+#define MLP_STAMP_PHASE 0  // per-slot stamps: 0/1/2 layer-1 XBULK chunks by log mode, 3 the 8-slot last log chunk, 4 the short first plain chunk, 10 hidden, 20 output
 #endif
 #ifdef MLP_STAMPS
 #define SLOT_STAMP(phase, s)                                          \
@@ -323,6 +331,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
     };
     // slot s of a chunk of KC slots: its share of staging chunk `gnext` into buffer `buf`.  The last
     // slot stages nothing: it opens with the chunk barrier (see run_slot).
+    // (KC need not be a multiple of 4: Q * per >= NVH commits every staged float4, and 4 Q - 1 <= KC - 1 ends before the last slot)
     auto stage_step = [&](int s, int KC, int gnext, int buf) {
         const int Q = KC / 4, per = (NVH + Q - 1) / Q;
         if (s == 0) issue_w(gnext, 0);
@@ -473,7 +482,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
         if (LOGM == 2) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                v[q] = __builtin_amdgcn_logf(v[q] < e.eps ? e.eps : v[q]) * 0.693147180559945f;
+                v[q] = __builtin_amdgcn_logf(max_keep_nan(v[q], e.eps)) * 0.693147180559945f;
         }
         v = v - e.center;  // (1 / std lives in the layer-1 weights)
         *reinterpret_cast<f32x4 *>(xs + (buf * 32 + kk) * kTileSamples + 4 * sg) = v;
@@ -589,12 +598,16 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
             // 8 also for the last chunk of a log block that the host padded with at least 16 zero rows (l1_short_log):
             // a dropped slot would add +-0 to every accumulator.  There a full chunk follows, which reads all 32 rows
             // of the input tile with no barrier but this chunk's own in between, so the whole tile is finished in slot 6,
-            // ahead of that barrier -- and five slots after its request rather than three.)
-            auto l1_chunk_bulk = [&](int cn, int64_t n0, auto with_log, auto kc1_c) __attribute__((always_inline)) {
+            // ahead of that barrier -- and five slots after its request rather than three.
+            // short_plain_c: the partial plain chunk that the host made the plain block's first (l1_short_plain), 13 slots;
+            // a full chunk follows it too, so the input tile is finished in slots 8..11, ahead of the barrier in slot 12.)
+            auto l1_chunk_bulk = [&](int cn, int64_t n0, auto with_log, auto kc1_c, auto short_plain_c) __attribute__((always_inline)) {
                 constexpr int KC1 = decltype(kc1_c)::value;
-                constexpr bool SHORT_LOG = KC1 == 8 && !L1SHORT;
-                constexpr int FIN0 = (KC1 == 16) ? 8 : SHORT_LOG ? 5 : 3;
-                constexpr int SPH = SHORT_LOG ? 3 : (int)decltype(with_log)::value;  // (stamped builds: the phase)
+                constexpr bool SHORT_PLAIN = decltype(short_plain_c)::value;
+                constexpr bool FIN_AT_ONCE = KC1 == 8 && !L1SHORT;  // (the 8-slot bodies that a full chunk follows)
+                static_assert(!SHORT_PLAIN || (!L1SHORT && KC1 >= 10 && KC1 < 16), "the short plain chunk finishes its inputs in four slots ahead of the last");
+                constexpr int FIN0 = (KC1 == 16) ? 8 : FIN_AT_ONCE ? 5 : SHORT_PLAIN ? (KC1 - 6 < 8 ? KC1 - 6 : 8) : 3;
+                constexpr int SPH = SHORT_PLAIN ? 4 : FIN_AT_ONCE ? 3 : (int)decltype(with_log)::value;  // (stamped builds: the phase)
                 const int gnext = (g + 1 < G) ? g + 1 : 0;
                 const float *xsb = xs + xb * 32 * kTileSamples + half * kTileSamples + wave * 32 + (lane & 31);
                 const float *xsn = xs + (xb ^ 1) * 32 * kTileSamples + half * kTileSamples + wave * 32 + (lane & 31);
@@ -628,7 +641,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
 #pragma unroll
                             for (int i = 0; i < 4; ++i) xn4[i] = xn_g[8 * i];
                         }
-                        if constexpr (SHORT_LOG) {
+                        if constexpr (FIN_AT_ONCE) {
                             if (s_ == FIN0 + 1) {
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) bulk_finish_e(xn4[i], i, xb ^ 1, with_log);
@@ -654,20 +667,29 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
                 // the last chunk brings in chunk 0 of the workgroup's next tile
                 const int64_t n1 = (next_tile < p.n_tiles ? next_tile : tile) * kTileSamples;
                 if constexpr (L1SHORT) {  // one chunk of at most 16 plain inputs (the host checks)
-                    l1_chunk_bulk(0, n1, M0_{}, std::integral_constant<int, 8>{});
+                    l1_chunk_bulk(0, n1, M0_{}, std::integral_constant<int, 8>{}, F_{});
                 } else {
                     int c = 0;  // chunk c prepares the inputs of chunk c + 1
-                    for (; c + 1 < NF; ++c) l1_chunk_bulk(c + 1, n0, M2_{}, KC16_{});
-                    for (; c + 1 < L; ++c) l1_chunk_bulk(c + 1, n0, M1_{}, KC16_{});
+                    for (; c + 1 < NF; ++c) l1_chunk_bulk(c + 1, n0, M2_{}, KC16_{}, F_{});
+                    for (; c + 1 < L; ++c) l1_chunk_bulk(c + 1, n0, M1_{}, KC16_{}, F_{});
                     // (c = L - 1, the last log chunk, whose call prepares the first plain one: 8 slots if the rest is padding)
                     if (p.l1_short_log) {
-                        l1_chunk_bulk(c + 1, n0, M0_{}, std::integral_constant<int, 8>{});
+                        l1_chunk_bulk(c + 1, n0, M0_{}, std::integral_constant<int, 8>{}, F_{});
                         ++c;
                     }
-                    for (; c < NC - 1; ++c) l1_chunk_bulk(c + 1, n0, M0_{}, KC16_{});
-                    if (NF > 0) l1_chunk_bulk(0, n1, M2_{}, KC16_{});
-                    else if (L > 0) l1_chunk_bulk(0, n1, M1_{}, KC16_{});
-                    else l1_chunk_bulk(0, n1, M0_{}, KC16_{});
+                    // (c = L, the first plain chunk, where it is the partial one: only the slots that hold real rows -- a dropped
+                    // slot would add +-0 to every accumulator.  At least one full plain chunk follows, so this is never the
+                    // tile's last chunk.  ONE slot count, and the host asks for it only where no full last log chunk has to run
+                    // first: with a second count to choose from, or a 16-slot body ahead of this one, the compiled bodies
+                    // shuttle the accumulators between AGPRs and VGPRs and the kernel spills -- DESIGN 4.1.)
+                    if (p.l1_short_plain) {
+                        l1_chunk_bulk(c + 1, n0, M0_{}, std::integral_constant<int, kShortPlainSlots>{}, T_{});
+                        ++c;
+                    }
+                    for (; c < NC - 1; ++c) l1_chunk_bulk(c + 1, n0, M0_{}, KC16_{}, F_{});
+                    if (NF > 0) l1_chunk_bulk(0, n1, M2_{}, KC16_{}, F_{});
+                    else if (L > 0) l1_chunk_bulk(0, n1, M1_{}, KC16_{}, F_{});
+                    else l1_chunk_bulk(0, n1, M0_{}, KC16_{}, F_{});
                 }
             } else {
                 // a chunk that mixes both kinds (the boundary chunk, or the re-derivation on the last
@@ -680,7 +702,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
 #pragma unroll
             for (int t = 0; t < HT; ++t)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) h[t][r] = (h[t][r] < 0.f) ? 0.f : h[t][r];
+                for (int r = 0; r < 16; ++r) h[t][r] = max_keep_nan(h[t][r], 0.f);
         }
         STAMP_END(0);
         // ================= hidden -> hidden =================
@@ -708,7 +730,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fused_kernel(const MlpLaunch 
 #pragma unroll
             for (int t = 0; t < HT; ++t)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) h[t][r] = (h2[t][r] < 0.f) ? 0.f : h2[t][r];
+                for (int r = 0; r < 16; ++r) h[t][r] = max_keep_nan(h2[t][r], 0.f);
         }
         STAMP_END(1);
         // ================= hidden -> outputs, one 32-feature tile per chunk =================
@@ -1777,8 +1799,8 @@ int pack_fused(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m, con
     const int n_out_chunks = nt_out;
     m->fused.n_log_chunks = (it.n_log_padded + 31) / 32;
     m->fused.n_logfast_chunks = it.eps_normal ? it.n_log_padded / 32 : 0;
-    // the log block was padded to whole chunks, the real rows of its last chunk fit 8 k-pair slots and a plain chunk follows
-    m->fused.l1_short_log = (it.n_log_padded % 32 == 0 && it.n_log % 32 >= 1 && it.n_log % 32 <= 16 && m->fused.n_log_chunks < m->fused.n_chunks1) ? 1 : 0;
+    m->fused.l1_short_log = it.short_log ? 1 : 0;
+    m->fused.l1_short_plain = it.short_plain_slots;
     // ---- packed weight stream ----
     // (+ one maximal chunk of zero padding: the two-half staging may read past a short last chunk)
     const size_t n_w = (size_t)(n_hid_chunks * CH_H + n_out_chunks * CH_O + (CH_H > CH_O ? CH_H : CH_O)) * 4;
@@ -1889,7 +1911,7 @@ int fill_model(const fv3hip_mlp_desc_t *d, const MlpDims &dm, fv3hip_mlp *m)
     m->n_slots = m->n_outputs + m->n_residual + (m->n_hout_tiles ? 1 : 0);
     // the tables (hidden-output models: the output table starts with the last hidden layer's features)
     InputTable it;
-    build_input_table(d, dm.K, m->n_ktab, it);
+    build_input_table(d, dm.K, m->n_ktab, it, !m->layered);
     std::vector<OEntry> otab;
     build_output_table(d, m->n_otab, 32 * m->n_hout_tiles, dm.hout ? m->width : 0, otab);
     std::vector<float> w, bias;
@@ -1984,6 +2006,23 @@ extern "C" int fv3hip_mlp_set_small_limit(fv3hip_mlp_t m, int64_t max_samples)
 }
 
 extern "C" const char *fv3hip_mlp_last_variant(fv3hip_mlp_t m) { return m ? m->last_variant : ""; }
+
+// Diagnostic, host only (no device call): the fused path's input table for a descriptor.  perm[0 .. return value) is the
+// original input feature of each table row (-1: a zero row), *n_log_padded the rows of the log block, *short_plain_slots
+// MlpLaunch::l1_short_plain.  Returns the row count, or -1 for a bad descriptor or `cap` below the table's size.
+extern "C" int fv3hip_diag_mlp_input_table(const fv3hip_mlp_desc_t *d, int *perm, int cap, int *n_log_padded, int *short_plain_slots)
+{
+    MlpDims dm;
+    if (!perm || !n_log_padded || !short_plain_slots || check_mlp_desc(d, perm, kMaxSources, kMaxOutputs, dm) != FV3HIP_OK) return -1;
+    const int n_ktab = 2 * 16 * (((dm.K + 1) / 2 + 15) / 16);  // (as fused_geometry)
+    if (cap < n_ktab) return -1;
+    InputTable it;
+    build_input_table(d, dm.K, n_ktab, it, true);
+    for (int k = 0; k < n_ktab; ++k) perm[k] = k < (int)it.perm.size() ? it.perm[k] : -1;
+    *n_log_padded = it.n_log_padded;
+    *short_plain_slots = it.short_plain_slots;
+    return n_ktab;
+}
 
 namespace {
 

@@ -108,11 +108,24 @@ struct InputTable {
     int n_log = 0;             // input features that take the logarithm
     int n_log_padded = 0;      // rows at the head of the table that take the logarithm (padded to whole 32-row chunks if room)
     bool eps_normal = true;    // every logarithm's floor is a normal number
+    bool short_log = false;    // the log block was padded to whole chunks, the real rows of its last chunk fit 8 of its 16 k-pair
+                               // slots and a plain chunk follows: the fused fast-I/O kernels run that chunk with 8 slots
+    int short_plain_slots = 0; // kShortPlainSlots where the partial plain chunk is the plain block's first and its real rows fit
+                               // that many k-pair slots (the fused fast-I/O kernels then run it with as many); 0: it is the last
 };
+
+// The one slot count (two rows per k-pair slot) the fused fast-I/O kernels have a short plain body for: the Zhao-Carr
+// emulator's partial plain chunk holds 26 real rows.
+constexpr int kShortPlainSlots = 13;
 
 // Network input k' is original input feature perm[k']: the log-transformed features come first (any order of the
 // contraction index is the same dense layer), so that whole 32-row chunks are either with or without the transform.
-inline void build_input_table(const fv3hip_mlp_desc_t *d, int K, int n_ktab, InputTable &t)
+// partial_plain_first (the fused path): where the plain block starts at a chunk boundary, spans two chunks or more and does
+// not fill them, its partial chunk's real rows fit kShortPlainSlots slots, and the chunk ahead of the block is none or the
+// 8-slot log chunk (short_log), that partial chunk is the block's FIRST, not its last -- real rows in unchanged order, then
+// the zero rows, then the full chunks -- and short_plain_slots is set.  The real rows keep their order in the contraction;
+// the zero rows, which add +-0 wherever they sit, move from the end of the table to the end of that chunk.
+inline void build_input_table(const fv3hip_mlp_desc_t *d, int K, int n_ktab, InputTable &t, bool partial_plain_first = false)
 {
     t.ktab.assign(n_ktab, KEntry{-1, 0, 0.f, 1.f, 0, 0.f, 0, 0});
     t.perm.clear();
@@ -141,12 +154,23 @@ inline void build_input_table(const fv3hip_mlp_desc_t *d, int K, int n_ktab, Inp
     if (n_log > 0 && n_log + n_pad + (K - n_log) <= n_ktab)
         for (int i = 0; i < n_pad; ++i) t.perm.push_back(-1);
     t.n_log_padded = (int)t.perm.size();
-    for (int k2 = 0; k2 < K; ++k2)
-        if (orig[k2].transform != FV3HIP_TRANSFORM_LOG) t.perm.push_back(k2);
+    const int n_plain = K - n_log, n_zero = n_ktab - t.n_log_padded - n_plain;  // (zero rows behind the plain block)
+    t.short_log = t.n_log_padded % 32 == 0 && n_log % 32 >= 1 && n_log % 32 <= 16 && t.n_log_padded < n_ktab;
+    t.short_plain_slots = 0;
+    if (partial_plain_first && (n_log == 0 || t.short_log) && n_zero > 0 && n_zero < 32 && n_plain > 32 && 32 - n_zero <= 2 * kShortPlainSlots)
+        t.short_plain_slots = kShortPlainSlots;
+    int n_placed = 0;
+    for (int k2 = 0; k2 < K; ++k2) {
+        if (orig[k2].transform == FV3HIP_TRANSFORM_LOG) continue;
+        if (t.short_plain_slots && n_placed == 32 - n_zero)
+            for (int i = 0; i < n_zero; ++i) t.perm.push_back(-1);
+        t.perm.push_back(k2);
+        ++n_placed;
+    }
     for (size_t k2 = 0; k2 < t.perm.size(); ++k2) {
         if (t.perm[k2] >= 0) {
             t.ktab[k2] = orig[t.perm[k2]];
-        } else {
+        } else if ((int)k2 < t.n_log_padded) {
             t.ktab[k2].transform = FV3HIP_TRANSFORM_LOG;
             t.ktab[k2].eps = 1.f;
         }
