@@ -20,6 +20,8 @@ TRANSFORM_NONE, TRANSFORM_LOG = 0, 1
 ACT_LINEAR, ACT_RELU, ACT_TANH = 0, 1, 2
 CONV_HALO_INPUT, CONV_HALO_STRIPS, CONV_HALO_CUBE = 0, 1, 2
 ARITH_EXACT, ARITH_FAST = 0, 1
+CYCLEGAN_CONV_REGULAR, CYCLEGAN_CONV_STRIDED, CYCLEGAN_CONV_TRANSPOSED = 0, 1, 2
+CYCLEGAN_HALO_ZEROS, CYCLEGAN_HALO_CUBE = 0, 1
 ABI_VERSION = 3
 
 OK, EINVAL, EUNSUPPORTED, EHIP, ENOMEM = 0, -1, -2, -3, -4
@@ -328,6 +330,15 @@ SIGNATURES = {
                                   c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fv3hip_graph_unpack": (c_int, [c_void_p, c_int64, c_int, c_int, POINTER(c_int), c_void_p, c_void_p, POINTER(c_void_p),
                                     c_void_p]),
+    "fv3hip_cyclegan_conv": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_void_p]),
+    "fv3hip_cyclegan_stats": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_double,
+                                      c_void_p]),
+    "fv3hip_cyclegan_apply": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                                      c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
+    "fv3hip_cyclegan_input": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
     "fv3hip_timer_create": (c_int, [POINTER(c_void_p)]),
     "fv3hip_timer_start": (c_int, [c_void_p, c_void_p]),
     "fv3hip_timer_stop": (c_int, [c_void_p, c_void_p]),

@@ -20,6 +20,8 @@ from .precipitative import (HipPrecipitativeModel, PrecipitativeHyperparameters,
                             train_precipitative_model)
 from .graph import (GraphHyperparameters, GraphUNetTwin, HipGraphAutoregressor, graph_unet_spec_from_state_dict,
                     state_dict_from_spec, train_graph_model, twin_from_spec)
+from .cyclegan import (GeneratorTwin, HipCycleGAN, cyclegan_spec_from_state_dict, cyclegan_state_dict_from_spec,
+                       generator_spec_from_state_dict)
 from .reservoir import (HybridReservoirComputingModel, HybridReservoirDatasetAdapter, ReservoirComputingModel,
                         ReservoirDatasetAdapter, split_multi_subdomain_model)
 
@@ -33,4 +35,5 @@ __all__ = [
     "HipPrecipitativeModel", "PrecipitativeHyperparameters", "precipitative_spec_from_arrays", "train_precipitative_model",
     "GraphHyperparameters", "GraphUNetTwin", "HipGraphAutoregressor", "graph_unet_spec_from_state_dict", "state_dict_from_spec",
     "train_graph_model", "twin_from_spec",
+    "GeneratorTwin", "HipCycleGAN", "cyclegan_spec_from_state_dict", "cyclegan_state_dict_from_spec", "generator_spec_from_state_dict",
 ]

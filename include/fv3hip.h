@@ -992,6 +992,58 @@ int fv3hip_graph_pack(const void *const *sources, const int *src_dtype, const in
 int fv3hip_graph_unpack(const float *state, int64_t n_rows, int n, int n_vars, const int *nfeat, const double *mean,
                         const double *std, double *const *outputs, void *stream);
 
+/*
+ * fv3fit's CycleGAN generators (external/fv3fit/fv3fit/pytorch/cyclegan/generator.py:19-270, modules.py): stateless layer
+ * kernels on channel-last float32 slices of the resident six-tile cube, addressed as the fv3hip_graph_* layers address them
+ * (row length, channel offset, sample stride; 0 = contiguous cubes).  The caller owns every buffer; nothing is allocated or
+ * synchronised; all arguments are checked on the host before any HIP call.  Pack and unpack are fv3hip_graph_pack / _unpack.
+ *
+ *   fv3hip_cyclegan_conv   one convolution as an implicit GEMM on the exact-f32 MFMA, rows = output cells flattened over
+ *                          (sample, tile, x, y).  `n` is the INPUT's cells per edge.  kind / k:
+ *                            _REGULAR     k in {3, 5, 7}, stride 1, halo (k - 1) / 2, w [k][k][c_in][c_out]; output n
+ *                            _STRIDED     k = 4, stride 2, halo 1: output (x, y) reads cells 2 x - 1 ... 2 x + 2, same in y;
+ *                                         w [4][4][c_in][c_out]; n even, output n / 2
+ *                            _TRANSPOSED  k = 4: ConvTranspose2d(4, stride 2) of the input padded by one halo line, cropped by
+ *                                         3.  Per axis output 2 m takes tap 1 of cell m and tap 3 of cell m - 1, output
+ *                                         2 m + 1 tap 0 of cell m + 1 and tap 2 of cell m.  w [px][py][a][b][c_in][c_out]:
+ *                                         parity (px, py) of the output cell, then its 2 x 2 taps, a / b = 0 the first-named
+ *                                         tap of the axis (torch's w[ci][co][kx][ky] with kx = 1 + 2 a for px = 0, 2 a for
+ *                                         px = 1); output 2 n
+ *                            any other k: FV3HIP_EUNSUPPORTED.
+ *                          halo_mode: _HALO_CUBE takes cells off the face from the neighbouring faces as AppendHalos does
+ *                          (corners zero), _HALO_ZEROS pads with zeros.  The halo must not be wider than the face.
+ *                          While loading, a source value v becomes relu((v - in_mean) * in_rstd + in_bias): in_mean / in_rstd
+ *                          [sample][6][c_in] (both or neither), in_bias [6][n][n][c_in] or null, in_relu 0 / 1 -- with the
+ *                          statistics and the bias cell of the face the value lies on; padding zeros stay zero.  Products are
+ *                          rounded separately.  The result is acc + bias[c_out] (or null) + out_bias [6][n_out][n_out][c_out]
+ *                          (or null), in this order.  ReLU keeps NaN.  Source and destination must not overlap.
+ *   fv3hip_cyclegan_stats  nn.InstanceNorm2d's statistics: per (sample, tile, channel) the mean over the face and
+ *                          rstd = 1 / sqrt(biased variance + eps), the variance taken about the mean in a second pass, both
+ *                          accumulated in float64 in a fixed order (no atomics); mean / rstd [sample][6][c] float32.
+ *   fv3hip_cyclegan_apply  dst = relu((src - mean) * rstd + bias) + res with every part optional (mean / rstd null: no norm;
+ *                          bias [6][n][n][c] or null; relu 0 / 1; res a slice or null).  dst may be src or res itself.
+ *   fv3hip_cyclegan_input  dst[..., :c] = state + bias ([6][n][n][c] or null); with lon [6][n][n], xyz [6][n][n][3] and theta
+ *                          [n_samples] (DEVICE; all three or none) dst[..., c:c+5] = sin(lon + theta_s), cos(lon + theta_s), x, y, z.
+ */
+#define FV3HIP_CYCLEGAN_CONV_REGULAR 0
+#define FV3HIP_CYCLEGAN_CONV_STRIDED 1
+#define FV3HIP_CYCLEGAN_CONV_TRANSPOSED 2
+#define FV3HIP_CYCLEGAN_HALO_ZEROS 0
+#define FV3HIP_CYCLEGAN_HALO_CUBE 1
+int fv3hip_cyclegan_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, const float *in_mean,
+                         const float *in_rstd, const float *in_bias, int in_relu, const float *w, const float *bias,
+                         const float *out_bias, float *dst, int64_t dst_ld, int64_t dst_off, int64_t dst_sample_stride,
+                         int64_t n_samples, int n, int c_in, int c_out, int kind, int k, int halo_mode, void *stream);
+int fv3hip_cyclegan_stats(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, float *mean, float *rstd,
+                          int64_t n_samples, int n, int c, double eps, void *stream);
+int fv3hip_cyclegan_apply(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, const float *mean,
+                          const float *rstd, const float *bias, int relu, const float *res, int64_t res_ld, int64_t res_off,
+                          int64_t res_sample_stride, float *dst, int64_t dst_ld, int64_t dst_off, int64_t dst_sample_stride,
+                          int64_t n_samples, int n, int c, void *stream);
+int fv3hip_cyclegan_input(const float *state, int64_t state_ld, int64_t state_off, int64_t state_sample_stride, const float *bias,
+                          const float *lon, const float *xyz, const float *theta, float *dst, int64_t dst_ld, int64_t dst_off,
+                          int64_t dst_sample_stride, int64_t n_samples, int n, int c, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
