@@ -17,6 +17,15 @@
 //   transposed  ConvTranspose2d(4, stride 2) of the input padded by one halo line, cropped by 3: per axis output 2 m takes
 //               tap 1 of cell m and tap 3 of cell m - 1, output 2 m + 1 tap 0 of cell m + 1 and tap 2 of cell m; the four
 //               output parities are four 2 x 2 convolutions (gridDim.z) with their own weight blocks
+//
+// A regular convolution may take context channels (fv3hip_cyclegan_conv_context; the step layers of the recurrent generator,
+// recurrent/generator.py:127-182): c_cell per-cell values [6][n][n][c_cell] and c_uni values that are
+// the same on every cell, appended to the source's channels without ever being stored there.  Summation order: the
+// taps x c_in source rows first, exactly as without a context, then the taps x (c_cell + c_uni) context rows (tap slowest,
+// cell channels before uniform ones) as further 16-row chunks into the same accumulators.  A context row is gathered through
+// the same table as the source: the cell context of a halo cell is that of the neighbouring face's cell, the uniform value is
+// present wherever the table names a cell, and both are zero where it names none (corners, zero padding).  The loader's
+// transform does not touch them.
 #include <cmath>
 
 #include "common.h"
@@ -50,6 +59,10 @@ struct ConvArgs {
     int n, n_out, mg;           // input edge, output edge, edge of the grid the rows are flattened over
     int C, N, kind, k, taps, h, cube;
     int64_t rows;               // n_samples * 6 * mg * mg
+    const float *ctx_cell;      // [6][n][n][c_cell] or null
+    const float *ctx_uni;       // [c_ctx - c_cell] or null
+    const float *w_ctx;         // [taps][c_ctx][N]
+    int c_cell, c_ctx;          // per-cell context channels; all context channels
     signed char nbr[24], nax[24], flip[24];
 };
 
@@ -79,8 +92,8 @@ __device__ inline int source_cell(const ConvArgs &a, int t, int x, int y)
 }
 
 // VEC: c_in is a multiple of 16 and every pointer and stride of the source side a multiple of four floats, so a chunk is 16
-// consecutive channels of one tap and a thread loads four of them at once
-template <int NT, bool VEC>
+// consecutive channels of one tap and a thread loads four of them at once.  CTX: context rows follow the source rows
+template <int NT, bool VEC, bool CTX = false>
 __global__ __launch_bounds__(kBlock) void cyclegan_conv_kernel(const ConvArgs a)
 {
     constexpr int AP = kBM + 2;   // the 16 K rows of one loader pass land on 32 distinct banks
@@ -199,6 +212,39 @@ __global__ __launch_bounds__(kBlock) void cyclegan_conv_kernel(const ConvArgs a)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv, wl[kr * NG + nt * 32 + l31], acc[nt], 0, 0, 0);
+        }
+    }
+    if (CTX) {
+        // the context rows: few (45 against 2 304 at the production step layer), so every thread loads single values
+        const int KC = a.taps * a.c_ctx;
+        for (int k0 = 0; k0 < KC; k0 += kRows) {
+            __syncthreads();
+            const int kg = k0 + kk;
+            const int tap = kg < KC ? kg / a.c_ctx : 0, c = kg - tap * a.c_ctx;
+            const bool cell = c < a.c_cell;
+            const float uni = (kg < KC && !cell) ? a.ctx_uni[c - a.c_cell] : 0.f;
+#pragma unroll
+            for (int i = 0; i < kRows * kBM / kBlock; ++i) {
+                const int r = (tid >> 4) + 16 * i;
+                float v = 0.f;
+                const int packed = kg < KC ? sidx[tap * kBM + r] : -1;
+                if (packed >= 0) v = cell ? a.ctx_cell[(int64_t)(packed & 0x0fffffff) * a.c_cell + c] : uni;
+                al[kk * AP + r] = v;
+            }
+            for (int e = tid; e < kRows * NG; e += kBlock) {
+                const int j = e % NG, r = e / NG;
+                const int nn = n0 + j;
+                wl[r * NG + j] = (k0 + r < KC && nn < a.N) ? a.w_ctx[(int64_t)(k0 + r) * a.N + nn] : 0.f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kp = 0; kp < kRows / 2; ++kp) {
+                const int kr = 2 * kp + hh;
+                const float xv = al[kr * AP + wave * 32 + l31];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv, wl[kr * NG + nt * 32 + l31], acc[nt], 0, 0, 0);
+            }
         }
     }
 
@@ -367,13 +413,12 @@ int check_cube(int64_t n_samples, int n)
     return FV3HIP_OK;
 }
 
-}  // namespace
-
-extern "C" int fv3hip_cyclegan_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride,
-                                    const float *in_mean, const float *in_rstd, const float *in_bias, int in_relu, const float *w,
-                                    const float *bias, const float *out_bias, float *dst, int64_t dst_ld, int64_t dst_off,
-                                    int64_t dst_sample_stride, int64_t n_samples, int n, int c_in, int c_out, int kind, int k,
-                                    int halo_mode, void *stream)
+// both convolution entry points: every argument is checked here, before any HIP call
+int launch_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, const float *in_mean,
+                const float *in_rstd, const float *in_bias, int in_relu, const float *w, const float *bias, const float *out_bias,
+                float *dst, int64_t dst_ld, int64_t dst_off, int64_t dst_sample_stride, int64_t n_samples, int n, int c_in, int c_out,
+                int kind, int k, int halo_mode, const float *ctx_cell, int c_cell, const float *ctx_uniform, int c_uni,
+                const float *w_ctx, void *stream)
 {
     FV3HIP_REQUIRE(c_in >= 1 && c_out >= 1 && c_in <= (1 << 16) && c_out <= (1 << 16), "c_in and c_out must be in [1, 2^16], got %d, %d",
                    c_in, c_out);
@@ -400,6 +445,14 @@ extern "C" int fv3hip_cyclegan_conv(const float *src, int64_t src_ld, int64_t sr
         return fail(FV3HIP_EUNSUPPORTED, "unknown convolution kind %d", kind);
     }
     FV3HIP_REQUIRE(h <= n, "the halo (%d cells) is wider than the face (%d)", h, n);
+    FV3HIP_REQUIRE(c_cell >= 0 && c_uni >= 0 && c_cell <= (1 << 12) && c_uni <= (1 << 12),
+                   "c_cell and c_uni must be in [0, 2^12], got %d, %d", c_cell, c_uni);
+    FV3HIP_REQUIRE((ctx_cell != nullptr) == (c_cell > 0), "ctx_cell is %s with c_cell = %d", ctx_cell ? "given" : "null", c_cell);
+    FV3HIP_REQUIRE((ctx_uniform != nullptr) == (c_uni > 0), "ctx_uniform is %s with c_uni = %d", ctx_uniform ? "given" : "null", c_uni);
+    const int c_ctx = c_cell + c_uni;
+    FV3HIP_REQUIRE((w_ctx != nullptr) == (c_ctx > 0), "w_ctx is %s with %d context channels", w_ctx ? "given" : "null", c_ctx);
+    if (c_ctx > 0 && kind != FV3HIP_CYCLEGAN_CONV_REGULAR)
+        return fail(FV3HIP_EUNSUPPORTED, "context channels are built for the regular convolution, got kind %d", kind);
     if ((rc = check_slice("src", src, src_ld, src_off, c_in)) || (rc = check_slice("dst", dst, dst_ld, dst_off, c_out)) ||
         (rc = check_stride("src", &src_sample_stride, n, src_ld)) || (rc = check_stride("dst", &dst_sample_stride, n_out, dst_ld)) ||
         (rc = check_no_alias(Slice{src, src_ld, src_off, src_sample_stride, c_in, n},
@@ -432,6 +485,11 @@ extern "C" int fv3hip_cyclegan_conv(const float *src, int64_t src_ld, int64_t sr
     a.h = h;
     a.cube = halo_mode == FV3HIP_CYCLEGAN_HALO_CUBE ? 1 : 0;
     a.rows = n_samples * 6 * a.mg * a.mg;
+    a.ctx_cell = ctx_cell;
+    a.ctx_uni = ctx_uniform;
+    a.w_ctx = w_ctx;
+    a.c_cell = c_cell;
+    a.c_ctx = c_ctx;
     for (int q = 0; q < 24; ++q) {
         a.nbr[q] = kNbr[q];
         a.nax[q] = kNax[q];
@@ -445,6 +503,17 @@ extern "C" int fv3hip_cyclegan_conv(const float *src, int64_t src_ld, int64_t sr
                      aligned16(in_mean) && aligned16(in_rstd) && aligned16(in_bias);
     const size_t lds = (size_t)taps * kBM * sizeof(int);
     const hipStream_t st = as_stream(stream);
+    if (c_ctx > 0) {
+        if (nt == 1 && vec)
+            hipLaunchKernelGGL((cyclegan_conv_kernel<1, true, true>), grid, dim3(kBlock), lds, st, a);
+        else if (nt == 1)
+            hipLaunchKernelGGL((cyclegan_conv_kernel<1, false, true>), grid, dim3(kBlock), lds, st, a);
+        else if (vec)
+            hipLaunchKernelGGL((cyclegan_conv_kernel<2, true, true>), grid, dim3(kBlock), lds, st, a);
+        else
+            hipLaunchKernelGGL((cyclegan_conv_kernel<2, false, true>), grid, dim3(kBlock), lds, st, a);
+        return check_launch("cyclegan_conv_kernel (context)");
+    }
     if (nt == 1 && vec)
         hipLaunchKernelGGL((cyclegan_conv_kernel<1, true>), grid, dim3(kBlock), lds, st, a);
     else if (nt == 1)
@@ -454,6 +523,30 @@ extern "C" int fv3hip_cyclegan_conv(const float *src, int64_t src_ld, int64_t sr
     else
         hipLaunchKernelGGL((cyclegan_conv_kernel<2, false>), grid, dim3(kBlock), lds, st, a);
     return check_launch("cyclegan_conv_kernel");
+}
+
+}  // namespace
+
+extern "C" int fv3hip_cyclegan_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride,
+                                    const float *in_mean, const float *in_rstd, const float *in_bias, int in_relu, const float *w,
+                                    const float *bias, const float *out_bias, float *dst, int64_t dst_ld, int64_t dst_off,
+                                    int64_t dst_sample_stride, int64_t n_samples, int n, int c_in, int c_out, int kind, int k,
+                                    int halo_mode, void *stream)
+{
+    return launch_conv(src, src_ld, src_off, src_sample_stride, in_mean, in_rstd, in_bias, in_relu, w, bias, out_bias, dst, dst_ld,
+                       dst_off, dst_sample_stride, n_samples, n, c_in, c_out, kind, k, halo_mode, nullptr, 0, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int fv3hip_cyclegan_conv_context(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride,
+                                            const float *in_mean, const float *in_rstd, const float *in_bias, int in_relu,
+                                            const float *w, const float *bias, const float *out_bias, float *dst, int64_t dst_ld,
+                                            int64_t dst_off, int64_t dst_sample_stride, int64_t n_samples, int n, int c_in, int c_out,
+                                            int kind, int k, int halo_mode, const float *ctx_cell, int c_cell,
+                                            const float *ctx_uniform, int c_uni, const float *w_ctx, void *stream)
+{
+    return launch_conv(src, src_ld, src_off, src_sample_stride, in_mean, in_rstd, in_bias, in_relu, w, bias, out_bias, dst, dst_ld,
+                       dst_off, dst_sample_stride, n_samples, n, c_in, c_out, kind, k, halo_mode, ctx_cell, c_cell, ctx_uniform, c_uni,
+                       w_ctx, stream);
 }
 
 extern "C" int fv3hip_cyclegan_stats(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, float *mean,

@@ -22,6 +22,8 @@ from .graph import (GraphHyperparameters, GraphUNetTwin, HipGraphAutoregressor, 
                     state_dict_from_spec, train_graph_model, twin_from_spec)
 from .cyclegan import (GeneratorTwin, HipCycleGAN, cyclegan_spec_from_state_dict, cyclegan_state_dict_from_spec,
                        generator_spec_from_state_dict)
+from .fmr import (HipFullModelReplacement, RecurrentGeneratorTwin, fmr_spec_from_state_dict, fmr_state_dict_from_spec,
+                  recurrent_generator_spec_from_state_dict, recurrent_twin_from_spec)
 from .reservoir import (HybridReservoirComputingModel, HybridReservoirDatasetAdapter, ReservoirComputingModel,
                         ReservoirDatasetAdapter, split_multi_subdomain_model)
 
@@ -36,4 +38,6 @@ __all__ = [
     "GraphHyperparameters", "GraphUNetTwin", "HipGraphAutoregressor", "graph_unet_spec_from_state_dict", "state_dict_from_spec",
     "train_graph_model", "twin_from_spec",
     "GeneratorTwin", "HipCycleGAN", "cyclegan_spec_from_state_dict", "cyclegan_state_dict_from_spec", "generator_spec_from_state_dict",
+    "HipFullModelReplacement", "RecurrentGeneratorTwin", "fmr_spec_from_state_dict", "fmr_state_dict_from_spec",
+    "recurrent_generator_spec_from_state_dict", "recurrent_twin_from_spec",
 ]

@@ -1017,6 +1017,19 @@ int fv3hip_graph_unpack(const float *state, int64_t n_rows, int n, int n_vars, c
  *                          statistics and the bias cell of the face the value lies on; padding zeros stay zero.  Products are
  *                          rounded separately.  The result is acc + bias[c_out] (or null) + out_bias [6][n_out][n_out][c_out]
  *                          (or null), in this order.  ReLU keeps NaN.  Source and destination must not overlap.
+ *   fv3hip_cyclegan_conv_context  fv3hip_cyclegan_conv with context channels (the step layers of the recurrent generator,
+ *                          recurrent/generator.py:127-182): the convolution of the channel-wise concatenation
+ *                          [ T(src) | ctx_cell | ctx_uniform ] with the concatenated weight, where T is the loader's transform
+ *                          above and touches the c_in source channels only.  ctx_cell [6][n][n][c_cell] (or null with
+ *                          c_cell = 0): per-cell values at the INPUT's resolution; ctx_uniform DEVICE [c_uni] (or null with
+ *                          c_uni = 0): one value per channel, the same on every cell of every sample; w_ctx
+ *                          [taps][c_cell + c_uni][c_out]: the weight rows of the context channels, cell channels first.  A tap
+ *                          off the face is resolved as for the source: with _HALO_CUBE the cell context is that of the
+ *                          neighbouring face's cell and the uniform value is present, both are zero at the corners; with
+ *                          _HALO_ZEROS both are zero everywhere off the face.  The taps x c_in source rows are summed first,
+ *                          exactly as fv3hip_cyclegan_conv sums them, then the taps x (c_cell + c_uni) context rows (tap
+ *                          slowest).  _REGULAR only: _STRIDED / _TRANSPOSED with a context return FV3HIP_EUNSUPPORTED.  With
+ *                          c_cell = c_uni = 0 (w_ctx null) it is fv3hip_cyclegan_conv, bit for bit.
  *   fv3hip_cyclegan_stats  nn.InstanceNorm2d's statistics: per (sample, tile, channel) the mean over the face and
  *                          rstd = 1 / sqrt(biased variance + eps), the variance taken about the mean in a second pass, both
  *                          accumulated in float64 in a fixed order (no atomics); mean / rstd [sample][6][c] float32.
@@ -1034,6 +1047,12 @@ int fv3hip_cyclegan_conv(const float *src, int64_t src_ld, int64_t src_off, int6
                          const float *in_rstd, const float *in_bias, int in_relu, const float *w, const float *bias,
                          const float *out_bias, float *dst, int64_t dst_ld, int64_t dst_off, int64_t dst_sample_stride,
                          int64_t n_samples, int n, int c_in, int c_out, int kind, int k, int halo_mode, void *stream);
+int fv3hip_cyclegan_conv_context(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, const float *in_mean,
+                                 const float *in_rstd, const float *in_bias, int in_relu, const float *w, const float *bias,
+                                 const float *out_bias, float *dst, int64_t dst_ld, int64_t dst_off, int64_t dst_sample_stride,
+                                 int64_t n_samples, int n, int c_in, int c_out, int kind, int k, int halo_mode,
+                                 const float *ctx_cell, int c_cell, const float *ctx_uniform, int c_uni, const float *w_ctx,
+                                 void *stream);
 int fv3hip_cyclegan_stats(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, float *mean, float *rstd,
                           int64_t n_samples, int n, int c, double eps, void *stream);
 int fv3hip_cyclegan_apply(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, const float *mean,
