@@ -139,9 +139,52 @@ def torch_layer(kind, k, halo, x, w, bias, transform=None, dtype=torch.float32):
     return y.reshape(S, 6, y.shape[1], y.shape[2], y.shape[3]).permute(0, 1, 3, 4, 2).contiguous().numpy()
 
 
-def device_layer(device, kind, k, halo, x, w, bias, transform=None, out_bias=None, src_off=0, src_width=None, dst_off=0, dst_width=None):
+SENTINEL = -7.0   # what every destination buffer is filled with before a launch
+
+
+def gapped(x, off=0, width=None, gap=0, lead=0, fill=np.nan):
+    """``x`` ``[S, 6, n, n, c]`` laid out for a launch: a flat float32 buffer filled with ``fill`` in which sample ``s``'s cube
+    starts at ``lead + s * (cube + gap)`` and ``x`` sits at channel ``off`` of rows ``width`` wide.  Returns (buffer, ld, stride)."""
+    S, _, n, _, c = x.shape
+    ld = width or c + off
+    cube = 6 * n * n * ld
+    buf = np.full(lead + S * (cube + gap), fill, np.float32)
+    buf[lead:].reshape(S, cube + gap)[:, :cube].reshape(S, 6, n, n, ld)[..., off:off + c] = x
+    return buf, ld, cube + gap
+
+
+def split(buf, S, n, ld, gap=0, lead=0):
+    """The inverse of ``gapped``: (the cubes ``[S, 6, n, n, ld]``, everything outside them as one flat array)."""
+    buf = np.asarray(buf).reshape(-1)
+    cube = 6 * n * n * ld
+    inside = np.zeros(buf.size, bool)
+    for s in range(S):
+        inside[lead + s * (cube + gap):lead + s * (cube + gap) + cube] = True
+    return buf[inside].reshape(S, 6, n, n, ld), buf[~inside]
+
+
+def untouched(a, fill=SENTINEL):
+    """Every element of ``a`` still holds the bits of ``fill``."""
+    return bool(np.all(np.ascontiguousarray(a, np.float32).view(np.uint32) == np.float32(fill).view(np.uint32)))
+
+
+def _up(device, a):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
+
+
+def _ptr(t, lead=0):
+    return None if t is None else t.data_ptr() + 4 * lead
+
+
+def device_layer(device, kind, k, halo, x, w, bias, transform=None, out_bias=None, src_off=0, src_width=None, dst_off=0, dst_width=None,
+                 src_gap=0, dst_gap=0, src_lead=0, dst_lead=0, into=None):
     """One ``fv3hip_cyclegan_conv`` launch.  ``x`` sits at channel ``src_off`` of a NaN-filled buffer ``src_width`` wide, the
-    result goes to channel ``dst_off`` of a buffer ``dst_width`` wide filled with the sentinel -7.  Returns that buffer (numpy)."""
+    result goes to channel ``dst_off`` of a buffer ``dst_width`` wide filled with the sentinel -7.  Returns that buffer (numpy).
+
+    ``src_gap`` / ``dst_gap``: extra floats between consecutive samples (NaN on the source side, the sentinel on the destination
+    side), ``src_lead`` / ``dst_lead``: floats in front of the first sample; the sample stride passed is then ``cube + gap``
+    (0, for "contiguous", when there is neither a gap nor a lead) and the whole flat destination buffer is returned, to be taken
+    apart with ``split``.  ``into``: a flat device tensor to write to in place of a fresh sentinel buffer."""
     from fv3net_amd import _lib
     from fv3net_amd.cyclegan import KINDS, split_transposed_weight
     from fv3net_amd.ops import _stream
@@ -149,33 +192,107 @@ def device_layer(device, kind, k, halo, x, w, bias, transform=None, out_bias=Non
     S, _, n, _, c = x.shape
     c_out = w.shape[1] if kind == "transposed" else w.shape[0]
     n_out = {"regular": n, "strided": n // 2, "transposed": 2 * n}[kind]
-    wide = np.full((S, 6, n, n, src_width or c + src_off), np.nan, np.float32)
-    wide[..., src_off:src_off + c] = x
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
-    src = up(wide)
-    dst = torch.full((S, 6, n_out, n_out, dst_width or c_out + dst_off), -7.0, dtype=torch.float32, device=device)
-    wk = up(split_transposed_weight(w) if kind == "transposed" else np.asarray(w).transpose(2, 3, 1, 0))
+    wide, src_ld, src_ss = gapped(x, src_off, src_width, src_gap, src_lead)
+    flat, dst_ld, dst_ss = gapped(np.full((S, 6, n_out, n_out, c_out), SENTINEL, np.float32), dst_off, dst_width, dst_gap, dst_lead, SENTINEL)
+    src, dst = _up(device, wide), _up(device, flat) if into is None else into
+    wk = _up(device, split_transposed_weight(w) if kind == "transposed" else np.asarray(w).transpose(2, 3, 1, 0))
     mean, rstd, cell_bias, relu = transform or (None, None, None, False)
-    held = [up(a) for a in (mean, rstd, cell_bias, bias, out_bias)]
-    ptr = lambda t: None if t is None else t.data_ptr()
-    _lib.call_on(device, "fv3hip_cyclegan_conv", src.data_ptr(), src.shape[-1], src_off, 0, ptr(held[0]), ptr(held[1]), ptr(held[2]),
-                 int(relu), wk.data_ptr(), ptr(held[3]), ptr(held[4]), dst.data_ptr(), dst.shape[-1], dst_off, 0, S, n, c, c_out,
-                 KINDS[kind], k, _lib.CYCLEGAN_HALO_CUBE if halo else _lib.CYCLEGAN_HALO_ZEROS, _stream(device))
+    held = [_up(device, a) for a in (mean, rstd, cell_bias, bias, out_bias)]
+    plain = lambda gap, lead, t: t is None and gap == 0 and lead == 0
+    _lib.call_on(device, "fv3hip_cyclegan_conv", _ptr(src, src_lead), src_ld, src_off, 0 if plain(src_gap, src_lead, None) else src_ss,
+                 _ptr(held[0]), _ptr(held[1]), _ptr(held[2]), int(relu), wk.data_ptr(), _ptr(held[3]), _ptr(held[4]), _ptr(dst, dst_lead),
+                 dst_ld, dst_off, 0 if plain(dst_gap, dst_lead, into) else dst_ss, S, n, c, c_out, KINDS[kind], k,
+                 _lib.CYCLEGAN_HALO_CUBE if halo else _lib.CYCLEGAN_HALO_ZEROS, _stream(device))
     torch.cuda.synchronize(device)
-    return dst.cpu().numpy()
+    out = dst.cpu().numpy()
+    return out.reshape(S, 6, n_out, n_out, dst_ld) if plain(dst_gap, dst_lead, into) else out
 
 
-def device_stats(device, x, eps=1e-5):
-    """``fv3hip_cyclegan_stats`` on ``x`` ``[S, 6, n, n, c]`` -> (mean, rstd) ``[S, 6, c]`` numpy."""
+def device_stats(device, x, eps=1e-5, src_off=0, src_width=None, src_gap=0):
+    """``fv3hip_cyclegan_stats`` on ``x`` ``[S, 6, n, n, c]`` -> (mean, rstd) ``[S, 6, c]`` numpy.  ``x`` sits at channel
+    ``src_off`` of a NaN-filled buffer ``src_width`` wide with ``src_gap`` NaNs between the samples."""
     from fv3net_amd import _lib
     from fv3net_amd.ops import _stream
 
     S, _, n, _, c = x.shape
-    src = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(device)
-    st = torch.full((2, S, 6, c), -7.0, dtype=torch.float32, device=device)
-    _lib.call_on(device, "fv3hip_cyclegan_stats", src.data_ptr(), c, 0, 0, st[0].data_ptr(), st[1].data_ptr(), S, n, c, eps, _stream(device))
+    wide, ld, ss = gapped(x, src_off, src_width, src_gap)
+    src = _up(device, wide)
+    st = torch.full((2, S, 6, c), SENTINEL, dtype=torch.float32, device=device)
+    _lib.call_on(device, "fv3hip_cyclegan_stats", src.data_ptr(), ld, src_off, ss if src_gap else 0, st[0].data_ptr(), st[1].data_ptr(), S, n,
+                 c, eps, _stream(device))
     torch.cuda.synchronize(device)
     return st[0].cpu().numpy(), st[1].cpu().numpy()
+
+
+def apply_np(x, mean=None, rstd=None, bias=None, relu=False, res=None, dtype=np.float32):
+    """``fv3hip_cyclegan_apply``'s expression in numpy, every step rounded to ``dtype``, in the kernel's order:
+    ``(v - mean) * rstd``, ``+ bias``, ReLU (``v < 0 ? 0 : v``: a NaN stays), ``+ res``.  ``x``, ``res`` ``[S, 6, n, n, c]``,
+    ``mean``, ``rstd`` ``[S, 6, c]``, ``bias`` ``[6, n, n, c]``."""
+    v = np.asarray(x, dtype)
+    if mean is not None:
+        v = (v - np.asarray(mean, dtype)[:, :, None, None]) * np.asarray(rstd, dtype)[:, :, None, None]
+    if bias is not None:
+        v = v + np.asarray(bias, dtype)
+    if relu:
+        v = np.where(v < 0, dtype(0), v)
+    if res is not None:
+        v = v + np.asarray(res, dtype)
+    assert v.dtype == dtype
+    return v
+
+
+def device_apply(device, x, mean=None, rstd=None, bias=None, relu=False, res=None, src_off=0, src_width=None, src_gap=0, res_off=0,
+                 res_width=None, res_gap=0, dst_off=0, dst_width=None, dst_gap=0, in_place=False, res_is_dst=False):
+    """One ``fv3hip_cyclegan_apply`` launch.  ``x`` and ``res`` ``[S, 6, n, n, c]`` sit in NaN-filled buffers of their own
+    (offset, width, gap as in ``device_layer``); the destination is a sentinel-filled one.  ``in_place``: the destination is the
+    source slice itself (the ``dst_*`` arguments are ignored; what surrounds the slice is NaN).  ``res_is_dst``: the residual is
+    what the destination slice holds before the launch (the ``res_*`` arguments are ignored; with ``in_place`` the residual is
+    ``x`` itself and ``res`` is ignored too).  Returns ``split`` of the destination: (cubes ``[S, 6, n, n, ld]``, the gaps)."""
+    from fv3net_amd import _lib
+    from fv3net_amd.ops import _stream
+
+    S, _, n, _, c = x.shape
+    wide, src_ld, src_ss = gapped(x, src_off, src_width, src_gap)
+    src = _up(device, wide)
+    if in_place:
+        dst, dst_ld, dst_off, dst_ss, dst_gap = src, src_ld, src_off, src_ss, src_gap
+    else:
+        first = res if res_is_dst else np.full(x.shape, SENTINEL, np.float32)
+        flat, dst_ld, dst_ss = gapped(first, dst_off, dst_width, dst_gap, fill=SENTINEL)
+        dst = _up(device, flat)
+    if res_is_dst:
+        rbuf, res_ld, res_off, res_ss, res_gap = dst, dst_ld, dst_off, dst_ss, dst_gap
+    elif res is not None:
+        flat, res_ld, res_ss = gapped(res, res_off, res_width, res_gap)
+        rbuf = _up(device, flat)
+    else:
+        rbuf, res_ld, res_off, res_ss, res_gap = None, 0, 0, 0, 0
+    held = [_up(device, a) for a in (mean, rstd, bias)]
+    _lib.call_on(device, "fv3hip_cyclegan_apply", src.data_ptr(), src_ld, src_off, src_ss if src_gap else 0, _ptr(held[0]), _ptr(held[1]),
+                 _ptr(held[2]), int(relu), _ptr(rbuf), res_ld, res_off, res_ss if res_gap else 0, dst.data_ptr(), dst_ld, dst_off,
+                 dst_ss if dst_gap else 0, S, n, c, _stream(device))
+    torch.cuda.synchronize(device)
+    return split(dst.cpu().numpy(), S, n, dst_ld, dst_gap)
+
+
+def device_input(device, x, bias=None, lon=None, xyz=None, theta=None, src_off=0, src_width=None, src_gap=0, dst_off=0, dst_width=None,
+                 dst_gap=0):
+    """One ``fv3hip_cyclegan_input`` launch.  The state ``x`` ``[S, 6, n, n, c]`` sits in a NaN-filled buffer, the ``c`` (with
+    ``lon`` ``[6, n, n]``, ``xyz`` ``[6, n, n, 3]`` and ``theta`` ``[S]``: ``c + 5``) output channels go to channel ``dst_off`` of
+    a sentinel-filled one.  Returns ``split`` of the destination: (cubes ``[S, 6, n, n, ld]``, the gaps)."""
+    from fv3net_amd import _lib
+    from fv3net_amd.ops import _stream
+
+    S, _, n, _, c = x.shape
+    wide, src_ld, src_ss = gapped(x, src_off, src_width, src_gap)
+    c_out = c + (0 if lon is None else 5)
+    flat, dst_ld, dst_ss = gapped(np.full((S, 6, n, n, c_out), SENTINEL, np.float32), dst_off, dst_width, dst_gap, fill=SENTINEL)
+    src, dst = _up(device, wide), _up(device, flat)
+    held = [_up(device, a) for a in (bias, lon, xyz, theta)]
+    _lib.call_on(device, "fv3hip_cyclegan_input", src.data_ptr(), src_ld, src_off, src_ss if src_gap else 0, _ptr(held[0]), _ptr(held[1]),
+                 _ptr(held[2]), _ptr(held[3]), dst.data_ptr(), dst_ld, dst_off, dst_ss if dst_gap else 0, S, n, c, _stream(device))
+    torch.cuda.synchronize(device)
+    return split(dst.cpu().numpy(), S, n, dst_ld, dst_gap)
 
 
 def device_instance_norm(device, x, relu=False, residual=None, in_place=False):

@@ -139,8 +139,10 @@ def torch_context_layer(k, halo, x, w, w_ctx, bias, ctx_cell=None, ctx_uniform=N
 
 
 def device_context_layer(device, k, halo, x, w, w_ctx, bias, ctx_cell=None, ctx_uniform=None, transform=None, kind="regular",
-                         src_off=0, src_width=None):
-    """One ``fv3hip_cyclegan_conv_context`` launch; the result goes to a buffer filled with the sentinel -7.  Returns it (numpy)."""
+                         src_off=0, src_width=None, out_bias=None, src_gap=0, dst_gap=0, dst_off=0, dst_width=None):
+    """One ``fv3hip_cyclegan_conv_context`` launch; the result goes to a buffer filled with the sentinel -7.  Returns it (numpy).
+    ``dst_off`` / ``dst_width`` and ``src_gap`` / ``dst_gap`` as in ``cyclegan_cases.device_layer``: with a ``dst_gap`` the whole
+    flat buffer is returned."""
     from fv3net_amd import _lib
     from fv3net_amd.cyclegan import KINDS
     from fv3net_amd.ops import _stream
@@ -148,18 +150,19 @@ def device_context_layer(device, k, halo, x, w, w_ctx, bias, ctx_cell=None, ctx_
     S, _, n, _, c = x.shape
     c_out = w.shape[0]
     n_out = {"regular": n, "strided": n // 2, "transposed": 2 * n}[kind]
-    wide = np.full((S, 6, n, n, src_width or c + src_off), np.nan, np.float32)
-    wide[..., src_off:src_off + c] = x
+    wide, src_ld, src_ss = cc.gapped(x, src_off, src_width, src_gap)
+    flat, dst_ld, dst_ss = cc.gapped(np.full((S, 6, n_out, n_out, c_out), cc.SENTINEL, np.float32), dst_off, dst_width, dst_gap, fill=cc.SENTINEL)
     up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
-    src = up(wide)
-    dst = torch.full((S, 6, n_out, n_out, c_out), -7.0, dtype=torch.float32, device=device)
+    src, dst = up(wide), up(flat)
     mean, rstd, cell_bias, relu = transform or (None, None, None, False)
-    held = [up(a) for a in (mean, rstd, cell_bias, bias, ctx_cell, ctx_uniform)]
+    held = [up(a) for a in (mean, rstd, cell_bias, bias, ctx_cell, ctx_uniform, out_bias)]
     wk, wc = up(np.asarray(w).transpose(2, 3, 1, 0)), None if w_ctx is None else up(np.asarray(w_ctx).transpose(2, 3, 1, 0))
     ptr = lambda t: None if t is None else t.data_ptr()
-    _lib.call_on(device, "fv3hip_cyclegan_conv_context", src.data_ptr(), src.shape[-1], src_off, 0, ptr(held[0]), ptr(held[1]),
-                 ptr(held[2]), int(relu), wk.data_ptr(), ptr(held[3]), None, dst.data_ptr(), c_out, 0, 0, S, n, c, c_out, KINDS[kind], k,
-                 _lib.CYCLEGAN_HALO_CUBE if halo else _lib.CYCLEGAN_HALO_ZEROS, ptr(held[4]), 0 if ctx_cell is None else ctx_cell.shape[-1],
-                 ptr(held[5]), 0 if ctx_uniform is None else ctx_uniform.shape[-1], ptr(wc), _stream(device))
+    _lib.call_on(device, "fv3hip_cyclegan_conv_context", src.data_ptr(), src_ld, src_off, src_ss if src_gap else 0, ptr(held[0]),
+                 ptr(held[1]), ptr(held[2]), int(relu), wk.data_ptr(), ptr(held[3]), ptr(held[6]), dst.data_ptr(), dst_ld, dst_off,
+                 dst_ss if dst_gap else 0, S, n, c, c_out, KINDS[kind], k, _lib.CYCLEGAN_HALO_CUBE if halo else _lib.CYCLEGAN_HALO_ZEROS,
+                 ptr(held[4]), 0 if ctx_cell is None else ctx_cell.shape[-1], ptr(held[5]), 0 if ctx_uniform is None else ctx_uniform.shape[-1],
+                 ptr(wc), _stream(device))
     torch.cuda.synchronize(device)
-    return dst.cpu().numpy()
+    out = dst.cpu().numpy()
+    return out if dst_gap else out.reshape(S, 6, n_out, n_out, dst_ld)
