@@ -22,6 +22,7 @@ CONV_HALO_INPUT, CONV_HALO_STRIPS, CONV_HALO_CUBE = 0, 1, 2
 ARITH_EXACT, ARITH_FAST = 0, 1
 CYCLEGAN_CONV_REGULAR, CYCLEGAN_CONV_STRIDED, CYCLEGAN_CONV_TRANSPOSED = 0, 1, 2
 CYCLEGAN_HALO_ZEROS, CYCLEGAN_HALO_CUBE = 0, 1
+CODEC_DENSE, CODEC_AFFINE = 0, 1
 ABI_VERSION = 3
 
 OK, EINVAL, EUNSUPPORTED, EHIP, ENOMEM = 0, -1, -2, -3, -4
@@ -166,6 +167,35 @@ class ReservoirDesc(ctypes.Structure):
         ("coefficients", POINTER(c_double)),
         ("intercepts", POINTER(c_double)),
         ("state", POINTER(c_double)),
+    ]
+
+
+class CodecDesc(ctypes.Structure):
+    _fields_ = [
+        ("kind", c_int),
+        ("n_variables", c_int),
+        ("var_nz", POINTER(c_int)),
+        ("n_latent", c_int),
+        ("center", POINTER(c_float)),
+        ("scale", POINTER(c_float)),
+        ("n_enc", c_int),
+        ("enc_units", POINTER(c_int)),
+        ("enc_kernels", POINTER(POINTER(c_float))),
+        ("enc_biases", POINTER(POINTER(c_float))),
+        ("n_dec", c_int),
+        ("dec_units", POINTER(c_int)),
+        ("dec_kernels", POINTER(POINTER(c_float))),
+        ("dec_biases", POINTER(POINTER(c_float))),
+        ("head_kernels", POINTER(POINTER(c_float))),
+        ("head_biases", POINTER(POINTER(c_float))),
+        ("out_min", POINTER(c_float)),
+        ("out_max", POINTER(c_float)),
+        ("mean", POINTER(c_double)),
+        ("std", POINTER(c_double)),
+        ("pca_mean", POINTER(c_double)),
+        ("components", POINTER(c_double)),
+        ("explained_variance", POINTER(c_double)),
+        ("enforce_positive", c_int),
     ]
 
 
@@ -315,6 +345,11 @@ SIGNATURES = {
     "fv3hip_reservoir_get_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fv3hip_reservoir_set_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fv3hip_reservoir_reset_state": (c_int, [c_void_p, c_void_p]),
+    "fv3hip_codec_create": (c_int, [POINTER(CodecDesc), POINTER(c_void_p)]),
+    "fv3hip_codec_destroy": (c_int, [c_void_p]),
+    "fv3hip_codec_encode": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), c_int, c_int, c_void_p,
+                                    c_void_p]),
+    "fv3hip_codec_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_int64), c_void_p]),
     "fv3hip_group_sums_chunk": (c_int, []),
     "fv3hip_group_sums_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "fv3hip_group_sums": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p,

@@ -24,8 +24,9 @@ from .cyclegan import (GeneratorTwin, HipCycleGAN, cyclegan_spec_from_state_dict
                        generator_spec_from_state_dict)
 from .fmr import (HipFullModelReplacement, RecurrentGeneratorTwin, fmr_spec_from_state_dict, fmr_state_dict_from_spec,
                   recurrent_generator_spec_from_state_dict, recurrent_twin_from_spec)
-from .reservoir import (HybridReservoirComputingModel, HybridReservoirDatasetAdapter, ReservoirComputingModel,
-                        ReservoirDatasetAdapter, split_multi_subdomain_model)
+from .reservoir import (DenseAutoencoder, DenseAutoencoderHyperparameters, HybridReservoirComputingModel,
+                        HybridReservoirDatasetAdapter, ReservoirComputingModel, ReservoirDatasetAdapter, SkTransformer,
+                        split_multi_subdomain_model, train_dense_autoencoder)
 
 __all__ = [
     "ChainedDataTransform", "ConstantOutputNoveltyDetector", "DATA_TRANSFORM_REGISTRY", "DataTransform", "MinMaxNoveltyDetector", "NoveltyDetector", "OCSVMNoveltyDetector",
@@ -40,4 +41,5 @@ __all__ = [
     "GeneratorTwin", "HipCycleGAN", "cyclegan_spec_from_state_dict", "cyclegan_state_dict_from_spec", "generator_spec_from_state_dict",
     "HipFullModelReplacement", "RecurrentGeneratorTwin", "fmr_spec_from_state_dict", "fmr_state_dict_from_spec",
     "recurrent_generator_spec_from_state_dict", "recurrent_twin_from_spec",
+    "DenseAutoencoder", "DenseAutoencoderHyperparameters", "SkTransformer", "train_dense_autoencoder",
 ]

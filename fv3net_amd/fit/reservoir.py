@@ -11,10 +11,14 @@ Two behaviours of the reference are kept on purpose: the 
 of the state when ``square_half_hidden_state`` is set (``square_even_terms(state, axis=0)``, model.py:225) where the hybrid
 model squares even state elements (axis -1, model.py:122); and a ``scale-spatial-concat-z`` transformer rejects inputs
 whose (x, y, z) extent differs from its own.  ``get_model_from_subdomain`` gives the sub-model a copy of the parent's
-state row instead of sharing the parent's reservoir object.  ``w_in_storage`` (``reservoir.WIN_AUTO`` / ``WIN_DENSE`` /
-``WIN_CSR``): dense storage, which AUTO picks from half the entries of ``W_in`` stored up, spreads a non-finite input over every
+state row instead of sharing the parent's reservoir object.  Where a transformer is a column codec (``DenseAutoencoder`` /
+``SkTransformer``) the device handle holds a one-variable do-nothing transformer of the latent size in
+its place: ``increment_state`` encodes the inputs into a latent buffer kept with the model and increments from it, ``predict``
+reads out into a float64 latent buffer and decodes it, and hybrid inputs are encoded over the extent without overlap.
+``w_in_storage`` (``reservoir.WIN_AUTO`` / ``WIN_DENSE`` / ``WIN_CSR``): dense storage, which AUTO picks from half the entries of ``W_in`` stored up, spreads a non-finite input over every
 state row of its subdomain where scipy's product reaches only the rows with a stored weight.
 """
+import dataclasses
 import os
 from typing import Hashable, List, Optional, Sequence
 
@@ -23,8 +27,9 @@ import torch
 import yaml
 
 from ..cubedsphere._device import compute_device
-from ..reservoir import (SQUARE_ELEMENTS, SQUARE_NONE, SQUARE_SUBDOMAINS, WIN_AUTO, RankXYDivider, ReservoirModel,
-                         SparseMatrix, _yaml_load, load_transformer)
+from ..reservoir import (SQUARE_ELEMENTS, SQUARE_NONE, SQUARE_SUBDOMAINS, WIN_AUTO, DenseAutoencoder, DoNothingTransformer,
+                         RankXYDivider, ReservoirModel, SkTransformer, SparseMatrix, _yaml_load, is_column_codec,
+                         load_transformer)
 from ..xr_compat import DataArray, Dataset, from_compat, to_compat
 from . import io
 from .predictor import Predictor
@@ -167,6 +172,35 @@ class ReservoirComputingModel(Predictor):
     _n_hybrid = 0
     _hybrid_mask = None
 
+    @staticmethod
+    def _device_transformer(tf):
+        """What the device handle holds for ``tf``: a column codec runs outside it, on its latent."""
+        return DoNothingTransformer([tf.n_latent_dims]) if is_column_codec(tf) else tf
+
+    def _latent(self, name: str, extent, n_latent: int, dtype, device) -> torch.Tensor:
+        """The latent buffer ``name`` of the model, allocated once (a captured graph replays into the same address)."""
+        buffers = self.__dict__.setdefault("_latent_buffers", {})
+        shape = (*extent, n_latent)
+        t = buffers.get(name)
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype or t.device != device:
+            t = buffers[name] = torch.empty(shape, dtype=dtype, device=device)
+        return t
+
+    def _encoded(self, name: str, tf, arrays, extent, device):
+        """The device inputs of the handle: the arrays, or a codec's latent of them."""
+        tensors = [_to_device(a, device) for a in arrays]
+        if not is_column_codec(tf):
+            return tensors
+        return [tf.encode_device(tensors, out=self._latent(name, extent, tf.n_latent_dims, tf.latent_dtype, device))]
+
+    def _readout(self, m: ReservoirModel, hybrid=None) -> List[torch.Tensor]:
+        tf = self.transformers.output
+        if not is_column_codec(tf):
+            return m.predict(hybrid)
+        latent = self._latent("output", self.rank_divider.rank_extent, tf.n_latent_dims, torch.float64, m.device)
+        m.predict(hybrid, outs=[latent])
+        return tf.decode_device(latent)
+
     def _model(self) -> ReservoirModel:
         if self._device_model is None:
             ns = self.rank_divider.n_subdomains
@@ -175,11 +209,13 @@ class ReservoirComputingModel(Predictor):
             state = self.reservoir.state
             mask = self.reservoir.input_mask_array
             self._device_model = ReservoirModel(
-                self.rank_divider, self.transformers.input, self.transformers.output, self.reservoir.W_in,
+                self.rank_divider, self._device_transformer(self.transformers.input),
+                self._device_transformer(self.transformers.output), self.reservoir.W_in,
                 self.reservoir.W_res, c.reshape((ns,) + c.shape[-2:]), b.reshape(ns, b.shape[-1]),
                 square=self._SQUARE if self.square_half_hidden_state else SQUARE_NONE,
                 input_mask=None if mask is None else np.asarray(mask).reshape(-1, self.reservoir.input_size)[-ns:],
-                hybrid_transformer=self.transformers.hybrid, n_hybrid=self._n_hybrid, hybrid_mask=self._hybrid_mask,
+                hybrid_transformer=self._device_transformer(self.transformers.hybrid), n_hybrid=self._n_hybrid,
+                hybrid_mask=self._hybrid_mask,
                 state=None if state is None else np.asarray(state).reshape(ns, -1), w_in_storage=self.w_in_storage,
                 device=compute_device())
         return self._device_model
@@ -205,7 +241,7 @@ class ReservoirComputingModel(Predictor):
         arrays = [_as_xyz(a) for a in prediction_with_overlap]
         self._check_inputs(arrays, self.transformers.input, self.rank_divider.overlap_rank_extent)
         m = self._model()
-        m.increment([_to_device(a, m.device) for a in arrays])
+        m.increment(self._encoded("input", self.transformers.input, arrays, self.rank_divider.overlap_rank_extent, m.device))
 
     def synchronize(self, synchronization_time_series: Sequence) -> None:
         """Reset, then one increment per time step of the [time, x, y, z] arrays."""
@@ -221,7 +257,7 @@ class ReservoirComputingModel(Predictor):
     def predict(self, device_output: bool = False):
         """The decoded readout of the current state: one (x, y, z) array per output variable (numpy unless
         ``device_output``)."""
-        return self._outputs(self._model().predict(), device_output)
+        return self._outputs(self._readout(self._model()), device_output)
 
     def get_model_from_subdomain(self, subdomain_index: int) -> "ReservoirComputingModel":
         """A model of subdomain ``subdomain_index`` alone, starting from that subdomain's current state."""
@@ -294,7 +330,8 @@ class HybridReservoirComputingModel(ReservoirComputingModel):
         arrays = [_as_xyz(a) for a in hybrid_input]
         self._check_inputs(arrays, self.transformers.hybrid, self.rank_divider.rank_extent)
         m = self._model()
-        outs = m.predict([_to_device(a, m.device) for a in arrays])
+        outs = self._readout(m, self._encoded("hybrid", self.transformers.hybrid, arrays, self.rank_divider.rank_extent,
+                                              m.device))
         return self._outputs(outs, _is_device(arrays) if device_output is None else device_output)
 
     def _sub_model(self, reservoir, readout, divider, subdomain_index):
@@ -424,3 +461,98 @@ def split_multi_subdomain_model(model) -> list:
     """One single-subdomain model per subdomain (adapters.py:240-255)."""
     divider = model.model.rank_divider if isinstance(model, ReservoirDatasetAdapter) else model.rank_divider
     return [model.get_model_from_subdomain(i) for i in range(divider.n_subdomains)]
+
+
+# ---------------------------------------------------------------------------------------------
+# the column codecs as artifacts of their own; their predict is the round trip (SkTransformer.predict, and the
+# DatasetPredictor that the reference's train_dense_autoencoder returns)
+# ---------------------------------------------------------------------------------------------
+
+io.register("hip-dense-autoencoder")(DenseAutoencoder)
+io.register("hip-sk-transformer")(SkTransformer)
+
+
+@dataclasses.dataclass
+class DenseAutoencoderHyperparameters:
+    """The fields of fv3fit's ``DenseAutoencoderHyperparameters`` (autoencoder.py:95-127) that shape the graph and its
+    training; ``output_limits`` maps a variable to its (min, max), either of them None."""
+
+    state_variables: Sequence[str]
+    latent_dim_size: int = 10
+    units: int = 20
+    n_dense_layers: int = 2
+    epochs: int = 10
+    batch_size: int = 512
+    learning_rate: float = 1e-3
+    normalization_fit_samples: int = 500_000
+    output_limits: dict = dataclasses.field(default_factory=dict)
+    seed: int = 0
+
+
+def train_dense_autoencoder(hyperparameters: DenseAutoencoderHyperparameters, arrays: Sequence[np.ndarray],
+                            device: Optional[str] = None) -> DenseAutoencoder:
+    """The counterpart of the reference's ``"dense_autoencoder"`` training function (autoencoder.py:179-275), offline in plain
+    torch: ``arrays`` holds one [sample, z] array per state variable.  The normalisation constants are the per-feature mean
+    and standard deviation of up to ``normalization_fit_samples`` samples, in float32; the graph is ``n_dense_layers``
+    ReLU layers of ``units`` and a ReLU latent layer of ``latent_dim_size``, the same number of ReLU layers back and one
+    linear head per variable (glorot-uniform kernels, zero biases, as Keras initialises a Dense layer); the loss is the MSE
+    of the standardised outputs summed over the variables, minimised by Adam from ``seed``.  The output limits are applied
+    at prediction only.  The callbacks and validation batches of the reference are out of scope."""
+    hp = hyperparameters
+    arrays = [np.asarray(a, np.float32) for a in arrays]
+    if len(arrays) != len(hp.state_variables) or any(a.ndim != 2 or a.shape[0] != arrays[0].shape[0] for a in arrays):
+        raise ValueError("arrays must hold one [sample, z] array per state variable, with a common sample count")
+    torch.manual_seed(hp.seed)
+    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    sizes = [a.shape[1] for a in arrays]
+    x = np.concatenate(arrays, axis=1)
+    nfit = hp.normalization_fit_samples
+    center = x[:nfit].mean(axis=0, dtype=np.float32)
+    scale = x[:nfit].std(axis=0, dtype=np.float32)
+    xn = torch.from_numpy((x - center) / (scale + np.float32(1e-7))).to(dev)
+
+    def dense(fan_in, fan_out):
+        lin = torch.nn.Linear(fan_in, fan_out)
+        torch.nn.init.xavier_uniform_(lin.weight)
+        torch.nn.init.zeros_(lin.bias)
+        return lin
+
+    widths = [hp.units] * hp.n_dense_layers
+    enc, fan = [], x.shape[1]
+    for w in widths + [hp.latent_dim_size]:
+        enc.append(dense(fan, w))
+        fan = w
+    dec = []
+    for w in widths:
+        dec.append(dense(fan, w))
+        fan = w
+    heads = [dense(fan, nz) for nz in sizes]
+    modules = torch.nn.ModuleList(enc + dec + heads).to(dev)
+
+    def forward(batch):
+        h = batch
+        for lin in enc + dec:
+            h = torch.relu(lin(h))
+        return torch.cat([head(h) for head in heads], dim=1)
+
+    opt = torch.optim.Adam(modules.parameters(), lr=hp.learning_rate)
+    n = xn.shape[0]
+    gen = torch.Generator().manual_seed(hp.seed)
+    for _ in range(hp.epochs):
+        order = torch.randperm(n, generator=gen).to(dev)
+        for start in range(0, n, hp.batch_size):
+            batch = xn[order[start:start + hp.batch_size]]
+            # the heads give standardised values, so the std-scaled MSE of each variable is its plain MSE here
+            err = (forward(batch) - batch) ** 2
+            loss = sum(part.mean() for part in torch.split(err, sizes, dim=1))
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+
+    kernel = lambda lin: lin.weight.detach().cpu().numpy().T.copy()  # noqa: E731  ([in, out] as Keras stores it)
+    bias = lambda lin: lin.bias.detach().cpu().numpy().copy()  # noqa: E731
+    limits = [hp.output_limits.get(v, (None, None)) for v in hp.state_variables]
+    return DenseAutoencoder(center, scale, sizes, [kernel(m) for m in enc], [bias(m) for m in enc],
+                            [kernel(m) for m in dec], [bias(m) for m in dec], [kernel(m) for m in heads],
+                            [bias(m) for m in heads], output_min=[lo for lo, _ in limits],
+                            output_max=[hi for _, hi in limits])

@@ -1,6 +1,7 @@
 """Reservoir computing: the rank divider, the transformers, the sparse weight files and the device handle.
 
-``RankXYDivider`` is the subdomain index arithmetic of fv3fit's ``reservoir/domain2.py`` (numpy only; pace's
+``DenseAutoencoder`` and ``SkTransformer`` are the two transformers that reduce the dimension of a column, on the GPU
+(``csrc/codec.hip``).  ``RankXYDivider`` is the subdomain index arithmetic of fv3fit's ``reservoir/domain2.py`` (numpy only; pace's
 ``TilePartitioner`` is replaced by its closed form: subdomain ``s`` covers x block ``s % layout_x`` and y block
 ``s // layout_x``).  ``DoNothingTransformer`` and ``ScaleSpatialConcatZTransformer`` read and write the reference's
 transformer directories.  ``SparseMatrix`` reads and writes ``scipy.sparse.save_npz`` files with numpy alone.
@@ -269,7 +270,390 @@ class ScaleSpatialConcatZTransformer:
                    config["num_variables"], mask=mask)
 
 
-# the reference's other transformer types, by a file each writes; they need TensorFlow or pickled code
+# ---------------------------------------------------------------------------------------------
+# column codecs: the transformers that reduce the dimension of a column (csrc/codec.hip)
+# ---------------------------------------------------------------------------------------------
+
+
+def _npz_load(path):
+    with np.load(path, allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
+
+
+class _ColumnCodec:
+    """What the two column codecs share: the device handle (``fv3hip_codec_t``, created on first use) and the four entry
+    points.  ``encode`` / ``decode`` take arrays whose last dimension is the feature dimension, ``encode_unstacked_xyz`` /
+    ``decode_unstacked_xyz`` take (x, y, z) arrays; all four return numpy for numpy and device tensors for device tensors.
+    There is no host path: the arithmetic runs in the HIP kernels."""
+
+    is_column_codec = True
+    kind = None  # not a transformer the reservoir handle knows: the model classes put a do-nothing transformer in its place
+    latent_dtype = torch.float32
+    output_dtype = torch.float32
+    original_feature_sizes: List[int]
+
+    @property
+    def n_variables(self) -> int:
+        return len(self.original_feature_sizes)
+
+    @property
+    def n_features(self) -> int:
+        return sum(self.original_feature_sizes)
+
+    def check_inputs(self, shapes: Sequence[Tuple[int, ...]]):
+        if len(shapes) != self.n_variables:
+            raise ValueError(f"Expected {self.n_variables} input arrays but got {len(shapes)}")
+        for i, (shape, nz) in enumerate(zip(shapes, self.original_feature_sizes)):
+            if len(shape) == 0 or shape[-1] != nz:
+                raise ValueError(f"input array {i} has shape {tuple(shape)}, its feature dimension must be {nz}")
+
+    # -- device ----------------------------------------------------------------------------------
+    def _fill(self, d, keep):
+        raise NotImplementedError
+
+    def _handle_on(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} needs a 'cuda' (ROCm) device; there is no CPU fallback")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        handles = self.__dict__.setdefault("_handles", {})
+        if device.index not in handles:
+            keep = []
+            d = _lib.CodecDesc()
+            d.n_variables = self.n_variables
+            nz = np.asarray(self.original_feature_sizes, np.intc)
+            keep.append(nz)
+            d.var_nz = _ptr(nz, ctypes.c_int)
+            d.n_latent = self.n_latent_dims
+            self._fill(d, keep)
+            h = ctypes.c_void_p()
+            with torch.cuda.device(device):
+                _require_device(torch.empty(1, device=device))
+                _lib.call("fv3hip_codec_create", ctypes.byref(d), ctypes.byref(h))
+            handles[device.index] = h
+        return handles[device.index]
+
+    def encode_device(self, tensors: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(x, y, z) device arrays, float32 or float64 and strided as they come, to the latent [x, y, n_latent] (written
+        into ``out`` when given: contiguous, of ``latent_dtype``).  One launch; nothing is allocated beside ``out``."""
+        self.check_inputs([tuple(t.shape) for t in tensors])
+        dev = _require_device(*tensors)
+        nx, ny = int(tensors[0].shape[0]), int(tensors[0].shape[1])
+        for i, t in enumerate(tensors):
+            if t.dim() != 3 or tuple(t.shape[:2]) != (nx, ny):
+                raise ValueError(f"input array {i} has shape {tuple(t.shape)}, expected ({nx}, {ny}, z)")
+        if out is None:
+            out = torch.empty((nx, ny, self.n_latent_dims), dtype=self.latent_dtype, device=dev)
+        elif (tuple(out.shape) != (nx, ny, self.n_latent_dims) or out.dtype != self.latent_dtype
+              or not out.is_contiguous()):
+            raise ValueError(f"the latent buffer must be a contiguous {self.latent_dtype} array of shape "
+                             f"{(nx, ny, self.n_latent_dims)}")
+        _lib.call_on(dev, "fv3hip_codec_encode", self._handle_on(dev), *ReservoirModel._sources(tensors), nx, ny,
+                     out.data_ptr(), _stream(dev))
+        return out
+
+    def decode_device(self, latent: torch.Tensor, outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+        """The latent [x, y, n_latent] (float32 or float64, contiguous) to one (x, y, z) array of ``output_dtype`` per variable
+        (written into ``outs`` when given, strided as they come)."""
+        dev = _require_device(latent)
+        if latent.dim() != 3 or latent.shape[-1] != self.n_latent_dims:
+            raise ValueError(f"the latent must have shape (x, y, {self.n_latent_dims}), got {tuple(latent.shape)}")
+        if latent.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"the latent must be float32 or float64, got {latent.dtype}")
+        latent = latent.contiguous()
+        nx, ny = int(latent.shape[0]), int(latent.shape[1])
+        if outs is None:
+            outs = [torch.empty((nx, ny, nz), dtype=self.output_dtype, device=dev) for nz in self.original_feature_sizes]
+        for i, (t, nz) in enumerate(zip(outs, self.original_feature_sizes)):
+            if tuple(t.shape) != (nx, ny, nz) or t.dtype != self.output_dtype:
+                raise ValueError(f"output array {i} must be {self.output_dtype} of shape {(nx, ny, nz)}")
+        _require_device(*outs)
+        k = len(outs)
+        _lib.call_on(dev, "fv3hip_codec_decode", self._handle_on(dev), latent.data_ptr(),
+                     _lib.F64 if latent.dtype == torch.float64 else _lib.F32, nx, ny,
+                     (ctypes.c_void_p * k)(*[t.data_ptr() for t in outs]),
+                     (ctypes.c_int64 * (3 * k))(*[s for t in outs for s in t.stride()]), _stream(dev))
+        return list(outs)
+
+    @staticmethod
+    def _default_device():
+        from .cubedsphere._device import compute_device
+
+        return compute_device()
+
+    def encode_unstacked_xyz(self, arrays: Sequence):
+        if all(isinstance(a, torch.Tensor) and a.is_cuda for a in arrays):
+            return self.encode_device(list(arrays))
+        dev = self._default_device()
+        return self.encode_device([torch.as_tensor(np.asarray(a)).to(dev) for a in arrays]).cpu().numpy()
+
+    def decode_unstacked_xyz(self, latent):
+        if isinstance(latent, torch.Tensor) and latent.is_cuda:
+            return self.decode_device(latent)
+        return [t.cpu().numpy() for t in self.decode_device(torch.as_tensor(np.asarray(latent)).to(self._default_device()))]
+
+    def encode(self, arrays: Sequence):
+        """Arrays [..., z_v] with the same leading dimensions to the latent [..., n_latent]."""
+        self.check_inputs([tuple(a.shape) for a in arrays])
+        lead = tuple(arrays[0].shape[:-1])
+        out = self.encode_unstacked_xyz([a.reshape(-1, 1, a.shape[-1]) for a in arrays])
+        return out.reshape(lead + (self.n_latent_dims,))
+
+    def decode(self, latent):
+        lead = tuple(latent.shape[:-1])
+        outs = self.decode_unstacked_xyz(latent.reshape(-1, 1, latent.shape[-1]))
+        return [o.reshape(lead + (o.shape[-1],)) for o in outs]
+
+    def predict(self, arrays: Sequence):
+        """The round trip ``decode(encode(arrays))``, as the reference's ``SkTransformer.predict``: what the codec loses."""
+        return self.decode(self.encode(arrays))
+
+    def __del__(self):
+        for h in self.__dict__.get("_handles", {}).values():
+            try:
+                _lib.load().fv3hip_codec_destroy(h)
+            except Exception:
+                pass
+
+
+def _f32_list(arrays, what):
+    out = [np.ascontiguousarray(a, np.float32) for a in arrays]
+    for a in out:
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{what} must be finite")
+    return out
+
+
+class DenseAutoencoder(_ColumnCodec):
+    """fv3fit's ``"dense-autoencoder"`` transformer as plain arrays (``dense_autoencoder.yaml`` + ``weights.npz``), float32
+    throughout as Keras computes it.
+
+    encode: ``(x - center) / (scale + 1e-7)`` per feature of the concatenated column, then ``relu(h @ W + b)`` per encoder
+    layer (kernels [in, out] as Keras stores them); the last encoder layer is the latent layer and is a ReLU too.  decode:
+    the decoder's ReLU layers, one linear head per variable, ``y * scale + center`` and the optional output limits
+    (``output_min`` / ``output_max`` per variable, None: no limit; below min -> min, at or above max -> max, NaN stays).
+    Without encoder layers it is the reference's "concat and scale only" form (no decoder layers, no heads).
+
+    There is no ``from_keras``: a TF SavedModel cannot be read without TensorFlow, and the normalisation constants are graph
+    constants that ``get_weights()`` does not return.  INTEGRATION.md shows the export."""
+
+    CONFIG_NAME = "dense_autoencoder.yaml"
+    WEIGHTS_NAME = "weights.npz"
+    latent_dtype = torch.float32
+    output_dtype = torch.float32
+    MAX_VARIABLES, MAX_FEATURES, MAX_WIDTH, MAX_LAYERS = 16, 1024, 256, 8
+
+    def __init__(self, center, scale, original_feature_sizes: Sequence[int], encoder_kernels=(), encoder_biases=(),
+                 decoder_kernels=(), decoder_biases=(), head_kernels=(), head_biases=(), output_min=None, output_max=None):
+        self.original_feature_sizes = [int(v) for v in original_feature_sizes]
+        k = self.n_features
+        self.center = np.ascontiguousarray(np.asarray(center).reshape(-1), np.float32)
+        self.scale = np.ascontiguousarray(np.asarray(scale).reshape(-1), np.float32)
+        if self.center.size != k or self.scale.size != k:
+            raise ValueError(f"center and scale need {k} values (the sum of original_feature_sizes), got "
+                             f"{self.center.size} and {self.scale.size}")
+        self.encoder_kernels = _f32_list(encoder_kernels, "encoder kernels")
+        self.encoder_biases = _f32_list(encoder_biases, "encoder biases")
+        self.decoder_kernels = _f32_list(decoder_kernels, "decoder kernels")
+        self.decoder_biases = _f32_list(decoder_biases, "decoder biases")
+        self.head_kernels = _f32_list(head_kernels, "head kernels")
+        self.head_biases = _f32_list(head_biases, "head biases")
+        n = self.n_variables
+        self.output_min = [None] * n if output_min is None else [None if v is None else float(v) for v in output_min]
+        self.output_max = [None] * n if output_max is None else [None if v is None else float(v) for v in output_max]
+        if len(self.output_min) != n or len(self.output_max) != n:
+            raise ValueError(f"output_min and output_max need one entry per variable ({n})")
+        for lo, hi in zip(self.output_min, self.output_max):
+            if lo is not None and hi is not None and hi <= lo:
+                raise ValueError(f"max value ({hi}) must be greater than min value ({lo}).")
+        self._check_chain()
+
+    def _check_chain(self):
+        k = self.n_features
+        if not self.encoder_kernels:
+            if self.decoder_kernels or self.head_kernels:
+                raise ValueError("an autoencoder without encoder layers (concat and scale only) has no decoder layers or heads")
+            return
+
+        def chain(side, width, kernels, biases):
+            if len(kernels) != len(biases):
+                raise ValueError(f"{side}: {len(kernels)} kernels but {len(biases)} biases")
+            for i, (w, b) in enumerate(zip(kernels, biases)):
+                if w.ndim != 2 or w.shape[0] != width or b.shape != (w.shape[1],):
+                    raise ValueError(f"{side} layer {i}: kernel {w.shape} / bias {b.shape} do not follow an input of "
+                                     f"width {width}")
+                width = w.shape[1]
+            return width
+
+        latent = chain("encoder", k, self.encoder_kernels, self.encoder_biases)
+        width = chain("decoder", latent, self.decoder_kernels, self.decoder_biases)
+        if len(self.head_kernels) != self.n_variables or len(self.head_biases) != self.n_variables:
+            raise ValueError(f"need one head per variable ({self.n_variables}), got {len(self.head_kernels)} kernels and "
+                             f"{len(self.head_biases)} biases")
+        for v, (w, b, nz) in enumerate(zip(self.head_kernels, self.head_biases, self.original_feature_sizes)):
+            if w.shape != (width, nz) or b.shape != (nz,):
+                raise ValueError(f"head {v}: kernel {w.shape} / bias {b.shape}, expected {(width, nz)} / {(nz,)}")
+
+    @property
+    def n_latent_dims(self) -> int:
+        return int(self.encoder_kernels[-1].shape[1]) if self.encoder_kernels else self.n_features
+
+    def _fill(self, d, keep):
+        d.kind = _lib.CODEC_DENSE
+        d.center, d.scale = _ptr(self.center, ctypes.c_float), _ptr(self.scale, ctypes.c_float)
+
+        def pointers(arrays):
+            arr = (ctypes.POINTER(ctypes.c_float) * max(len(arrays), 1))(*[_ptr(a, ctypes.c_float) for a in arrays])
+            keep.append(arr)
+            return arr
+
+        def units(kernels):
+            u = np.asarray([w.shape[1] for w in kernels], np.intc)
+            keep.append(u)
+            return _ptr(u, ctypes.c_int)
+
+        d.n_enc, d.n_dec = len(self.encoder_kernels), len(self.decoder_kernels)
+        if d.n_enc:
+            d.enc_units, d.enc_kernels, d.enc_biases = (units(self.encoder_kernels), pointers(self.encoder_kernels),
+                                                        pointers(self.encoder_biases))
+            d.head_kernels, d.head_biases = pointers(self.head_kernels), pointers(self.head_biases)
+        if d.n_dec:
+            d.dec_units, d.dec_kernels, d.dec_biases = (units(self.decoder_kernels), pointers(self.decoder_kernels),
+                                                        pointers(self.decoder_biases))
+        for name, bounds in (("out_min", self.output_min), ("out_max", self.output_max)):
+            if any(v is not None for v in bounds):
+                a = np.asarray([np.nan if v is None else v for v in bounds], np.float32)
+                keep.append(a)
+                setattr(d, name, _ptr(a, ctypes.c_float))
+
+    def dump(self, path: str) -> None:
+        os.makedirs(path, exist_ok=True)
+        with open(os.path.join(path, self.CONFIG_NAME), "w") as f:
+            yaml.safe_dump({"original_feature_sizes": self.original_feature_sizes,
+                            "n_encoder_layers": len(self.encoder_kernels), "n_decoder_layers": len(self.decoder_kernels),
+                            "output_min": self.output_min, "output_max": self.output_max}, f)
+        arrays = {"center": self.center, "scale": self.scale}
+        for prefix, ws, bs in (("encoder", self.encoder_kernels, self.encoder_biases),
+                               ("decoder", self.decoder_kernels, self.decoder_biases),
+                               ("head", self.head_kernels, self.head_biases)):
+            for i, (w, b) in enumerate(zip(ws, bs)):
+                arrays[f"{prefix}_kernel_{i}"], arrays[f"{prefix}_bias_{i}"] = w, b
+        with open(os.path.join(path, self.WEIGHTS_NAME), "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, path: str) -> "DenseAutoencoder":
+        with open(os.path.join(path, cls.CONFIG_NAME)) as f:
+            config = _yaml_load(f.read())
+        z = _npz_load(os.path.join(path, cls.WEIGHTS_NAME))
+        n_enc, n_dec = config["n_encoder_layers"], config["n_decoder_layers"]
+        n_head = len(config["original_feature_sizes"]) if n_enc else 0
+        pick = lambda prefix, what, n: [z[f"{prefix}_{what}_{i}"] for i in range(n)]  # noqa: E731
+        return cls(z["center"], z["scale"], config["original_feature_sizes"], pick("encoder", "kernel", n_enc),
+                   pick("encoder", "bias", n_enc), pick("decoder", "kernel", n_dec), pick("decoder", "bias", n_dec),
+                   pick("head", "kernel", n_head), pick("head", "bias", n_head), config.get("output_min"),
+                   config.get("output_max"))
+
+
+class SkTransformer(_ColumnCodec):
+    """fv3fit's ``"sk-transformer"`` (``StandardScaler`` + ``PCA``) as plain arrays (``sk_transformer.yaml`` +
+    ``arrays.npz``), float64 throughout.
+
+    encode: ``z = (((x - scaler_mean) / scaler_scale) - pca_mean) @ components.T``, divided by
+    ``sqrt(explained_variance)`` when the PCA whitens.  decode: ``z @ components`` (row j times
+    ``sqrt(explained_variance[j])`` when it whitens) ``+ pca_mean``, times ``scaler_scale`` plus ``scaler_mean``; with
+    ``enforce_positive_outputs`` then ``np.where(decoded >= 0, decoded, 0.0)``, which turns a NaN into 0.0 as the
+    reference's does.  ``scaler_mean`` / ``scaler_scale`` of None are ``with_mean=False`` / ``with_std=False``.
+
+    Two deliberate differences from the reference: sklearn keeps an all-float32 pack in float32 where this codec always
+    computes in float64 (float32 sources are widened first, the outputs are float64); and ``original_feature_sizes`` is
+    required here, where the reference sets it on the first ``encode``, because ``decode`` and the reservoir's rank divider
+    need it before any data has been seen."""
+
+    CONFIG_NAME = "sk_transformer.yaml"
+    ARRAYS_NAME = "arrays.npz"
+    latent_dtype = torch.float64
+    output_dtype = torch.float64
+
+    def __init__(self, components, pca_mean, original_feature_sizes: Sequence[int], explained_variance=None,
+                 scaler_mean=None, scaler_scale=None, enforce_positive_outputs: bool = False):
+        if original_feature_sizes is None:
+            raise ValueError("original_feature_sizes is required (the reference sets it on the first encode)")
+        self.original_feature_sizes = [int(v) for v in original_feature_sizes]
+        k = self.n_features
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)  # noqa: E731
+        self.components, self.pca_mean = f64(components), f64(pca_mean).reshape(-1)
+        self.explained_variance = f64(explained_variance)
+        self.scaler_mean, self.scaler_scale = f64(scaler_mean), f64(scaler_scale)
+        self.enforce_positive_outputs = bool(enforce_positive_outputs)
+        if self.components.ndim != 2 or self.components.shape[1] != k or self.pca_mean.shape != (k,):
+            raise ValueError(f"components {self.components.shape} / pca_mean {self.pca_mean.shape} do not match the "
+                             f"{k} features of original_feature_sizes")
+        for name, a, n in (("explained_variance", self.explained_variance, self.components.shape[0]),
+                           ("scaler_mean", self.scaler_mean, k), ("scaler_scale", self.scaler_scale, k)):
+            if a is not None and a.shape != (n,):
+                raise ValueError(f"{name} needs shape {(n,)}, got {a.shape}")
+
+    @property
+    def n_latent_dims(self) -> int:
+        return int(self.components.shape[0])
+
+    @classmethod
+    def from_sklearn(cls, transformer, scaler, enforce_positive_outputs: bool = False,
+                     original_feature_sizes: Optional[Sequence[int]] = None) -> "SkTransformer":
+        """From a fitted ``sklearn.decomposition.PCA`` (whitened or not) and ``StandardScaler``, by their attributes alone
+        (sklearn is not imported).  Any other transformer is refused by its type."""
+        if type(transformer).__name__ != "PCA" or not hasattr(transformer, "components_"):
+            raise ValueError(f"transformer of type '{type(transformer).__name__}' is not supported: only a fitted "
+                             "sklearn.decomposition.PCA is")
+        if type(scaler).__name__ != "StandardScaler" or not hasattr(scaler, "n_features_in_"):
+            raise ValueError(f"scaler of type '{type(scaler).__name__}' is not supported: only a fitted "
+                             "sklearn.preprocessing.StandardScaler is")
+        if original_feature_sizes is None:
+            raise ValueError("original_feature_sizes is required (the reference sets it on the first encode)")
+        return cls(transformer.components_, transformer.mean_, original_feature_sizes,
+                   explained_variance=transformer.explained_variance_ if transformer.whiten else None,
+                   scaler_mean=scaler.mean_ if scaler.with_mean else None,
+                   scaler_scale=scaler.scale_ if scaler.with_std else None,
+                   enforce_positive_outputs=enforce_positive_outputs)
+
+    def _fill(self, d, keep):
+        d.kind = _lib.CODEC_AFFINE
+        d.pca_mean, d.components = _ptr(self.pca_mean, ctypes.c_double), _ptr(self.components, ctypes.c_double)
+        for name, a in (("mean", self.scaler_mean), ("std", self.scaler_scale),
+                        ("explained_variance", self.explained_variance)):
+            if a is not None:
+                setattr(d, name, _ptr(a, ctypes.c_double))
+        d.enforce_positive = int(self.enforce_positive_outputs)
+
+    def dump(self, path: str) -> None:
+        os.makedirs(path, exist_ok=True)
+        with open(os.path.join(path, self.CONFIG_NAME), "w") as f:
+            yaml.safe_dump({"original_feature_sizes": self.original_feature_sizes,
+                            "enforce_positive_outputs": self.enforce_positive_outputs}, f)
+        arrays = {"components": self.components, "pca_mean": self.pca_mean}
+        for name in ("explained_variance", "scaler_mean", "scaler_scale"):
+            if getattr(self, name) is not None:
+                arrays[name] = getattr(self, name)
+        with open(os.path.join(path, self.ARRAYS_NAME), "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, path: str) -> "SkTransformer":
+        with open(os.path.join(path, cls.CONFIG_NAME)) as f:
+            config = _yaml_load(f.read())
+        z = _npz_load(os.path.join(path, cls.ARRAYS_NAME))
+        return cls(z["components"], z["pca_mean"], config["original_feature_sizes"],
+                   explained_variance=z.get("explained_variance"), scaler_mean=z.get("scaler_mean"),
+                   scaler_scale=z.get("scaler_scale"), enforce_positive_outputs=config["enforce_positive_outputs"])
+
+
+def is_column_codec(tf) -> bool:
+    return bool(getattr(tf, "is_column_codec", False))
+
+
+# the reference's own files of those two types; they need TensorFlow or pickled code
 _FOREIGN_TRANSFORMERS = (("encoder.tf", "dense-autoencoder"), ("decoder.tf", "dense-autoencoder"),
                          ("sk_transformer.pkl", "sk-transformer"), ("sk_scaler.pkl", "sk-transformer"))
 
@@ -280,6 +664,9 @@ def load_transformer(path: str):
         return DoNothingTransformer.load(path)
     if os.path.exists(os.path.join(path, ScaleSpatialConcatZTransformer.CONFIG_NAME)):
         return ScaleSpatialConcatZTransformer.load(path)
+    for codec in (DenseAutoencoder, SkTransformer):
+        if os.path.exists(os.path.join(path, codec.CONFIG_NAME)):
+            return codec.load(path)
     name = None
     if os.path.exists(os.path.join(path, "name")):
         with open(os.path.join(path, "name")) as f:
@@ -289,7 +676,9 @@ def load_transformer(path: str):
             name = kind
     if name is not None:
         raise ValueError(f"transformer of type '{name}' in {path} is not supported: it needs the reference's "
-                         "TensorFlow/sklearn stack; supported: do-nothing-transformer, scale-spatial-concat-z-transformer")
+                         "TensorFlow/sklearn stack; supported: do-nothing-transformer, scale-spatial-concat-z-transformer, "
+                         "and the array exports of the other two (DenseAutoencoder / SkTransformer.from_sklearn, "
+                         "INTEGRATION.md)")
     raise ValueError(f"{path} holds no transformer this package can read")
 
 
@@ -504,13 +893,21 @@ class ReservoirModel:
         dev = _require_device(*inputs)
         _lib.call_on(dev, "fv3hip_reservoir_increment", self._handle, *self._sources(inputs), _stream(dev))
 
-    def predict(self, hybrid_inputs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    def predict(self, hybrid_inputs: Optional[Sequence[torch.Tensor]] = None,
+                outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
         """The readout decoded into one (x, y, z) device array per output variable (float32 for a scale-spatial output
-        transformer, float64 otherwise)."""
+        transformer, float64 otherwise); written into ``outs`` when given."""
         rx, ry = self.divider.rank_extent
         dtype = torch.float32 if self.output_transformer.kind == 1 else torch.float64
-        outs = [torch.empty((rx, ry, nz), dtype=dtype, device=self.device)
-                for nz in self.output_transformer.original_feature_sizes]
+        sizes = self.output_transformer.original_feature_sizes
+        if outs is None:
+            outs = [torch.empty((rx, ry, nz), dtype=dtype, device=self.device) for nz in sizes]
+        else:
+            outs = list(outs)
+            _require_device(*outs)
+            if len(outs) != len(sizes) or any(tuple(t.shape) != (rx, ry, nz) or t.dtype != dtype
+                                              for t, nz in zip(outs, sizes)):
+                raise ValueError(f"outs must be {dtype} arrays of shapes {[(rx, ry, nz) for nz in sizes]}")
         k = len(outs)
         out_args = ((ctypes.c_void_p * k)(*[t.data_ptr() for t in outs]),
                     (ctypes.c_int64 * (3 * k))(*[s for t in outs for s in t.stride()]))

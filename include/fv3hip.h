@@ -674,6 +674,76 @@ int fv3hip_reservoir_get_state(fv3hip_reservoir_t model, double *state, void *st
 int fv3hip_reservoir_set_state(fv3hip_reservoir_t model, const double *state, void *stream);
 int fv3hip_reservoir_reset_state(fv3hip_reservoir_t model, void *stream);
 
+/*
+ * Column codecs of the reservoir models: fv3fit.reservoir's "dense-autoencoder" (transformers/autoencoder.py:48-247) and
+ * "sk-transformer" (transformers/sk_transformer.py:17-134, StandardScaler + PCA), DESIGN.md section 19.  A codec maps the
+ * K = sum(var_nz) values of a column, the variables concatenated along z, to n_latent values and back; it runs once per
+ * reservoir step before fv3hip_reservoir_increment and after fv3hip_reservoir_predict, one launch per direction.
+ *
+ * FV3HIP_CODEC_DENSE, float32 throughout as Keras computes it:
+ *   encode  h = (float(x) - center) / (scale + 1e-7f) (IEEE subtraction and division), then n_enc layers
+ *           h = relu(h . W + b), W [in][out]; the last one is the latent layer (enc_units[n_enc - 1] == n_latent);
+ *   decode  float(latent), n_dec layers relu(h . W + b), one linear head per variable, y * scale + center (two roundings),
+ *           then per variable: y < out_min -> out_min, y >= out_max -> out_max (a NaN bound: no bound; NaN y stays NaN).
+ *   n_enc == 0 is the "concat and scale only" form: no layers, no heads, n_dec == 0 and n_latent == K.
+ * FV3HIP_CODEC_AFFINE, float64 throughout:
+ *   encode  z = (((x - mean) / std) - pca_mean) . components^T, divided by sqrt(explained_variance) when that is given;
+ *   decode  xh = z . (components, row j times sqrt(explained_variance[j]) when given) + pca_mean, x = xh * std + mean,
+ *           then with enforce_positive x >= 0 ? x : 0.0 (a NaN becomes 0.0, as np.where does).
+ * Every dot product is an fma chain in ascending input index from 0, the bias added after the sum; no atomics: the bits
+ * depend on the shapes only.
+ * Caps, checked by fv3hip_codec_create on the host before any HIP call (FV3HIP_EINVAL): n_variables <= 16, K <= 1024,
+ * every layer width and n_latent <= 256, n_enc <= 8 and n_dec <= 8.
+ */
+#define FV3HIP_CODEC_DENSE 0
+#define FV3HIP_CODEC_AFFINE 1
+#define FV3HIP_CODEC_MAX_VARIABLES 16
+#define FV3HIP_CODEC_MAX_FEATURES 1024
+#define FV3HIP_CODEC_MAX_WIDTH 256
+#define FV3HIP_CODEC_MAX_LAYERS 8
+typedef struct {
+    int kind;                          /* FV3HIP_CODEC_DENSE / _AFFINE */
+    int n_variables;
+    const int *var_nz;                 /* [n_variables] z size of each variable */
+    int n_latent;
+    /* dense */
+    const float *center;               /* [K] */
+    const float *scale;                /* [K] */
+    int n_enc;                         /* encoder layers, the latent layer included (0: scale only) */
+    const int *enc_units;              /* [n_enc] */
+    const float *const *enc_kernels;   /* [n_enc] each [in][out] */
+    const float *const *enc_biases;    /* [n_enc] each [out] */
+    int n_dec;                         /* decoder layers before the heads */
+    const int *dec_units;              /* [n_dec] */
+    const float *const *dec_kernels;
+    const float *const *dec_biases;
+    const float *const *head_kernels;  /* [n_variables] each [in][var_nz[v]] (n_enc > 0) */
+    const float *const *head_biases;   /* [n_variables] each [var_nz[v]] */
+    const float *out_min;              /* optional [n_variables], NaN: no lower bound */
+    const float *out_max;              /* optional [n_variables], NaN: no upper bound */
+    /* affine */
+    const double *mean;                /* optional [K] (StandardScaler with_mean) */
+    const double *std;                 /* optional [K] (StandardScaler with_std: scale_) */
+    const double *pca_mean;            /* [K] */
+    const double *components;          /* [n_latent][K] */
+    const double *explained_variance;  /* [n_latent] when the PCA whitens, else NULL */
+    int enforce_positive;
+} fv3hip_codec_desc_t;
+
+typedef struct fv3hip_codec *fv3hip_codec_t;
+
+int fv3hip_codec_create(const fv3hip_codec_desc_t *desc, fv3hip_codec_t *out);
+int fv3hip_codec_destroy(fv3hip_codec_t codec);
+/* sources[v]: variable v, dtype src_dtype[v] (F32/F64), element (x, y, z) at x * strides[3v] + y * strides[3v+1] +
+ * z * strides[3v+2], over nx x ny columns.  latent: contiguous [nx][ny][n_latent], float32 (dense) or float64 (affine).
+ * No host synchronisation and no allocation. */
+int fv3hip_codec_encode(fv3hip_codec_t codec, const void *const *sources, const int *src_dtype, const int64_t *strides,
+                        int nx, int ny, void *latent, void *stream);
+/* latent: contiguous [nx][ny][n_latent] of latent_dtype (F32/F64), cast to the codec's own precision.  outputs[v]: float32
+ * (dense) or float64 (affine), addressed through out_strides as the sources above. */
+int fv3hip_codec_decode(fv3hip_codec_t codec, const void *latent, int latent_dtype, int nx, int ny, void *const *outputs,
+                        const int64_t *out_strides, void *stream);
+
 /* `n_workgroups` idle wavefronts of `microseconds` (<= 100000) each on `stream`: the host layer times a small one beside a large one
  * on another stream to learn which streams the runtime lets run side by side (cubedsphere/_device.py: the pipelines' side streams). */
 int fv3hip_spin(int64_t microseconds, int n_workgroups, void *stream);
