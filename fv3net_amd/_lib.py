@@ -345,6 +345,20 @@ SIGNATURES = {
     "fv3hip_reservoir_get_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fv3hip_reservoir_set_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fv3hip_reservoir_reset_state": (c_int, [c_void_p, c_void_p]),
+    "fv3hip_reservoir_train_series": (
+        c_int,
+        [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), c_void_p, POINTER(c_void_p), POINTER(c_int),
+         POINTER(c_int64), c_int64, c_int, c_void_p, c_void_p],
+    ),
+    "fv3hip_reservoir_encode_targets": (
+        c_int,
+        [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), c_int64, c_void_p, c_void_p],
+    ),
+    "fv3hip_gram_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "fv3hip_gram_destroy": (c_int, [c_void_p]),
+    "fv3hip_gram_reset": (c_int, [c_void_p, c_void_p]),
+    "fv3hip_gram_update": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "fv3hip_gram_get": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "fv3hip_codec_create": (c_int, [POINTER(CodecDesc), POINTER(c_void_p)]),
     "fv3hip_codec_destroy": (c_int, [c_void_p]),
     "fv3hip_codec_encode": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), c_int, c_int, c_void_p,

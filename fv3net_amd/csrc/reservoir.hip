@@ -13,6 +13,10 @@
 //   res_readout_kernel    partial readouts over slices of the readout input j: f(state) (square_even_terms) then the
 //                         hybrid inputs, staged in LDS; C in 16-byte loads, k contiguous.
 //   res_epilogue_kernel   adds the slices in order, + intercept, merges the subdomains and decodes into the output arrays.
+// training series (fv3hip_reservoir_train_series): per time step the increment's launches as they are,
+//   res_add_noise_kernel  (noise given) u += noise[t] * input_mask, between the encoding and the input product;
+//   res_pack_kernel       row t of the readout inputs: the new state (even elements squared when asked), then the hybrid
+//                         encoding of time t.
 // No atomics anywhere: the bits depend on the shapes only.
 #include <vector>
 
@@ -308,6 +312,44 @@ __global__ void res_get_state_kernel(const double *state, const int *parity, dou
 {
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (e < n) out[e] = state[(*parity ? n : 0) + e];
+}
+
+// u [k][s] += noise [s][k] * mask [s][k]: for a 0/1 mask the reference's (u + noise) * mask, u being masked already
+__global__ __launch_bounds__(kBlock) void res_add_noise_kernel(double *u, const double *noise, const double *mask, int64_t n_in,
+                                                               int64_t n_sub)
+{
+    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= n_sub * n_in) return;
+    const int64_t s = e / n_in;
+    const int64_t k = e - s * n_in;
+    double v = noise[e];
+    if (mask) v = v * mask[e];
+    u[k * n_sub + s] = u[k * n_sub + s] + v;
+}
+
+struct PackArgs {
+    const double *state;  // [2][s][S]
+    const int *parity;
+    const double *hyb;    // [s][H]
+    double *row;          // [s][S + H]
+    int S, H, n_sub, square;
+};
+
+__global__ __launch_bounds__(kBlock) void res_pack_kernel(PackArgs a)
+{
+    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int J = a.S + a.H;
+    if (e >= (int64_t)a.n_sub * J) return;
+    const int64_t s = e / J;
+    const int j = (int)(e - s * J);
+    double v;
+    if (j < a.S) {
+        v = a.state[(*a.parity ? (int64_t)a.n_sub * a.S : 0) + s * a.S + j];
+        if (a.square && j % 2 == 0) v = v * v;  // square_even_terms(axis=-1), train.py:389
+    } else {
+        v = a.hyb[s * a.H + (j - a.S)];
+    }
+    a.row[e] = v;
 }
 
 struct HostTf {
@@ -626,15 +668,12 @@ extern "C" int fv3hip_reservoir_plan(fv3hip_reservoir_t m, int64_t out[8])
     return FV3HIP_OK;
 }
 
-extern "C" int fv3hip_reservoir_increment(fv3hip_reservoir_t m, const void *const *sources, const int *src_dtype,
-                                          const int64_t *strides, void *stream)
+namespace {
+
+// encode -> (noise) -> input product -> finish; a.src and a.src_all_f32 are filled by the caller
+int increment_launches(fv3hip_reservoir_t m, EncArgs &a, const double *noise, hipStream_t st)
 {
-    int rc = check_device(m);
-    if (rc) return rc;
-    EncArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = fill_sources(m->in.t, sources, src_dtype, strides, a.src, &a.src_all_f32))) return rc;
-    const hipStream_t st = as_stream(stream);
+    int rc;
     a.tf = m->in.t;
     a.lx = m->lx;
     a.sub_x = m->rx / m->lx + 2 * m->ov;
@@ -650,6 +689,12 @@ extern "C" int fv3hip_reservoir_increment(fv3hip_reservoir_t m, const void *cons
     a.out_lk = m->n_sub;
     a.parity = m->d_parity;
     if ((rc = launch_encode(a, st))) return rc;
+    if (noise) {
+        const int64_t n = (int64_t)m->n_sub * m->n_in;
+        hipLaunchKernelGGL(res_add_noise_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, st, m->d_u, noise,
+                           m->d_pmask, (int64_t)m->n_in, (int64_t)m->n_sub);
+        if ((rc = check_launch("res_add_noise_kernel"))) return rc;
+    }
     if (m->dense) {
         switch (m->in_sb) {
         case 32: launch_in_dense<32>(m, st); break;
@@ -678,6 +723,19 @@ extern "C" int fv3hip_reservoir_increment(fv3hip_reservoir_t m, const void *cons
     f.n_sub = m->n_sub;
     hipLaunchKernelGGL(res_finish_kernel, dim3((unsigned)ceil_div(m->S, kBlock), (unsigned)m->n_sub), dim3(kBlock), 0, st, f);
     return check_launch("res_finish_kernel");
+}
+
+}  // namespace
+
+extern "C" int fv3hip_reservoir_increment(fv3hip_reservoir_t m, const void *const *sources, const int *src_dtype,
+                                          const int64_t *strides, void *stream)
+{
+    int rc = check_device(m);
+    if (rc) return rc;
+    EncArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = fill_sources(m->in.t, sources, src_dtype, strides, a.src, &a.src_all_f32))) return rc;
+    return increment_launches(m, a, nullptr, as_stream(stream));
 }
 
 extern "C" int fv3hip_reservoir_predict(fv3hip_reservoir_t m, const void *const *hybrid_sources, const int *hybrid_dtype,
@@ -772,5 +830,98 @@ extern "C" int fv3hip_reservoir_reset_state(fv3hip_reservoir_t m, void *stream)
     int rc = check_device(m);
     if (rc) return rc;
     FV3HIP_CHECK_HIP(hipMemsetAsync(m->d_state, 0, 2 * (size_t)m->n_sub * m->S * sizeof(double), as_stream(stream)));
+    return FV3HIP_OK;
+}
+
+namespace {
+
+// the sources of time t of [t, x, y, z] arrays (strides: four per variable) as fill_sources takes them
+int fill_sources_at(const Tf &tf, const void *const *p, const int *dtype, const int64_t *strides, int64_t t, Src *src, int *all_f32)
+{
+    FV3HIP_REQUIRE(p && dtype && strides, "null source pointer");
+    const void *at[kMaxVars];
+    int64_t xyz[3 * kMaxVars];
+    for (int v = 0; v < tf.n_var; ++v) {
+        FV3HIP_REQUIRE(p[v], "source %d is null", v);
+        FV3HIP_REQUIRE(is_float(dtype[v]), "source %d: dtype must be F32 or F64", v);
+        const int64_t bytes = dtype[v] == FV3HIP_F64 ? 8 : 4;
+        at[v] = static_cast<const char *>(p[v]) + t * strides[4 * v] * bytes;
+        for (int q = 0; q < 3; ++q) xyz[3 * v + q] = strides[4 * v + 1 + q];
+    }
+    return fill_sources(tf, at, dtype, xyz, src, all_f32);
+}
+
+// an encoding over the subdomains without overlap, [subdomain][feature] (the hybrid path of the readout)
+void no_overlap_args(fv3hip_reservoir_t m, const Tf &tf, int64_t n_flat, EncArgs &a)
+{
+    a.tf = tf;
+    a.lx = m->lx;
+    a.sub_x = a.step_x = m->rx / m->lx;
+    a.sub_y = a.step_y = m->ry / m->ly;
+    a.n_flat = n_flat;
+    a.n_sub = m->n_sub;
+    a.out_ls = n_flat;
+    a.out_lk = 1;
+}
+
+}  // namespace
+
+extern "C" int fv3hip_reservoir_train_series(fv3hip_reservoir_t m, const void *const *sources, const int *src_dtype,
+                                             const int64_t *strides, const double *noise, const void *const *hybrid_sources,
+                                             const int *hybrid_dtype, const int64_t *hybrid_strides, int64_t n_times,
+                                             int square_even_elements, double *X, void *stream)
+{
+    int rc = check_device(m);
+    if (rc) return rc;
+    FV3HIP_REQUIRE(n_times >= 0 && n_times < (1ll << 30), "bad n_times %lld", (long long)n_times);
+    FV3HIP_REQUIRE(X || n_times == 0, "null X");
+    const hipStream_t st = as_stream(stream);
+    const int64_t J = (int64_t)m->S + m->H;
+    for (int64_t t = 0; t < n_times; ++t) {
+        EncArgs a;
+        memset(&a, 0, sizeof(a));
+        if ((rc = fill_sources_at(m->in.t, sources, src_dtype, strides, t, a.src, &a.src_all_f32))) return rc;
+        if ((rc = increment_launches(m, a, noise ? noise + t * m->n_sub * m->n_in : nullptr, st))) return rc;
+        if (m->H > 0) {
+            EncArgs h;
+            memset(&h, 0, sizeof(h));
+            if ((rc = fill_sources_at(m->hyb.t, hybrid_sources, hybrid_dtype, hybrid_strides, t, h.src, &h.src_all_f32)))
+                return rc;
+            no_overlap_args(m, m->hyb.t, m->H, h);
+            h.pmask = m->d_hmask;
+            h.pmask_f32 = m->hmask_f32;
+            h.out = m->d_hyb;
+            if ((rc = launch_encode(h, st))) return rc;
+        }
+        PackArgs p;
+        p.state = m->d_state;
+        p.parity = m->d_parity;
+        p.hyb = m->d_hyb;
+        p.row = X + t * m->n_sub * J;
+        p.S = m->S;
+        p.H = m->H;
+        p.n_sub = m->n_sub;
+        p.square = square_even_elements ? 1 : 0;
+        hipLaunchKernelGGL(res_pack_kernel, dim3((unsigned)ceil_div(m->n_sub * J, kBlock)), dim3(kBlock), 0, st, p);
+        if ((rc = check_launch("res_pack_kernel"))) return rc;
+    }
+    return FV3HIP_OK;
+}
+
+extern "C" int fv3hip_reservoir_encode_targets(fv3hip_reservoir_t m, const void *const *sources, const int *src_dtype,
+                                               const int64_t *strides, int64_t n_times, double *Y, void *stream)
+{
+    int rc = check_device(m);
+    if (rc) return rc;
+    FV3HIP_REQUIRE(n_times >= 0 && n_times < (1ll << 30), "bad n_times %lld", (long long)n_times);
+    FV3HIP_REQUIRE(Y || n_times == 0, "null Y");
+    for (int64_t t = 0; t < n_times; ++t) {
+        EncArgs a;
+        memset(&a, 0, sizeof(a));
+        if ((rc = fill_sources_at(m->out.t, sources, src_dtype, strides, t, a.src, &a.src_all_f32))) return rc;
+        no_overlap_args(m, m->out.t, m->n_out, a);
+        a.out = Y + t * m->n_sub * m->n_out;
+        if ((rc = launch_encode(a, as_stream(stream)))) return rc;
+    }
     return FV3HIP_OK;
 }

@@ -24,9 +24,11 @@ from .cyclegan import (GeneratorTwin, HipCycleGAN, cyclegan_spec_from_state_dict
                        generator_spec_from_state_dict)
 from .fmr import (HipFullModelReplacement, RecurrentGeneratorTwin, fmr_spec_from_state_dict, fmr_state_dict_from_spec,
                   recurrent_generator_spec_from_state_dict, recurrent_twin_from_spec)
-from .reservoir import (DenseAutoencoder, DenseAutoencoderHyperparameters, HybridReservoirComputingModel,
-                        HybridReservoirDatasetAdapter, ReservoirComputingModel, ReservoirDatasetAdapter, SkTransformer,
-                        split_multi_subdomain_model, train_dense_autoencoder)
+from .reservoir import (BatchLinearRegressor, BatchLinearRegressorHyperparameters, CubedsphereSubdomainConfig, DenseAutoencoder,
+                        DenseAutoencoderHyperparameters, HybridReservoirComputingModel, HybridReservoirDatasetAdapter,
+                        NotFittedError, Reservoir, ReservoirComputingModel, ReservoirDatasetAdapter, ReservoirHyperparameters,
+                        ReservoirTrainingConfig, SkTransformer, SynchronizationTracker, TransformerGroup,
+                        split_multi_subdomain_model, train_dense_autoencoder, train_reservoir_model)
 
 __all__ = [
     "ChainedDataTransform", "ConstantOutputNoveltyDetector", "DATA_TRANSFORM_REGISTRY", "DataTransform", "MinMaxNoveltyDetector", "NoveltyDetector", "OCSVMNoveltyDetector",
@@ -42,4 +44,6 @@ __all__ = [
     "HipFullModelReplacement", "RecurrentGeneratorTwin", "fmr_spec_from_state_dict", "fmr_state_dict_from_spec",
     "recurrent_generator_spec_from_state_dict", "recurrent_twin_from_spec",
     "DenseAutoencoder", "DenseAutoencoderHyperparameters", "SkTransformer", "train_dense_autoencoder",
+    "BatchLinearRegressor", "BatchLinearRegressorHyperparameters", "CubedsphereSubdomainConfig", "NotFittedError", "Reservoir",
+    "ReservoirHyperparameters", "ReservoirTrainingConfig", "SynchronizationTracker", "TransformerGroup", "train_reservoir_model",
 ]

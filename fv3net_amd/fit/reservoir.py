@@ -5,7 +5,10 @@ on the MI355X.
 The artifact is the reference's own layout, read and written with numpy and YAML only: ``reservoir/`` (W_in and W_res as
 ``scipy.sparse.save_npz`` files, ``metadata.bin``, optional ``input_mask.npy`` and ``state.npy``), ``readout/``
 (``coefficients.npz``, which ``np.save`` writes despite its name, and ``intercepts.npy``), ``metadata.yaml``,
-``rank_divider.yaml`` and ``transformers/{input,output,hybrid}_transformer/``.  Training stays the reference's.
+``rank_divider.yaml`` and ``transformers/{input,output,hybrid}_transformer/``.  ``train_reservoir_model`` makes one
+(DESIGN.md section 20): the reservoir steps over the training series, the per-subdomain Gram sums of the readout's ridge
+regression (``csrc/gram.hip``) and its solve all run on the device; fitting the reference's default normalising transformer
+is out of scope, so the transformers are given.
 
 Two behaviours of the reference are kept on purpose: the pure model squares the even *subdomains*
 of the state when ``square_half_hidden_state`` is set (``square_even_terms(state, axis=0)``, model.py:225) where the hybrid
@@ -20,7 +23,7 @@ state row of its subdomain where scipy's product reaches only the rows with a st
 """
 import dataclasses
 import os
-from typing import Hashable, List, Optional, Sequence
+from typing import Hashable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -28,7 +31,7 @@ import yaml
 
 from ..cubedsphere._device import compute_device
 from ..reservoir import (SQUARE_ELEMENTS, SQUARE_NONE, SQUARE_SUBDOMAINS, WIN_AUTO, DenseAutoencoder, DoNothingTransformer,
-                         RankXYDivider, ReservoirModel, SkTransformer, SparseMatrix, _yaml_load, is_column_codec,
+                         GramAccumulator, RankXYDivider, ReservoirModel, SkTransformer, SparseMatrix, _yaml_load, is_column_codec,
                          load_transformer)
 from ..xr_compat import DataArray, Dataset, from_compat, to_compat
 from . import io
@@ -59,6 +62,46 @@ class Reservoir:
     @property
     def state_size(self) -> int:
         return int(self.hyperparameters["state_size"])
+
+    @classmethod
+    def generate(cls, hyperparameters: "ReservoirHyperparameters", input_size: int,
+                 input_mask_array: Optional[np.ndarray] = None) -> "Reservoir":
+        """Random weights as the reference draws them (reservoir.py:23-138), on the host with scipy: ``W_in`` column by
+        column, so that every input has the same number of stored entries, uniform in +-``input_coupling_scaling``;
+        ``W_res`` uniform in [0, 1) at density ``1 - adjacency_matrix_sparsity``, scaled so that its largest-magnitude
+        eigenvalue has modulus ``spectral_radius``.  Seeded by ``hyperparameters.seed`` through a generator of its own (the
+        reference seeds numpy's global one): a restatement, not the reference's random stream."""
+        import scipy.sparse
+        import scipy.sparse.linalg
+
+        hp = hyperparameters
+        size, rs = int(hp.state_size), np.random.RandomState(hp.seed)
+
+        def uniform_sparse(m, n, sparsity, lo, hi):
+            return scipy.sparse.random(m, n, density=1.0 - sparsity, format="csc", random_state=rs,
+                                       data_rvs=lambda d: rs.uniform(lo, hi, size=d))
+
+        scale = hp.input_coupling_scaling
+        w_in = scipy.sparse.hstack([uniform_sparse(size, 1, hp.input_coupling_sparsity, -scale, scale)
+                                    for _ in range(int(input_size))], format="csc")
+        w_res = uniform_sparse(size, size, hp.adjacency_matrix_sparsity, 0.0, 1.0)
+        if size > 3:  # ARPACK needs k < n - 1
+            largest = scipy.sparse.linalg.eigs(w_res, return_eigenvectors=False, k=1, which="LM",
+                                               v0=rs.uniform(size=size)).item()
+        else:
+            largest = max(np.linalg.eigvals(w_res.toarray()), key=abs)
+        if abs(largest) == 0:
+            raise ValueError("W_res has no nonzero eigenvalue to scale to the spectral radius; lower "
+                             "adjacency_matrix_sparsity or raise state_size")
+        w_res = (hp.spectral_radius / abs(largest)) * w_res
+
+        def sparse_matrix(m):
+            m = m.tocsc()
+            return SparseMatrix("csc", m.shape, {"indices": m.indices, "indptr": m.indptr, "format": np.array(b"csc"),
+                                                 "shape": np.asarray(m.shape, np.int64), "data": m.data})
+
+        return cls(dataclasses.asdict(hp), input_size, sparse_matrix(w_in), sparse_matrix(w_res),
+                   input_mask_array=input_mask_array)
 
     def dump(self, path: str) -> None:
         os.makedirs(path, exist_ok=True)
@@ -556,3 +599,343 @@ def train_dense_autoencoder(hyperparameters: DenseAutoencoderHyperparameters, ar
                             [kernel(m) for m in dec], [bias(m) for m in dec], [kernel(m) for m in heads],
                             [bias(m) for m in heads], output_min=[lo for lo, _ in limits],
                             output_max=[hi for _, hi in limits])
+
+
+# ---------------------------------------------------------------------------------------------
+# training (reservoir/config.py, readout.py:14-70, utils.py:40-75, train.py:165-396)
+# ---------------------------------------------------------------------------------------------
+
+
+@dataclasses.dataclass
+class CubedsphereSubdomainConfig:
+    layout: Tuple[int, int]
+    overlap: int
+    rank_dims: Sequence[str]
+
+
+@dataclasses.dataclass
+class ReservoirHyperparameters:
+    """``state_size``: W_res is [state_size, state_size]; ``adjacency_matrix_sparsity``: fraction of W_res that is zero;
+    ``spectral_radius``: modulus of W_res' largest eigenvalue; ``input_coupling_sparsity``: fraction of each input's
+    column of W_in that is zero; ``input_coupling_scaling``: W_in is uniform in +- this."""
+
+    state_size: int
+    adjacency_matrix_sparsity: float
+    spectral_radius: float
+    seed: int = 0
+    input_coupling_sparsity: float = 0.0
+    input_coupling_scaling: float = 1.0
+
+
+@dataclasses.dataclass
+class BatchLinearRegressorHyperparameters:
+    """``l2``: ridge coefficient; ``add_bias_term``: append a constant feature for the intercept;
+    ``use_least_squares_solve``: ``np.linalg.lstsq`` on the host, for small underdetermined cases."""
+
+    l2: float
+    add_bias_term: bool = True
+    use_least_squares_solve: bool = False
+
+
+@dataclasses.dataclass
+class TransformerConfig:
+    input: Optional[str] = None
+    output: Optional[str] = None
+    hybrid: Optional[str] = None
+
+
+def _from_dict(cls, data, casts=True):
+    """A dataclass from a mapping, strictly (unknown or missing keys are errors), scalars cast to the annotated type."""
+    if isinstance(data, cls):
+        return data
+    fields = {f.name: f for f in dataclasses.fields(cls)}
+    unknown = set(data) - set(fields)
+    if unknown:
+        raise ValueError(f"{cls.__name__} has no field(s) {sorted(unknown)}")
+    missing = [n for n, f in fields.items() if n not in data and f.default is dataclasses.MISSING
+               and f.default_factory is dataclasses.MISSING]
+    if missing:
+        raise ValueError(f"{cls.__name__} is missing field(s) {missing}")
+    kwargs = {}
+    for name, value in data.items():
+        kind = fields[name].type
+        if casts and value is not None and kind in (int, float, bool, str):
+            value = kind(value)
+        elif casts and value is not None and kind == Tuple[int, int]:
+            value = tuple(int(v) for v in value)
+        kwargs[name] = value
+    return cls(**kwargs)
+
+
+@dataclasses.dataclass
+class ReservoirTrainingConfig:
+    """The reference's training configuration, field for field.  ``n_jobs`` and ``validate_sst_only`` are kept for parity
+    and unused: the subdomains update in one launch, and validation is the caller's.  ``transformers`` names artifacts by
+    path in the reference; ``train_reservoir_model`` takes the loaded ``TransformerGroup`` as an argument instead."""
+
+    input_variables: Sequence[str]
+    output_variables: Sequence[str]
+    subdomain: CubedsphereSubdomainConfig
+    reservoir_hyperparameters: ReservoirHyperparameters
+    readout_hyperparameters: BatchLinearRegressorHyperparameters
+    n_timesteps_synchronize: int
+    input_noise: float
+    seed: int = 0
+    transformers: Optional[TransformerConfig] = None
+    n_jobs: Optional[int] = 1
+    square_half_hidden_state: bool = False
+    hybrid_variables: Optional[Sequence[str]] = None
+    mask_reservoir_inputs: bool = False
+    mask_hybrid_inputs: bool = False
+    mask_variable: Optional[str] = None
+    validate_sst_only: bool = False
+
+    def __post_init__(self):
+        if self.hybrid_variables is not None:
+            if set(self.hybrid_variables).intersection(self.input_variables):
+                raise ValueError(f"Hybrid variables {self.hybrid_variables} cannot overlap with input variables "
+                                 f"{self.input_variables}.")
+        if (self.mask_reservoir_inputs or self.mask_hybrid_inputs) and self.mask_variable is None:
+            raise ValueError("mask_variable must be specified if masking is enabled")
+
+    @property
+    def variables(self) -> set:
+        extra = list(self.hybrid_variables or []) + ([] if self.mask_variable is None else [self.mask_variable])
+        return set(list(self.input_variables) + list(self.output_variables) + extra)
+
+    @classmethod
+    def from_dict(cls, kwargs) -> "ReservoirTrainingConfig":
+        kwargs = {**kwargs}
+        for name, kind in (("reservoir_hyperparameters", ReservoirHyperparameters),
+                           ("readout_hyperparameters", BatchLinearRegressorHyperparameters),
+                           ("subdomain", CubedsphereSubdomainConfig), ("transformers", TransformerConfig)):
+            kwargs[name] = _from_dict(kind, kwargs.get(name) or {})
+        return _from_dict(cls, kwargs, casts=False)
+
+
+class NotFittedError(Exception):
+    pass
+
+
+class BatchLinearRegressor:
+    """Solves ``(A + l2 I) W = B`` with ``A = X.T X`` and ``B = X.T y`` summed over batches (readout.py:19-70), for every
+    subdomain at once and on the device: the sums are ``GramAccumulator``'s, the solve ``torch.linalg.solve`` in float64,
+    one subdomain at a time so that the workspace stays one matrix.
+
+    ``batch_update(X, y)`` takes [time, subdomain, feature] arrays (numpy or device tensors; strided device views are
+    used as they are), or the reference's [time, feature], which is one subdomain.  ``get_weights()`` returns
+    ``(coefficients, intercepts)`` as numpy, [subdomain, feature, out] and [subdomain, out] (without the subdomain
+    dimension after [time, feature] updates)."""
+
+    def __init__(self, hyperparameters: BatchLinearRegressorHyperparameters, device=None):
+        self.hyperparameters = hyperparameters
+        self._device = device
+        self._acc: Optional[GramAccumulator] = None
+        self._squeeze = False
+
+    def _as_device(self, a) -> torch.Tensor:
+        dev = torch.device(self._device) if self._device is not None else compute_device()
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, np.float64))
+        return t.to(dev, torch.float64)
+
+    def batch_update(self, X, y) -> None:
+        X, y = self._as_device(X), self._as_device(y)
+        if X.dim() == 2:
+            X, y, self._squeeze = X[:, None, :], y[:, None, :], True
+        if X.dim() != 3 or y.dim() != 3 or X.shape[:2] != y.shape[:2]:
+            raise ValueError(f"X and y must be [time, subdomain, feature] arrays with common leading dimensions, got "
+                             f"{tuple(X.shape)} and {tuple(y.shape)}")
+        if not self.hyperparameters.add_bias_term:
+            last = X[:, :, -1]
+            if not torch.allclose(last, torch.ones_like(last)):
+                raise ValueError("Last column of X array must all be ones if add_bias_term is False.")
+        if self._acc is None:
+            self._acc = GramAccumulator(X.shape[1], X.shape[2], y.shape[2], add_bias=self.hyperparameters.add_bias_term,
+                                        device=X.device)
+        self._acc.update(X, y)
+
+    def sums(self, subdomain: Optional[int] = None):
+        """(A, B) as device tensors: of one subdomain, or of all with a leading subdomain dimension."""
+        if self._acc is None:
+            raise NotFittedError("At least one call of batch_update on data must be done before solving for weights.")
+        return self._acc.get(subdomain)
+
+    def get_weights(self):
+        if self._acc is None:
+            raise NotFittedError("At least one call of batch_update on data must be done before solving for weights.")
+        acc, hp = self._acc, self.hyperparameters
+        weights = np.empty((acc.n_subdomains, acc.n_rows, acc.n_outputs))
+        for s in range(acc.n_subdomains):
+            a, b = acc.get(s)
+            a.diagonal().add_(hp.l2)
+            if hp.use_least_squares_solve:
+                weights[s] = np.linalg.lstsq(a.cpu().numpy(), b.cpu().numpy(), rcond=None)[0]
+            else:
+                weights[s] = torch.linalg.solve(a, b).cpu().numpy()
+        coefficients, intercepts = weights[:, :-1, :], weights[:, -1, :]
+        return (coefficients[0], intercepts[0]) if self._squeeze else (coefficients, intercepts)
+
+
+class SynchronizationTracker:
+    """The reference's ``SynchronziationTracker`` (utils.py:40-75), counting as it counts: synchronization is complete only
+    once *more than* ``n_synchronize`` steps have been counted, and the trim keeps the last ``steps_past_sync`` samples of
+    the array it is given, however many of them the current batch contributed."""
+
+    def __init__(self, n_synchronize: int):
+        self.n_synchronize = n_synchronize
+        self.n_steps_synchronized = 0
+
+    @property
+    def completed_synchronization(self) -> bool:
+        return self.n_steps_synchronized > self.n_synchronize
+
+    def count_synchronization_steps(self, n_samples: int) -> None:
+        self.n_steps_synchronized += n_samples
+
+    def trim_synchronization_samples_if_needed(self, arr):
+        if not self.completed_synchronization:
+            return arr[:0]
+        steps_past_sync = self.n_steps_synchronized - self.n_synchronize
+        return arr if steps_past_sync > len(arr) else arr[-steps_past_sync:]
+
+
+def _txyz(arr):
+    """assure_txyz_dims (utils.py:18-37): [t, x, y] gains a feature dimension, [x, y] a time dimension too."""
+    if arr.ndim == 4:
+        return arr
+    if arr.ndim == 3:
+        return arr[..., None]
+    if arr.ndim == 2:
+        return arr[None, :, :, None]
+    raise ValueError(f"Tensor data has {arr.ndim} dims, must either have either 4 dims (t, x, y, z) or 3 dims (t, x, y) "
+                     "or 2 dims (x, y).")
+
+
+def _host(arr) -> np.ndarray:
+    return arr.cpu().numpy() if isinstance(arr, torch.Tensor) else np.asarray(arr)
+
+
+def _mask_array(mask_variable: str, batch: Mapping, divider: RankXYDivider, trim_halo: bool = False) -> np.ndarray:
+    """_get_input_mask_array (train.py:92-118): the mask variable's first time step over every latent feature, per subdomain
+    and flat; its values must be 0 and 1."""
+    if mask_variable not in batch:
+        raise KeyError(f"'{mask_variable}' must be included in training data if the mask_variable is specified in training "
+                       "configuration.")
+    mask = _txyz(_host(batch[mask_variable]))
+    mask = mask * np.ones((*divider.overlap_rank_extent, divider.z_feature_size))
+    if trim_halo:
+        mask = divider.trim_halo_from_rank_data(mask)
+        divider = divider.get_no_overlap_rank_divider()
+    mask = divider.get_all_subdomains_with_flat_feature(mask[0])
+    if set(np.unique(mask)) != {0, 1}:
+        raise ValueError(f"Mask variable values in field {mask_variable} are not all in {{0, 1}}.")
+    return mask
+
+
+def _series_inputs(tf, arrays, extent, device) -> List[torch.Tensor]:
+    """[t, x, y, z] arrays as the device handle's series inputs; a column codec encodes each time step into a latent
+    series first (the existing per-step path)."""
+    tensors = [_to_device(a, device) for a in arrays]
+    tf.check_inputs([tuple(t.shape) for t in tensors])
+    if not is_column_codec(tf):
+        return tensors
+    latent = torch.empty((tensors[0].shape[0], *extent, tf.n_latent_dims), dtype=tf.latent_dtype, device=device)
+    for t in range(latent.shape[0]):
+        tf.encode_device([a[t] for a in tensors], out=latent[t])
+    return [latent]
+
+
+def train_reservoir_model(hyperparameters: ReservoirTrainingConfig, train_batches, transformers: TransformerGroup):
+    """The reference's ``"reservoir"`` training function (train.py:165-362) on the device.
+
+    ``train_batches``: a sequence of batches, each a mapping from variable name to a [t, x, y(, z)] array (numpy or device
+    tensor) over the rank extent with its overlap, or a sequence of such sequences; the reservoir state is reset at the
+    first batch of each sequence and synchronized over its first ``n_timesteps_synchronize`` steps, which do not enter the
+    regression.  ``transformers``: the ``TransformerGroup`` to encode with (any transformers the model classes accept);
+    fitting the reference's default normalising transformer when none is configured is out of scope.
+
+    Per batch the handle steps the reservoir over the series (``input_noise`` > 0 adds
+    ``RandomState(hyperparameters.seed).normal`` draws of shape [t, subdomain, input], made on the host, to the encoded
+    inputs), the targets are encoded without their halo, ``X = states[:-1] (|| hybrid[:-1])`` and ``Y = targets[1:]`` are
+    trimmed by the tracker and summed into the Gram accumulators; one ridge solve per subdomain gives the readout.  Returns
+    a ``ReservoirDatasetAdapter`` or ``HybridReservoirDatasetAdapter`` whose ``dump`` is the reference's layout.
+
+    One deliberate narrowing: the hybrid input mask is taken from the first batch, and a later batch whose mask differs is
+    an error (the reference recomputes it per batch and keeps the last one)."""
+    hp = hyperparameters
+    if transformers is None or any(getattr(transformers, side, None) is None for side in ("input", "output", "hybrid")):
+        raise ValueError("train_reservoir_model needs the input, output and hybrid transformers: fitting the reference's "
+                         "default normalising transformer when none is configured is out of scope")
+    sequences = list(train_batches)
+    if not sequences:
+        raise ValueError("train_batches is empty")
+    if isinstance(sequences[0], Mapping):
+        sequences = [sequences]
+    sequences = [list(seq) for seq in sequences]
+    sample = sequences[0][0]
+    hybrid = hp.hybrid_variables is not None
+    overlap_extent = tuple(_txyz(sample[hp.input_variables[0]]).shape[1:-1])
+    divider = RankXYDivider(tuple(hp.subdomain.layout), hp.subdomain.overlap, overlap_rank_extent=overlap_extent,
+                            z_feature_size=transformers.input.n_latent_dims)
+    input_mask = _mask_array(hp.mask_variable, sample, divider) if hp.mask_reservoir_inputs else None
+    reservoir = Reservoir.generate(hp.reservoir_hyperparameters, divider.flat_subdomain_len, input_mask)
+
+    no_overlap = divider.get_no_overlap_rank_divider()
+    n_out = no_overlap.get_new_zdim_rank_divider(transformers.output.n_latent_dims).flat_subdomain_len
+    hybrid_divider = divider.get_new_zdim_rank_divider(transformers.hybrid.n_latent_dims) if hybrid else None
+    hybrid_mask = _mask_array(hp.mask_variable, sample, hybrid_divider, trim_halo=True) \
+        if hybrid and hp.mask_hybrid_inputs else None
+    n_hybrid = hybrid_divider.get_no_overlap_rank_divider().flat_subdomain_len if hybrid else 0
+    size, ns = reservoir.state_size, divider.n_subdomains
+    # the model with an empty readout: its device handle steps the reservoir and encodes; the readout follows
+    readout = ReservoirComputingReadout(np.zeros((ns, size + n_hybrid, n_out)), np.zeros((ns, n_out)))
+    if hybrid:
+        model = HybridReservoirComputingModel(hp.input_variables, hp.hybrid_variables, hp.output_variables, reservoir, readout,
+                                              divider, transformers, hp.square_half_hidden_state,
+                                              hybrid_input_mask=hybrid_mask)
+    else:
+        model = ReservoirComputingModel(hp.input_variables, hp.output_variables, reservoir, readout, divider, transformers,
+                                        hp.square_half_hidden_state)
+    handle = model._model()
+    dev = handle.device
+    regressor = BatchLinearRegressor(hp.readout_hyperparameters, device=dev)
+    noise_rs = np.random.RandomState(hp.seed)
+    o = divider.overlap
+    trim = (lambda a: a[:, o:a.shape[1] - o, o:a.shape[2] - o]) if o else (lambda a: a)
+
+    for batches in sequences:
+        tracker = SynchronizationTracker(hp.n_timesteps_synchronize)
+        for b, batch in enumerate(batches):
+            inputs = _series_inputs(transformers.input, [_txyz(batch[v]) for v in hp.input_variables],
+                                    divider.overlap_rank_extent, dev)
+            n_t = int(inputs[0].shape[0])
+            if b == 0:
+                handle.reset_state()
+            targets = _series_inputs(transformers.output,
+                                     [trim(_txyz(batch[v])) for v in hp.output_variables], divider.rank_extent, dev)
+            hybrid_inputs = None
+            if hybrid:
+                hybrid_inputs = _series_inputs(transformers.hybrid,
+                                               [trim(_txyz(batch[v])) for v in hp.hybrid_variables], divider.rank_extent, dev)
+                if hp.mask_hybrid_inputs and not np.array_equal(
+                        _mask_array(hp.mask_variable, batch, hybrid_divider, trim_halo=True), hybrid_mask):
+                    raise ValueError(f"the hybrid input mask of field {hp.mask_variable} differs between batches; one mask "
+                                     "per training run is supported")
+            noise = None
+            if hp.input_noise > 0:
+                noise = torch.from_numpy(noise_rs.normal(0.0, hp.input_noise, (n_t, ns, reservoir.input_size))).to(dev)
+            states = handle.train_series(inputs, hybrid_inputs, noise=noise,
+                                         square_even_elements=hp.square_half_hidden_state)
+            encoded_targets = handle.encode_targets(targets)
+            tracker.count_synchronization_steps(n_t)
+            if tracker.completed_synchronization:
+                regressor.batch_update(tracker.trim_synchronization_samples_if_needed(states[:-1]),
+                                       tracker.trim_synchronization_samples_if_needed(encoded_targets[1:]))
+
+    coefficients, intercepts = regressor.get_weights()
+    model.readout = ReservoirComputingReadout(coefficients, intercepts)
+    # the state after the last training step goes with the model, as the reference's reservoir keeps it; the next call
+    # uploads it with the trained readout
+    model.reservoir.state = handle.get_state().cpu().numpy()
+    model._device_model = None
+    return HybridReservoirDatasetAdapter(model) if hybrid else ReservoirDatasetAdapter(model)

@@ -935,10 +935,132 @@ class ReservoirModel:
     def reset_state(self) -> None:
         _lib.call_on(self.device, "fv3hip_reservoir_reset_state", self._handle, _stream(self.device))
 
+    # -- training (DESIGN.md section 20) --------------------------------------------------------------
+    @staticmethod
+    def _series_sources(tensors: Sequence[torch.Tensor], extent, sizes, n_times: int, what: str):
+        """[t, x, y, z] device arrays as the series entry points take them; every shape is checked here, since the kernels
+        index by the model's extents alone."""
+        if len(tensors) != len(sizes):
+            raise ValueError(f"Expected {len(sizes)} {what} arrays but got {len(tensors)}")
+        strides = []
+        for i, (t, nz) in enumerate(zip(tensors, sizes)):
+            if tuple(t.shape) != (n_times, *extent, nz):
+                raise ValueError(f"{what} array {i} has shape {tuple(t.shape)}, expected {(n_times, *extent, nz)}")
+            if t.dtype not in (torch.float32, torch.float64):
+                raise TypeError(f"{what} arrays must be float32 or float64, got {t.dtype}")
+            strides += list(t.stride())
+        n = len(tensors)
+        return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors]),
+                (ctypes.c_int * n)(*[_lib.F64 if t.dtype == torch.float64 else _lib.F32 for t in tensors]),
+                (ctypes.c_int64 * (4 * n))(*strides))
+
+    def train_series(self, inputs: Sequence[torch.Tensor], hybrid_inputs: Optional[Sequence[torch.Tensor]] = None,
+                     noise: Optional[torch.Tensor] = None, square_even_elements: bool = False) -> torch.Tensor:
+        """One increment per time step of the [t, x, y, z] device arrays (over the overlapped rank extent) and the readout
+        inputs after each: X [t, subdomain, state_size + n_hybrid] float64, the state with its even elements squared when
+        asked, then the encoded, masked hybrid inputs ([t, x, y, z] over the rank extent) of the same time step.  ``noise``
+        [t, subdomain, input_size] float64 is added to the encoded inputs, times the input mask."""
+        dev = _require_device(*inputs)
+        n_t = int(inputs[0].shape[0])
+        src = self._series_sources(inputs, self.divider.overlap_rank_extent, self.input_transformer.original_feature_sizes,
+                                   n_t, "input")
+        if self.n_hybrid:
+            _require_device(*hybrid_inputs)
+            hyb = self._series_sources(hybrid_inputs, self.divider.rank_extent, self.hybrid_transformer.original_feature_sizes,
+                                       n_t, "hybrid")
+        else:
+            hyb = (None, None, None)
+        n_in = self.divider.flat_subdomain_len
+        if noise is not None:
+            _require_device(noise)
+            if tuple(noise.shape) != (n_t, self.n_subdomains, n_in) or noise.dtype != torch.float64:
+                raise ValueError(f"noise must be a float64 array of shape {(n_t, self.n_subdomains, n_in)}")
+            noise = noise.contiguous()
+        out = torch.empty((n_t, self.n_subdomains, self.state_size + self.n_hybrid), dtype=torch.float64, device=self.device)
+        _lib.call_on(dev, "fv3hip_reservoir_train_series", self._handle, *src, None if noise is None else noise.data_ptr(),
+                     *hyb, n_t, int(bool(square_even_elements)), out.data_ptr(), _stream(dev))
+        self._keep = noise  # alive until the launches on the stream have run
+        return out
+
+    def encode_targets(self, outputs: Sequence[torch.Tensor]) -> torch.Tensor:
+        """The output transformer's encoding of [t, x, y, z] device arrays over the rank extent without overlap, per
+        subdomain: Y [t, subdomain, n_out] float64."""
+        dev = _require_device(*outputs)
+        n_t = int(outputs[0].shape[0])
+        src = self._series_sources(outputs, self.divider.rank_extent, self.output_transformer.original_feature_sizes, n_t,
+                                   "output")
+        out = torch.empty((n_t, self.n_subdomains, self.n_out), dtype=torch.float64, device=self.device)
+        _lib.call_on(dev, "fv3hip_reservoir_encode_targets", self._handle, *src, n_t, out.data_ptr(), _stream(dev))
+        return out
+
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h:
             try:
                 _lib.load().fv3hip_reservoir_destroy(h)
+            except Exception:
+                pass
+
+
+class GramAccumulator:
+    """Device handle of the readout regression's sums (``fv3hip_gram_t``, ``csrc/gram.hip``): per subdomain
+    ``A += X.T @ X`` [J1, J1] and ``B += X.T @ Y`` [J1, n_out] in float64, J1 = J + 1 with ``add_bias`` (a column of ones
+    that is never materialised).  The bits depend on the shapes only and every ``A[s]`` is bitwise symmetric."""
+
+    K_STEP = 4  # time steps per MFMA: two updates equal one bit for bit when the first has a multiple of this many
+
+    def __init__(self, n_subdomains: int, n_features: int, n_outputs: int, add_bias: bool = True, device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("GramAccumulator needs a 'cuda' (ROCm) device; there is no CPU fallback")
+        self.n_subdomains, self.n_features, self.n_outputs = int(n_subdomains), int(n_features), int(n_outputs)
+        self.add_bias = bool(add_bias)
+        self.n_rows = self.n_features + int(self.add_bias)
+        with torch.cuda.device(self.device):
+            _require_device(torch.empty(1, device=self.device))
+            h = ctypes.c_void_p()
+            _lib.call("fv3hip_gram_create", self.n_subdomains, self.n_features, self.n_outputs, int(self.add_bias),
+                      ctypes.byref(h))
+            self._handle = h
+
+    def reset(self) -> None:
+        _lib.call_on(self.device, "fv3hip_gram_reset", self._handle, _stream(self.device))
+
+    def update(self, X: torch.Tensor, Y: torch.Tensor) -> None:
+        """``X`` [t, subdomain, J] and ``Y`` [t, subdomain, n_out]: float64 device arrays, strided views allowed in the
+        time and subdomain dimensions (the feature dimension must be contiguous)."""
+        _require_device(X, Y)
+        n_t = int(X.shape[0]) if X.dim() == 3 else -1
+        if X.dim() != 3 or tuple(X.shape[1:]) != (self.n_subdomains, self.n_features):
+            raise ValueError(f"X must have shape (t, {self.n_subdomains}, {self.n_features}), got {tuple(X.shape)}")
+        if tuple(Y.shape) != (n_t, self.n_subdomains, self.n_outputs):
+            raise ValueError(f"y must have shape ({n_t}, {self.n_subdomains}, {self.n_outputs}), got {tuple(Y.shape)}")
+        if X.dtype != torch.float64 or Y.dtype != torch.float64:
+            raise TypeError("X and y must be float64")
+        if n_t == 0:
+            return
+        fix = lambda a: a if (a.shape[2] == 1 or a.stride(2) == 1) and a.stride(0) >= 0 and a.stride(1) >= 0 \
+            else a.contiguous()  # noqa: E731
+        X, Y = fix(X), fix(Y)
+        _lib.call_on(self.device, "fv3hip_gram_update", self._handle, X.data_ptr(), X.stride(0), X.stride(1), Y.data_ptr(),
+                     Y.stride(0), Y.stride(1), n_t, _stream(self.device))
+        self._keep = (X, Y)  # alive until the launch on the stream has run
+
+    def get(self, subdomain: Optional[int] = None):
+        """(A, B) of one subdomain ([J1, J1], [J1, n_out]), or of all of them with a leading subdomain dimension."""
+        lead = (self.n_subdomains,) if subdomain is None else ()
+        if subdomain is not None and not 0 <= subdomain < self.n_subdomains:
+            raise ValueError(f"subdomain {subdomain} is outside [0, {self.n_subdomains})")
+        a = torch.empty(lead + (self.n_rows, self.n_rows), dtype=torch.float64, device=self.device)
+        b = torch.empty(lead + (self.n_rows, self.n_outputs), dtype=torch.float64, device=self.device)
+        _lib.call_on(self.device, "fv3hip_gram_get", self._handle, -1 if subdomain is None else int(subdomain), a.data_ptr(),
+                     b.data_ptr(), _stream(self.device))
+        return a, b
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h:
+            try:
+                _lib.load().fv3hip_gram_destroy(h)
             except Exception:
                 pass

@@ -675,6 +675,44 @@ int fv3hip_reservoir_set_state(fv3hip_reservoir_t model, const double *state, vo
 int fv3hip_reservoir_reset_state(fv3hip_reservoir_t model, void *stream);
 
 /*
+ * Training series of a reservoir model (fv3fit.reservoir train.py:211-282): n_times reservoir steps
+ * from [t, x, y, z] arrays, each one the launches of the increment entry above, and row t of the readout inputs after step
+ * t.  sources[v]: input variable v over the overlapped rank extent, element (t, x, y, z) at t * strides[4v] +
+ * x * strides[4v+1] + y * strides[4v+2] + z * strides[4v+3].  noise: optional [n_times][n_subdomains][input_size] float64,
+ * added to the encoded input as u += noise[t] * input_mask (for a 0/1 mask the reference's (u + noise) * mask).
+ * hybrid_sources: as sources over the rank extent without overlap (NULL for a pure model).  X: [n_times][n_subdomains]
+ * [state_size + n_hybrid] float64, contiguous: the new state, its even elements squared when square_even_elements is set
+ * (axis -1, the training rule of train.py:389, whatever the model's own square mode), then the hybrid transformer's
+ * encoding of time t times hybrid_mask.  The model's state afterwards is that of n_times increments.
+ */
+int fv3hip_reservoir_train_series(fv3hip_reservoir_t model, const void *const *sources, const int *src_dtype,
+                                  const int64_t *strides, const double *noise, const void *const *hybrid_sources,
+                                  const int *hybrid_dtype, const int64_t *hybrid_strides, int64_t n_times,
+                                  int square_even_elements, double *X, void *stream);
+/* The readout targets of a training series: the output transformer's encoding of the output variables over the rank extent
+ * without overlap (sources and strides as above), per no-overlap subdomain, Y [n_times][n_subdomains][n_out] float64. */
+int fv3hip_reservoir_encode_targets(fv3hip_reservoir_t model, const void *const *sources, const int *src_dtype,
+                                    const int64_t *strides, int64_t n_times, double *Y, void *stream);
+
+/*
+ * Gram sums of the readout's ridge regression (readout.py:39-52): per subdomain s,
+ * A[s] [J1][J1] += X_s^T X_s and B[s] [J1][n_outputs] += X_s^T Y_s in float64, J1 = n_features + 1 with add_bias (a column of
+ * ones after the features, never materialised) and n_features otherwise.  X element (t, s, j) is at t * x_time_stride +
+ * s * x_sub_stride + j, Y likewise; both float64 device arrays.  One MFMA chain per element in ascending time, no atomics:
+ * the bits depend on the shapes only, and A[s] is bitwise symmetric.  The accumulators start at zero.
+ * Reading back copies subdomain `subdomain` (A [J1][J1], B [J1][n_outputs]), or every subdomain for -1, into device arrays;
+ * either destination may be NULL.
+ */
+typedef struct fv3hip_gram *fv3hip_gram_t;
+
+int fv3hip_gram_create(int n_subdomains, int n_features, int n_outputs, int add_bias, fv3hip_gram_t *out);
+int fv3hip_gram_destroy(fv3hip_gram_t acc);
+int fv3hip_gram_reset(fv3hip_gram_t acc, void *stream);
+int fv3hip_gram_update(fv3hip_gram_t acc, const double *X, int64_t x_time_stride, int64_t x_sub_stride, const double *Y,
+                       int64_t y_time_stride, int64_t y_sub_stride, int64_t n_times, void *stream);
+int fv3hip_gram_get(fv3hip_gram_t acc, int subdomain, double *A, double *B, void *stream);
+
+/*
  * Column codecs of the reservoir models: fv3fit.reservoir's "dense-autoencoder" (transformers/autoencoder.py:48-247) and
  * "sk-transformer" (transformers/sk_transformer.py:17-134, StandardScaler + PCA), DESIGN.md section 19.  A codec maps the
  * K = sum(var_nz) values of a column, the variables concatenated along z, to n_latent values and back; it runs once per
