@@ -391,6 +391,20 @@ SIGNATURES = {
                                       c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
     "fv3hip_cyclegan_input": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                       c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
+    "fv3hip_train_chunk_rows": (c_int, []),
+    "fv3hip_train_backward_weight_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "fv3hip_train_loss_workspace_doubles": (c_int, []),
+    "fv3hip_train_linear_forward": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                            c_int64, c_int, c_int, c_int, c_void_p]),
+    "fv3hip_train_linear_backward_data": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                                  c_int64, c_int, c_int, c_void_p]),
+    "fv3hip_train_linear_backward_weight": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                                    c_void_p, c_void_p, c_size_t, c_int64, c_int, c_int, c_void_p]),
+    "fv3hip_train_mse_grad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
+                                      c_void_p]),
+    "fv3hip_train_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_double, c_double, c_double, c_double,
+                                  c_void_p]),
     "fv3hip_timer_create": (c_int, [POINTER(c_void_p)]),
     "fv3hip_timer_start": (c_int, [c_void_p, c_void_p]),
     "fv3hip_timer_stop": (c_int, [c_void_p, c_void_p]),

@@ -6,6 +6,7 @@ from .io import dump, load
 from .predictor import Predictor
 from .stacking import SAMPLE_DIM_NAME, match_prediction_to_input_coords, stack
 from .dense import DenseHyperparameters, HipDenseModel, spec_from_arrays, train_dense_model
+from .input_sensitivity import InputSensitivity, JacobianInputSensitivity, RandomForestInputSensitivity
 from .testing import ConstantOutputNoveltyDetector, ConstantOutputPredictor
 from .derived import DerivedMapping, DerivedModel
 from .models import (CombinedOutputModel, EnsembleModel, SquashedOutputConfig, SquashedOutputModel, TaperConfig, TaperedModel,
@@ -46,4 +47,5 @@ __all__ = [
     "DenseAutoencoder", "DenseAutoencoderHyperparameters", "SkTransformer", "train_dense_autoencoder",
     "BatchLinearRegressor", "BatchLinearRegressorHyperparameters", "CubedsphereSubdomainConfig", "NotFittedError", "Reservoir",
     "ReservoirHyperparameters", "ReservoirTrainingConfig", "SynchronizationTracker", "TransformerGroup", "train_reservoir_model",
+    "InputSensitivity", "JacobianInputSensitivity", "RandomForestInputSensitivity",
 ]

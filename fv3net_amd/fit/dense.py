@@ -6,8 +6,9 @@ re-done for MI355X.
   ``predict(X) -> Dataset``, ``dump`` / ``load`` through the ``name``-file registry.  The network
   runs in the fused HIP kernel; the dataset is consumed in its native ``[z, ...]`` layout, there
   is no stack / unstack copy (xr_prediction.py:111-139 does two).
-* ``train_dense_model`` is the offline training step (dense.py:90-107,165-310) in PyTorch-ROCm:
-  the only place PyTorch computes anything.
+* ``train_dense_model`` is the offline training step (dense.py:90-107,165-310): ``backend="torch"`` (the default) steps through
+  PyTorch-ROCm, ``backend="hip"`` through ``fv3net_amd.train.DenseTrainer`` and the kernels of csrc/mlp_train.hip.
+* ``HipDenseModel.input_sensitivity`` is the reference's Jacobian report (pure_keras.py:127-145) on the same kernels.
 * The artifact is ``name`` ("hip-dense") + ``config.yaml`` (the reference's keys) +
   ``spec.yaml`` + ``weights.npz``; TensorFlow SavedModels cannot be read without TensorFlow.
 """
@@ -23,6 +24,7 @@ from ..cubedsphere._device import compute_device, download_all, on_device
 from ..mlp import InputSpec, MlpModel, MlpSpec, OutputSpec
 from ..xr_compat import DataArray, Dataset, from_compat, to_compat
 from . import io
+from .input_sensitivity import InputSensitivity, nondimensionalize_jacobians
 from .predictor import Predictor
 from .stacking import column_sources, match_prediction_to_input_coords
 
@@ -75,6 +77,7 @@ class HipDenseModel(Predictor):
         if missing:
             raise ValueError(f"output variables {missing} are not produced by the network ({names})")
         self._model: Optional[MlpModel] = None  # created on first predict (needs the GPU)
+        self._trainer = None                    # created on first input_sensitivity
 
     @property
     def model(self) -> MlpModel:
@@ -106,6 +109,30 @@ class HipDenseModel(Predictor):
         for name in self.output_variables:
             result[name] = DataArray(shaped[name], dims=dims_of[name])
         return from_compat(match_prediction_to_input_coords(x, result), X)
+
+    # -- sensitivity ------------------------------------------------------------------------
+    def jacobians(self, profiles: Mapping[str, np.ndarray]):
+        """``{output: {input: d output / d input}}`` of the predict graph at one profile per input (see
+        ``fv3net_amd.train.predict_graph_jacobians``), for the model's output variables."""
+        from ..train import DenseTrainer, predict_graph_jacobians
+
+        if self._trainer is None:
+            self._trainer = DenseTrainer.from_spec(self.spec, compute_device())
+        jac = predict_graph_jacobians(self.spec, profiles, trainer=self._trainer)
+        return {name: jac[name] for name in self.output_variables if name in jac}
+
+    def input_sensitivity(self, stacked_sample) -> InputSensitivity:
+        """The Jacobian of every output with respect to every input at the sample-mean profile, times ``std(input)`` along the
+        columns and over ``std(output)`` along the rows (pure_keras.py:127-145).  ``stacked_sample`` holds the inputs and the
+        outputs as ``[sample, feature]`` (``[sample]``: one feature); an output missing from it raises ``KeyError``."""
+        sample = to_compat(stacked_sample)
+        data = {}
+        for var in list(self.input_variables) + list(self.output_variables):
+            values = sample[var].values
+            data[var] = values.reshape(-1, 1) if values.ndim == 1 else values
+        jac = self.jacobians({name: data[name].mean(axis=0) for name in self.input_variables})
+        std = {name: np.std(values, axis=0) for name, values in data.items()}
+        return InputSensitivity(jacobians=nondimensionalize_jacobians(jac, std))
 
     # -- serialisation ----------------------------------------------------------------------
     def dump(self, path: str) -> None:
@@ -175,7 +202,7 @@ def spec_from_arrays(
 
 
 # ---------------------------------------------------------------------------------------------
-# offline training (PyTorch-ROCm)
+# offline training (PyTorch-ROCm, or the project's own kernels with backend="hip")
 # ---------------------------------------------------------------------------------------------
 @dataclasses.dataclass
 class DenseHyperparameters:
@@ -208,14 +235,25 @@ def _stack_for_training(batches: Sequence[Dataset], names: Sequence[str], unstac
     return [np.concatenate(c, axis=0).astype(np.float32) for c in cols]
 
 
-def train_dense_model(hyperparameters: DenseHyperparameters, train_batches: Sequence[Dataset],
-                      device: Optional[str] = None) -> HipDenseModel:
-    """Fit normalisation on up to ``normalization_fit_samples`` samples, train
-    ``Dense(width, relu) x (depth-1) -> Dense per output`` with Adam on the std-scaled MSE of the
-    (clipped) outputs, and return the predictor (dense.py:165-310, training_loop.py:86-138)."""
-    hp = hyperparameters
+@dataclasses.dataclass
+class _DenseTraining:
+    """What both backends of ``train_dense_model`` start from: the fitted normalisation, the normalised inputs, the targets and
+    the freshly initialised layers (created on the host, so that the start does not depend on the device)."""
+
+    xin: np.ndarray                 # [n, K] normalised, clipped inputs
+    y: List[np.ndarray]             # the outputs as stacked, [n, nfeat] each
+    yc: List[np.ndarray]            # ... with the output clip applied
+    x_mean: List[np.ndarray]
+    x_std: List[np.ndarray]
+    y_mean: List[np.ndarray]
+    y_std: List[np.ndarray]
+    yc_std: List[np.ndarray]
+    trunk: torch.nn.Sequential
+    heads: torch.nn.ModuleList
+
+
+def _prepare_dense_training(hp: DenseHyperparameters, train_batches: Sequence[Dataset]) -> _DenseTraining:
     torch.manual_seed(hp.seed)
-    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
     X = _stack_for_training(train_batches, hp.input_variables, hp.unstacked_dims)
     y = _stack_for_training(train_batches, hp.output_variables, hp.unstacked_dims)
     nfit = hp.normalization_fit_samples
@@ -232,28 +270,34 @@ def train_dense_model(hyperparameters: DenseHyperparameters, train_batches: Sequ
     yc_std = [np.std(a[:nfit], axis=0, dtype=np.float32) for a in yc]
 
     eps = np.float32(1e-7)
-    xin = torch.from_numpy(np.concatenate([(a - m) / (s + eps) for a, m, s in zip(Xc, x_mean, x_std)], axis=1)).to(dev)
-    k = xin.shape[1]
+    xin = np.concatenate([(a - m) / (s + eps) for a, m, s in zip(Xc, x_mean, x_std)], axis=1)
     layers: List[torch.nn.Module] = []
-    fan = k
+    fan = xin.shape[1]
     for _ in range(hp.depth - 1):
         lin = torch.nn.Linear(fan, hp.width)
         torch.nn.init.xavier_uniform_(lin.weight)  # Keras Dense default: glorot_uniform, zero bias
         torch.nn.init.zeros_(lin.bias)
         layers += [lin, torch.nn.ReLU()]
         fan = hp.width
-    trunk = torch.nn.Sequential(*layers).to(dev)
+    trunk = torch.nn.Sequential(*layers)
     heads = torch.nn.ModuleList()
     for a in y:
         lin = torch.nn.Linear(fan, a.shape[1])
         torch.nn.init.xavier_uniform_(lin.weight)
         torch.nn.init.zeros_(lin.bias)
         heads.append(lin)
-    heads = heads.to(dev)
-    targets = [torch.from_numpy(a).to(dev) for a in yc]
-    t_mean = [torch.from_numpy(m).to(dev) for m in y_mean]
-    t_std = [torch.from_numpy(s).to(dev) for s in y_std]
-    t_cstd = [torch.from_numpy(np.maximum(s, 1e-12)).to(dev) for s in yc_std]
+    return _DenseTraining(xin=xin, y=y, yc=yc, x_mean=x_mean, x_std=x_std, y_mean=y_mean, y_std=y_std, yc_std=yc_std, trunk=trunk,
+                          heads=heads)
+
+
+def _train_torch(hp: DenseHyperparameters, prep: _DenseTraining, dev: torch.device):
+    """Adam on the std-scaled MSE through ``torch.nn.Linear`` and autograd; returns the four weight lists."""
+    xin = torch.from_numpy(prep.xin).to(dev)
+    trunk, heads = prep.trunk.to(dev), prep.heads.to(dev)
+    targets = [torch.from_numpy(a).to(dev) for a in prep.yc]
+    t_mean = [torch.from_numpy(m).to(dev) for m in prep.y_mean]
+    t_std = [torch.from_numpy(s).to(dev) for s in prep.y_std]
+    t_cstd = [torch.from_numpy(np.maximum(s, 1e-12)).to(dev) for s in prep.yc_std]
     opt = torch.optim.Adam(list(trunk.parameters()) + list(heads.parameters()), lr=hp.learning_rate)
     n = xin.shape[0]
     g = torch.Generator().manual_seed(hp.seed)
@@ -274,15 +318,81 @@ def train_dense_model(hyperparameters: DenseHyperparameters, train_batches: Sequ
             opt.zero_grad()
             loss.backward()
             opt.step()
-
     lin_layers = [m for m in trunk if isinstance(m, torch.nn.Linear)]
-    spec = spec_from_arrays(
-        hp.input_variables, x_mean, x_std,
-        [m.weight.detach().cpu().numpy().T.copy() for m in lin_layers],
-        [m.bias.detach().cpu().numpy().copy() for m in lin_layers],
-        hp.output_variables,
-        [h.weight.detach().cpu().numpy().T.copy() for h in heads],
-        [h.bias.detach().cpu().numpy().copy() for h in heads],
-        y_mean, y_std, clip=hp.clip, limits=hp.limits,
-    )
+    return ([m.weight.detach().cpu().numpy().T.copy() for m in lin_layers], [m.bias.detach().cpu().numpy().copy() for m in lin_layers],
+            [h.weight.detach().cpu().numpy().T.copy() for h in heads], [h.bias.detach().cpu().numpy().copy() for h in heads])
+
+
+def dense_mse_loss(hp: DenseHyperparameters, prep: _DenseTraining):
+    """The loss of ``_train_torch`` as the per-feature arrays the device step takes (``fv3net_amd.train.MseLoss``)."""
+    from ..train import MseLoss
+
+    inv, lo_all, hi_all, keep, kept = [], [], [], [], []
+    for name, a, cstd in zip(hp.output_variables, prep.y, prep.yc_std):
+        nf = a.shape[1]
+        mask = np.zeros(nf, np.float32)
+        mask[hp.clip[name] if name in hp.clip else slice(None)] = 1.0
+        full = np.zeros(nf, np.float64)
+        full[mask != 0] = 1.0 / np.maximum(cstd, 1e-12).astype(np.float64) ** 2
+        lo, hi = hp.limits.get(name, (None, None))
+        inv.append(full.astype(np.float32))
+        lo_all.append(np.full(nf, -np.inf if lo is None else lo, np.float32))
+        hi_all.append(np.full(nf, np.inf if hi is None else hi, np.float32))
+        keep.append(mask)
+        kept.append(np.full(nf, mask.sum(), np.float64))
+    return MseLoss(scale=np.concatenate(prep.y_std), center=np.concatenate(prep.y_mean), inv_cstd2=np.concatenate(inv),
+                   lo=np.concatenate(lo_all), hi=np.concatenate(hi_all), keep=np.concatenate(keep), kept=np.concatenate(kept))
+
+
+def dense_trainer(hp: DenseHyperparameters, prep: _DenseTraining, dev: torch.device):
+    """The device training state of ``backend="hip"``: the layers of ``prep``, the resident inputs and targets, the loss."""
+    from ..train import DenseTrainer
+
+    lins = [m for m in prep.trunk if isinstance(m, torch.nn.Linear)]
+    kernels = [m.weight.detach().numpy().T.copy() for m in lins]
+    biases = [m.bias.detach().numpy().copy() for m in lins]
+    kernels.append(np.concatenate([h.weight.detach().numpy().T for h in prep.heads], axis=1))
+    biases.append(np.concatenate([h.bias.detach().numpy() for h in prep.heads]))
+    return DenseTrainer(kernels, biases, device=dev, xin=prep.xin, targets=np.concatenate(prep.y, axis=1), loss=dense_mse_loss(hp, prep),
+                        max_batch=min(hp.batch_size, prep.xin.shape[0]), learning_rate=hp.learning_rate)
+
+
+def _train_hip(hp: DenseHyperparameters, prep: _DenseTraining, dev: torch.device):
+    """The same minibatches in the same order through ``fv3net_amd.train.DenseTrainer`` (csrc/mlp_train.hip)."""
+    trainer = dense_trainer(hp, prep, dev)
+    n = prep.xin.shape[0]
+    g = torch.Generator().manual_seed(hp.seed)
+    for _ in range(hp.epochs):
+        perm = torch.randperm(n, generator=g).to(dev)
+        for i in range(0, n, hp.batch_size):
+            trainer.step(perm[i:i + hp.batch_size])
+    return trainer.parameters([a.shape[1] for a in prep.y])
+
+
+def train_dense_model(hyperparameters: DenseHyperparameters, train_batches: Sequence[Dataset],
+                      device: Optional[str] = None, backend: Optional[str] = None) -> HipDenseModel:
+    """Fit normalisation on up to ``normalization_fit_samples`` samples, train
+    ``Dense(width, relu) x (depth-1) -> Dense per output`` with Adam on the std-scaled MSE of the
+    (clipped) outputs, and return the predictor (dense.py:165-310, training_loop.py:86-138).
+
+    ``backend``: ``None`` / ``"torch"`` steps through ``torch.nn.Linear``, autograd and ``torch.optim.Adam``; ``"hip"`` through
+    the project's own kernels (needs a GPU).  Normalisation, initialisation and the minibatch sequence are shared: both start
+    from bitwise-equal parameters and see the same rows in the same order."""
+    hp = hyperparameters
+    if backend not in (None, "torch", "hip"):
+        raise ValueError(f"backend must be None, 'torch' or 'hip', got {backend!r}")
+    if backend == "hip":
+        dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
+        if dev.type != "cuda":
+            from .. import ops
+
+            ops._require_device(torch.empty(0, device=dev))  # raises: there is no CPU path
+        prep = _prepare_dense_training(hp, train_batches)
+        weights = _train_hip(hp, prep, dev)
+    else:
+        dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
+        prep = _prepare_dense_training(hp, train_batches)
+        weights = _train_torch(hp, prep, dev)
+    spec = spec_from_arrays(hp.input_variables, prep.x_mean, prep.x_std, weights[0], weights[1], hp.output_variables, weights[2],
+                            weights[3], prep.y_mean, prep.y_std, clip=hp.clip, limits=hp.limits)
     return HipDenseModel(hp.input_variables, hp.output_variables, spec, unstacked_dims=hp.unstacked_dims)

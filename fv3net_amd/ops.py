@@ -1097,6 +1097,149 @@ def _as_float(t: torch.Tensor) -> torch.Tensor:
     return t if t.dtype in (torch.float32, torch.float64) else cast(t, torch.float64)
 
 
+# ---------------------------------------------------------------------------------------------
+# training the dense column network (csrc/mlp_train.hip): the caller owns every tensor, nothing is allocated or synchronised
+# ---------------------------------------------------------------------------------------------
+def train_chunk_rows() -> int:
+    """Rows per chunk of ``train_linear_backward_weight``: a longer batch needs its workspace."""
+    return int(_lib.load().fv3hip_train_chunk_rows())
+
+
+def train_backward_weight_workspace_floats(n: int, k: int, o: int) -> int:
+    return int(_lib.load().fv3hip_train_backward_weight_workspace_bytes(int(n), int(k), int(o))) // 4
+
+
+def train_loss_workspace_doubles() -> int:
+    return int(_lib.load().fv3hip_train_loss_workspace_doubles())
+
+
+def _rows_f32(t: torch.Tensor, what: str, features: Optional[int] = None):
+    """(rows, features, ld) of a float32 [rows, features] tensor or view whose features are contiguous."""
+    if t.dtype != torch.float32 or t.dim() != 2:
+        raise TypeError(f"{what} must be a 2-D float32 tensor, got {t.dtype} with {t.dim()} dimensions")
+    rows, feats = int(t.shape[0]), int(t.shape[1])
+    if feats > 1 and t.stride(1) != 1:
+        raise ValueError(f"{what}: the features must be contiguous")
+    ld = int(t.stride(0)) if rows > 1 else max(int(t.stride(0)), feats)
+    if ld < feats:
+        raise ValueError(f"{what}: row stride {ld} is shorter than its {feats} features")
+    if features is not None and feats != features:
+        raise ValueError(f"{what} has {feats} features, expected {features}")
+    return rows, feats, ld
+
+
+def _vec(t: Optional[torch.Tensor], what: str, n: int, dtype=torch.float32):
+    if t is None:
+        return None
+    if t.dtype != dtype or t.dim() != 1 or int(t.shape[0]) != n or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} vector of {n} values")
+    return t
+
+
+def _batch_rows(idx: Optional[torch.Tensor], table_rows: int) -> int:
+    if idx is None:
+        return table_rows
+    if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
+        raise TypeError("idx must be a contiguous 1-D int64 tensor")
+    return int(idx.shape[0])
+
+
+def train_linear_forward(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor,
+                         idx: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+    """``out[n] = act(a[row(n)] @ w + bias)`` with ``row(n) = idx[n]`` (int64, on the device) or ``n``."""
+    dev = _require_device(*(t for t in (a, w, bias, out, idx) if t is not None))
+    a_rows, k, lda = _rows_f32(a, "a")
+    _, o, ldw = _rows_f32(w, "w")
+    if int(w.shape[0]) != k:
+        raise ValueError(f"w has {w.shape[0]} rows, a has {k} features")
+    n = _batch_rows(idx, a_rows)
+    h_rows, _, ldh = _rows_f32(out, "out", o)
+    if h_rows < n:
+        raise ValueError(f"out has {h_rows} rows, the batch {n}")
+    _lib.call_on(dev, "fv3hip_train_linear_forward", _ptr(a), lda, a_rows, _ptr(idx), _ptr(w), ldw, _ptr(_vec(bias, "bias", o)), _ptr(out),
+                 ldh, n, k, o, _lib.ACT_RELU if relu else _lib.ACT_LINEAR, _stream(dev))
+    return out
+
+
+def train_linear_backward_data(dh: torch.Tensor, w: torch.Tensor, p: Optional[torch.Tensor], out: torch.Tensor,
+                               shared_p: bool = False) -> torch.Tensor:
+    """``out[n] = (dh[n] @ w.T) * (p[n] > 0)``; ``p`` None: no mask; ``shared_p``: every row is masked by ``p[0]``."""
+    dev = _require_device(*(t for t in (dh, w, p, out) if t is not None))
+    n, o, lddh = _rows_f32(dh, "dh")
+    k, _, ldw = _rows_f32(w, "w", o)
+    a_rows, _, ldda = _rows_f32(out, "out", k)
+    if a_rows < n:
+        raise ValueError(f"out has {a_rows} rows, the batch {n}")
+    ldp = 0
+    if p is not None:
+        p_rows, _, ldp = _rows_f32(p, "p", k)
+        if p_rows < (1 if shared_p else n):
+            raise ValueError(f"p has {p_rows} rows, the batch {n}")
+    _lib.call_on(dev, "fv3hip_train_linear_backward_data", _ptr(dh), lddh, _ptr(w), ldw, _ptr(p), ldp, 0 if shared_p else 1, _ptr(out),
+                 ldda, n, k, o, _stream(dev))
+    return out
+
+
+def train_linear_backward_weight(a: torch.Tensor, dh: torch.Tensor, dw: torch.Tensor, db: torch.Tensor,
+                                 idx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """``dw = a[rows].T @ dh``, ``db = dh.sum(0)``; a batch longer than ``train_chunk_rows()`` needs a float32 ``workspace`` of
+    ``train_backward_weight_workspace_floats(n, k, o)`` values."""
+    dev = _require_device(*(t for t in (a, dh, dw, db, idx, workspace) if t is not None))
+    a_rows, k, lda = _rows_f32(a, "a")
+    n = _batch_rows(idx, a_rows)
+    dh_rows, o, lddh = _rows_f32(dh, "dh")
+    if dh_rows < n:
+        raise ValueError(f"dh has {dh_rows} rows, the batch {n}")
+    w_rows, _, lddw = _rows_f32(dw, "dw", o)
+    if w_rows != k:
+        raise ValueError(f"dw has {w_rows} rows, a has {k} features")
+    ws_bytes = 0
+    if workspace is not None:
+        if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+            raise TypeError("workspace must be a contiguous float32 tensor")
+        ws_bytes = workspace.numel() * 4
+    _lib.call_on(dev, "fv3hip_train_linear_backward_weight", _ptr(a), lda, a_rows, _ptr(idx), _ptr(dh), lddh, _ptr(dw), lddw,
+                 _ptr(_vec(db, "db", o)), _ptr(workspace), ws_bytes, n, k, o, _stream(dev))
+    return dw, db
+
+
+def train_mse_grad(yhat: torch.Tensor, scale, center, inv_cstd2, lo, hi, keep, wnorm, targets: torch.Tensor, dy: torch.Tensor,
+                   loss: torch.Tensor, loss_workspace: torch.Tensor, idx: Optional[torch.Tensor] = None, n: Optional[int] = None):
+    """The std-scaled MSE of the clamped, clipped heads (see ``fv3hip_train_mse_grad``): writes ``dy`` and the float64
+    ``loss[0]``.  The seven per-feature arrays are float32 ``[F_out]``; ``targets`` is read through ``idx``."""
+    dev = _require_device(*(t for t in (yhat, scale, center, inv_cstd2, lo, hi, keep, wnorm, targets, dy, loss, loss_workspace, idx)
+                            if t is not None))
+    y_rows, f, ldy = _rows_f32(yhat, "yhat")
+    t_rows, _, ldt = _rows_f32(targets, "targets", f)
+    n = int(n) if n is not None else _batch_rows(idx, y_rows)
+    _batch_rows(idx, 0)
+    d_rows, _, lddy = _rows_f32(dy, "dy", f)
+    if y_rows < n or d_rows < n or (idx is not None and int(idx.shape[0]) < n) or (idx is None and t_rows < n):
+        raise ValueError(f"the batch has {n} rows; yhat {y_rows}, dy {d_rows}")
+    if loss.dtype != torch.float64 or loss.numel() < 1 or loss_workspace.dtype != torch.float64 or \
+            loss_workspace.numel() < train_loss_workspace_doubles() or not loss_workspace.is_contiguous():
+        raise ValueError(f"loss must be float64 and loss_workspace {train_loss_workspace_doubles()} contiguous float64 values")
+    vecs = [_vec(t, name, f) for t, name in ((scale, "scale"), (center, "center"), (inv_cstd2, "inv_cstd2"), (lo, "lo"), (hi, "hi"),
+                                            (keep, "keep"), (wnorm, "wnorm"))]
+    _lib.call_on(dev, "fv3hip_train_mse_grad", _ptr(yhat), ldy, *(_ptr(v) for v in vecs), _ptr(targets), ldt, t_rows, _ptr(idx), _ptr(dy),
+                 lddy, _ptr(loss), _ptr(loss_workspace), n, f, _stream(dev))
+    return dy, loss
+
+
+def train_adam(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor, lr: float = 1e-3,
+               beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
+    """``torch.optim.Adam``'s default update of one flat float32 buffer; ``step`` is an int64 device scalar holding the number of
+    steps taken so far, advanced on the device."""
+    dev = _require_device(params, grad, m, v, step)
+    count = int(params.numel())
+    for t, name in ((params, "params"), (grad, "grad"), (m, "m"), (v, "v")):
+        _vec(t, name, count)
+    if step.dtype != torch.int64 or step.numel() != 1:
+        raise TypeError("step must be an int64 tensor of one element")
+    _lib.call_on(dev, "fv3hip_train_adam", _ptr(params), _ptr(grad), _ptr(m), _ptr(v), count, _ptr(step), float(lr), float(beta1),
+                 float(beta2), float(eps), _stream(dev))
+
+
 class HipTimer:
     """HIP events recorded on torch's current stream (used by bench.py)."""
 

@@ -1,0 +1,252 @@
+"""Training state of the dense column network on the device, and its Jacobian (csrc/mlp_train.hip).
+
+``DenseTrainer`` owns every tensor the stateless ``fv3hip_train_*`` entry points work on: one flat float32 parameter buffer
+(per layer the kernel ``[in][out]`` followed by its bias; the heads are one concatenated layer, as ``MlpSpec.out_kernel`` is),
+the gradient and Adam moment buffers of the same layout, the device-resident step counter, the activation buffers of the
+largest batch, the chunk workspace of the weight gradient, and -- for training -- the resident normalised inputs and the
+targets.  PyTorch supplies memory and the stream only.
+"""
+import dataclasses
+from typing import Dict, List, Mapping, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+@dataclasses.dataclass
+class MseLoss:
+    """Per-feature arrays ``[F_out]`` of the loss of ``fit.train_dense_model``: sum over the outputs of
+    ``mean(((clamp(yhat * scale + center, lo, hi) - t) / cstd) ** 2)`` over the kept (not clipped away) features."""
+
+    scale: np.ndarray
+    center: np.ndarray
+    inv_cstd2: np.ndarray
+    lo: np.ndarray        # -inf: no lower limit
+    hi: np.ndarray        # +inf: no upper limit
+    keep: np.ndarray      # 0 / 1
+    kept: np.ndarray      # kept features of the feature's output
+
+    def wnorm(self, n: int) -> np.ndarray:
+        return (1.0 / (float(n) * np.maximum(np.asarray(self.kept, np.float64), 1.0))).astype(np.float32)
+
+
+class DenseTrainer:
+    """``kernels[l]`` is ``[in][out]``; every layer but the last is followed by ReLU (``relu=False``: by nothing)."""
+
+    def __init__(self, kernels: Sequence[np.ndarray], biases: Sequence[np.ndarray], device="cuda", xin: Optional[np.ndarray] = None,
+                 targets: Optional[np.ndarray] = None, loss: Optional[MseLoss] = None, max_batch: int = 512,
+                 learning_rate: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, relu: bool = True):
+        self.device = torch.device(device)
+        ops._require_device(torch.empty(1, device=self.device))
+        if len(kernels) != len(biases) or not kernels:
+            raise ValueError("one bias per kernel, at least one layer")
+        self.shapes = [(int(k.shape[0]), int(k.shape[1])) for k in kernels]
+        for l, ((_, o), b) in enumerate(zip(self.shapes, biases)):
+            if tuple(np.shape(b)) != (o,) or (l + 1 < len(self.shapes) and self.shapes[l + 1][0] != o):
+                raise ValueError("layer shapes do not chain")
+        self.relu = bool(relu)
+        self.lr, self.betas, self.eps = float(learning_rate), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_batch = int(max_batch)
+        dev = self.device
+
+        flat = np.concatenate([np.concatenate([np.asarray(k, np.float32).reshape(-1), np.asarray(b, np.float32)])
+                               for k, b in zip(kernels, biases)])
+        self.params = torch.from_numpy(flat).to(dev)
+        self.grads, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.w, self.b, self.dw, self.db = [], [], [], []
+        off = 0
+        for k, o in self.shapes:
+            self.w.append(self.params[off:off + k * o].view(k, o))
+            self.dw.append(self.grads[off:off + k * o].view(k, o))
+            off += k * o
+            self.b.append(self.params[off:off + o])
+            self.db.append(self.grads[off:off + o])
+            off += o
+
+        self.k_in, self.f_out = self.shapes[0][0], self.shapes[-1][1]
+        self._h = [torch.zeros((self.max_batch, o), dtype=torch.float32, device=dev) for _, o in self.shapes]
+        self._dh = [torch.zeros((self.max_batch, o), dtype=torch.float32, device=dev) for _, o in self.shapes]
+        ws = max(ops.train_backward_weight_workspace_floats(self.max_batch, k, o) for k, o in self.shapes)
+        self._ws = torch.zeros(ws, dtype=torch.float32, device=dev) if ws else None
+        self._loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._loss_ws = torch.zeros(ops.train_loss_workspace_doubles(), dtype=torch.float64, device=dev)
+
+        self.xin = self.targets = None
+        self._loss_arrays: Optional[Dict[str, torch.Tensor]] = None
+        self._wnorm: Dict[int, torch.Tensor] = {}
+        self._mse = loss
+        if xin is not None:
+            if targets is None or loss is None:
+                raise ValueError("training needs xin, targets and loss together")
+            self.xin = torch.from_numpy(np.ascontiguousarray(xin, np.float32)).to(dev)
+            self.targets = torch.from_numpy(np.ascontiguousarray(targets, np.float32)).to(dev)
+            if self.xin.shape[1] != self.k_in or self.targets.shape[1] != self.f_out or self.xin.shape[0] != self.targets.shape[0]:
+                raise ValueError("xin / targets do not match the network")
+            self._loss_arrays = {name: torch.from_numpy(np.ascontiguousarray(getattr(loss, name), np.float32)).to(dev)
+                                 for name in ("scale", "center", "inv_cstd2", "lo", "hi", "keep")}
+        self._jac = None
+
+    @classmethod
+    def from_spec(cls, spec, device="cuda") -> "DenseTrainer":
+        """The network of an ``MlpSpec`` (no training data: for ``jacobian``)."""
+        return cls(list(spec.hidden_kernels) + [spec.out_kernel], list(spec.hidden_biases) + [spec.out_bias], device=device, max_batch=1,
+                   relu=spec.activation == "relu")
+
+    # -- one optimiser step ------------------------------------------------------------------
+    def _forward(self, a: torch.Tensor, idx: Optional[torch.Tensor], n: int):
+        last = len(self.shapes) - 1
+        for l in range(last + 1):
+            ops.train_linear_forward(a, self.w[l], self.b[l], self._h[l][:n], idx=idx, relu=self.relu and l < last)
+            a, idx = self._h[l][:n], None
+
+    def step(self, idx: torch.Tensor) -> None:
+        """One Adam step on the minibatch ``idx`` (int64 row numbers, on the device); the loss stays on the device."""
+        if self.xin is None:
+            raise RuntimeError("this trainer holds no training data")
+        n = int(idx.shape[0])
+        if not 1 <= n <= self.max_batch:
+            raise ValueError(f"a batch of {n} rows does not fit the buffers of {self.max_batch}")
+        self.backward(idx)
+        ops.train_adam(self.params, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps)
+
+    def backward(self, idx: torch.Tensor) -> None:
+        """Forward, loss and the gradient of every parameter for the minibatch ``idx``, into ``self.grads``."""
+        n = int(idx.shape[0])
+        wn = self._wnorm.get(n)
+        if wn is None:
+            wn = self._wnorm[n] = torch.from_numpy(self._mse.wnorm(n)).to(self.device)
+        la = self._loss_arrays
+        last = len(self.shapes) - 1
+        self._forward(self.xin, idx, n)
+        ops.train_mse_grad(self._h[last][:n], la["scale"], la["center"], la["inv_cstd2"], la["lo"], la["hi"], la["keep"], wn,
+                           self.targets, self._dh[last][:n], self._loss, self._loss_ws, idx=idx)
+        for l in range(last, -1, -1):
+            if l == 0:
+                ops.train_linear_backward_weight(self.xin, self._dh[0][:n], self.dw[0], self.db[0], idx=idx, workspace=self._ws)
+            else:
+                ops.train_linear_backward_weight(self._h[l - 1][:n], self._dh[l][:n], self.dw[l], self.db[l], workspace=self._ws)
+                ops.train_linear_backward_data(self._dh[l][:n], self.w[l], self._h[l - 1][:n] if self.relu else None, self._dh[l - 1][:n])
+
+    def capture(self, idx: torch.Tensor) -> "torch.cuda.CUDAGraph":
+        """A HIP graph of ``step(idx)`` reading the row numbers from ``idx``'s memory: refill ``idx`` in place and ``replay()``.
+        One eager step is taken first (on a side stream, as torch asks) so that nothing is initialised under capture; it
+        counts as a step."""
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            self.step(idx)
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self.step(idx)
+        return graph
+
+    def loss(self) -> float:
+        """The loss of the last step's minibatch (before its update), read back."""
+        return float(self._loss.cpu()[0])
+
+    # -- reading the state back ----------------------------------------------------------------
+    def _split(self, flat: torch.Tensor, head_sizes: Optional[Sequence[int]]):
+        host = flat.cpu().numpy()
+        kernels, biases, off = [], [], 0
+        for k, o in self.shapes:
+            kernels.append(host[off:off + k * o].reshape(k, o).copy())
+            off += k * o
+            biases.append(host[off:off + o].copy())
+            off += o
+        if head_sizes is None:
+            head_sizes = [self.f_out]
+        if sum(head_sizes) != self.f_out:
+            raise ValueError(f"head sizes {list(head_sizes)} do not add up to {self.f_out} output features")
+        cuts = np.cumsum([0] + list(head_sizes))
+        out_k = [kernels[-1][:, a:b].copy() for a, b in zip(cuts[:-1], cuts[1:])]
+        out_b = [biases[-1][a:b].copy() for a, b in zip(cuts[:-1], cuts[1:])]
+        return kernels[:-1], biases[:-1], out_k, out_b
+
+    def parameters(self, head_sizes: Optional[Sequence[int]] = None):
+        """``(hidden_kernels, hidden_biases, output_kernels, output_biases)`` as numpy arrays, the order ``fit.spec_from_arrays``
+        takes them in; the concatenated head layer is cut into ``head_sizes``."""
+        return self._split(self.params, head_sizes)
+
+    def gradients(self, head_sizes: Optional[Sequence[int]] = None):
+        """The gradient buffer in the layout of ``parameters``."""
+        return self._split(self.grads, head_sizes)
+
+    # -- Jacobian --------------------------------------------------------------------------------
+    def jacobian(self, x_row) -> Tuple[np.ndarray, np.ndarray]:
+        """``(J, yhat)``: ``J[f][k]`` = d yhat[f] / d x[k] of the raw head outputs at the normalised input row ``x_row`` -- one
+        forward pass of one row, then backward-data on ``F_out`` one-hot cotangent rows that share its activations."""
+        dev, f, last = self.device, self.f_out, len(self.shapes) - 1
+        x = torch.as_tensor(np.asarray(x_row, np.float32).reshape(1, self.k_in)).to(dev)
+        if self._jac is None:
+            self._jac = ([torch.zeros((1, o), dtype=torch.float32, device=dev) for _, o in self.shapes],
+                         [torch.zeros((f, k), dtype=torch.float32, device=dev) for k, _ in self.shapes],
+                         torch.eye(f, dtype=torch.float32, device=dev))
+        acts, cots, eye = self._jac
+        a = x
+        for l in range(last + 1):
+            ops.train_linear_forward(a, self.w[l], self.b[l], acts[l], relu=self.relu and l < last)
+            a = acts[l]
+        dh = eye
+        for l in range(last, -1, -1):
+            p = acts[l - 1] if (l > 0 and self.relu) else None
+            ops.train_linear_backward_data(dh, self.w[l], p, cots[l], shared_p=True)
+            dh = cots[l]
+        return cots[0].cpu().numpy(), acts[last].cpu().numpy()[0]
+
+
+def predict_graph_jacobians(spec, profiles: Mapping[str, np.ndarray], device="cuda",
+                            trainer: Optional[DenseTrainer] = None) -> Dict[str, Dict[str, np.ndarray]]:
+    """``{output: {source: d output / d source}}`` of an ``MlpSpec``'s predict graph at one profile per source (``[nfeat]``,
+    cast to float32 as ``predict`` casts): input clip, ``log(max(x, eps))`` where the spec asks for it, normalisation, network,
+    de-normalisation, limits and masked levels.  Each array is ``[nfeat_out][len(profile)]`` in float64; columns of levels
+    that no input reads, rows of masked levels and rows of outputs outside a limit (bounds inclusive) are exactly 0.  Residual
+    outputs and the hidden output are left out."""
+    trainer = trainer or DenseTrainer.from_spec(spec, device)
+    prof = {name: np.atleast_1d(np.asarray(profiles[name])).astype(np.float32) for name in dict.fromkeys(i.source for i in spec.inputs)}
+    cols, slopes = [], []
+    for i in spec.inputs:
+        x = prof[i.source][i.start:i.start + i.nfeat]
+        if x.shape[0] != i.nfeat:
+            raise ValueError(f"{i.source!r} has {prof[i.source].shape[0]} features, the model reads [{i.start}, {i.start + i.nfeat})")
+        slope = np.ones(i.nfeat, np.float64)
+        if i.transform == "log":
+            eps = np.float32(i.eps)
+            with np.errstate(divide="ignore"):
+                slope = np.where(x > eps, 1.0 / x.astype(np.float64), 0.0)
+            x = np.log(np.maximum(x, eps))
+        center = np.zeros(i.nfeat, np.float32) if i.center is None else np.broadcast_to(np.asarray(i.center, np.float32), (i.nfeat,))
+        scale = np.ones(i.nfeat, np.float32) if i.scale is None else np.broadcast_to(np.asarray(i.scale, np.float32), (i.nfeat,))
+        cols.append((x - center) / scale)
+        slopes.append(slope / scale.astype(np.float64))
+    jac, yhat = trainer.jacobian(np.concatenate(cols))
+    jac = jac.astype(np.float64)
+
+    out: Dict[str, Dict[str, np.ndarray]] = {}
+    f0 = 0
+    for o in spec.outputs:
+        rows = jac[f0:f0 + o.nfeat]
+        y = yhat[f0:f0 + o.nfeat]
+        f0 += o.nfeat
+        scale = np.ones(o.nfeat, np.float32) if o.scale is None else np.broadcast_to(np.asarray(o.scale, np.float32), (o.nfeat,))
+        center = np.zeros(o.nfeat, np.float32) if o.center is None else np.broadcast_to(np.asarray(o.center, np.float32), (o.nfeat,))
+        p = y * scale + center
+        factor = scale.astype(np.float64)
+        if o.min is not None:
+            factor = np.where(p >= np.float32(o.min), factor, 0.0)
+        if o.max is not None:
+            factor = np.where(p <= np.float32(o.max), factor, 0.0)
+        if o.mask is not None:
+            factor = np.where(np.asarray(o.mask) != 0, factor, 0.0)
+        per_source = {name: np.zeros((o.nfeat, p_.shape[0]), np.float64) for name, p_ in prof.items()}
+        c0 = 0
+        for i, slope in zip(spec.inputs, slopes):
+            block = rows[:, c0:c0 + i.nfeat] * slope[None, :]
+            block = np.where(factor[:, None] != 0, block * factor[:, None], 0.0)
+            per_source[i.source][:, i.start:i.start + i.nfeat] += block
+            c0 += i.nfeat
+        out[o.name] = per_source
+    return out

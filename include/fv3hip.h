@@ -1171,6 +1171,57 @@ int fv3hip_cyclegan_input(const float *state, int64_t state_ld, int64_t state_of
                           const float *lon, const float *xyz, const float *theta, float *dst, int64_t dst_ld, int64_t dst_off,
                           int64_t dst_sample_stride, int64_t n_samples, int n, int c, void *stream);
 
+/* ---- training the dense column network (fv3fit's "dense" training function, keras/_models/dense.py:165-310) and its Jacobian.
+ * Stateless like the fv3hip_graph_* layers: the caller owns every DEVICE pointer, nothing is allocated or synchronised, all
+ * arguments are checked on the host before any HIP call.  Activations are float32 row-major [row][feature] with a leading
+ * dimension ld >= features; weights are [in][out] (Keras Dense: h = x W + b) with their own ld.  Every contraction runs on the
+ * exact-float32 MFMA in a fixed order; there are no atomics, so results are bitwise reproducible and depend on the shapes
+ * only.  A whole optimiser step (forwards, loss gradient, backward weight / data per layer, Adam) on one stream can be captured
+ * in a HIP graph.
+ *   idx (int64, DEVICE, or null): row n of the batch is row idx[n] of A (of the targets); an index outside [0, a_rows) reads
+ *   as a row of zeros (a target row of NaN).
+ *   fv3hip_train_linear_forward          H[n][o] = act(sum_k A[row(n)][k] W[k][o] + b[o]); act FV3HIP_ACT_LINEAR or _RELU; bias
+ *                                        may be null.
+ *   fv3hip_train_linear_backward_data    dA[n][k] = sum_o dH[n][o] W[k][o] where P[n * p_stride][k] > 0, else 0 (relu'(0) = 0 as
+ *                                        in torch; a NaN activation masks too).  P: the post-ReLU activation that fed the layer,
+ *                                        or null for no mask; p_stride 1, or 0 when every row shares the activation row P[0]
+ *                                        (the Jacobian: dH holds one-hot cotangent rows).
+ *   fv3hip_train_linear_backward_weight  dW[k][o] = sum_n A[row(n)][k] dH[n][o], db[o] = sum_n dH[n][o].  The batch is cut into
+ *                                        chunks of fv3hip_train_chunk_rows() (512) rows: a batch of one chunk writes dW and db
+ *                                        directly; a longer one writes each chunk's partial to `workspace` (at least
+ *                                        fv3hip_train_backward_weight_workspace_bytes(n, k, o) bytes) and a second kernel adds
+ *                                        the partials in ascending chunk order.
+ *   fv3hip_train_mse_grad                per element, with p = yhat * scale + center and pc = p clamped to [lo, hi] (+-inf: no
+ *                                        limit): dY = keep * [lo <= p <= hi] * 2 (pc - t) * inv_cstd2 * scale * wnorm (the
+ *                                        products taken left to right in float32; torch.clamp's gradient, bounds inclusive),
+ *                                        and loss[0] (float64) = sum over the kept elements of (pc - t)^2 inv_cstd2 wnorm,
+ *                                        accumulated in float64: per-block partials in loss_workspace (at least
+ *                                        fv3hip_train_loss_workspace_doubles() doubles), then one block adds them in order.
+ *                                        wnorm[j] = 1 / (n * kept features of j's output) makes it the sum over outputs of
+ *                                        mean(((p - t) / cstd)^2).  keep[j] == 0: the element gives an exact 0 and is not read.
+ *   fv3hip_train_adam                    torch.optim.Adam's default update of one flat buffer at step t = step[0] + 1:
+ *                                        m = b1 m + (1 - b1) g, taken as torch's lerp takes it: fma(1 - b1, g - m, m);
+ *                                        v = b2 v + ((1 - b2) g) g;
+ *                                        p -= (float)(lr / (1 - b1^t)) * m / (sqrt(v) / (float)sqrt(1 - b2^t) + eps), every
+ *                                        product rounded; then step[0] += 1 on the device (int64), so a captured step replays.
+ */
+int fv3hip_train_chunk_rows(void);
+size_t fv3hip_train_backward_weight_workspace_bytes(int64_t n, int k, int o);
+int fv3hip_train_loss_workspace_doubles(void);
+int fv3hip_train_linear_forward(const float *A, int64_t lda, int64_t a_rows, const int64_t *idx, const float *W, int64_t ldw,
+                                const float *bias, float *H, int64_t ldh, int64_t n, int k, int o, int act, void *stream);
+int fv3hip_train_linear_backward_data(const float *dH, int64_t lddh, const float *W, int64_t ldw, const float *P, int64_t ldp,
+                                      int p_stride, float *dA, int64_t ldda, int64_t n, int k, int o, void *stream);
+int fv3hip_train_linear_backward_weight(const float *A, int64_t lda, int64_t a_rows, const int64_t *idx, const float *dH,
+                                        int64_t lddh, float *dW, int64_t lddw, float *db, float *workspace, size_t workspace_bytes,
+                                        int64_t n, int k, int o, void *stream);
+int fv3hip_train_mse_grad(const float *yhat, int64_t ldy, const float *scale, const float *center, const float *inv_cstd2,
+                          const float *lo, const float *hi, const float *keep, const float *wnorm, const float *targets, int64_t ldt,
+                          int64_t t_rows, const int64_t *idx, float *dY, int64_t lddy, double *loss, double *loss_workspace,
+                          int64_t n, int f, void *stream);
+int fv3hip_train_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step, double lr, double beta1,
+                      double beta2, double eps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
