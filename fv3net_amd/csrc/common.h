@@ -113,6 +113,8 @@ inline int grow(void **p, size_t *have, size_t need)
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+using f32x16 = __attribute__((ext_vector_type(16))) float;   // the accumulator of one 32 x 32 MFMA tile
+
 // Running maximum of np.max: NaN once any value is NaN, so that `logit == max` is hot nowhere in a column of class logits
 // with a NaN (the one-hot decode of emulation.hip and local.hip: logits == np.max(logits), ties all hot).
 template <typename T>

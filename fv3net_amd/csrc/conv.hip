@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "cube.h"
 
 using namespace fv3hip;
 
@@ -23,8 +24,6 @@ constexpr int kMaxConvOutputs = 8;
 constexpr int kMaxKernelSize = 7;
 constexpr int kTile = 16;     // spatial tile edge: 256 output pixels per block
 constexpr int kBlock = 256;   // four waves, two 32-pixel MFMA tiles each
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 struct ConvArray {           // one input variable or one output: element (batch b, tile t, x, y, channel c)
     const void *p;
@@ -56,7 +55,7 @@ struct LayerArgs {
     int tiles_y;
     int swap;                // 1: x is the faster axis in memory -> x runs fastest inside the tile
     int cfast;               // 1: the channel is the fastest axis in memory
-    signed char nbr[24], nax[24], flip[24];   // [tile][side]: neighbour, 1 if joined through its x axis, 1 if reversed
+    CubeSeams seams;         // halo mode 2
 };
 
 __device__ inline float load_value(const void *p, int f64, int64_t off)
@@ -79,25 +78,14 @@ __device__ inline float load_raw(const LayerArgs &a, int b, int t, int c, int gx
     if (!inx && !iny) return 0.f;   // the corners stay zero (halos.py:135-160)
     const int n = a.nx;             // (modes 1 and 2 need square tiles)
     int side, d, j;
-    if (!inx) {
-        side = x < 0 ? 0 : 1;
-        d = x < 0 ? -1 - x : x - n;
-        j = y;
-    } else {
-        side = y < 0 ? 2 : 3;
-        d = y < 0 ? -1 - y : y - n;
-        j = x;
-    }
+    seam_side(n, x, y, inx, side, d, j);
     if (a.mode == FV3HIP_CONV_HALO_STRIPS) {
         const int64_t off = (((((int64_t)b * a.n_tiles + t) * 4 + side) * a.h + d) * a.C + c) * n + j;
         return load_value(a.strips, a.strips_f64, off);
     }
-    // resident cube: line d of the neighbour counted inward from the shared edge, along the edge as the connection says
-    const int q = t * 4 + side;
-    const int line = (side & 1) ? d : n - 1 - d;
-    const int jj = a.flip[q] ? n - 1 - j : j;
-    const int xx = a.nax[q] ? line : jj, yy = a.nax[q] ? jj : line;
-    return load_value(s.p, s.f64, b * s.sb + (int64_t)a.nbr[q] * s.st + xx * s.sx + yy * s.sy + lc * s.sc);
+    int tt, xx, yy;   // resident cube
+    seam_cross(a.seams, n, t, side, d, j, tt, xx, yy);
+    return load_value(s.p, s.f64, b * s.sb + (int64_t)tt * s.st + xx * s.sx + yy * s.sy + lc * s.sc);
 }
 
 template <int K>
@@ -271,10 +259,6 @@ int upload(T **dptr, const std::vector<T> &v)
     FV3HIP_CHECK_HIP(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return FV3HIP_OK;
 }
-
-// cube connectivity (xgcm's FV3 face connections): [tile][x-low, x-high, y-low, y-high] -> (neighbour, joined through its x axis)
-const signed char kNbr[24] = {4, 1, 5, 2, 0, 3, 5, 2, 0, 3, 1, 4, 2, 5, 1, 4, 2, 5, 3, 0, 4, 1, 3, 0};
-const signed char kNax[24] = {0, 1, 0, 1, 1, 0, 1, 0, 0, 1, 0, 1, 1, 0, 1, 0, 0, 1, 0, 1, 1, 0, 1, 0};
 
 struct HostConv {
     std::vector<int> ch_src, ch_local, och_out, och_local;
@@ -497,11 +481,7 @@ extern "C" int fv3hip_conv_predict(fv3hip_conv_t m, const void *const *sources, 
             a.ch_scale = m->d_scale;
             a.strips = strips;
             a.strips_f64 = strips_dtype == FV3HIP_F64 ? 1 : 0;
-            for (int q = 0; q < 24; ++q) {
-                a.nbr[q] = kNbr[q];
-                a.nax[q] = kNax[q];
-                a.flip[q] = (kNax[q] == 1) != (q % 4 < 2) ? 1 : 0;   // reversed when joined through the other axis
-            }
+            a.seams = cube_seams();
             a.C = m->C;
         } else {
             // the previous layer's output: [sample][x][y][F]

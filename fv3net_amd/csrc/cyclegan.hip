@@ -9,7 +9,7 @@
 // wave): a 12 x 12 or 6 x 6 face at the bottom of the network fills the rows as well as a 48 x 48 one.  N = up to 64 output
 // channels per block (gridDim.y: further channels).  K = taps x c_in flattened with the channel fastest, walked 16 rows at a
 // time.  A block first writes, per (tap, row), the source cell that the tap reads -- on the face, on the neighbouring face
-// across a cube seam (the rule of load_raw mode 2 in conv.hip), or nowhere (corners, zero padding) -- into LDS; the loader
+// across a cube seam (the rule of cube.h), or nowhere (corners, zero padding) -- into LDS; the loader
 // then gathers the K rows through that table and applies the producing layer's instance norm, per-cell bias and ReLU on the
 // way, with the statistics and the bias cell of the face the value comes from.
 //   regular     k x k, stride 1, halo (k - 1) / 2:  output (x, y) reads (x + dx - h, y + dy - h)
@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "cube.h"
 
 using namespace fv3hip;
 
@@ -39,12 +40,7 @@ constexpr int kBM = 128;      // output cells per block: one 32-row MFMA tile pe
 constexpr int kRows = 16;     // K rows per chunk
 constexpr int kStatCh = 16;   // statistics: channels per block, 16 groups of cells each
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// cube connectivity, as in conv.hip and graph.hip: [tile][x-low, x-high, y-low, y-high] -> (neighbour, joined through its
-// x axis); the edge is walked in reverse when the neighbour is joined through the other axis than the side's own
-const signed char kNbr[24] = {4, 1, 5, 2, 0, 3, 5, 2, 0, 3, 1, 4, 2, 5, 1, 4, 2, 5, 3, 0, 4, 1, 3, 0};
-const signed char kNax[24] = {0, 1, 0, 1, 1, 0, 1, 0, 0, 1, 0, 1, 1, 0, 1, 0, 0, 1, 0, 1, 1, 0, 1, 0};
+constexpr CubeLimits kLimits{1 << 20, "2^20", 4096};
 
 struct ConvArgs {
     const float *src;        // channel offset applied
@@ -63,7 +59,7 @@ struct ConvArgs {
     const float *ctx_uni;       // [c_ctx - c_cell] or null
     const float *w_ctx;         // [taps][c_ctx][N]
     int c_cell, c_ctx;          // per-cell context channels; all context channels
-    signed char nbr[24], nax[24], flip[24];
+    CubeSeams seams;
 };
 
 // cell (t * n + x) * n + y that position (x, y) of tile t's padded field shows, with the tile in bits 28-30; -1: a zero
@@ -73,21 +69,9 @@ __device__ inline int source_cell(const ConvArgs &a, int t, int x, int y)
     const bool inx = (unsigned)x < (unsigned)n, iny = (unsigned)y < (unsigned)n;
     if (inx && iny) return ((t * n + x) * n + y) | (t << 28);
     if (!a.cube || (!inx && !iny)) return -1;   // zero padding; the corners of the halo stay zero (modules.py:446-463)
-    int side, d, j;
-    if (!inx) {
-        side = x < 0 ? 0 : 1;
-        d = x < 0 ? -1 - x : x - n;
-        j = y;
-    } else {
-        side = y < 0 ? 2 : 3;
-        d = y < 0 ? -1 - y : y - n;
-        j = x;
-    }
-    const int q = t * 4 + side;
-    const int line = (side & 1) ? d : n - 1 - d;
-    const int jj = a.flip[q] ? n - 1 - j : j;
-    const int xx = a.nax[q] ? line : jj, yy = a.nax[q] ? jj : line;
-    const int tt = a.nbr[q];
+    int side, d, j, tt, xx, yy;
+    seam_side(n, x, y, inx, side, d, j);
+    seam_cross(a.seams, n, t, side, d, j, tt, xx, yy);
     return ((tt * n + xx) * n + yy) | (tt << 28);
 }
 
@@ -216,6 +200,8 @@ __global__ __launch_bounds__(kBlock) void cyclegan_conv_kernel(const ConvArgs a)
     }
     if (CTX) {
         // the context rows: few (45 against 2 304 at the production step layer), so every thread loads single values
+        // (the panel fill and the MFMA sweep stand here a second time: as shared helpers -- functions or lambdas -- they
+        // change the instruction order of all eight instantiations, which measured 0.3 - 0.8 % slower on the generator)
         const int KC = a.taps * a.c_ctx;
         for (int k0 = 0; k0 < KC; k0 += kRows) {
             __syncthreads();
@@ -362,55 +348,9 @@ __global__ __launch_bounds__(kBlock) void cyclegan_input_kernel(const float *src
     }
 }
 
-int check_slice(const char *what, const void *p, int64_t ld, int64_t off, int c)
-{
-    FV3HIP_REQUIRE(p, "%s is null", what);
-    FV3HIP_REQUIRE(off >= 0 && ld >= 1 && off + c <= ld && ld <= (1 << 24),
-                   "%s: channels [%lld, %lld) do not fit a row of %lld", what, (long long)off, (long long)(off + c), (long long)ld);
-    return FV3HIP_OK;
-}
-
-int check_stride(const char *what, int64_t *ss, int n, int64_t ld)
-{
-    const int64_t cube = 6LL * n * n * ld;
-    if (*ss == 0) *ss = cube;
-    FV3HIP_REQUIRE(*ss >= cube, "%s: sample stride %lld is shorter than a cube of %lld elements", what, (long long)*ss, (long long)cube);
-    return FV3HIP_OK;
-}
-
-struct Slice {
-    const float *p;
-    int64_t ld, off, ss;
-    int c, n;
-};
-
 bool same_slice(const Slice &a, const Slice &b)
 {
     return a.p == b.p && a.ld == b.ld && a.off == b.off && a.ss == b.ss && a.c == b.c && a.n == b.n;
-}
-
-// a layer must not read what it writes: two slices of one buffer (same base, row length, stride and edge) must be disjoint in
-// channels; two buffers must not overlap
-int check_no_alias(const Slice &a, const Slice &b, int64_t n_samples)
-{
-    if (a.p == b.p && a.ld == b.ld && a.ss == b.ss && a.n == b.n) {
-        FV3HIP_REQUIRE(a.off + a.c <= b.off || b.off + b.c <= a.off,
-                       "source channels [%lld, %lld) and destination channels [%lld, %lld) of one buffer overlap", (long long)a.off,
-                       (long long)(a.off + a.c), (long long)b.off, (long long)(b.off + b.c));
-        return FV3HIP_OK;
-    }
-    if (n_samples == 0) return FV3HIP_OK;
-    const uintptr_t a0 = (uintptr_t)a.p, a1 = a0 + (uintptr_t)((n_samples - 1) * a.ss + 6LL * a.n * a.n * a.ld) * 4;
-    const uintptr_t b0 = (uintptr_t)b.p, b1 = b0 + (uintptr_t)((n_samples - 1) * b.ss + 6LL * b.n * b.n * b.ld) * 4;
-    if (a1 <= b0 || b1 <= a0) return FV3HIP_OK;
-    return fail(FV3HIP_EINVAL, "source and destination buffers overlap");
-}
-
-int check_cube(int64_t n_samples, int n)
-{
-    FV3HIP_REQUIRE(n_samples >= 0 && n_samples <= (1 << 20), "n_samples must be in [0, 2^20], got %lld", (long long)n_samples);
-    FV3HIP_REQUIRE(n >= 1 && n <= 4096, "n must be in [1, 4096], got %d", n);
-    return FV3HIP_OK;
 }
 
 // both convolution entry points: every argument is checked here, before any HIP call
@@ -426,7 +366,7 @@ int launch_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_s
     FV3HIP_REQUIRE((in_mean == nullptr) == (in_rstd == nullptr), "in_mean and in_rstd come together");
     FV3HIP_REQUIRE(halo_mode == FV3HIP_CYCLEGAN_HALO_ZEROS || halo_mode == FV3HIP_CYCLEGAN_HALO_CUBE, "unknown halo mode %d", halo_mode);
     int rc;
-    if ((rc = check_cube(n_samples, n))) return rc;
+    if ((rc = check_cube(n_samples, n, kLimits))) return rc;
     int n_out = n, taps = k * k, h = (k - 1) / 2;
     if (kind == FV3HIP_CYCLEGAN_CONV_REGULAR) {
         if (k != 3 && k != 5 && k != 7) return fail(FV3HIP_EUNSUPPORTED, "regular convolution with k = %d: 3, 5 and 7 are built", k);
@@ -456,7 +396,7 @@ int launch_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_s
     if ((rc = check_slice("src", src, src_ld, src_off, c_in)) || (rc = check_slice("dst", dst, dst_ld, dst_off, c_out)) ||
         (rc = check_stride("src", &src_sample_stride, n, src_ld)) || (rc = check_stride("dst", &dst_sample_stride, n_out, dst_ld)) ||
         (rc = check_no_alias(Slice{src, src_ld, src_off, src_sample_stride, c_in, n},
-                             Slice{dst, dst_ld, dst_off, dst_sample_stride, c_out, n_out}, n_samples)))
+                             Slice{dst, dst_ld, dst_off, dst_sample_stride, c_out, n_out}, n_samples, false)))
         return rc;
     if (n_samples == 0) return FV3HIP_OK;
     ConvArgs a;
@@ -490,11 +430,7 @@ int launch_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_s
     a.w_ctx = w_ctx;
     a.c_cell = c_cell;
     a.c_ctx = c_ctx;
-    for (int q = 0; q < 24; ++q) {
-        a.nbr[q] = kNbr[q];
-        a.nax[q] = kNax[q];
-        a.flip[q] = (kNax[q] == 1) != (q % 4 < 2) ? 1 : 0;
-    }
+    a.seams = cube_seams();
     const int nt = c_out > 32 ? 2 : 1;
     FV3HIP_REQUIRE(ceil_div(c_out, nt * 32) <= 65535 && ceil_div(a.rows, kBM) <= 0x7fffffff, "the grid of %lld cells x %d channels is too large",
                    (long long)a.rows, c_out);
@@ -502,27 +438,14 @@ int launch_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_s
     const bool vec = c_in % 16 == 0 && src_ld % 4 == 0 && src_off % 4 == 0 && src_sample_stride % 4 == 0 && aligned16(src) &&
                      aligned16(in_mean) && aligned16(in_rstd) && aligned16(in_bias);
     const size_t lds = (size_t)taps * kBM * sizeof(int);
-    const hipStream_t st = as_stream(stream);
-    if (c_ctx > 0) {
-        if (nt == 1 && vec)
-            hipLaunchKernelGGL((cyclegan_conv_kernel<1, true, true>), grid, dim3(kBlock), lds, st, a);
-        else if (nt == 1)
-            hipLaunchKernelGGL((cyclegan_conv_kernel<1, false, true>), grid, dim3(kBlock), lds, st, a);
-        else if (vec)
-            hipLaunchKernelGGL((cyclegan_conv_kernel<2, true, true>), grid, dim3(kBlock), lds, st, a);
-        else
-            hipLaunchKernelGGL((cyclegan_conv_kernel<2, false, true>), grid, dim3(kBlock), lds, st, a);
-        return check_launch("cyclegan_conv_kernel (context)");
-    }
-    if (nt == 1 && vec)
-        hipLaunchKernelGGL((cyclegan_conv_kernel<1, true>), grid, dim3(kBlock), lds, st, a);
-    else if (nt == 1)
-        hipLaunchKernelGGL((cyclegan_conv_kernel<1, false>), grid, dim3(kBlock), lds, st, a);
-    else if (vec)
-        hipLaunchKernelGGL((cyclegan_conv_kernel<2, true>), grid, dim3(kBlock), lds, st, a);
-    else
-        hipLaunchKernelGGL((cyclegan_conv_kernel<2, false>), grid, dim3(kBlock), lds, st, a);
-    return check_launch("cyclegan_conv_kernel");
+    using Kernel = void (*)(const ConvArgs);
+    static const Kernel kernels[2][2][2] = {   // [nt - 1][vec][ctx]
+        {{cyclegan_conv_kernel<1, false, false>, cyclegan_conv_kernel<1, false, true>},
+         {cyclegan_conv_kernel<1, true, false>, cyclegan_conv_kernel<1, true, true>}},
+        {{cyclegan_conv_kernel<2, false, false>, cyclegan_conv_kernel<2, false, true>},
+         {cyclegan_conv_kernel<2, true, false>, cyclegan_conv_kernel<2, true, true>}}};
+    hipLaunchKernelGGL(kernels[nt - 1][vec][c_ctx > 0], grid, dim3(kBlock), lds, as_stream(stream), a);
+    return check_launch(c_ctx > 0 ? "cyclegan_conv_kernel (context)" : "cyclegan_conv_kernel");
 }
 
 }  // namespace
@@ -556,7 +479,7 @@ extern "C" int fv3hip_cyclegan_stats(const float *src, int64_t src_ld, int64_t s
     FV3HIP_REQUIRE(mean && rstd, "null statistics");
     FV3HIP_REQUIRE(eps >= 0, "eps must not be negative");
     int rc;
-    if ((rc = check_cube(n_samples, n)) || (rc = check_slice("src", src, src_ld, src_off, c)) ||
+    if ((rc = check_cube(n_samples, n, kLimits)) || (rc = check_slice("src", src, src_ld, src_off, c)) ||
         (rc = check_stride("src", &src_sample_stride, n, src_ld)))
         return rc;
     if (n_samples == 0) return FV3HIP_OK;
@@ -574,17 +497,17 @@ extern "C" int fv3hip_cyclegan_apply(const float *src, int64_t src_ld, int64_t s
     FV3HIP_REQUIRE(c >= 1 && c <= (1 << 16), "c must be in [1, 2^16], got %d", c);
     FV3HIP_REQUIRE((mean == nullptr) == (rstd == nullptr), "mean and rstd come together");
     int rc;
-    if ((rc = check_cube(n_samples, n)) || (rc = check_slice("src", src, src_ld, src_off, c)) ||
+    if ((rc = check_cube(n_samples, n, kLimits)) || (rc = check_slice("src", src, src_ld, src_off, c)) ||
         (rc = check_slice("dst", dst, dst_ld, dst_off, c)) || (rc = check_stride("src", &src_sample_stride, n, src_ld)) ||
         (rc = check_stride("dst", &dst_sample_stride, n, dst_ld)))
         return rc;
     // the pass works element by element, so the destination may be the source or the residual itself; any other overlap is refused
     const Slice s{src, src_ld, src_off, src_sample_stride, c, n}, d{dst, dst_ld, dst_off, dst_sample_stride, c, n};
-    if (!same_slice(s, d) && (rc = check_no_alias(s, d, n_samples))) return rc;
+    if (!same_slice(s, d) && (rc = check_no_alias(s, d, n_samples, false))) return rc;
     if (res) {
         if ((rc = check_slice("res", res, res_ld, res_off, c)) || (rc = check_stride("res", &res_sample_stride, n, res_ld))) return rc;
         const Slice r{res, res_ld, res_off, res_sample_stride, c, n};
-        if (!same_slice(r, d) && (rc = check_no_alias(r, d, n_samples))) return rc;
+        if (!same_slice(r, d) && (rc = check_no_alias(r, d, n_samples, false))) return rc;
     }
     const int64_t total = n_samples * 6 * n * n * c;
     if (total == 0) return FV3HIP_OK;
@@ -603,11 +526,11 @@ extern "C" int fv3hip_cyclegan_input(const float *state, int64_t state_ld, int64
     FV3HIP_REQUIRE((lon == nullptr) == (xyz == nullptr) && (lon == nullptr) == (theta == nullptr), "lon, xyz and theta come together");
     const int c_out = c + (lon ? 5 : 0);
     int rc;
-    if ((rc = check_cube(n_samples, n)) || (rc = check_slice("state", state, state_ld, state_off, c)) ||
+    if ((rc = check_cube(n_samples, n, kLimits)) || (rc = check_slice("state", state, state_ld, state_off, c)) ||
         (rc = check_slice("dst", dst, dst_ld, dst_off, c_out)) || (rc = check_stride("state", &state_sample_stride, n, state_ld)) ||
         (rc = check_stride("dst", &dst_sample_stride, n, dst_ld)) ||
         (rc = check_no_alias(Slice{state, state_ld, state_off, state_sample_stride, c, n},
-                             Slice{dst, dst_ld, dst_off, dst_sample_stride, c_out, n}, n_samples)))
+                             Slice{dst, dst_ld, dst_off, dst_sample_stride, c_out, n}, n_samples, false)))
         return rc;
     const int64_t total = n_samples * 6 * n * n * c_out;
     if (total == 0) return FV3HIP_OK;

@@ -9,7 +9,7 @@
 // as one GEMM with K = 2 c_in on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32): M = the 256 cells of a 16 x 16 spatial tile, N =
 // up to 64 output channels per block (further channels: gridDim.z), K walked in chunks of 8 source channels = 16 K rows (8
 // "self" rows, then 8 "mean" rows).  The loader reads a cell and its four neighbours straight from the resident cube --
-// across a seam by the rule of load_raw mode 2 in conv.hip, corners are never needed -- and writes the cell's value and
+// across a seam by the rule of cube.h, corners are never needed -- and writes the cell's value and
 //     mean5 = ((((self + x-low) + x-high) + y-low) + y-high) / 5      (float32, left to right, one correctly rounded division)
 // into LDS: no gathered or averaged copy of the activations exists in memory.
 // graph_gemm_kernel<NT, true> is the 2 x 2 / stride 2 transposed convolution on the same skeleton: K = c_in (16 channels per
@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "cube.h"
 
 using namespace fv3hip;
 
@@ -28,12 +29,7 @@ constexpr int kBlock = 256;   // four waves, two 32-cell MFMA tiles each
 constexpr int kRows = 16;     // K rows per chunk
 constexpr int kMaxGraphVars = 16;
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// cube connectivity, as in conv.hip: [tile][x-low, x-high, y-low, y-high] -> (neighbour, joined through its x axis); the edge
-// is walked in reverse when the neighbour is joined through the other axis than the side's own
-const signed char kNbr[24] = {4, 1, 5, 2, 0, 3, 5, 2, 0, 3, 1, 4, 2, 5, 1, 4, 2, 5, 3, 0, 4, 1, 3, 0};
-const signed char kNax[24] = {0, 1, 0, 1, 1, 0, 1, 0, 0, 1, 0, 1, 1, 0, 1, 0, 0, 1, 0, 1, 1, 0, 1, 0};
+constexpr CubeLimits kLimits{10922, "10922", 16384};   // gridDim.y = 6 n_samples
 
 struct GemmArgs {
     const float *src;        // channel offset applied
@@ -43,7 +39,7 @@ struct GemmArgs {
     const float *w1;         // SAGE: W_neigh [c_in][c_out]
     const float *bias;       // [c_out]
     int n, C, N, c_out, act, tiles_y;
-    signed char nbr[24], nax[24], flip[24];
+    CubeSeams seams;
 };
 
 // cell index (t * n + x) * n + y of (x, y) on tile t, where at most one of x, y lies one step outside the tile: then the cell
@@ -53,13 +49,15 @@ __device__ inline int64_t cell_index(const GemmArgs &a, int t, int x, int y)
     const int n = a.n;
     const bool inx = (unsigned)x < (unsigned)n, iny = (unsigned)y < (unsigned)n;
     if (inx && iny) return ((int64_t)t * n + x) * n + y;
+    // seam_side and seam_cross of cube.h with d = 0, written out: through the shared functions the compiler orders the
+    // kernel's instructions differently, which measured 0.4 % slower on the m = 4 rollout (and as much faster on the wide ones)
     const int side = !inx ? (x < 0 ? 0 : 1) : (y < 0 ? 2 : 3);
     const int j = !inx ? y : x;
     const int q = t * 4 + side;
     const int line = (side & 1) ? 0 : n - 1;
-    const int jj = a.flip[q] ? n - 1 - j : j;
-    const int xx = a.nax[q] ? line : jj, yy = a.nax[q] ? jj : line;
-    return ((int64_t)a.nbr[q] * n + xx) * n + yy;
+    const int jj = a.seams.flip[q] ? n - 1 - j : j;
+    const int xx = a.seams.nax[q] ? line : jj, yy = a.seams.nax[q] ? jj : line;
+    return ((int64_t)a.seams.nbr[q] * n + xx) * n + yy;
 }
 
 template <int NT, bool UP>
@@ -231,63 +229,6 @@ __global__ __launch_bounds__(kBlock) void graph_unpack_kernel(const PackArgs a, 
     }
 }
 
-int check_slice(const char *what, const void *p, int64_t ld, int64_t off, int c)
-{
-    FV3HIP_REQUIRE(p, "%s is null", what);
-    FV3HIP_REQUIRE(off >= 0 && ld >= 1 && off + c <= ld && ld <= (1 << 24),
-                   "%s: channels [%lld, %lld) do not fit a row of %lld", what, (long long)off, (long long)(off + c), (long long)ld);
-    return FV3HIP_OK;
-}
-
-// a layer must not read what it writes: two slices of one buffer (same base, same row length) must be disjoint in channels;
-// two buffers must not overlap -- except that cubes laid out with one common sample stride may interleave (time i and
-// time i + 1 of a rollout array [sample][time][cube])
-int check_no_alias(const float *src, int64_t src_ld, int64_t src_off, int c_in, int64_t src_cube, int64_t src_ss,
-                   const float *dst, int64_t dst_ld, int64_t dst_off, int c_out, int64_t dst_cube, int64_t dst_ss, int64_t n_samples)
-{
-    if (src == dst && src_ld == dst_ld && src_ss == dst_ss) {
-        FV3HIP_REQUIRE(src_off + c_in <= dst_off || dst_off + c_out <= src_off,
-                       "source channels [%lld, %lld) and destination channels [%lld, %lld) of one buffer overlap", (long long)src_off,
-                       (long long)(src_off + c_in), (long long)dst_off, (long long)(dst_off + c_out));
-        return FV3HIP_OK;
-    }
-    const int64_t src_span = n_samples ? (n_samples - 1) * src_ss + src_cube : 0, dst_span = n_samples ? (n_samples - 1) * dst_ss + dst_cube : 0;
-    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (uintptr_t)src_span * 4, d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)dst_span * 4;
-    if (s1 <= d0 || d1 <= s0) return FV3HIP_OK;
-    if (src_ss == dst_ss) {   // interleaved: the destination cubes sit in the gaps between the source cubes
-        const uintptr_t period = (uintptr_t)src_ss * 4;
-        const uintptr_t shift = d0 >= s0 ? (d0 - s0) % period : (period - (s0 - d0) % period) % period;
-        if (shift >= (uintptr_t)src_cube * 4 && shift + (uintptr_t)dst_cube * 4 <= period) return FV3HIP_OK;
-    }
-    return fail(FV3HIP_EINVAL, "source and destination buffers overlap");
-}
-
-int check_cube(int64_t n_samples, int n)
-{
-    FV3HIP_REQUIRE(n_samples >= 0 && n_samples * 6 <= 65535, "n_samples must be in [0, 10922], got %lld", (long long)n_samples);
-    FV3HIP_REQUIRE(n >= 1 && n <= 16384, "n must be in [1, 16384], got %d", n);
-    return FV3HIP_OK;
-}
-
-int64_t cube_floats(int n, int64_t ld) { return 6LL * n * n * ld; }
-
-int check_stride(const char *what, int64_t *ss, int n, int64_t ld)
-{
-    const int64_t cube = 6LL * n * n * ld;
-    if (*ss == 0) *ss = cube;
-    FV3HIP_REQUIRE(*ss >= cube, "%s: sample stride %lld is shorter than a cube of %lld elements", what, (long long)*ss, (long long)cube);
-    return FV3HIP_OK;
-}
-
-void fill_tables(GemmArgs &a)
-{
-    for (int q = 0; q < 24; ++q) {
-        a.nbr[q] = kNbr[q];
-        a.nax[q] = kNax[q];
-        a.flip[q] = (kNax[q] == 1) != (q % 4 < 2) ? 1 : 0;
-    }
-}
-
 template <bool UP>
 int launch_gemm(const GemmArgs &a, int64_t n_samples, hipStream_t st)
 {
@@ -334,11 +275,11 @@ extern "C" int fv3hip_graph_sage(const float *src, int64_t src_ld, int64_t src_o
     if (act != FV3HIP_ACT_LINEAR && act != FV3HIP_ACT_RELU && act != FV3HIP_ACT_TANH)
         return fail(FV3HIP_EUNSUPPORTED, "activation code %d: FV3HIP_ACT_LINEAR, _RELU and _TANH are built", act);
     int rc;
-    if ((rc = check_cube(n_samples, n)) || (rc = check_slice("src", src, src_ld, src_off, c_in)) ||
+    if ((rc = check_cube(n_samples, n, kLimits)) || (rc = check_slice("src", src, src_ld, src_off, c_in)) ||
         (rc = check_slice("dst", dst, dst_ld, dst_off, c_out)) || (rc = check_stride("src", &src_sample_stride, n, src_ld)) ||
         (rc = check_stride("dst", &dst_sample_stride, n, dst_ld)) ||
-        (rc = check_no_alias(src, src_ld, src_off, c_in, cube_floats(n, src_ld), src_sample_stride, dst, dst_ld, dst_off, c_out,
-                             cube_floats(n, dst_ld), dst_sample_stride, n_samples)))
+        (rc = check_no_alias(Slice{src, src_ld, src_off, src_sample_stride, c_in, n},
+                             Slice{dst, dst_ld, dst_off, dst_sample_stride, c_out, n}, n_samples, true)))
         return rc;
     if (n_samples == 0) return FV3HIP_OK;
     GemmArgs a;
@@ -357,7 +298,7 @@ extern "C" int fv3hip_graph_sage(const float *src, int64_t src_ld, int64_t src_o
     a.N = a.c_out = c_out;
     a.act = act;
     a.tiles_y = (int)ceil_div(n, kTile);
-    fill_tables(a);
+    a.seams = cube_seams();
     return launch_gemm<false>(a, n_samples, as_stream(stream));
 }
 
@@ -368,13 +309,12 @@ extern "C" int fv3hip_graph_up2(const float *src, int64_t src_ld, int64_t src_of
                    c_in, c_out);
     FV3HIP_REQUIRE(w, "null weights");
     int rc;
-    if ((rc = check_cube(n_samples, n))) return rc;
+    if ((rc = check_cube(n_samples, n, kLimits))) return rc;
     FV3HIP_REQUIRE(n <= 8192, "n must be at most 8192 (the output has 2 n cells per edge), got %d", n);
     int64_t src_ss = 0, dst_ss = 0;
     if ((rc = check_slice("src", src, src_ld, src_off, c_in)) || (rc = check_slice("dst", dst, dst_ld, dst_off, c_out)) ||
         (rc = check_stride("src", &src_ss, n, src_ld)) || (rc = check_stride("dst", &dst_ss, 2 * n, dst_ld)) ||
-        (rc = check_no_alias(src, src_ld, src_off, c_in, cube_floats(n, src_ld), src_ss, dst, dst_ld, dst_off, c_out,
-                             cube_floats(2 * n, dst_ld), dst_ss, n_samples)))
+        (rc = check_no_alias(Slice{src, src_ld, src_off, src_ss, c_in, n}, Slice{dst, dst_ld, dst_off, dst_ss, c_out, 2 * n}, n_samples, true)))
         return rc;
     if (n_samples == 0) return FV3HIP_OK;
     GemmArgs a;
@@ -393,7 +333,7 @@ extern "C" int fv3hip_graph_up2(const float *src, int64_t src_ld, int64_t src_of
     a.N = 4 * c_out;
     a.act = FV3HIP_ACT_LINEAR;
     a.tiles_y = (int)ceil_div(n, kTile);
-    fill_tables(a);
+    a.seams = cube_seams();
     return launch_gemm<true>(a, n_samples, as_stream(stream));
 }
 
@@ -402,13 +342,12 @@ extern "C" int fv3hip_graph_pool2(const float *src, int64_t src_ld, int64_t src_
 {
     FV3HIP_REQUIRE(c >= 1 && c <= (1 << 20), "c must be in [1, 2^20], got %d", c);
     int rc;
-    if ((rc = check_cube(n_samples, n))) return rc;
+    if ((rc = check_cube(n_samples, n, kLimits))) return rc;
     FV3HIP_REQUIRE(n % 2 == 0, "n must be even to pool 2 x 2, got %d", n);
     int64_t src_ss = 0, dst_ss = 0;
     if ((rc = check_slice("src", src, src_ld, src_off, c)) || (rc = check_slice("dst", dst, dst_ld, dst_off, c)) ||
         (rc = check_stride("src", &src_ss, n, src_ld)) || (rc = check_stride("dst", &dst_ss, n / 2, dst_ld)) ||
-        (rc = check_no_alias(src, src_ld, src_off, c, cube_floats(n, src_ld), src_ss, dst, dst_ld, dst_off, c,
-                             cube_floats(n / 2, dst_ld), dst_ss, n_samples)))
+        (rc = check_no_alias(Slice{src, src_ld, src_off, src_ss, c, n}, Slice{dst, dst_ld, dst_off, dst_ss, c, n / 2}, n_samples, true)))
         return rc;
     if (n_samples == 0) return FV3HIP_OK;
     const int64_t total = n_samples * 6 * (n / 2) * (n / 2) * c;

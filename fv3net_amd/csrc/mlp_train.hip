@@ -30,7 +30,6 @@ constexpr int kPanel = kBK * kMP;     // floats per panel (>= 64 * kKP)
 
 enum { NN = 0, NT = 1, TN = 2 };
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 struct TrainGemmArgs {
     const float *a;          // NN, TN: activations [rows][lda];  NT: dH [n][lda]

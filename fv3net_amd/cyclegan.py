@@ -17,7 +17,6 @@ and ``c_l = m 2**l`` on faces of ``n / 2**l`` cells per edge, the layers are
 ReLU are applied by the loader of the convolution that reads it; only the residual sums and the last ``up`` layer are written
 out normalised.  DESIGN.md section 17.
 """
-import ctypes
 import dataclasses
 from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 
@@ -25,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .graph import check_cube_shape
+from .cube import StatePacker, _Slice, check_cube_shape, cuda_device
 from .ops import _require_device, _stream
 
 CONVOLUTION_TYPES = {"halo_conv2d": _lib.CYCLEGAN_HALO_CUBE, "conv2d": _lib.CYCLEGAN_HALO_ZEROS}
@@ -136,6 +135,45 @@ def theta_from_seconds(seconds: np.ndarray) -> np.ndarray:
     return ((np.remainder(t, day) / day) * np.float32(2)) * np.float32(np.pi)
 
 
+def check_plan_arrays(plan, weights: Mapping[str, np.ndarray], biases: Mapping[str, np.ndarray]):
+    """Every layer of the plan has its float32 weight (``weight_shape``) and bias ``[c_out]``, and there are no others."""
+    names = {p[0] for p in plan}
+    if set(weights) != names or set(biases) != names:
+        raise ValueError(f"weights {sorted(weights)} / biases {sorted(biases)} differ from the layers {sorted(names)}")
+    for name, kind, ci, co, k, _ in plan:
+        for what, a, shape in (("weight", weights[name], weight_shape(kind, ci, co, k)), ("bias", biases[name], (co,))):
+            a = np.asarray(a)
+            if a.shape != shape or a.dtype != np.float32:
+                raise ValueError(f"layer {name!r}: {what} has shape {a.shape} and dtype {a.dtype}, expected float32 {shape}")
+
+
+def check_optional_arrays(spec, shapes: Mapping[str, Tuple[int, ...]]):
+    """The optional arrays of a generator spec that are given are float32 of their shapes."""
+    for what, shape in shapes.items():
+        a = getattr(spec, what)
+        if a is not None and (np.asarray(a).shape != shape or np.asarray(a).dtype != np.float32):
+            raise ValueError(f"{what} has shape {np.asarray(a).shape} and dtype {np.asarray(a).dtype}, expected float32 {shape}")
+
+
+def spec_to_arrays(spec, prefix: str, optional: Sequence[str]) -> Dict[str, np.ndarray]:
+    """``"{prefix}{layer}.weight"`` / ``.bias`` of every layer and ``"{prefix}{key}"`` of every optional array that is given."""
+    arrays = {}
+    for name in spec.weights:
+        arrays[f"{prefix}{name}.weight"] = np.asarray(spec.weights[name], np.float32)
+        arrays[f"{prefix}{name}.bias"] = np.asarray(spec.biases[name], np.float32)
+    for key in optional:
+        if getattr(spec, key) is not None:
+            arrays[f"{prefix}{key}"] = np.asarray(getattr(spec, key), np.float32)
+    return arrays
+
+
+def spec_from_arrays(arrays: Mapping[str, np.ndarray], prefix: str, plan, meta: Mapping, flags: Mapping[str, str]):
+    """The reverse: (weights, biases, optional arrays -- ``None`` where ``meta[flags[key]]`` is off)."""
+    get = lambda key: np.asarray(arrays[prefix + key], np.float32)
+    return ({p[0]: get(p[0] + ".weight") for p in plan}, {p[0]: get(p[0] + ".bias") for p in plan},
+            {key: get(key) if meta[flag] else None for key, flag in flags.items()})
+
+
 @dataclasses.dataclass
 class GeneratorSpec:
     """One generator.  ``weights[name]`` in torch's layout (``weight_shape``), ``biases[name]`` ``[c_out]``; the geographic
@@ -194,27 +232,17 @@ class GeneratorSpec:
         if self.channels < 1:
             raise ValueError(f"a generator needs at least one channel, got {self.channels}")
         check_grid(self.nx, self.nx, self.n_convolutions)
-        plan = self.plan
-        names = {p[0] for p in plan}
-        if set(self.weights) != names or set(self.biases) != names:
-            raise ValueError(f"weights {sorted(self.weights)} / biases {sorted(self.biases)} differ from the layers {sorted(names)}")
-        for name, kind, ci, co, k, _ in plan:
-            for what, a, shape in (("weight", self.weights[name], weight_shape(kind, ci, co, k)), ("bias", self.biases[name], (co,))):
-                a = np.asarray(a)
-                if a.shape != shape or a.dtype != np.float32:
-                    raise ValueError(f"layer {name!r}: {what} has shape {a.shape} and dtype {a.dtype}, expected float32 {shape}")
+        check_plan_arrays(self.plan, self.weights, self.biases)
         n, C, m = self.nx, self.channels, self.min_filters
         if (self.input_bias is None) != (self.output_bias is None):
             raise ValueError("input_bias and output_bias come together (use_geographic_bias)")
         if (self.lon is None) != (self.xyz is None):
             raise ValueError("lon and xyz come together (use_geographic_features)")
-        for what, a, shape in (("input_bias", self.input_bias, (6, C, n, n)), ("output_bias", self.output_bias, (6, C, n, n)),
-                               ("embedded_bias", self.embedded_bias, (6, m, n, n)), ("lon", self.lon, (6, n, n)),
-                               ("xyz", self.xyz, (6, 3, n, n))):
-            if a is not None and (np.asarray(a).shape != shape or np.asarray(a).dtype != np.float32):
-                raise ValueError(f"{what} has shape {np.asarray(a).shape} and dtype {np.asarray(a).dtype}, expected float32 {shape}")
+        check_optional_arrays(self, {"input_bias": (6, C, n, n), "output_bias": (6, C, n, n), "embedded_bias": (6, m, n, n),
+                                     "lon": (6, n, n), "xyz": (6, 3, n, n)})
 
-    _OPTIONAL = ("input_bias", "output_bias", "embedded_bias", "lon", "xyz")
+    _FLAGS = {"input_bias": "use_geographic_bias", "output_bias": "use_geographic_bias", "embedded_bias": "use_geographic_embedded_bias",
+              "lon": "use_geographic_features", "xyz": "use_geographic_features"}
 
     def to_arrays(self, prefix: str = ""):
         meta = {"channels": int(self.channels), "nx": int(self.nx), "n_convolutions": int(self.n_convolutions),
@@ -222,14 +250,7 @@ class GeneratorSpec:
                 "strided_kernel_size": int(self.strided_kernel_size), "max_filters": int(self.max_filters),
                 "use_geographic_bias": self.use_geographic_bias, "use_geographic_features": self.use_geographic_features,
                 "use_geographic_embedded_bias": self.use_geographic_embedded_bias, "disable_convolutions": False}
-        arrays = {}
-        for name in self.weights:
-            arrays[f"{prefix}{name}.weight"] = np.asarray(self.weights[name], np.float32)
-            arrays[f"{prefix}{name}.bias"] = np.asarray(self.biases[name], np.float32)
-        for key in self._OPTIONAL:
-            if getattr(self, key) is not None:
-                arrays[f"{prefix}{key}"] = np.asarray(getattr(self, key), np.float32)
-        return meta, arrays
+        return meta, spec_to_arrays(self, prefix, self._FLAGS)
 
     @classmethod
     def from_arrays(cls, meta: Mapping, arrays: Mapping[str, np.ndarray], prefix: str = "") -> "GeneratorSpec":
@@ -237,13 +258,9 @@ class GeneratorSpec:
                            meta["max_filters"], meta.get("disable_convolutions", False))
         plan = layer_plan(int(meta["channels"]), int(meta["n_convolutions"]), int(meta["n_resnet"]), int(meta["kernel_size"]),
                           meta["max_filters"], bool(meta["use_geographic_features"]))
-        get = lambda key: np.asarray(arrays[prefix + key], np.float32)
-        flags = {"input_bias": "use_geographic_bias", "output_bias": "use_geographic_bias",
-                 "embedded_bias": "use_geographic_embedded_bias", "lon": "use_geographic_features", "xyz": "use_geographic_features"}
-        return cls(int(meta["channels"]), int(meta["nx"]), {p[0]: get(p[0] + ".weight") for p in plan},
-                   {p[0]: get(p[0] + ".bias") for p in plan}, int(meta["n_convolutions"]), int(meta["n_resnet"]),
-                   int(meta["kernel_size"]), int(meta.get("strided_kernel_size", 4)), meta["max_filters"],
-                   **{key: get(key) if meta[flag] else None for key, flag in flags.items()})
+        weights, biases, optional = spec_from_arrays(arrays, prefix, plan, meta, cls._FLAGS)
+        return cls(int(meta["channels"]), int(meta["nx"]), weights, biases, int(meta["n_convolutions"]), int(meta["n_resnet"]),
+                   int(meta["kernel_size"]), int(meta.get("strided_kernel_size", 4)), meta["max_filters"], **optional)
 
 
 @dataclasses.dataclass
@@ -324,13 +341,6 @@ class CycleGanSpec:
         return cls(gens["a_to_b"], gens["b_to_a"], variables, scalers, meta["convolution_type"])
 
 
-class _Slice:
-    """A channel slice of a channel-last device buffer ``[S][6][n][n][ld]``."""
-
-    def __init__(self, tensor: torch.Tensor, ld: int, off: int = 0, stride: int = 0):
-        self.tensor, self.ptr, self.ld, self.off, self.stride = tensor, tensor.data_ptr(), int(ld), int(off), int(stride)
-
-
 class _Pending:
     """What the next reader of a raw convolution output applies while loading: ``relu((v - mean) * rstd + bias)``."""
 
@@ -342,38 +352,51 @@ _NONE = _Pending()
 _ptr = lambda t: None if t is None else t.data_ptr()
 
 
-class GeneratorModel:
-    """One generator on one device: the weights uploaded once in the kernels' layout, and a workspace that is kept between
-    calls.  ``forward`` works through the samples in chunks of at most ``max_chunk`` samples whose workspace stays within
-    ``workspace_limit`` bytes; a sample's result does not depend on the chunk it falls into."""
+class _GeneratorRuntime:
+    """What ``GeneratorModel`` and ``RecurrentGeneratorModel`` (fmr.py) share: the weights uploaded once in the kernels' layout,
+    a workspace that is kept between calls, the three layer launches, and the two chains both networks run -- ``first`` ->
+    ``down{l}`` and ``up{l}`` -> ``last``.  Samples are worked through in chunks of at most ``max_chunk`` whose workspace stays
+    within ``workspace_limit`` bytes; a sample's result does not depend on the chunk it falls into.
 
-    def __init__(self, spec: GeneratorSpec, convolution_type: str = "halo_conv2d", device="cuda",
-                 workspace_limit: int = 2 << 30, max_chunk: int = REFERENCE_BATCH):
+    A subclass sets ``_SAMPLE`` (what it calls a sample), ``_bottom`` (whether the ``x``, ``a``, ``b`` buffers of the bottom
+    level exist) and ``_in_channels`` (the channels of the ``in`` buffer of an input pass; 0: none)."""
+
+    _SAMPLE, _in_channels = "sample", 0
+
+    def __init__(self, spec, convolution_type, device, workspace_limit, max_chunk):
         spec.validate()
         self.spec = spec
         self.halo_mode = check_convolution_type(convolution_type)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("GeneratorModel needs a 'cuda' (ROCm) device; there is no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = cuda_device(device, type(self).__name__)
         if max_chunk < 1 or workspace_limit < 1:
             raise ValueError(f"max_chunk and workspace_limit must be positive, got {max_chunk}, {workspace_limit}")
         _lib.load()
         self.workspace_limit, self.max_chunk = int(workspace_limit), int(max_chunk)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device)
-        self._w, self._b = {}, {}
-        for name, kind, *_ in spec.plan:
+        self._layers = {p[0]: p for p in spec.plan}
+        self._w, self._w_ctx, self._b = {}, {}, {}
+        for name, kind, ci, *_ in spec.plan:
             w = np.asarray(spec.weights[name])
+            n_ctx = self._context_channels(name)
+            if n_ctx:     # [k][k][c][c_out] for the source's channels and for the context's
+                self._w_ctx[name] = self._up(w[:, ci - n_ctx:].transpose(2, 3, 1, 0))
+                w = w[:, :ci - n_ctx]
             # [k][k][c_in][c_out]; the transposed layer as its four parity sub-kernels [px][py][a][b][c_in][c_out]
-            self._w[name] = up(split_transposed_weight(w) if kind == "transposed" else w.transpose(2, 3, 1, 0))
-            self._b[name] = up(spec.biases[name])
-        last = lambda a: None if a is None else up(np.asarray(a).transpose(0, 2, 3, 1))    # [6][n][n][c]
-        self._input_bias, self._output_bias, self._embedded_bias = last(spec.input_bias), last(spec.output_bias), last(spec.embedded_bias)
-        self._lon = None if spec.lon is None else up(spec.lon)
-        self._xyz = last(spec.xyz)
+            self._w[name] = self._up(split_transposed_weight(w) if kind == "transposed" else w.transpose(2, 3, 1, 0))
+            self._b[name] = self._up(spec.biases[name])
+        self._input_bias, self._output_bias = self._channel_last(spec.input_bias), self._channel_last(spec.output_bias)
         self._ws: Dict[str, torch.Tensor] = {}
         self._ws_chunk = 0
+
+    def _context_channels(self, name: str) -> int:
+        """How many of layer ``name``'s input channels, the last ones, are context channels."""
+        return 0
+
+    def _up(self, a) -> torch.Tensor:
+        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device)
+
+    def _channel_last(self, a) -> Optional[torch.Tensor]:
+        """``[6][c][n][n]`` -> ``[6][n][n][c]`` on the device."""
+        return None if a is None else self._up(np.asarray(a).transpose(0, 2, 3, 1))
 
     # -- workspace -----------------------------------------------------------------------------------
     def _buffers(self) -> Dict[str, Tuple[int, int]]:
@@ -381,17 +404,23 @@ class GeneratorModel:
         s = self.spec
         n, m, nc = s.nx, s.min_filters, s.n_convolutions
         out = {f"raw{l}": (n >> l, m * 2 ** l) for l in range(nc + 1)}
-        if s.use_geographic_features or s.use_geographic_bias:
-            out["in"] = (n, s.channels + (N_GEOGRAPHIC_FEATURES if s.use_geographic_features else 0))
-        if s.n_resnet:
+        if self._in_channels:
+            out["in"] = (n, self._in_channels)
+        if self._bottom:
             out.update({key: (n >> nc, m * 2 ** nc) for key in ("x", "a", "b")})
         return out
 
+    def _stat_keys(self) -> Dict[str, int]:
+        """name -> channels of every pair of instance-norm statistics (mean, rstd) ``[2][S][6][c]``, in the order of the
+        layers; the ``.a`` layers of the bottom level share one pair, the ``.b`` layers another."""
+        out = {}
+        for name, _, _, co, _, _ in self.spec.plan:
+            if name != "last":
+                out.setdefault("st:" + (name[-1] if name[-2:] in (".a", ".b") else name), co)
+        return out
+
     def workspace_bytes_per_sample(self) -> int:
-        acts = sum(6 * n * n * c for n, c in self._buffers().values())
-        stats = sum(2 * 6 * co for name, _, _, co, _, _ in self.spec.plan if name != "last" and not name.startswith("res"))
-        stats += 4 * 6 * self.spec.min_filters * 2 ** self.spec.n_convolutions if self.spec.n_resnet else 0
-        return 4 * (acts + stats)
+        return 4 * (sum(6 * n * n * c for n, c in self._buffers().values()) + sum(2 * 6 * c for c in self._stat_keys().values()))
 
     def chunk_size(self, n_samples: int) -> int:
         return max(1, min(self.max_chunk, self.workspace_limit // self.workspace_bytes_per_sample(), max(n_samples, 1)))
@@ -400,20 +429,34 @@ class GeneratorModel:
         if chunk > self._ws_chunk:
             new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
             self._ws = {key: new(chunk, 6, n, n, c) for key, (n, c) in self._buffers().items()}
-            for name, _, _, co, _, _ in self.spec.plan:
-                if name != "last":
-                    key = "st:res." + name[-1] if name.startswith("res") else "st:" + name
-                    if key not in self._ws:
-                        self._ws[key] = new(2, chunk, 6, co)
+            self._ws.update({key: new(2, chunk, 6, c) for key, c in self._stat_keys().items()})
             self._ws_chunk = chunk
         return self._ws
 
-    # -- layers --------------------------------------------------------------------------------------
-    def _conv(self, name, src: _Slice, pend: _Pending, dst: _Slice, S, n_in, out_bias=None):
-        _, kind, ci, co, k, _ = next(p for p in self.spec.plan if p[0] == name)
-        _lib.call_on(self.device, "fv3hip_cyclegan_conv", src.ptr, src.ld, src.off, src.stride, _ptr(pend.mean), _ptr(pend.rstd),
-                     _ptr(pend.bias), int(pend.relu), self._w[name].data_ptr(), self._b[name].data_ptr(), _ptr(out_bias), dst.ptr,
-                     dst.ld, dst.off, dst.stride, S, n_in, ci, co, KINDS[kind], k, self.halo_mode, _stream(self.device))
+    def _buf(self, key) -> _Slice:
+        return _Slice(self._ws[key], self._ws[key].shape[-1])
+
+    def _chunks(self, S: int, chunk: Optional[int]) -> List[Tuple[int, int]]:
+        """The (first, end) sample of every chunk, with the workspace made ready for them."""
+        if S == 0:
+            return []
+        chunk = self.chunk_size(S) if chunk is None else max(1, int(chunk))
+        self._workspace(chunk)
+        return [(i, min(S, i + chunk)) for i in range(0, S, chunk)]
+
+    # -- layer launches ------------------------------------------------------------------------------
+    def _conv(self, name, src: _Slice, pend: _Pending, dst: _Slice, S, n_in, out_bias=None, ctx_cell=None, ctx_uniform: int = 0,
+              c_uni: int = 0):
+        """``ctx_cell``: per-cell context ``[6][n][n][c]``; ``ctx_uniform``: the device address of ``c_uni`` values (0: none).
+        A layer without context rows goes through the same entry point."""
+        _, kind, ci, co, k, _ = self._layers[name]
+        c_cell = 0 if ctx_cell is None else int(ctx_cell.shape[-1])
+        c_uni = c_uni if ctx_uniform else 0
+        _lib.call_on(self.device, "fv3hip_cyclegan_conv_context", src.ptr, src.ld, src.off, src.stride, _ptr(pend.mean),
+                     _ptr(pend.rstd), _ptr(pend.bias), int(pend.relu), self._w[name].data_ptr(), self._b[name].data_ptr(),
+                     _ptr(out_bias), dst.ptr, dst.ld, dst.off, dst.stride, S, n_in, ci - c_cell - c_uni, co, KINDS[kind], k,
+                     self.halo_mode, _ptr(ctx_cell), c_cell, ctx_uniform or None, c_uni, _ptr(self._w_ctx.get(name)),
+                     _stream(self.device))
 
     def _stats(self, key, src: _Slice, S, n, c, bias=None, relu=True) -> _Pending:
         st = self._ws[key]
@@ -427,45 +470,35 @@ class GeneratorModel:
                      _ptr(pend.bias), int(pend.relu), r.ptr if res else None, r.ld, r.off, r.stride, dst.ptr, dst.ld, dst.off,
                      dst.stride, S, n, c, _stream(self.device))
 
-    def _forward_chunk(self, state: torch.Tensor, theta: Optional[torch.Tensor], out: torch.Tensor, ws):
+    # -- the two chains ------------------------------------------------------------------------------
+    def _down_chain(self, src: _Slice, pend: _Pending, S: int, ctx_cell=None, first_bias=None) -> Tuple[_Slice, _Pending]:
+        """``first`` and the ``down{l}`` layers; returns the raw output of the last one and what its reader applies."""
         s = self.spec
-        S, n, C, m, nc = int(state.shape[0]), s.nx, s.channels, s.min_filters, s.n_convolutions
-        buf = lambda key: _Slice(ws[key], ws[key].shape[-1])
-        cur = _Slice(state, C)
-        if "in" in ws:
-            _lib.call_on(self.device, "fv3hip_cyclegan_input", cur.ptr, C, 0, 0, _ptr(self._input_bias), _ptr(self._lon),
-                         _ptr(self._xyz), _ptr(theta), ws["in"].data_ptr(), ws["in"].shape[-1], 0, 0, S, n, C, _stream(self.device))
-            cur = buf("in")
-        self._conv("first", cur, _NONE, buf("raw0"), S, n)
-        cur, pend = buf("raw0"), self._stats("st:first", buf("raw0"), S, n, m, bias=self._embedded_bias)
-        for l in range(nc):
-            dst = buf(f"raw{l + 1}")
+        n, m = s.nx, s.min_filters
+        raw0 = self._buf("raw0")
+        self._conv("first", src, pend, raw0, S, n, ctx_cell=ctx_cell)
+        cur, pend = raw0, self._stats("st:first", raw0, S, n, m, bias=first_bias)
+        for l in range(s.n_convolutions):
+            dst = self._buf(f"raw{l + 1}")
             self._conv(f"down{l}", cur, pend, dst, S, n >> l)
             cur, pend = dst, self._stats(f"st:down{l}", dst, S, n >> (l + 1), m * 2 ** (l + 1))
-        if s.n_resnet:
-            nb, cb = n >> nc, m * 2 ** nc
-            x, a, b = buf("x"), buf("a"), buf("b")
-            self._apply(cur, pend, x, S, nb, cb)
-            for j in range(s.n_resnet):
-                self._conv(f"res{j}.a", x, _NONE, a, S, nb)
-                pa = self._stats("st:res.a", a, S, nb, cb)
-                self._conv(f"res{j}.b", a, pa, b, S, nb)
-                pb = self._stats("st:res.b", b, S, nb, cb, relu=False)
-                self._apply(b, pb, x, S, nb, cb, res=x)
-            cur, pend = x, _NONE
-        for l in reversed(range(nc)):
-            dst = buf(f"raw{l}")
+        return cur, pend
+
+    def _up_chain(self, cur: _Slice, pend: _Pending, out: _Slice, S: int):
+        """The ``up{l}`` layers and ``last``, which writes ``out``."""
+        s = self.spec
+        n, m = s.nx, s.min_filters
+        for l in reversed(range(s.n_convolutions)):
+            dst = self._buf(f"raw{l}")
             self._conv(f"up{l}", cur, pend, dst, S, n >> (l + 1))
             cur, pend = dst, self._stats(f"st:up{l}", dst, S, n >> l, m * 2 ** l)
         self._apply(cur, pend, cur, S, n, m)      # in place: the 49 taps of the last layer read it as it is
-        self._conv("last", cur, _NONE, _Slice(out, C), S, n, out_bias=self._output_bias)
+        self._conv("last", cur, _NONE, out, S, n, out_bias=self._output_bias)
 
-    def forward(self, state: torch.Tensor, theta: Optional[torch.Tensor] = None, chunk: Optional[int] = None) -> torch.Tensor:
-        """Normalised ``[S, 6, n, n, C]`` float32 and ``theta`` ``[S]`` float32 (the local-time offset of every sample in
-        radians; not needed without geographic features) -> the generated normalised state, a new tensor."""
+    def _check_state(self, state) -> torch.Tensor:
         s = self.spec
         if not isinstance(state, torch.Tensor) or state.dim() != 5:
-            raise ValueError("the state must be a [sample, tile, x, y, feature] tensor")
+            raise ValueError(f"the state must be a [{self._SAMPLE}, tile, x, y, feature] tensor")
         check_cube_shape(state.shape)
         if state.shape[-1] != s.channels:
             raise ValueError(f"the state has {state.shape[-1]} features, the network needs {s.channels}")
@@ -474,9 +507,51 @@ class GeneratorModel:
         if state.dtype != torch.float32:
             raise TypeError(f"the normalised state must be float32, got {state.dtype}")
         _require_device(state)
-        state = state.contiguous()
+        return state.contiguous()
+
+
+class GeneratorModel(_GeneratorRuntime):
+    """One generator on one device.  ``forward`` works through the samples in chunks (see ``_GeneratorRuntime``)."""
+
+    def __init__(self, spec: GeneratorSpec, convolution_type: str = "halo_conv2d", device="cuda",
+                 workspace_limit: int = 2 << 30, max_chunk: int = REFERENCE_BATCH):
+        super().__init__(spec, convolution_type, device, workspace_limit, max_chunk)
+        self._bottom = spec.n_resnet > 0
+        if spec.use_geographic_features or spec.use_geographic_bias:
+            self._in_channels = spec.channels + (N_GEOGRAPHIC_FEATURES if spec.use_geographic_features else 0)
+        self._embedded_bias = self._channel_last(spec.embedded_bias)
+        self._lon = None if spec.lon is None else self._up(spec.lon)
+        self._xyz = self._channel_last(spec.xyz)
+
+    def _forward_chunk(self, state: torch.Tensor, theta: Optional[torch.Tensor], out: torch.Tensor):
+        s = self.spec
+        S, n, C = int(state.shape[0]), s.nx, s.channels
+        cur = _Slice(state, C)
+        if "in" in self._ws:
+            dst = self._buf("in")
+            _lib.call_on(self.device, "fv3hip_cyclegan_input", cur.ptr, C, 0, 0, _ptr(self._input_bias), _ptr(self._lon),
+                         _ptr(self._xyz), _ptr(theta), dst.ptr, dst.ld, 0, 0, S, n, C, _stream(self.device))
+            cur = dst
+        cur, pend = self._down_chain(cur, _NONE, S, first_bias=self._embedded_bias)
+        if s.n_resnet:
+            nb, cb = n >> s.n_convolutions, s.min_filters * 2 ** s.n_convolutions
+            x, a, b = self._buf("x"), self._buf("a"), self._buf("b")
+            self._apply(cur, pend, x, S, nb, cb)
+            for j in range(s.n_resnet):
+                self._conv(f"res{j}.a", x, _NONE, a, S, nb)
+                pa = self._stats("st:a", a, S, nb, cb)
+                self._conv(f"res{j}.b", a, pa, b, S, nb)
+                pb = self._stats("st:b", b, S, nb, cb, relu=False)
+                self._apply(b, pb, x, S, nb, cb, res=x)
+            cur, pend = x, _NONE
+        self._up_chain(cur, pend, _Slice(out, C), S)
+
+    def forward(self, state: torch.Tensor, theta: Optional[torch.Tensor] = None, chunk: Optional[int] = None) -> torch.Tensor:
+        """Normalised ``[S, 6, n, n, C]`` float32 and ``theta`` ``[S]`` float32 (the local-time offset of every sample in
+        radians; not needed without geographic features) -> the generated normalised state, a new tensor."""
+        state = self._check_state(state)
         S = int(state.shape[0])
-        if s.use_geographic_features:
+        if self.spec.use_geographic_features:
             if theta is None:
                 raise ValueError("a generator with geographic features needs the time of every sample (theta)")
             theta = torch.as_tensor(theta, dtype=torch.float32).to(self.device).contiguous()
@@ -485,13 +560,8 @@ class GeneratorModel:
         else:
             theta = None
         out = torch.empty_like(state)
-        if S == 0:
-            return out
-        chunk = self.chunk_size(S) if chunk is None else max(1, int(chunk))
-        ws = self._workspace(chunk)
-        for i in range(0, S, chunk):
-            j = min(S, i + chunk)
-            self._forward_chunk(state[i:j], None if theta is None else theta[i:j], out[i:j], ws)
+        for i, j in self._chunks(S, chunk):
+            self._forward_chunk(state[i:j], None if theta is None else theta[i:j], out[i:j])
         return out
 
 
@@ -500,16 +570,10 @@ class CycleGanModel:
 
     def __init__(self, spec: CycleGanSpec, device="cuda", **generator_kwargs):
         spec.validate()
-        self.spec, self.device, self._kwargs = spec, torch.device(device), generator_kwargs
-        if self.device.type != "cuda":
-            raise RuntimeError("CycleGanModel needs a 'cuda' (ROCm) device; there is no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.spec, self.device, self._kwargs = spec, cuda_device(device, "CycleGanModel"), generator_kwargs
         _lib.load()
         self._generators: Dict[bool, GeneratorModel] = {}
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(self.device)
-        self._scalers = {d: tuple(up(a) for a in spec.scaler_arrays(d)) for d in "ab"}
-        self._nfeat = (ctypes.c_int * len(spec.variables))(*[f for _, f in spec.variables])
+        self._packers = {d: StatePacker(spec.variables, *spec.scaler_arrays(d), self.device) for d in "ab"}
 
     def generator(self, reverse: bool = False) -> GeneratorModel:
         if reverse not in self._generators:
@@ -518,36 +582,9 @@ class CycleGanModel:
 
     def pack(self, sources: Sequence[torch.Tensor], domain: str) -> torch.Tensor:
         """``sources[v]``: a ``[time, tile, x, y, level]`` view (any strides, float32 or float64) of state variable v ->
-        float32 ``[time, 6, n, n, F]``, ``(x - mean) / std`` in float64 with the domain's scalers (``fv3hip_graph_pack`` with
-        one time per window)."""
-        spec = self.spec
-        if len(sources) != len(spec.variables):
-            raise ValueError(f"{len(spec.variables)} sources are needed, got {len(sources)}")
-        dev = _require_device(*sources)
-        for (name, nfeat), t in zip(spec.variables, sources):
-            if t.dim() != 5 or t.shape[-1] != nfeat:
-                raise ValueError(f"variable {name!r} must be [time, tile, x, y, {nfeat}], got shape {tuple(t.shape)}")
-            if tuple(t.shape[:4]) != tuple(sources[0].shape[:4]):
-                raise ValueError("the state variables differ in their time, tile, x or y extent")
-            if t.dtype not in (torch.float32, torch.float64):
-                raise TypeError(f"variable {name!r} must be float32 or float64, got {t.dtype}")
-        T, n, k = int(sources[0].shape[0]), int(sources[0].shape[2]), len(sources)
-        mean, std = self._scalers[domain]
-        state = torch.empty((T, 6, n, n, spec.n_features), dtype=torch.float32, device=dev)
-        _lib.call_on(dev, "fv3hip_graph_pack", (ctypes.c_void_p * k)(*[t.data_ptr() for t in sources]),
-                     (ctypes.c_int * k)(*[_lib.F64 if t.dtype == torch.float64 else _lib.F32 for t in sources]),
-                     (ctypes.c_int64 * (5 * k))(*[s for t in sources for s in t.stride()]), k, self._nfeat, mean.data_ptr(),
-                     std.data_ptr(), T, 1, 1, n, state.data_ptr(), _stream(dev))
-        return state
+        float32 ``[time, 6, n, n, F]``, ``(x - mean) / std`` in float64 with the domain's scalers: one time per window."""
+        return self._packers[domain].pack(sources, None, 1, 1).squeeze(1)
 
     def unpack(self, state: torch.Tensor, domain: str) -> List[torch.Tensor]:
         """Float32 ``[time, 6, n, n, F]`` -> per variable float64 ``[time, 6, n, n, nfeat]``, ``float64(x) * std + mean``."""
-        dev = _require_device(state)
-        state = state.contiguous()
-        lead, n = tuple(state.shape[:-1]), int(state.shape[-2])
-        outs = [torch.empty(lead + (f,), dtype=torch.float64, device=dev) for _, f in self.spec.variables]
-        mean, std = self._scalers[domain]
-        _lib.call_on(dev, "fv3hip_graph_unpack", state.data_ptr(), int(state.shape[0]), n, len(outs), self._nfeat, mean.data_ptr(),
-                     std.data_ptr(), (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs]), _stream(dev))
-        return outs
-
+        return self._packers[domain].unpack(state)

@@ -18,18 +18,17 @@ restarts in every call.  ``RecurrentGeneratorModel`` runs the layers with the st
 current stream.  The context is never stored with the latent: ``fv3hip_cyclegan_conv_context`` reads the per-cell table and the
 clock's two numbers from where they lie.  DESIGN.md section 18.
 """
-import ctypes
 import dataclasses
 from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
-from .cyclegan import (INSTANCE_NORM_EPS, KINDS, MAX_VARIABLES, REFERENCE_BATCH, _NONE, _Pending, _ptr, _Slice,
-                       check_architecture, check_convolution_type, check_grid, split_transposed_weight, weight_shape)
-from .graph import check_cube_shape
-from .ops import _require_device, _stream
+from .cube import StatePacker, _Slice
+from .cyclegan import (MAX_VARIABLES, REFERENCE_BATCH, _NONE, _GeneratorRuntime, _Pending, check_architecture,
+                       check_convolution_type, check_grid, check_optional_arrays, check_plan_arrays, spec_from_arrays,
+                       spec_to_arrays)
+from .ops import _require_device
 
 STEP_TYPES = ("resnet", "conv")
 N_XYZ, N_CLOCK = 3, 2
@@ -149,26 +148,17 @@ class RecurrentGeneratorSpec:
         if self.samples_per_day is not None and int(self.samples_per_day) < 1:
             raise ValueError(f"samples_per_day must be at least 1 (or None), got {self.samples_per_day}")
         check_grid(self.nx, self.nx, self.n_convolutions)
-        plan = self.plan
-        names = {p[0] for p in plan}
-        if set(self.weights) != names or set(self.biases) != names:
-            raise ValueError(f"weights {sorted(self.weights)} / biases {sorted(self.biases)} differ from the layers {sorted(names)}")
-        for name, kind, ci, co, k, _ in plan:
-            for what, a, shape in (("weight", self.weights[name], weight_shape(kind, ci, co, k)), ("bias", self.biases[name], (co,))):
-                a = np.asarray(a)
-                if a.shape != shape or a.dtype != np.float32:
-                    raise ValueError(f"layer {name!r}: {what} has shape {a.shape} and dtype {a.dtype}, expected float32 {shape}")
+        check_plan_arrays(self.plan, self.weights, self.biases)
         n, nb, C = self.nx, self.nx_bottom, self.channels
         if (self.input_bias is None) != (self.output_bias is None):
             raise ValueError("input_bias and output_bias come together (use_geographic_bias)")
         if (self.xyz is None) != (self.xyz_bottom is None):
             raise ValueError("xyz and xyz_bottom come together (use_geographic_features)")
-        for what, a, shape in (("input_bias", self.input_bias, (6, C, n, n)), ("output_bias", self.output_bias, (6, C, n, n)),
-                               ("xyz", self.xyz, (6, 3, n, n)), ("xyz_bottom", self.xyz_bottom, (6, 3, nb, nb))):
-            if a is not None and (np.asarray(a).shape != shape or np.asarray(a).dtype != np.float32):
-                raise ValueError(f"{what} has shape {np.asarray(a).shape} and dtype {np.asarray(a).dtype}, expected float32 {shape}")
+        check_optional_arrays(self, {"input_bias": (6, C, n, n), "output_bias": (6, C, n, n), "xyz": (6, 3, n, n),
+                                     "xyz_bottom": (6, 3, nb, nb)})
 
-    _OPTIONAL = ("input_bias", "output_bias", "xyz", "xyz_bottom")
+    _FLAGS = {"input_bias": "use_geographic_bias", "output_bias": "use_geographic_bias", "xyz": "use_geographic_features",
+              "xyz_bottom": "use_geographic_features"}
 
     def to_arrays(self, prefix: str = ""):
         meta = {"channels": int(self.channels), "nx": int(self.nx), "n_convolutions": int(self.n_convolutions),
@@ -177,14 +167,7 @@ class RecurrentGeneratorSpec:
                 "step_type": str(self.step_type),
                 "samples_per_day": None if self.samples_per_day is None else int(self.samples_per_day),
                 "use_geographic_bias": self.use_geographic_bias, "use_geographic_features": self.use_geographic_features}
-        arrays = {}
-        for name in self.weights:
-            arrays[f"{prefix}{name}.weight"] = np.asarray(self.weights[name], np.float32)
-            arrays[f"{prefix}{name}.bias"] = np.asarray(self.biases[name], np.float32)
-        for key in self._OPTIONAL:
-            if getattr(self, key) is not None:
-                arrays[f"{prefix}{key}"] = np.asarray(getattr(self, key), np.float32)
-        return meta, arrays
+        return meta, spec_to_arrays(self, prefix, self._FLAGS)
 
     @classmethod
     def from_arrays(cls, meta: Mapping, arrays: Mapping[str, np.ndarray], prefix: str = "") -> "RecurrentGeneratorSpec":
@@ -194,13 +177,10 @@ class RecurrentGeneratorSpec:
         spd = meta.get("samples_per_day")
         plan = layer_plan(int(meta["channels"]), int(meta["n_convolutions"]), int(meta["n_resnet"]), int(meta["kernel_size"]),
                           meta["max_filters"], meta["step_type"], bool(meta["use_geographic_features"]), spd)
-        get = lambda key: np.asarray(arrays[prefix + key], np.float32)
-        flags = {"input_bias": "use_geographic_bias", "output_bias": "use_geographic_bias", "xyz": "use_geographic_features",
-                 "xyz_bottom": "use_geographic_features"}
-        return cls(int(meta["channels"]), int(meta["nx"]), {p[0]: get(p[0] + ".weight") for p in plan},
-                   {p[0]: get(p[0] + ".bias") for p in plan}, int(meta["n_convolutions"]), int(meta["n_resnet"]),
+        weights, biases, optional = spec_from_arrays(arrays, prefix, plan, meta, cls._FLAGS)
+        return cls(int(meta["channels"]), int(meta["nx"]), weights, biases, int(meta["n_convolutions"]), int(meta["n_resnet"]),
                    int(meta["kernel_size"]), int(meta.get("strided_kernel_size", 4)), meta["max_filters"], meta["step_type"],
-                   None if spd is None else int(spd), **{key: get(key) if meta[flag] else None for key, flag in flags.items()})
+                   None if spd is None else int(spd), **optional)
 
 
 @dataclasses.dataclass
@@ -268,113 +248,28 @@ class FullModelReplacementSpec:
                    meta["convolution_type"])
 
 
-class RecurrentGeneratorModel:
-    """One recurrent generator on one device: the weights uploaded once in the kernels' layout (a layer that reads context
-    channels as the source's rows and the context's rows), the two ``xyz`` tables and the clock table, and a workspace that is
-    kept between calls.  Windows are worked through in chunks of at most ``max_chunk`` whose workspace stays within
-    ``workspace_limit`` bytes; a window's result does not depend on the chunk it falls into."""
+class RecurrentGeneratorModel(_GeneratorRuntime):
+    """One recurrent generator on one device: the shared runtime of cyclegan.py (a layer that reads context channels holds its
+    weights as the source's rows and the context's rows), the two ``xyz`` tables and the clock table.  A sample is a window."""
+
+    _SAMPLE, _bottom = "window", True
 
     def __init__(self, spec: RecurrentGeneratorSpec, convolution_type: str = "halo_conv2d", device="cuda",
                  workspace_limit: int = 2 << 30, max_chunk: int = REFERENCE_BATCH):
-        spec.validate()
-        self.spec = spec
-        self.halo_mode = check_convolution_type(convolution_type)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("RecurrentGeneratorModel needs a 'cuda' (ROCm) device; there is no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if max_chunk < 1 or workspace_limit < 1:
-            raise ValueError(f"max_chunk and workspace_limit must be positive, got {max_chunk}, {workspace_limit}")
-        _lib.load()
-        self.workspace_limit, self.max_chunk = int(workspace_limit), int(max_chunk)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device)
-        c_cell, c_uni = spec.context_channels
-        self._layers = {p[0]: p for p in spec.plan}
-        self._w, self._w_ctx, self._b = {}, {}, {}
-        for name, kind, ci, co, k, _ in spec.plan:
-            w = np.asarray(spec.weights[name])
-            n_ctx = (c_cell if name == "first" else c_cell + c_uni) if name == "first" or name.endswith(".a") else 0
-            if n_ctx:     # [k][k][c][c_out] for the source's channels and for the context's
-                self._w_ctx[name] = up(w[:, ci - n_ctx:].transpose(2, 3, 1, 0))
-                w = w[:, :ci - n_ctx]
-            self._w[name] = up(split_transposed_weight(w) if kind == "transposed" else w.transpose(2, 3, 1, 0))
-            self._b[name] = up(spec.biases[name])
-        last = lambda a: None if a is None else up(np.asarray(a).transpose(0, 2, 3, 1))    # [6][n][n][c]
-        self._input_bias, self._output_bias = last(spec.input_bias), last(spec.output_bias)
-        self._xyz, self._xyz_bottom = last(spec.xyz), last(spec.xyz_bottom)
-        self._clock = None if spec.samples_per_day is None else up(clock_table(spec.samples_per_day))
-        self._ws: Dict[str, torch.Tensor] = {}
-        self._ws_chunk = 0
+        super().__init__(spec, convolution_type, device, workspace_limit, max_chunk)
+        self._xyz, self._xyz_bottom = self._channel_last(spec.xyz), self._channel_last(spec.xyz_bottom)
+        self._clock = None if spec.samples_per_day is None else self._up(clock_table(spec.samples_per_day))
 
-    # -- workspace -----------------------------------------------------------------------------------
-    def _buffers(self) -> Dict[str, Tuple[int, int]]:
-        """name -> (cells per edge, channels) of every activation buffer of one window."""
-        s = self.spec
-        out = {f"raw{l}": (s.nx >> l, s.min_filters * 2 ** l) for l in range(s.n_convolutions + 1)}
-        out.update({key: (s.nx_bottom, s.max_filters) for key in ("x", "a", "b")})
-        return out
-
-    def _stat_keys(self) -> Dict[str, int]:
-        s = self.spec
-        out = {"st:first": s.min_filters, "st:a": s.max_filters, "st:b": s.max_filters}
-        for l in range(s.n_convolutions):
-            out[f"st:down{l}"], out[f"st:up{l}"] = s.min_filters * 2 ** (l + 1), s.min_filters * 2 ** l
-        return out
-
-    def workspace_bytes_per_sample(self) -> int:
-        return 4 * (sum(6 * n * n * c for n, c in self._buffers().values()) + sum(2 * 6 * c for c in self._stat_keys().values()))
-
-    def chunk_size(self, n_samples: int) -> int:
-        return max(1, min(self.max_chunk, self.workspace_limit // self.workspace_bytes_per_sample(), max(n_samples, 1)))
-
-    def _workspace(self, chunk: int):
-        if chunk > self._ws_chunk:
-            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
-            self._ws = {key: new(chunk, 6, n, n, c) for key, (n, c) in self._buffers().items()}
-            self._ws.update({key: new(2, chunk, 6, c) for key, c in self._stat_keys().items()})
-            self._ws_chunk = chunk
-        return self._ws
-
-    # -- layer launches ------------------------------------------------------------------------------
-    def _conv(self, name, src: _Slice, pend: _Pending, dst: _Slice, S, n_in, out_bias=None, ctx_cell=None, ctx_uniform: int = 0):
-        """``ctx_uniform``: a device address (0: none).  A layer without context rows goes through the same entry point."""
-        _, kind, ci, co, k, _ = self._layers[name]
-        w_ctx = self._w_ctx.get(name)
-        c_cell = 0 if ctx_cell is None else int(ctx_cell.shape[-1])
-        c_uni = N_CLOCK if ctx_uniform else 0
-        _lib.call_on(self.device, "fv3hip_cyclegan_conv_context", src.ptr, src.ld, src.off, src.stride, _ptr(pend.mean),
-                     _ptr(pend.rstd), _ptr(pend.bias), int(pend.relu), self._w[name].data_ptr(), self._b[name].data_ptr(),
-                     _ptr(out_bias), dst.ptr, dst.ld, dst.off, dst.stride, S, n_in, ci - c_cell - c_uni, co, KINDS[kind], k,
-                     self.halo_mode, _ptr(ctx_cell), c_cell, ctx_uniform or None, c_uni, _ptr(w_ctx), _stream(self.device))
-
-    def _stats(self, key, src: _Slice, S, n, c, relu=True) -> _Pending:
-        st = self._ws[key]
-        _lib.call_on(self.device, "fv3hip_cyclegan_stats", src.ptr, src.ld, src.off, src.stride, st[0].data_ptr(), st[1].data_ptr(), S,
-                     n, c, INSTANCE_NORM_EPS, _stream(self.device))
-        return _Pending(st[0], st[1], None, relu)
-
-    def _apply(self, src: _Slice, pend: _Pending, dst: _Slice, S, n, c, res: Optional[_Slice] = None):
-        r = res or _Slice(src.tensor, 1)
-        _lib.call_on(self.device, "fv3hip_cyclegan_apply", src.ptr, src.ld, src.off, src.stride, _ptr(pend.mean), _ptr(pend.rstd),
-                     _ptr(pend.bias), int(pend.relu), r.ptr if res else None, r.ld, r.off, r.stride, dst.ptr, dst.ld, dst.off,
-                     dst.stride, S, n, c, _stream(self.device))
-
-    def _buf(self, key) -> _Slice:
-        return _Slice(self._ws[key], self._ws[key].shape[-1])
+    def _context_channels(self, name: str) -> int:
+        c_cell, c_uni = self.spec.context_channels
+        return c_cell if name == "first" else c_cell + c_uni if name.endswith(".a") else 0
 
     # -- the three parts on one chunk ----------------------------------------------------------------
     def _encode_chunk(self, state: torch.Tensor, x: _Slice):
         s = self.spec
-        S, n, m, nc = int(state.shape[0]), s.nx, s.min_filters, s.n_convolutions
-        raw0 = self._buf("raw0")
+        S = int(state.shape[0])
         # the geographic bias is added, and x, y, z read, by the loader of the 7 x 7 convolution: no input pass
-        self._conv("first", _Slice(state, s.channels), _Pending(bias=self._input_bias), raw0, S, n, ctx_cell=self._xyz)
-        cur, pend = raw0, self._stats("st:first", raw0, S, n, m)
-        for l in range(nc):
-            dst = self._buf(f"raw{l + 1}")
-            self._conv(f"down{l}", cur, pend, dst, S, n >> l)
-            cur, pend = dst, self._stats(f"st:down{l}", dst, S, n >> (l + 1), m * 2 ** (l + 1))
+        cur, pend = self._down_chain(_Slice(state, s.channels), _Pending(bias=self._input_bias), S, ctx_cell=self._xyz)
         self._apply(cur, pend, x, S, s.nx_bottom, s.max_filters)
 
     def _step_chunk(self, x: _Slice, i: int, S: int):
@@ -384,7 +279,7 @@ class RecurrentGeneratorModel:
         # row (i - 1) % spd of the clock table: two floats
         clock = 0 if self._clock is None else self._clock.data_ptr() + 4 * N_CLOCK * ((i - 1) % s.samples_per_day)
         for stem in s.step_stems:
-            self._conv(f"{stem}.a", x, _NONE, a, S, nb, ctx_cell=self._xyz_bottom, ctx_uniform=clock)
+            self._conv(f"{stem}.a", x, _NONE, a, S, nb, ctx_cell=self._xyz_bottom, ctx_uniform=clock, c_uni=N_CLOCK)
             pa = self._stats("st:a", a, S, nb, cb)
             self._conv(f"{stem}.b", a, pa, b, S, nb)
             if s.step_type == "resnet":
@@ -393,30 +288,7 @@ class RecurrentGeneratorModel:
                 self._apply(b, self._stats("st:b", b, S, nb, cb), x, S, nb, cb)
 
     def _decode_chunk(self, x: _Slice, out: _Slice, S: int):
-        s = self.spec
-        n, m, nc = s.nx, s.min_filters, s.n_convolutions
-        cur, pend = x, _NONE
-        for l in reversed(range(nc)):
-            dst = self._buf(f"raw{l}")
-            self._conv(f"up{l}", cur, pend, dst, S, n >> (l + 1))
-            cur, pend = dst, self._stats(f"st:up{l}", dst, S, n >> l, m * 2 ** l)
-        self._apply(cur, pend, cur, S, n, m)      # in place: the 49 taps of the last layer read it as it is
-        self._conv("last", cur, _NONE, out, S, n, out_bias=self._output_bias)
-
-    # -- checks --------------------------------------------------------------------------------------
-    def _check_state(self, state) -> torch.Tensor:
-        s = self.spec
-        if not isinstance(state, torch.Tensor) or state.dim() != 5:
-            raise ValueError("the state must be a [window, tile, x, y, feature] tensor")
-        check_cube_shape(state.shape)
-        if state.shape[-1] != s.channels:
-            raise ValueError(f"the state has {state.shape[-1]} features, the network needs {s.channels}")
-        if state.shape[2] != s.nx:
-            raise ValueError(f"the state has faces of {state.shape[2]} cells per edge, the generator was built for nx = {s.nx}")
-        if state.dtype != torch.float32:
-            raise TypeError(f"the normalised state must be float32, got {state.dtype}")
-        _require_device(state)
-        return state.contiguous()
+        self._up_chain(x, _NONE, out, S)
 
     def _check_latent(self, latent) -> torch.Tensor:
         s = self.spec
@@ -430,11 +302,6 @@ class RecurrentGeneratorModel:
         if not latent.is_contiguous():
             raise ValueError("the latent must be contiguous")
         return latent
-
-    def _chunks(self, S: int, chunk: Optional[int]):
-        chunk = self.chunk_size(S) if chunk is None else max(1, int(chunk))
-        self._workspace(chunk)
-        return [(i, min(S, i + chunk)) for i in range(0, S, chunk)]
 
     # -- public --------------------------------------------------------------------------------------
     def encode(self, state: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
@@ -498,46 +365,14 @@ class FullModelReplacementModel:
         self.spec = spec
         self.generator = RecurrentGeneratorModel(spec.generator, spec.convolution_type, device, **generator_kwargs)
         self.device = self.generator.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(self.device)
-        self._mean, self._std = (up(a) for a in spec.scaler_arrays())
-        self._nfeat = (ctypes.c_int * len(spec.variables))(*[f for _, f in spec.variables])
+        self._packer = StatePacker(spec.variables, *spec.scaler_arrays(), self.device)
 
     def pack(self, sources: Sequence[torch.Tensor], n_windows: int, timesteps: int) -> torch.Tensor:
         """``sources[v]``: a ``[time, tile, x, y, level]`` view (any strides, float32 or float64) of state variable v ->
         float32 ``[n_windows, timesteps + 1, 6, n, n, F]``, ``(x - mean) / std`` in float64, window w from times
         ``w * timesteps ...`` (``fv3hip_graph_pack``)."""
-        spec = self.spec
-        if len(sources) != len(spec.variables):
-            raise ValueError(f"{len(spec.variables)} sources are needed, got {len(sources)}")
-        dev = _require_device(*sources)
-        for (name, nfeat), t in zip(spec.variables, sources):
-            if t.dim() != 5 or t.shape[-1] != nfeat:
-                raise ValueError(f"variable {name!r} must be [time, tile, x, y, {nfeat}], got shape {tuple(t.shape)}")
-            check_cube_shape(t.shape[:-1] + (0,), f"variable {name!r}")
-            if tuple(t.shape[:4]) != tuple(sources[0].shape[:4]):
-                raise ValueError("the state variables differ in their time, tile, x or y extent")
-            if t.dtype not in (torch.float32, torch.float64):
-                raise TypeError(f"variable {name!r} must be float32 or float64, got {t.dtype}")
-        if timesteps < 1 or n_windows < 0 or n_windows * timesteps + 1 > sources[0].shape[0]:
-            raise ValueError(f"{n_windows} windows of {timesteps} steps do not fit {sources[0].shape[0]} times")
-        n, k = int(sources[0].shape[2]), len(sources)
-        state = torch.empty((n_windows, timesteps + 1, 6, n, n, spec.n_features), dtype=torch.float32, device=dev)
-        _lib.call_on(dev, "fv3hip_graph_pack", (ctypes.c_void_p * k)(*[t.data_ptr() for t in sources]),
-                     (ctypes.c_int * k)(*[_lib.F64 if t.dtype == torch.float64 else _lib.F32 for t in sources]),
-                     (ctypes.c_int64 * (5 * k))(*[s for t in sources for s in t.stride()]), k, self._nfeat, self._mean.data_ptr(),
-                     self._std.data_ptr(), n_windows, timesteps + 1, timesteps, n, state.data_ptr(), _stream(dev))
-        return state
+        return self._packer.pack(sources, n_windows, timesteps + 1, timesteps)
 
     def unpack(self, state: torch.Tensor) -> List[torch.Tensor]:
         """Float32 ``[..., 6, n, n, F]`` -> per variable float64 ``[..., 6, n, n, nfeat]``, ``float64(x) * std + mean``."""
-        check_cube_shape(state.shape)
-        if state.dtype != torch.float32 or state.shape[-1] != self.spec.n_features:
-            raise ValueError(f"the state must be float32 with {self.spec.n_features} features")
-        dev = _require_device(state)
-        state = state.contiguous()
-        lead, n = tuple(state.shape[:-1]), int(state.shape[-2])
-        outs = [torch.empty(lead + (f,), dtype=torch.float64, device=dev) for _, f in self.spec.variables]
-        rows = int(np.prod(lead[:-3])) if lead[:-3] else 1
-        _lib.call_on(dev, "fv3hip_graph_unpack", state.data_ptr(), rows, n, len(outs), self._nfeat, self._mean.data_ptr(),
-                     self._std.data_ptr(), (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs]), _stream(dev))
-        return outs
+        return self._packer.unpack(state)

@@ -16,7 +16,6 @@ state's feature count,
 ``GraphModel`` keeps the weights on the device and runs the layers with the stateless ``fv3hip_graph_*`` kernels on torch's
 current stream, one launch after the other (no side streams: a captured rollout is one linear chain).  DESIGN.md section 16.
 """
-import ctypes
 import dataclasses
 from typing import Dict, List, Mapping, Sequence, Tuple
 
@@ -24,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .cube import StatePacker, _Slice, check_cube_shape, cuda_device  # noqa: F401  (check_cube_shape: imported from here)
 from .ops import _require_device, _stream
 
 ACTIVATIONS = {"linear": _lib.ACT_LINEAR, "relu": _lib.ACT_RELU, "tanh": _lib.ACT_TANH}
@@ -189,41 +189,19 @@ class GraphUNetSpec:
                    pooling_size=int(meta.get("pooling_size", 2)), pooling_stride=int(meta.get("pooling_stride", 2)))
 
 
-class _Slice:
-    """A channel slice of a channel-last device buffer ``[S][6][n][n][ld]`` (``stride``: elements between samples)."""
-
-    def __init__(self, tensor: torch.Tensor, ld: int, off: int = 0, stride: int = 0):
-        self.tensor, self.ptr, self.ld, self.off, self.stride = tensor, tensor.data_ptr(), int(ld), int(off), int(stride)
-
-
-def check_cube_shape(shape: Sequence[int], what: str = "state"):
-    """``[..., tile, x, y, feature]``: six square tiles."""
-    if len(shape) < 4:
-        raise ValueError(f"{what} must be [..., tile, x, y, feature], got shape {tuple(shape)}")
-    if shape[-4] != 6:
-        raise ValueError(f"{what} must hold the six tiles of the cube, got {shape[-4]} tiles")
-    if shape[-3] != shape[-2]:
-        raise ValueError(f"cube tiles are square, got {shape[-3]} x {shape[-2]}")
-
-
 class GraphModel:
     """The network and the scalers of a ``GraphUNetSpec`` on one device."""
 
     def __init__(self, spec: GraphUNetSpec, device="cuda"):
         spec.validate()
         self.spec = spec
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("GraphModel needs a 'cuda' (ROCm) device; there is no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = cuda_device(device, "GraphModel")
         _lib.load()
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
         self._weights = {name: {f.name: up(getattr(layer, f.name)) for f in dataclasses.fields(layer)}
                          for name, layer in spec.layers.items()}
-        self._mean = up(np.concatenate([np.asarray(v.mean, np.float64) for v in spec.variables]))
-        self._std = up(np.concatenate([np.asarray(v.std, np.float64) for v in spec.variables]))
-        self._nfeat = (ctypes.c_int * len(spec.variables))(*[v.nfeat for v in spec.variables])
+        self._packer = StatePacker([(v.name, v.nfeat) for v in spec.variables], np.concatenate([v.mean for v in spec.variables]),
+                                   np.concatenate([v.std for v in spec.variables]), self.device)
         self._act = ACTIVATIONS[spec.activation]
 
     # -- layers ------------------------------------------------------------------------------------
@@ -307,39 +285,8 @@ class GraphModel:
     def pack(self, sources: Sequence[torch.Tensor], n_windows: int, timesteps: int) -> torch.Tensor:
         """``sources[v]``: a ``[time, tile, x, y, level]`` view (any strides, float32 or float64) of state variable v ->
         normalised float32 ``[n_windows, timesteps + 1, 6, n, n, F]``, window w from times ``w * timesteps ...``."""
-        spec = self.spec
-        if len(sources) != len(spec.variables):
-            raise ValueError(f"{len(spec.variables)} sources are needed, got {len(sources)}")
-        dev = _require_device(*sources)
-        n = int(sources[0].shape[2])
-        for v, t in zip(spec.variables, sources):
-            if t.dim() != 5 or t.shape[-1] != v.nfeat:
-                raise ValueError(f"variable {v.name!r} must be [time, tile, x, y, {v.nfeat}], got shape {tuple(t.shape)}")
-            check_cube_shape(t.shape[:-1] + (0,), f"variable {v.name!r}")
-            if tuple(t.shape[:4]) != tuple(sources[0].shape[:4]):
-                raise ValueError("the state variables differ in their time, tile, x or y extent")
-            if t.dtype not in (torch.float32, torch.float64):
-                raise TypeError(f"variable {v.name!r} must be float32 or float64, got {t.dtype}")
-        if timesteps < 1 or n_windows < 0 or n_windows * timesteps + 1 > sources[0].shape[0]:
-            raise ValueError(f"{n_windows} windows of {timesteps} steps do not fit {sources[0].shape[0]} times")
-        k = len(sources)
-        state = torch.empty((n_windows, timesteps + 1, 6, n, n, spec.n_features), dtype=torch.float32, device=dev)
-        _lib.call_on(dev, "fv3hip_graph_pack", (ctypes.c_void_p * k)(*[t.data_ptr() for t in sources]),
-                     (ctypes.c_int * k)(*[_lib.F64 if t.dtype == torch.float64 else _lib.F32 for t in sources]),
-                     (ctypes.c_int64 * (5 * k))(*[s for t in sources for s in t.stride()]), k, self._nfeat, self._mean.data_ptr(),
-                     self._std.data_ptr(), n_windows, timesteps + 1, timesteps, n, state.data_ptr(), _stream(dev))
-        return state
+        return self._packer.pack(sources, n_windows, timesteps + 1, timesteps)
 
     def unpack(self, state: torch.Tensor) -> List[torch.Tensor]:
         """Normalised float32 ``[..., 6, n, n, F]`` -> per variable float64 ``[..., 6, n, n, nfeat]``, ``x * std + mean``."""
-        check_cube_shape(state.shape)
-        if state.dtype != torch.float32 or state.shape[-1] != self.spec.n_features:
-            raise ValueError(f"the state must be float32 with {self.spec.n_features} features")
-        dev = _require_device(state)
-        state = state.contiguous()
-        lead, n = tuple(state.shape[:-1]), int(state.shape[-2])
-        outs = [torch.empty(lead + (v.nfeat,), dtype=torch.float64, device=dev) for v in self.spec.variables]
-        rows = int(np.prod(lead[:-3])) if lead[:-3] else 1
-        _lib.call_on(dev, "fv3hip_graph_unpack", state.data_ptr(), rows, n, len(outs), self._nfeat, self._mean.data_ptr(),
-                     self._std.data_ptr(), (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs]), _stream(dev))
-        return outs
+        return self._packer.unpack(state)

@@ -17,6 +17,7 @@ import torch
 import yaml
 
 from . import _lib
+from .cube import cuda_device
 from .ops import _require_device, _stream
 
 # ---------------------------------------------------------------------------------------------
@@ -312,11 +313,7 @@ class _ColumnCodec:
         raise NotImplementedError
 
     def _handle_on(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"{type(self).__name__} needs a 'cuda' (ROCm) device; there is no CPU fallback")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = cuda_device(device, type(self).__name__)
         handles = self.__dict__.setdefault("_handles", {})
         if device.index not in handles:
             keep = []
