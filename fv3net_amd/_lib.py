@@ -23,6 +23,7 @@ ARITH_EXACT, ARITH_FAST = 0, 1
 CYCLEGAN_CONV_REGULAR, CYCLEGAN_CONV_STRIDED, CYCLEGAN_CONV_TRANSPOSED = 0, 1, 2
 CYCLEGAN_HALO_ZEROS, CYCLEGAN_HALO_CUBE = 0, 1
 CODEC_DENSE, CODEC_AFFINE = 0, 1
+FOREST_TRAIN_SUMS, FOREST_TRAIN_SCAN, FOREST_TRAIN_SPLIT, FOREST_TRAIN_ALL = 1, 2, 4, 7
 ABI_VERSION = 3
 
 OK, EINVAL, EUNSUPPORTED, EHIP, ENOMEM = 0, -1, -2, -3, -4
@@ -197,6 +198,20 @@ class CodecDesc(ctypes.Structure):
         ("explained_variance", POINTER(c_double)),
         ("enforce_positive", c_int),
     ]
+
+
+class ForestTrain(ctypes.Structure):
+    """``fv3hip_forest_train_t``: every buffer of one tree's growth (device pointers as integers)."""
+
+    _fields_ = (
+        [("n", c_int64), ("F", c_int), ("O", c_int)]
+        + [(k, c_void_p) for k in ("xt", "y", "ysq", "order", "weight", "list_a", "list_b", "side", "pos_node", "seg_a", "seg_b",
+                                   "node_a", "node_b", "stats", "carry", "count", "proxy", "best_proxy", "best_pos", "n_left",
+                                   "dst_left", "dst_right")]
+        + [("k_cap", c_int64), ("node_cap", c_int64)]
+        + [(k, c_void_p) for k in ("left", "right", "feature", "threshold", "missing_left", "value", "impurity", "weighted_n",
+                                   "n_samples", "level")]
+    )
 
 
 # name -> (restype, argtypes); every name here must be declared in include/fv3hip.h
@@ -405,6 +420,10 @@ SIGNATURES = {
                                       c_void_p]),
     "fv3hip_train_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_double, c_double, c_double, c_double,
                                   c_void_p]),
+    "fv3hip_forest_train_chunk": (c_int, []),
+    "fv3hip_forest_train_begin": (c_int, [POINTER(ForestTrain), c_int64, c_void_p]),
+    "fv3hip_forest_train_level": (c_int, [POINTER(ForestTrain), c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_int64,
+                                          c_int, c_void_p]),
     "fv3hip_timer_create": (c_int, [POINTER(c_void_p)]),
     "fv3hip_timer_start": (c_int, [c_void_p, c_void_p]),
     "fv3hip_timer_stop": (c_int, [c_void_p, c_void_p]),

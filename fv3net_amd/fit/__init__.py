@@ -15,7 +15,7 @@ from .data_transform import DATA_TRANSFORM_REGISTRY, ChainedDataTransform, DataT
 from .novelty import (MinMaxNoveltyDetector, NoveltyDetector, OCSVMNoveltyDetector, get_taper_function, taper_decay, taper_mask,
                       taper_ramp)
 from .transformed import OutOfSampleModel, TransformedPredictor
-from .forest import RandomForest
+from .forest import RandomForest, RandomForestHyperparameters, train_random_forest
 from .conv import HipConvolutionalModel, conv_spec_from_arrays
 from .precipitative import (HipPrecipitativeModel, PrecipitativeHyperparameters, precipitative_spec_from_arrays,
                             train_precipitative_model)
@@ -48,4 +48,5 @@ __all__ = [
     "BatchLinearRegressor", "BatchLinearRegressorHyperparameters", "CubedsphereSubdomainConfig", "NotFittedError", "Reservoir",
     "ReservoirHyperparameters", "ReservoirTrainingConfig", "SynchronizationTracker", "TransformerGroup", "train_reservoir_model",
     "InputSensitivity", "JacobianInputSensitivity", "RandomForestInputSensitivity",
+    "RandomForestHyperparameters", "train_random_forest",
 ]

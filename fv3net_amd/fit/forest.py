@@ -1,24 +1,29 @@
 """The random-forest predictor: ``fv3fit.sklearn.RandomForest`` (registered ``"sklearn"``,
 external/fv3fit/fv3fit/sklearn/_random_forest.py:65-377), predicting on the MI355X.
 
-Training stays sklearn's, offline.  ``from_sklearn`` exports a fitted ``RandomForestRegressor`` / ``ExtraTreesRegressor``
-to plain arrays (``fv3net_amd.forest.tree_arrays``); ``predict`` runs ``fv3hip_forest_predict`` and returns what
+``train_random_forest`` (the reference's ``"sklearn_random_forest"`` training function, _random_forest.py:39-62) grows the trees
+on the device (``fv3net_amd.forest_train``, csrc/forest_train.hip): the trees of sklearn's ``RandomForestRegressor`` with the
+same hyperparameters and ``random_state`` -- the same partition of the training samples into leaves, leaf values equal to
+rounding.  ``from_sklearn`` exports a forest that sklearn fitted (``RandomForestRegressor`` / ``ExtraTreesRegressor``) to the same
+plain arrays (``fv3net_amd.forest.tree_arrays``); ``predict`` runs ``fv3hip_forest_predict`` and returns what
 ``SklearnWrapper.predict`` returns, bit for bit.  The artifact is ``name`` ("sklearn") + ``forest.npz`` + ``metadata.yaml``,
 nothing executable.  ``load`` also reads a directory in the reference's own layout (``sklearn.pkl`` + ``scaler.bin`` +
 ``metadata.bin``) where sklearn and joblib import, converting it on the way.
 """
+import dataclasses
 import io as _bytes_io
 import os
-from typing import Dict, Hashable, Mapping, Optional, Sequence, Tuple
+from typing import Dict, Hashable, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 import yaml
 
 from ..cubedsphere._device import compute_device, download_all
-from ..forest import TREE_ARRAYS, ForestInput, ForestModel, ForestOutput, ForestSpec, tree_arrays
+from ..forest import TREE_ARRAYS, TREE_STATS, ForestInput, ForestModel, ForestOutput, ForestSpec, tree_arrays
 from ..xr_compat import DataArray, Dataset, from_compat, to_compat
 from . import io
+from .input_sensitivity import InputSensitivity, RandomForestInputSensitivity
 from .novelty import Clip, _slice
 from .predictor import Predictor
 from .stacking import column_sources, match_prediction_to_input_coords
@@ -55,6 +60,8 @@ class RandomForest(Predictor):
         if len(self.output_features) != len(self.output_variables):
             raise ValueError("output_features needs one feature count per output variable")
         self.trees = {k: np.asarray(trees[k]) for k in TREE_ARRAYS}
+        if all(k in trees for k in TREE_STATS):  # (a forest exported before the statistics were kept has none)
+            self.trees.update({k: np.asarray(trees[k]) for k in TREE_STATS})
         self.n_features_in = int(n_features_in)
         self.mean = np.asarray(mean, np.float64).reshape(-1)
         self.std = np.asarray(std, np.float64).reshape(-1)
@@ -127,6 +134,38 @@ class RandomForest(Predictor):
         for name in self.output_variables:
             result[name] = DataArray(shaped[name], dims=dims_of[name])
         return from_compat(match_prediction_to_input_coords(x, result), X)
+
+    # -- sensitivity -------------------------------------------------------------------------
+    def feature_importances(self) -> np.ndarray:
+        """[tree, packed input feature]: sklearn's ``feature_importances_`` of every tree."""
+        from ..forest_train import feature_importances
+
+        if not all(k in self.trees for k in TREE_STATS):
+            raise NotImplementedError("this forest carries no impurity statistics (" + ", ".join(TREE_STATS) + "): it was exported "
+                                      "before they were kept; export it again from the fitted estimator, or train it here")
+        return feature_importances(self.trees, self.n_features_in)
+
+    def input_sensitivity(self, stacked_sample) -> InputSensitivity:
+        """Mean and standard deviation over the trees of sklearn's feature importances, grouped by input variable
+        (_random_forest.py:127-172).  ``stacked_sample`` holds the inputs as ``[sample, feature]`` (``[sample]``: a scalar, whose
+        index is NaN); it is read for its feature counts only."""
+        importances = self.feature_importances()
+        mean, std = importances.mean(axis=0), importances.std(axis=0)
+        sample = to_compat(stacked_sample)
+        out, col = {}, 0
+        for name in self.input_variables:
+            values = sample[name].values
+            if values.ndim == 1:
+                indices: List = [float("nan")]
+            else:
+                indices = list(range(len(range(values.shape[-1])[_slice(self.clip, name)])))
+            nf = len(indices)
+            out[name] = RandomForestInputSensitivity(mean_importances=mean[col:col + nf].tolist(),
+                                                     std_importances=std[col:col + nf].tolist(), indices=indices)
+            col += nf
+        if col != self.n_features_in:
+            raise ValueError(f"the sample has {col} input features, but the forest was fitted on {self.n_features_in}")
+        return InputSensitivity(rf_feature_importances=out)
 
     # -- serialisation -----------------------------------------------------------------------
     def dump(self, path: str) -> None:
@@ -202,3 +241,90 @@ def _read_standard_scaler(blob: bytes):
         if "mean" not in z.files or "std" not in z.files:
             raise ValueError("Target scaler not present.")
         return np.asarray(z["mean"], np.float64), np.asarray(z["std"], np.float64)
+
+
+# ---------------------------------------------------------------------------------------------
+# training (csrc/forest_train.hip)
+# ---------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class RandomForestHyperparameters:
+    """fv3fit's ``RandomForestHyperparameters`` (training_config.py:280-332), same fields and defaults.  ``packer_config`` is
+    ``{"clip": {name: {"start", "stop", "step"}}}``.  ``n_jobs`` is accepted and ignored: the trees grow on the device."""
+
+    input_variables: List[str]
+    output_variables: List[str]
+    scaler_type: str = "standard"
+    scaler_kwargs: Optional[Mapping] = None
+    n_jobs: int = 8
+    random_state: int = 0
+    n_estimators: int = 100
+    max_depth: Optional[int] = None
+    min_samples_split: Union[int, float] = 2
+    min_samples_leaf: Union[int, float] = 1
+    max_features: Union[str, int, float, None] = "auto"
+    max_samples: Optional[Union[int, float]] = None
+    bootstrap: bool = True
+    packer_config: Mapping = dataclasses.field(default_factory=lambda: {"clip": {}})
+    predict_columns: bool = True
+
+    @property
+    def clip(self) -> Dict:
+        pc = self.packer_config
+        clip = pc.get("clip") if isinstance(pc, Mapping) else getattr(pc, "clip", None)
+        return {name: dict(c) if isinstance(c, Mapping) else {"start": c.start, "stop": c.stop, "step": c.step}
+                for name, c in (clip or {}).items()}
+
+
+def _pack_batches(batches, names, clip) -> Tuple[np.ndarray, List[int]]:
+    """``pack_tfdataset`` over the concatenated batches: every variable ``[sample]`` or ``[sample, feature]`` (ensure_nd(2)),
+    float64 cast to float32 (tfdataset.float64_to_float32), clipped along the feature dimension, side by side."""
+    cols: List[List[np.ndarray]] = [[] for _ in names]
+    for batch in batches:
+        batch = to_compat(batch) if not isinstance(batch, Mapping) else batch
+        for i, name in enumerate(names):
+            a = batch[name]
+            a = np.asarray(a.values if hasattr(a, "values") else a)
+            if a.ndim == 1:
+                a = a[:, None]
+            if a.ndim != 2:
+                raise ValueError(f"{name!r} has shape {a.shape}: batches must be stacked with at most one non-sample dimension")
+            if a.dtype == np.float64:
+                a = a.astype(np.float32)
+            cols[i].append(a[:, _slice(clip, name)])
+    if not cols or not cols[0]:
+        raise ValueError("no training batches")
+    packed = [np.concatenate(c, axis=0) for c in cols]
+    return np.concatenate(packed, axis=1), [int(p.shape[1]) for p in packed]
+
+
+def train_random_forest(hyperparameters: RandomForestHyperparameters, train_batches, validation_batches=None) -> RandomForest:
+    """The reference's ``train_random_forest`` (_random_forest.py:39-62, SklearnWrapper.fit :232-257) with the trees grown on the
+    device: all batches in one, float64 cast to float32, the inputs clipped by ``packer_config``, the targets normalised by a
+    ``StandardScaler`` fitted on them, then ``n_estimators`` trees seeded and bootstrapped as ``RandomForestRegressor`` seeds and
+    bootstraps them.  ``validation_batches`` is ignored, as there."""
+    from ..forest_train import check_max_features, forest_arrays, grow_forest
+
+    hp = hyperparameters
+    if hp.scaler_type != "standard":
+        raise NotImplementedError("only 'standard' scaler_type is implemented")
+    clip = hp.clip
+    for name in clip:
+        if name in hp.output_variables:
+            raise NotImplementedError("Clipping for ML outputs is not implemented.")
+        if _slice(clip, name).step not in (None, 1):  # (what the predictor could not run is refused before it is trained)
+            raise NotImplementedError(f"clip of {name!r} has a step; only contiguous level ranges are supported")
+    X, _ = _pack_batches(train_batches, [str(v) for v in hp.input_variables], clip)
+    y, output_features = _pack_batches(train_batches, [str(v) for v in hp.output_variables], {})
+    check_max_features(hp.max_features, X.shape[1])
+    if not np.isfinite(X).all() or not np.isfinite(y).all():
+        raise ValueError("the training inputs and targets must be finite")
+    # StandardScaler.fit / normalize (_shared/scaler.py:56-68): statistics in the data's dtype, then float64
+    mean = np.mean(y, axis=0).astype(np.float64)
+    std = np.std(y, axis=0).astype(np.float64) + 1e-12  # (the wrapper builds its scaler without scaler_kwargs)
+    y_norm = (y - mean) / std
+    trees = grow_forest(X.astype(np.float32), y_norm, n_estimators=hp.n_estimators, random_state=hp.random_state,
+                        max_depth=hp.max_depth, min_samples_split=hp.min_samples_split, min_samples_leaf=hp.min_samples_leaf,
+                        max_features=hp.max_features, max_samples=hp.max_samples, bootstrap=hp.bootstrap,
+                        device=torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu")
+    return RandomForest(hp.input_variables, hp.output_variables, output_features, forest_arrays(trees), X.shape[1], mean, std,
+                        clip=clip, predict_columns=hp.predict_columns)

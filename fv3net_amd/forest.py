@@ -19,6 +19,9 @@ from .ops import _require_device, _stream
 # the arrays of a ForestSpec, in the order they are saved
 TREE_ARRAYS = ("node_offset", "children_left", "children_right", "feature", "threshold", "missing_go_to_left", "leaf_row",
                "leaf_values")
+# optional per-node training statistics (sklearn's ``tree_`` arrays of the same names), concatenated like the node arrays: a
+# forest that carries them can report feature importances
+TREE_STATS = ("impurity", "n_node_samples", "weighted_n_node_samples")
 
 
 def float32_floor(t: np.ndarray) -> np.ndarray:
@@ -33,8 +36,10 @@ def float32_floor(t: np.ndarray) -> np.ndarray:
 
 def tree_arrays(estimator) -> Dict[str, np.ndarray]:
     """sklearn ``tree_`` arrays of every tree of a fitted forest (``estimator.estimators_``), concatenated with tree-local
-    node ids, thresholds as ``float32_floor``, and the leaves' values renumbered into one ``[leaf_row, n_out]`` table."""
+    node ids, thresholds as ``float32_floor``, and the leaves' values renumbered into one ``[leaf_row, n_out]`` table; plus the
+    ``TREE_STATS`` of every node."""
     offsets, left, right, feature, threshold, missing, leaf_row, values = [0], [], [], [], [], [], [], []
+    impurity, n_node, weighted_n = [], [], []
     n_rows = 0
     for est in estimator.estimators_:
         t = est.tree_
@@ -52,6 +57,9 @@ def tree_arrays(estimator) -> Dict[str, np.ndarray]:
         missing.append(np.zeros(cl.shape, np.uint8) if mgl is None else np.asarray(mgl, np.uint8))
         leaf_row.append(rows)
         values.append(np.asarray(t.value, np.float64)[is_leaf, :, 0])
+        impurity.append(np.asarray(t.impurity, np.float64))
+        n_node.append(np.asarray(t.n_node_samples, np.int64))
+        weighted_n.append(np.asarray(t.weighted_n_node_samples, np.float64))
     return {
         "node_offset": np.asarray(offsets, np.int64),
         "children_left": np.concatenate(left),
@@ -61,6 +69,9 @@ def tree_arrays(estimator) -> Dict[str, np.ndarray]:
         "missing_go_to_left": np.concatenate(missing),
         "leaf_row": np.concatenate(leaf_row),
         "leaf_values": np.ascontiguousarray(np.concatenate(values, axis=0)),
+        "impurity": np.concatenate(impurity),
+        "n_node_samples": np.concatenate(n_node),
+        "weighted_n_node_samples": np.concatenate(weighted_n),
     }
 
 

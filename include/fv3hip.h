@@ -1222,6 +1222,69 @@ int fv3hip_train_mse_grad(const float *yhat, int64_t ldy, const float *scale, co
 int fv3hip_train_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step, double lr, double beta1,
                       double beta2, double eps, void *stream);
 
+/* ---- training random forests (fv3fit's "sklearn_random_forest"; sklearn's RandomForestRegressor.fit: squared error, exact
+ * best split, all features).  Stateless like fv3hip_train_*: the caller owns every DEVICE buffer below, nothing is allocated or
+ * synchronised, the arguments are checked on the host before any HIP call.  One tree grows level by level:
+ *   fv3hip_forest_train_begin   compacts every row of `order` to the samples with weight > 0 (list_a; n_inbag of them) and makes
+ *                               them the root's segment; level = {1, n_inbag, 1, 0}.
+ *   fv3hip_forest_train_level   one level of the tree over n_open open nodes that cover n_positions list positions, the tree
+ *                               holding n_nodes nodes so far (all three as `level` reported them); parity 0 reads list_a / seg_a /
+ *                               node_a and writes the b set, parity 1 the reverse.  Writes the records of the level's nodes and
+ *                               level = {open nodes of the next level, their positions, nodes so far, 0}.  The caller reads
+ *                               `level` back, stops at level[0] == 0 and otherwise calls again with depth + 1 and the other
+ *                               parity.  max_depth < 0: unlimited.
+ * A node is a leaf at depth >= max_depth, with fewer than min_samples_split or 2 min_samples_leaf samples, with impurity <=
+ * DBL_EPSILON or without an admissible position; positions p | p + 1 of a feature's sorted segment are admissible where
+ * x[p + 1] > x[p] + 1e-7f (float32) and both sides hold min_samples_leaf samples.  The greatest proxy
+ * sum_k SL_k^2 / WL + sum_k (S_k - SL_k)^2 / WR wins, then the lowest feature, then the lowest position.  Children are numbered
+ * level by level (left, right, in node order); the caller renumbers.  Every sum has a fixed order; there are no atomics on
+ * floating-point values.
+ * Buffer sizes, with C = fv3hip_forest_train_chunk() and chunks = ceil(n / C): k_cap >= the most open nodes of a level (at most
+ * min(n_inbag, 2^max_depth)), node_cap >= the nodes of the tree (at most min(2 n_inbag - 1, 2^(max_depth + 1) - 1)). */
+typedef struct {
+    int64_t n;               /* samples */
+    int F, O;                /* features, outputs */
+    const float *xt;         /* [F][n] inputs, feature-major */
+    const double *y;         /* [n][O] targets */
+    const double *ysq;       /* [n] sum_k y[i][k]^2 */
+    const int32_t *order;    /* [F][n] stable argsort of each feature */
+    const int32_t *weight;   /* [n] bootstrap counts of this tree */
+    int32_t *list_a, *list_b;   /* [F][n] */
+    uint8_t *side;           /* [n] */
+    int32_t *pos_node;       /* [n] */
+    int64_t *seg_a, *seg_b;  /* [k_cap + 1] (at least 2) */
+    int32_t *node_a, *node_b;   /* [k_cap] */
+    double *stats;           /* [k_cap][O + 2] */
+    double *carry;           /* [F][chunks][O + 2] */
+    int32_t *count;          /* [F][chunks] */
+    double *proxy;           /* [F][n] */
+    double *best_proxy;      /* [k_cap][F] */
+    int64_t *best_pos;       /* [k_cap][F] */
+    int64_t *n_left, *dst_left, *dst_right;   /* [k_cap] */
+    int64_t k_cap, node_cap;
+    /* the tree, [node_cap] each (value: [node_cap][O]) */
+    int32_t *left, *right, *feature;
+    double *threshold;
+    uint8_t *missing_left;
+    double *value, *impurity, *weighted_n;
+    int32_t *n_samples;
+    int64_t *level;          /* [4] */
+} fv3hip_forest_train_t;
+
+/* the phases of a level, in the order they must run (FV3HIP_FOREST_TRAIN_ALL in one call, or one call each to time them):
+ * the chunk sums and node statistics; the scan and the best position per (node, feature); the split records, the children and
+ * the partition of the lists */
+#define FV3HIP_FOREST_TRAIN_SUMS 1
+#define FV3HIP_FOREST_TRAIN_SCAN 2
+#define FV3HIP_FOREST_TRAIN_SPLIT 4
+#define FV3HIP_FOREST_TRAIN_ALL 7
+
+int fv3hip_forest_train_chunk(void);
+int fv3hip_forest_train_begin(const fv3hip_forest_train_t *ws, int64_t n_inbag, void *stream);
+int fv3hip_forest_train_level(const fv3hip_forest_train_t *ws, int parity, int64_t n_open, int64_t n_positions, int64_t n_nodes,
+                              int depth, int max_depth, int64_t min_samples_split, int64_t min_samples_leaf, int phases,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif
