@@ -19,7 +19,7 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
+#include "columns.h"
 
 using namespace fv3hip;
 
@@ -43,17 +43,6 @@ __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, 
 __device__ __forceinline__ double mul_rn(double a, double b) { return __dmul_rn(a, b); }
 __device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
 __device__ __forceinline__ double div_rn(double a, double b) { return __ddiv_rn(a, b); }
-
-struct Src {
-    const void *p;
-    int64_t sx, sy, sz;
-    int f64;
-};
-
-struct Dst {
-    void *p;
-    int64_t sx, sy, sz;
-};
 
 template <class T>
 struct Layer {
@@ -79,7 +68,7 @@ struct Net {
 template <class T>
 struct EncArgs {
     Net<T> n;
-    Src src[kMaxVars];
+    XyzSrc src[kMaxVars];
     const T *sub, *div, *sub2;  // per feature, each optional: ((x - sub) / div) - sub2
     T *latent;
 };
@@ -90,18 +79,11 @@ struct DecArgs {
     const void *latent;
     int latent_f64;
     int has_head;               // the last layer is the heads (else the latent is the normalised column)
-    Dst out[kMaxVars];
+    XyzDst out[kMaxVars];
     const T *mul, *add;         // per feature, each optional: y * mul + add
     T lo[kMaxVars], hi[kMaxVars];  // per variable, NaN: no bound
     int positive;
 };
-
-__device__ __forceinline__ int var_of(const int *zoff, int n_var, int k)
-{
-    int v = 0;
-    while (v + 1 < n_var && k >= zoff[v + 1]) ++v;
-    return v;
-}
 
 // the staged copies of the layers that fit, once per block
 template <class T>
@@ -162,9 +144,7 @@ __global__ __launch_bounds__(kBlock) void codec_encode_kernel(EncArgs<T> a)
             const int v = var_of(n.zoff, n.n_var, k);
             const int64_t col = c0 + c;
             const int64_t x = col / n.ny, y = col - x * n.ny;
-            const Src &s = a.src[v];
-            const int64_t off = x * s.sx + y * s.sy + (k - n.zoff[v]) * s.sz;
-            T val = s.f64 ? (T) static_cast<const double *>(s.p)[off] : (T) static_cast<const float *>(s.p)[off];
+            T val = load_xyz<T>(a.src[v], x, y, k - n.zoff[v]);
             if (a.sub) val = sub_rn(val, a.sub[k]);
             if (a.div) val = div_rn(val, a.div[k]);
             if (a.sub2) val = sub_rn(val, a.sub2[k]);
@@ -180,6 +160,8 @@ __global__ __launch_bounds__(kBlock) void codec_encode_kernel(EncArgs<T> a)
             const Layer<T> &ly = n.layer[l];
             T *dst = (l & 1) ? act1 : act0;
             const bool last = l + 1 == n.n_layers;
+            // four calls, not one over selected pointers: each keeps its address spaces (LDS or global weights, LDS or
+            // global destination); folded, the weights are read by flat loads and the double kernel's registers change
             if (ly.lds >= 0) {
                 const T *w = wl + ly.lds;
                 const T *b = ly.b ? w + ly.in * ly.out : nullptr;
@@ -259,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void codec_decode_kernel(DecArgs<T> a)
             if (a.positive) r = r >= (T)0 ? r : (T)0;  // np.where(decoded >= 0, decoded, 0.0): a NaN becomes 0.0
             const int64_t col = c0 + c;
             const int64_t x = col / n.ny, y = col - x * n.ny;
-            const Dst &o = a.out[v];
+            const XyzDst &o = a.out[v];
             static_cast<T *>(o.p)[x * o.sx + y * o.sy + (k - n.zoff[v]) * o.sz] = r;
         }
     }
@@ -290,20 +272,24 @@ struct fv3hip_codec {
     double lo[kMaxVars], hi[kMaxVars];
     Model<float> f;
     Model<double> d;
-    std::vector<void *> allocs;
+    DeviceAllocs mem;
 };
 
 namespace {
 
+// f(m->f) or f(m->d): the precision the codec computes in
+template <class Fn>
+int with_model(fv3hip_codec *m, Fn f)
+{
+    return m->kind == FV3HIP_CODEC_DENSE ? f(m->f) : f(m->d);
+}
+
+// an empty array is an absent one: a null pointer, which the kernels test
 template <class T>
 int to_device(fv3hip_codec *m, const std::vector<T> &host, T **dptr)
 {
     *dptr = nullptr;
-    if (host.empty()) return FV3HIP_OK;
-    FV3HIP_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(dptr), host.size() * sizeof(T)));
-    m->allocs.push_back(*dptr);
-    FV3HIP_CHECK_HIP(hipMemcpy(*dptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    return FV3HIP_OK;
+    return host.empty() ? FV3HIP_OK : m->mem.upload(dptr, host.data(), host.size());
 }
 
 inline int odd(int n) { return n | 1; }
@@ -490,21 +476,15 @@ int build(const fv3hip_codec_desc_t *d, fv3hip_codec *m)
 {
     FV3HIP_REQUIRE(d, "null descriptor");
     FV3HIP_REQUIRE(d->kind == FV3HIP_CODEC_DENSE || d->kind == FV3HIP_CODEC_AFFINE, "unknown codec kind %d", d->kind);
-    FV3HIP_REQUIRE(d->n_variables >= 1 && d->n_variables <= kMaxVars, "n_variables must be in [1, %d], got %d", kMaxVars,
-                   d->n_variables);
-    FV3HIP_REQUIRE(d->var_nz, "null var_nz");
+    const int rc = fill_zoff(d->var_nz, d->n_variables, kMaxVars, "", m->zoff);
+    if (rc) return rc;
     m->kind = d->kind;
     m->n_var = d->n_variables;
-    int64_t K = 0;
-    for (int v = 0; v < d->n_variables; ++v) {
-        FV3HIP_REQUIRE(d->var_nz[v] >= 1 && d->var_nz[v] < (1 << 20), "bad z size %d of variable %d", d->var_nz[v], v);
-        K += d->var_nz[v];
-        m->zoff[v + 1] = (int)K;
-    }
-    FV3HIP_REQUIRE(K <= kMaxK, "K = sum(var_nz) = %d exceeds the cap of %d features", (int)K, kMaxK);
+    const int K = m->zoff[m->n_var];
+    FV3HIP_REQUIRE(K <= kMaxK, "K = sum(var_nz) = %d exceeds the cap of %d features", K, kMaxK);
     FV3HIP_REQUIRE(d->n_latent >= 1 && (d->n_latent <= kMaxWidth || (d->kind == FV3HIP_CODEC_DENSE && d->n_enc == 0)),
                    "n_latent %d is outside [1, %d] (the cap on n_latent)", d->n_latent, kMaxWidth);
-    m->K = (int)K;
+    m->K = K;
     m->L = d->n_latent;
     return d->kind == FV3HIP_CODEC_DENSE ? build_dense(d, m) : build_affine(d, m);
 }
@@ -512,10 +492,7 @@ int build(const fv3hip_codec_desc_t *d, fv3hip_codec *m)
 int check_device(fv3hip_codec_t m)
 {
     FV3HIP_REQUIRE(m, "null codec handle");
-    int cur = -1;
-    FV3HIP_CHECK_HIP(hipGetDevice(&cur));
-    FV3HIP_REQUIRE(cur == m->device, "the codec lives on device %d but the current device is %d", m->device, cur);
-    return FV3HIP_OK;
+    return check_handle_device(m->device, "codec");
 }
 
 int check_extent(int nx, int ny)
@@ -536,15 +513,11 @@ template <class T>
 int launch_encode(fv3hip_codec_t m, Model<T> &mod, const void *const *sources, const int *src_dtype, const int64_t *strides,
                   int nx, int ny, void *latent, hipStream_t st)
 {
-    EncArgs<T> a;
-    memset(&a, 0, sizeof(a));
+    EncArgs<T> a{};
+    const int rc = fill_sources(m->n_var, sources, src_dtype, strides, 3, 0, a.src, nullptr);
+    if (rc) return rc;
     a.n = mod.ne;
     set_extent(a.n, nx, ny);
-    for (int v = 0; v < m->n_var; ++v) {
-        FV3HIP_REQUIRE(sources[v], "source %d is null", v);
-        FV3HIP_REQUIRE(is_float(src_dtype[v]), "source %d: dtype must be F32 or F64", v);
-        a.src[v] = Src{sources[v], strides[3 * v], strides[3 * v + 1], strides[3 * v + 2], src_dtype[v] == FV3HIP_F64 ? 1 : 0};
-    }
     a.sub = mod.d_sub;
     a.div = mod.d_div;
     a.sub2 = mod.d_sub2;
@@ -558,16 +531,15 @@ template <class T>
 int launch_decode(fv3hip_codec_t m, Model<T> &mod, const void *latent, int latent_dtype, int nx, int ny, void *const *outputs,
                   const int64_t *out_strides, hipStream_t st)
 {
-    DecArgs<T> a;
-    memset(&a, 0, sizeof(a));
+    DecArgs<T> a{};
+    const int rc = fill_outputs(m->n_var, outputs, out_strides, a.out);
+    if (rc) return rc;
     a.n = mod.nd;
     set_extent(a.n, nx, ny);
     a.latent = latent;
     a.latent_f64 = latent_dtype == FV3HIP_F64 ? 1 : 0;
     a.has_head = m->has_head;
     for (int v = 0; v < m->n_var; ++v) {
-        FV3HIP_REQUIRE(outputs[v], "output %d is null", v);
-        a.out[v] = Dst{outputs[v], out_strides[3 * v], out_strides[3 * v + 1], out_strides[3 * v + 2]};
         a.lo[v] = (T)m->lo[v];
         a.hi[v] = (T)m->hi[v];
     }
@@ -602,9 +574,7 @@ extern "C" int fv3hip_codec_create(const fv3hip_codec_desc_t *desc, fv3hip_codec
 
 extern "C" int fv3hip_codec_destroy(fv3hip_codec_t m)
 {
-    if (!m) return FV3HIP_OK;
-    for (void *q : m->allocs) (void)hipFree(q);
-    delete m;
+    delete m;  // its DeviceAllocs frees the buffers
     return FV3HIP_OK;
 }
 
@@ -613,11 +583,11 @@ extern "C" int fv3hip_codec_encode(fv3hip_codec_t m, const void *const *sources,
 {
     int rc = check_device(m);
     if (rc || (rc = check_extent(nx, ny))) return rc;
-    FV3HIP_REQUIRE(sources && src_dtype && strides, "null source pointer");
+    FV3HIP_REQUIRE(sources && src_dtype && strides, "null source pointer");  // the first check, before the latent's
     FV3HIP_REQUIRE(latent, "null latent");
-    if (m->kind == FV3HIP_CODEC_DENSE)
-        return launch_encode(m, m->f, sources, src_dtype, strides, nx, ny, latent, as_stream(stream));
-    return launch_encode(m, m->d, sources, src_dtype, strides, nx, ny, latent, as_stream(stream));
+    return with_model(m, [&](auto &mod) {
+        return launch_encode(m, mod, sources, src_dtype, strides, nx, ny, latent, as_stream(stream));
+    });
 }
 
 extern "C" int fv3hip_codec_decode(fv3hip_codec_t m, const void *latent, int latent_dtype, int nx, int ny,
@@ -627,8 +597,7 @@ extern "C" int fv3hip_codec_decode(fv3hip_codec_t m, const void *latent, int lat
     if (rc || (rc = check_extent(nx, ny))) return rc;
     FV3HIP_REQUIRE(latent, "null latent");
     FV3HIP_REQUIRE(is_float(latent_dtype), "latent dtype must be F32 or F64");
-    FV3HIP_REQUIRE(outputs && out_strides, "null output pointer");
-    if (m->kind == FV3HIP_CODEC_DENSE)
-        return launch_decode(m, m->f, latent, latent_dtype, nx, ny, outputs, out_strides, as_stream(stream));
-    return launch_decode(m, m->d, latent, latent_dtype, nx, ny, outputs, out_strides, as_stream(stream));
+    return with_model(m, [&](auto &mod) {
+        return launch_decode(m, mod, latent, latent_dtype, nx, ny, outputs, out_strides, as_stream(stream));
+    });
 }

@@ -17,7 +17,7 @@
 // f64 C/D map of the instruction: col = lane & 15, row = (lane >> 4) + 4 * reg; A operand A[i = lane & 15][k = lane >> 4],
 // B operand B[k = lane >> 4][j = lane & 15], one double per lane each -- both are rows of the time-major series, read from
 // LDS with no transpose.
-#include "common.h"
+#include "columns.h"
 
 using namespace fv3hip;
 
@@ -192,10 +192,7 @@ namespace {
 int check_device(fv3hip_gram_t g)
 {
     FV3HIP_REQUIRE(g, "null Gram accumulator");
-    int cur = -1;
-    FV3HIP_CHECK_HIP(hipGetDevice(&cur));
-    FV3HIP_REQUIRE(cur == g->device, "the Gram accumulator lives on device %d but the current device is %d", g->device, cur);
-    return FV3HIP_OK;
+    return check_handle_device(g->device, "Gram accumulator");
 }
 
 size_t a_count(fv3hip_gram_t g) { return (size_t)g->n_sub * g->J1 * g->J1; }

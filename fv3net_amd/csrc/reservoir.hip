@@ -18,9 +18,15 @@
 //   res_pack_kernel       row t of the readout inputs: the new state (even elements squared when asked), then the hybrid
 //                         encoding of time t.
 // No atomics anywhere: the bits depend on the shapes only.
+//
+// Each rule once: locate() (with FEATURE_INDEX / MASK_INDEX) places a flat subdomain element for the encode and the
+// epilogue kernel; readout_input() is a row of the readout input for the readout and the pack kernel; on the host
+// encode_args() builds the three encodings' launch arguments and encode() is their one launch, slice_plan() cuts both
+// reductions, and columns.h (shared with codec.hip) turns the caller's pointer, dtype and stride tables into kernel
+// arguments and owns the device buffers.
 #include <vector>
 
-#include "common.h"
+#include "columns.h"
 
 using namespace fv3hip;
 
@@ -35,12 +41,6 @@ constexpr int kTargetBlocks = 1024;
 constexpr int kInTargetWaves = 3072;  // about three waves per SIMD: res_in_dense_kernel holds ~160 registers per lane
 constexpr double kDenseDensity = 0.5;  // FV3HIP_RESERVOIR_WIN_AUTO: dense W_in from this fraction of nonzeros up
 
-struct Src {
-    const void *p;
-    int64_t sx, sy, sz;
-    int f64;
-};
-
 // a transformer as the kernels see it
 struct Tf {
     int kind, n_var, zlat, nx, ny, nz0, mask_f32;
@@ -49,10 +49,17 @@ struct Tf {
     const double *mask;
 };
 
+// How the subdomains are cut from an (x, y) extent: lx of them side by side in x, one of sub_x by sub_y cells every
+// (step_x, step_y) cells; the subdomains overlap where the step is shorter than the extent.  locate() needs no sub_x (x is
+// the slowest index of a subdomain); the field keeps the kernel's argument offsets where they were.
+struct Divider {
+    int lx, sub_x, sub_y, step_x, step_y;
+};
+
 struct EncArgs {
     Tf tf;
-    Src src[kMaxVars];
-    int lx, sub_x, sub_y, step_x, step_y;  // divider
+    XyzSrc src[kMaxVars];
+    Divider div;
     int64_t n_flat, n_sub;
     const double *pmask;                   // per-subdomain mask [s][k] or null
     int pmask_f32, src_all_f32;
@@ -61,18 +68,31 @@ struct EncArgs {
     int *parity;                           // flipped by thread 0 when not null
 };
 
-__device__ __forceinline__ double load_src(const Src &s, int64_t x, int64_t y, int64_t z)
+// Where flat element k of subdomain s lies: the cell (X, Y) of the extent the subdomains were cut from, the latent level
+// zl, and the variable v with the level zz within it.  locate() takes the divider's numbers by reference and fills a point
+// it is handed, and the two index sums below are macros: in this form res_encode_kernel and res_epilogue_kernel compile to
+// the instructions they had with the sums written out in each; as value-returning functions they are simplified before
+// they are inlined and res_encode_kernel gets another schedule, which showed as a slow mode of back-to-back encodings.
+struct SubPoint {
+    int64_t X, Y;
+    int zl, v, zz;
+};
+
+__device__ __forceinline__ void locate(const Tf &tf, const int &lx, const int &step_x, const int &step_y, const int &sub_y,
+                                       int64_t s, int64_t k, SubPoint &p)
 {
-    const int64_t off = x * s.sx + y * s.sy + z * s.sz;
-    return s.f64 ? static_cast<const double *>(s.p)[off] : (double)static_cast<const float *>(s.p)[off];
+    p.zl = (int)(k % tf.zlat);
+    const int64_t t = k / tf.zlat;
+    const int yi = (int)(t % sub_y), xi = (int)(t / sub_y);
+    p.X = (s % lx) * step_x + xi;
+    p.Y = (s / lx) * step_y + yi;
+    p.v = var_of(tf.zoff, tf.n_var, p.zl);
+    p.zz = p.zl - tf.zoff[p.v];
 }
 
-__device__ __forceinline__ int var_of(const Tf &t, int zl)
-{
-    int v = 0;
-    while (v + 1 < t.n_var && zl >= t.zoff[v + 1]) ++v;
-    return v;
-}
+// scale-spatial: the point's element of center and scale [variable][x][y][z] / of mask [x][y][latent level]
+#define FEATURE_INDEX(tf, p) ((int64_t)(p).v * (tf).nx * (tf).ny * (tf).nz0 + ((p).X * (tf).ny + (p).Y) * (tf).nz0 + (p).zz)
+#define MASK_INDEX(tf, p) (((p).X * (tf).ny + (p).Y) * (tf).zlat + (p).zl)
 
 __global__ __launch_bounds__(kBlock) void res_encode_kernel(EncArgs a)
 {
@@ -81,24 +101,20 @@ __global__ __launch_bounds__(kBlock) void res_encode_kernel(EncArgs a)
     if (e >= a.n_sub * a.n_flat) return;
     const int64_t s = e / a.n_flat;
     const int64_t k = e - s * a.n_flat;
-    const int zl = (int)(k % a.tf.zlat);
-    const int64_t t = k / a.tf.zlat;
-    const int yi = (int)(t % a.sub_y), xi = (int)(t / a.sub_y);
-    const int64_t X = (s % a.lx) * a.step_x + xi, Y = (s / a.lx) * a.step_y + yi;
-    const int v = var_of(a.tf, zl);
-    const int zz = zl - a.tf.zoff[v];
-    const double raw = load_src(a.src[v], X, Y, zz);
+    SubPoint p;
+    locate(a.tf, a.div.lx, a.div.step_x, a.div.step_y, a.div.sub_y, s, k, p);
+    const double raw = load_xyz<double>(a.src[p.v], p.X, p.Y, p.zz);
     double val;
     bool f32;
     if (a.tf.kind == FV3HIP_RESERVOIR_SCALE_SPATIAL) {
         // NormLayer.forward in float32: (x - center) / (scale + 1e-7), IEEE subtraction and division
-        const int64_t fi = (int64_t)v * a.tf.nx * a.tf.ny * a.tf.nz0 + (X * a.tf.ny + Y) * a.tf.nz0 + zz;
+        const int64_t fi = FEATURE_INDEX(a.tf, p);
         const float den = __fadd_rn(a.tf.scale[fi], 1.0e-7f);
         const float enc = __fdiv_rn(__fsub_rn((float)raw, a.tf.center[fi]), den);
         val = (double)enc;
         f32 = true;
         if (a.tf.mask) {  // float32 * float64 is float64 in numpy; float32 * float32 rounds to float32
-            val = val * a.tf.mask[(X * a.tf.ny + Y) * a.tf.zlat + zl];
+            val = val * a.tf.mask[MASK_INDEX(a.tf, p)];
             f32 = a.tf.mask_f32 != 0;
             if (f32) val = (double)(float)val;
         }
@@ -216,6 +232,18 @@ struct ReadArgs {
     int S, H, n_sub, j_chunk, square;
 };
 
+// Row j of the readout input of subdomain s: the state, squared by square_even_terms in the even subdomains (pure model,
+// axis 0) or in its even elements (hybrid model and train.py:389, axis -1), then the hybrid encoding.
+__device__ __forceinline__ double readout_input(const double *state_row, const double *hyb_row, int s, int j, int S, int square)
+{
+    if (j >= S) return hyb_row[j - S];
+    const double v = state_row[j];
+    const bool sq = square == FV3HIP_RESERVOIR_SQUARE_SUBDOMAINS ? (s % 2 == 0)
+                    : square == FV3HIP_RESERVOIR_SQUARE_ELEMENTS ? (j % 2 == 0)
+                                                                    : false;
+    return sq ? v * v : v;
+}
+
 __global__ __launch_bounds__(kBlock) void res_readout_kernel(ReadArgs a)
 {
     __shared__ double vin[kReadRows];
@@ -232,21 +260,8 @@ __global__ __launch_bounds__(kBlock) void res_readout_kernel(ReadArgs a)
     for (int j0 = j_begin; j0 < j_end; j0 += kReadRows) {
         const int nj = min(kReadRows, j_end - j0);
         __syncthreads();
-        if (threadIdx.x < nj) {
-            const int j = j0 + threadIdx.x;
-            double v;
-            if (j < a.S) {
-                v = st[j];
-                // square_even_terms: of even subdomains (pure model, axis 0) or of even state elements (hybrid, axis -1)
-                const bool sq = a.square == FV3HIP_RESERVOIR_SQUARE_SUBDOMAINS ? (s % 2 == 0)
-                                : a.square == FV3HIP_RESERVOIR_SQUARE_ELEMENTS ? (j % 2 == 0)
-                                                                                : false;
-                if (sq) v = v * v;
-            } else {
-                v = a.hyb[(int64_t)s * a.H + (j - a.S)];
-            }
-            vin[threadIdx.x] = v;
-        }
+        if (threadIdx.x < nj)
+            vin[threadIdx.x] = readout_input(st, a.hyb + (int64_t)s * a.H, s, j0 + threadIdx.x, a.S, a.square);
         __syncthreads();
         const double2 *row = C2 + (int64_t)j0 * n2;
         int jj = 0;
@@ -291,20 +306,16 @@ __global__ __launch_bounds__(kBlock) void res_epilogue_kernel(EpiArgs a)
     double y = 0.0;
     for (int q = 0; q < a.n_split; ++q) y += a.part[((int64_t)q * a.n_sub + s) * a.ldc + k];
     y = y + a.bias[s * a.n_out + k];
-    const int zl = (int)(k % a.tf.zlat);
-    const int64_t t = k / a.tf.zlat;
-    const int yi = (int)(t % a.sub_y), xi = (int)(t / a.sub_y);
-    const int64_t X = (s % a.lx) * a.sub_x + xi, Y = (s / a.lx) * a.sub_y + yi;
-    const int v = var_of(a.tf, zl);
-    const int zz = zl - a.tf.zoff[v];
-    const int64_t off = X * a.ox[v] + Y * a.oy[v] + zz * a.oz[v];
+    SubPoint p;
+    locate(a.tf, a.lx, a.sub_x, a.sub_y, a.sub_y, s, k, p);  // no overlap: the step is the extent
+    const int64_t off = p.X * a.ox[p.v] + p.Y * a.oy[p.v] + p.zz * a.oz[p.v];
     if (a.tf.kind == FV3HIP_RESERVOIR_SCALE_SPATIAL) {
-        if (a.tf.mask) y = y * a.tf.mask[(X * a.tf.ny + Y) * a.tf.zlat + zl];
+        if (a.tf.mask) y = y * a.tf.mask[MASK_INDEX(a.tf, p)];
         // NormLayer.backward in float32: x * scale + center, two roundings
-        const int64_t fi = (int64_t)v * a.tf.nx * a.tf.ny * a.tf.nz0 + (X * a.tf.ny + Y) * a.tf.nz0 + zz;
-        static_cast<float *>(a.out[v])[off] = __fadd_rn(__fmul_rn((float)y, a.tf.scale[fi]), a.tf.center[fi]);
+        const int64_t fi = FEATURE_INDEX(a.tf, p);
+        static_cast<float *>(a.out[p.v])[off] = __fadd_rn(__fmul_rn((float)y, a.tf.scale[fi]), a.tf.center[fi]);
     } else {
-        static_cast<double *>(a.out[v])[off] = y;
+        static_cast<double *>(a.out[p.v])[off] = y;
     }
 }
 
@@ -341,15 +352,8 @@ __global__ __launch_bounds__(kBlock) void res_pack_kernel(PackArgs a)
     const int J = a.S + a.H;
     if (e >= (int64_t)a.n_sub * J) return;
     const int64_t s = e / J;
-    const int j = (int)(e - s * J);
-    double v;
-    if (j < a.S) {
-        v = a.state[(*a.parity ? (int64_t)a.n_sub * a.S : 0) + s * a.S + j];
-        if (a.square && j % 2 == 0) v = v * v;  // square_even_terms(axis=-1), train.py:389
-    } else {
-        v = a.hyb[s * a.H + (j - a.S)];
-    }
-    a.row[e] = v;
+    const double *st = a.state + (*a.parity ? (int64_t)a.n_sub * a.S : 0) + s * a.S;
+    a.row[e] = readout_input(st, a.hyb + s * a.H, (int)s, (int)(e - s * J), a.S, a.square);
 }
 
 struct HostTf {
@@ -384,50 +388,29 @@ struct fv3hip_reservoir {
     double *d_in_part = nullptr;
     double *d_out_part = nullptr;
     int pmask_f32 = 0, hmask_f32 = 0, in_split = 1, in_chunk = 0, in_sb = 1, out_split = 1, out_chunk = 0;
-    std::vector<void *> allocs;
+    DeviceAllocs mem;
 };
 
 namespace {
 
-template <class T>
-int upload(fv3hip_reservoir *m, T **dptr, const T *host, size_t n)
-{
-    FV3HIP_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(dptr), (n ? n : 1) * sizeof(T)));
-    m->allocs.push_back(*dptr);
-    if (host && n) FV3HIP_CHECK_HIP(hipMemcpy(*dptr, host, n * sizeof(T), hipMemcpyHostToDevice));
-    return FV3HIP_OK;
-}
-
-template <class T>
-int alloc(fv3hip_reservoir *m, T **dptr, size_t n)
-{
-    return upload<T>(m, dptr, nullptr, n);
-}
-
+// `which`: "input transformer", ...
 int check_tf(const fv3hip_reservoir_transformer_t &d, const char *which, int nx, int ny, HostTf &h)
 {
     FV3HIP_REQUIRE(d.kind == FV3HIP_RESERVOIR_DO_NOTHING || d.kind == FV3HIP_RESERVOIR_SCALE_SPATIAL,
-                   "%s transformer: unknown kind %d", which, d.kind);
-    FV3HIP_REQUIRE(d.n_variables >= 1 && d.n_variables <= kMaxVars, "%s transformer: n_variables must be in [1, %d], got %d",
-                   which, kMaxVars, d.n_variables);
-    FV3HIP_REQUIRE(d.var_nz, "%s transformer: null var_nz", which);
+                   "%s: unknown kind %d", which, d.kind);
     Tf &t = h.t;
+    const int rc = fill_zoff(d.var_nz, d.n_variables, kMaxVars, which, t.zoff);
+    if (rc) return rc;
     t.kind = d.kind;
     t.n_var = d.n_variables;
-    t.zoff[0] = 0;
-    for (int v = 0; v < d.n_variables; ++v) {
-        FV3HIP_REQUIRE(d.var_nz[v] >= 1 && d.var_nz[v] < (1 << 20), "%s transformer: bad z size %d of variable %d", which,
-                       d.var_nz[v], v);
-        t.zoff[v + 1] = t.zoff[v] + d.var_nz[v];
-    }
     t.zlat = t.zoff[d.n_variables];
     t.nz0 = d.var_nz[0];
     if (d.kind == FV3HIP_RESERVOIR_SCALE_SPATIAL) {
         for (int v = 1; v < d.n_variables; ++v)
-            FV3HIP_REQUIRE(d.var_nz[v] == d.var_nz[0], "%s transformer: scale-spatial variables must share one z size", which);
-        FV3HIP_REQUIRE(d.nx == nx && d.ny == ny, "%s transformer: its spatial features (%d, %d) differ from the extent it "
+            FV3HIP_REQUIRE(d.var_nz[v] == d.var_nz[0], "%s: scale-spatial variables must share one z size", which);
+        FV3HIP_REQUIRE(d.nx == nx && d.ny == ny, "%s: its spatial features (%d, %d) differ from the extent it "
                        "transforms (%d, %d)", which, d.nx, d.ny, nx, ny);
-        FV3HIP_REQUIRE(d.center && d.scale, "%s transformer: null center or scale", which);
+        FV3HIP_REQUIRE(d.center && d.scale, "%s: null center or scale", which);
         const size_t n = (size_t)d.n_variables * nx * ny * d.var_nz[0];
         h.center.assign(d.center, d.center + n);
         h.scale.assign(d.scale, d.scale + n);
@@ -478,8 +461,8 @@ int build(const fv3hip_reservoir_desc_t *d, fv3hip_reservoir *m)
     m->square = d->square;
     const int bx = d->rank_x / d->layout_x, by = d->rank_y / d->layout_y;
     int rc;
-    if ((rc = check_tf(d->input, "input", d->rank_x + 2 * d->overlap, d->rank_y + 2 * d->overlap, m->in))) return rc;
-    if ((rc = check_tf(d->output, "output", d->rank_x, d->rank_y, m->out))) return rc;
+    if ((rc = check_tf(d->input, "input transformer", d->rank_x + 2 * d->overlap, d->rank_y + 2 * d->overlap, m->in))) return rc;
+    if ((rc = check_tf(d->output, "output transformer", d->rank_x, d->rank_y, m->out))) return rc;
     const int64_t n_in = (int64_t)(bx + 2 * d->overlap) * (by + 2 * d->overlap) * m->in.t.zlat;
     FV3HIP_REQUIRE(d->input_size == n_in && n_in < (1 << 30), "input_size %d does not match the subdomain extent (%d, %d) "
                    "times the input transformer's %d latent levels", d->input_size, bx + 2 * d->overlap,
@@ -487,7 +470,7 @@ int build(const fv3hip_reservoir_desc_t *d, fv3hip_reservoir *m)
     m->n_in = d->input_size;
     m->n_out = (int64_t)bx * by * m->out.t.zlat;
     if (d->n_hybrid > 0) {
-        if ((rc = check_tf(d->hybrid, "hybrid", d->rank_x, d->rank_y, m->hyb))) return rc;
+        if ((rc = check_tf(d->hybrid, "hybrid transformer", d->rank_x, d->rank_y, m->hyb))) return rc;
         FV3HIP_REQUIRE((int64_t)d->n_hybrid == (int64_t)bx * by * m->hyb.t.zlat, "n_hybrid %d does not match the subdomain "
                        "extent (%d, %d) times the hybrid transformer's %d latent levels", d->n_hybrid, bx, by, m->hyb.t.zlat);
         m->H = d->n_hybrid;
@@ -508,13 +491,39 @@ int upload_tf(fv3hip_reservoir *m, HostTf &h)
     float *c = nullptr, *s = nullptr;
     double *mk = nullptr;
     if (h.t.kind != FV3HIP_RESERVOIR_SCALE_SPATIAL) return FV3HIP_OK;
-    if ((rc = upload(m, &c, h.center.data(), h.center.size())) || (rc = upload(m, &s, h.scale.data(), h.scale.size())))
+    if ((rc = m->mem.upload(&c, h.center.data(), h.center.size())) || (rc = m->mem.upload(&s, h.scale.data(), h.scale.size())))
         return rc;
-    if (!h.mask.empty() && (rc = upload(m, &mk, h.mask.data(), h.mask.size()))) return rc;
+    if (!h.mask.empty() && (rc = m->mem.upload(&mk, h.mask.data(), h.mask.size()))) return rc;
     h.t.center = c;
     h.t.scale = s;
     h.t.mask = mk;
     return FV3HIP_OK;
+}
+
+// a CSR matrix of `rows` rows as the finish kernel walks it
+int upload_csr(fv3hip_reservoir *m, const int64_t *ptr, const int32_t *idx, const double *val, int64_t rows, int64_t **d_ptr,
+               int32_t **d_idx, double **d_val)
+{
+    int rc;
+    const size_t nnz = (size_t)ptr[rows];
+    if ((rc = m->mem.upload(d_ptr, ptr, (size_t)(rows + 1))) || (rc = m->mem.upload(d_idx, idx, nnz))) return rc;
+    return m->mem.upload(d_val, val, nnz);
+}
+
+// How a sum over `total` rows, taken in steps of `unit` rows, is cut into slices of whole steps: as many slices as bring a
+// launch of `base` blocks per slice to `target` blocks, at most one per step.  The slices are added in order afterwards, so
+// the bits of a model follow this plan.
+struct Slices {
+    int chunk, n;  // rows per slice, slices
+};
+
+Slices slice_plan(int64_t total, int unit, int64_t base, int64_t target)
+{
+    const int64_t steps = ceil_div(total, unit);
+    int64_t split = ceil_div(target, base);
+    split = split < 1 ? 1 : split > steps ? steps : split;
+    const int64_t chunk = ceil_div(steps, split) * unit;
+    return Slices{(int)chunk, (int)ceil_div(total, chunk)};
 }
 
 int upload_all(const fv3hip_reservoir_desc_t *d, fv3hip_reservoir *m)
@@ -524,7 +533,7 @@ int upload_all(const fv3hip_reservoir_desc_t *d, fv3hip_reservoir *m)
     if ((rc = upload_tf(m, m->in)) || (rc = upload_tf(m, m->out)) || (rc = upload_tf(m, m->hyb))) return rc;
     const int64_t S = m->S, NS = m->n_sub, N = m->n_in;
     // state: both buffers hold the initial state, parity 0
-    if ((rc = alloc(m, &m->d_state, (size_t)(2 * NS * S))) || (rc = alloc(m, &m->d_parity, 1))) return rc;
+    if ((rc = m->mem.alloc(&m->d_state, (size_t)(2 * NS * S))) || (rc = m->mem.alloc(&m->d_parity, 1))) return rc;
     FV3HIP_CHECK_HIP(hipMemset(m->d_parity, 0, sizeof(int)));
     if (d->state) {
         FV3HIP_CHECK_HIP(hipMemcpy(m->d_state, d->state, NS * S * sizeof(double), hipMemcpyHostToDevice));
@@ -532,8 +541,7 @@ int upload_all(const fv3hip_reservoir_desc_t *d, fv3hip_reservoir *m)
     } else {
         FV3HIP_CHECK_HIP(hipMemset(m->d_state, 0, 2 * NS * S * sizeof(double)));
     }
-    if ((rc = alloc(m, &m->d_u, (size_t)(N * NS)))) return rc;
-    const int64_t nnz_in = d->w_in_indptr[S];
+    if ((rc = m->mem.alloc(&m->d_u, (size_t)(N * NS)))) return rc;
     if (m->dense) {
         // column-major W_in, rows padded to an even count (16-byte pairs), k padded to whole LDS steps; duplicates summed
         m->ldw = (S + 1) / 2 * 2;
@@ -542,79 +550,96 @@ int upload_all(const fv3hip_reservoir_desc_t *d, fv3hip_reservoir *m)
         for (int64_t i = 0; i < S; ++i)
             for (int64_t n = d->w_in_indptr[i]; n < d->w_in_indptr[i + 1]; ++n)
                 w[(size_t)d->w_in_indices[n] * m->ldw + i] += d->w_in_data[n];
-        if ((rc = upload(m, &m->d_w, w.data(), w.size()))) return rc;
+        if ((rc = m->mem.upload(&m->d_w, w.data(), w.size()))) return rc;
         // slices of k: enough waves to fill the chip, whole LDS steps each
         m->in_sb = NS >= 32 ? 32 : NS > 8 ? 16 : NS > 4 ? 8 : NS > 2 ? 4 : NS;
-        const int64_t base = ceil_div(m->ldw / 2, 64) * ceil_div(NS, m->in_sb);
-        const int64_t steps = m->kpad / kInKT;
-        int64_t split = ceil_div(kInTargetWaves, base);
-        split = split < 1 ? 1 : split > steps ? steps : split;
-        m->in_chunk = (int)(ceil_div(steps, split) * kInKT);
-        m->in_split = (int)ceil_div(m->kpad, m->in_chunk);
-        if ((rc = alloc(m, &m->d_in_part, (size_t)(m->in_split * NS * S)))) return rc;
-    } else {
-        if ((rc = upload(m, &m->d_in_ptr, d->w_in_indptr, (size_t)(S + 1))) ||
-            (rc = upload(m, &m->d_in_idx, d->w_in_indices, (size_t)nnz_in)) ||
-            (rc = upload(m, &m->d_in_val, d->w_in_data, (size_t)nnz_in)))
-            return rc;
-    }
-    const int64_t nnz_res = d->w_res_indptr[S];
-    if ((rc = upload(m, &m->d_res_ptr, d->w_res_indptr, (size_t)(S + 1))) ||
-        (rc = upload(m, &m->d_res_idx, d->w_res_indices, (size_t)nnz_res)) ||
-        (rc = upload(m, &m->d_res_val, d->w_res_data, (size_t)nnz_res)))
+        const Slices in = slice_plan(m->kpad, kInKT, ceil_div(m->ldw / 2, 64) * ceil_div(NS, m->in_sb), kInTargetWaves);
+        m->in_chunk = in.chunk;
+        m->in_split = in.n;
+        if ((rc = m->mem.alloc(&m->d_in_part, (size_t)(m->in_split * NS * S)))) return rc;
+    } else if ((rc = upload_csr(m, d->w_in_indptr, d->w_in_indices, d->w_in_data, S, &m->d_in_ptr, &m->d_in_idx, &m->d_in_val))) {
         return rc;
-    if (d->input_mask && (rc = upload(m, &m->d_pmask, d->input_mask, (size_t)(NS * N)))) return rc;
+    }
+    if ((rc = upload_csr(m, d->w_res_indptr, d->w_res_indices, d->w_res_data, S, &m->d_res_ptr, &m->d_res_idx, &m->d_res_val)))
+        return rc;
+    if (d->input_mask && (rc = m->mem.upload(&m->d_pmask, d->input_mask, (size_t)(NS * N)))) return rc;
     const int64_t H = m->H, J = S + H;
     if (H > 0) {
-        if ((rc = alloc(m, &m->d_hyb, (size_t)(NS * H)))) return rc;
-        if (d->hybrid_mask && (rc = upload(m, &m->d_hmask, d->hybrid_mask, (size_t)(NS * H)))) return rc;
+        if ((rc = m->mem.alloc(&m->d_hyb, (size_t)(NS * H)))) return rc;
+        if (d->hybrid_mask && (rc = m->mem.upload(&m->d_hmask, d->hybrid_mask, (size_t)(NS * H)))) return rc;
     }
     // readout: C rows padded to an even length for 16-byte loads
     m->ldc = (m->n_out + 1) / 2 * 2;
     if (m->ldc == m->n_out) {
-        if ((rc = upload(m, &m->d_C, d->coefficients, (size_t)(NS * J * m->ldc)))) return rc;
+        if ((rc = m->mem.upload(&m->d_C, d->coefficients, (size_t)(NS * J * m->ldc)))) return rc;
     } else {
         std::vector<double> c((size_t)(NS * J * m->ldc), 0.0);
         for (int64_t r = 0; r < NS * J; ++r)
             memcpy(&c[(size_t)(r * m->ldc)], d->coefficients + r * m->n_out, m->n_out * sizeof(double));
-        if ((rc = upload(m, &m->d_C, c.data(), c.size()))) return rc;
+        if ((rc = m->mem.upload(&m->d_C, c.data(), c.size()))) return rc;
     }
-    if ((rc = upload(m, &m->d_bias, d->intercepts, (size_t)(NS * m->n_out)))) return rc;
+    if ((rc = m->mem.upload(&m->d_bias, d->intercepts, (size_t)(NS * m->n_out)))) return rc;
     // slices of j from the row length alone (not the subdomain count), so a single-subdomain model split off a larger
     // one adds in the same order
-    const int64_t base = ceil_div(m->ldc / 2, kBlock);
-    const int64_t steps = ceil_div(J, kReadRows);
-    int64_t split = ceil_div(2 * kTargetBlocks, base);
-    split = split < 1 ? 1 : split > steps ? steps : split;
-    m->out_chunk = (int)(ceil_div(steps, split) * kReadRows);
-    m->out_split = (int)ceil_div(J, m->out_chunk);
-    return alloc(m, &m->d_out_part, (size_t)(m->out_split * NS * m->ldc));
+    const Slices out = slice_plan(J, kReadRows, ceil_div(m->ldc / 2, kBlock), 2 * kTargetBlocks);
+    m->out_chunk = out.chunk;
+    m->out_split = out.n;
+    return m->mem.alloc(&m->d_out_part, (size_t)(m->out_split * NS * m->ldc));
 }
 
 int check_device(fv3hip_reservoir_t m)
 {
     FV3HIP_REQUIRE(m, "null reservoir handle");
-    int cur = -1;
-    FV3HIP_CHECK_HIP(hipGetDevice(&cur));
-    FV3HIP_REQUIRE(cur == m->device, "the reservoir lives on device %d but the current device is %d", m->device, cur);
-    return FV3HIP_OK;
+    return check_handle_device(m->device, "reservoir");
 }
 
-int fill_sources(const Tf &t, const void *const *p, const int *dtype, const int64_t *strides, Src *src, int *all_f32)
+// The three encodings.  The input's: over the subdomains with their overlap, times input_mask, u [k][s], and it flips the
+// state's parity.  The hybrid's and the target's: over the subdomains without overlap, [s][k]; the hybrid's times
+// hybrid_input_mask into d_hyb, the target's unmasked to where the caller points `out`.  encode() fills the sources.
+enum class Enc { Input, Hybrid, Target };
+
+Divider divider(fv3hip_reservoir_t m, int overlap)
 {
-    FV3HIP_REQUIRE(p && dtype && strides, "null source pointer");
-    *all_f32 = 1;
-    for (int v = 0; v < t.n_var; ++v) {
-        FV3HIP_REQUIRE(p[v], "source %d is null", v);
-        FV3HIP_REQUIRE(dtype[v] == FV3HIP_F32 || dtype[v] == FV3HIP_F64, "source %d: dtype must be F32 or F64", v);
-        src[v] = Src{p[v], strides[3 * v], strides[3 * v + 1], strides[3 * v + 2], dtype[v] == FV3HIP_F64 ? 1 : 0};
-        if (dtype[v] == FV3HIP_F64) *all_f32 = 0;
+    const int bx = m->rx / m->lx, by = m->ry / m->ly;
+    return Divider{m->lx, bx + 2 * overlap, by + 2 * overlap, bx, by};
+}
+
+EncArgs encode_args(fv3hip_reservoir_t m, Enc which)
+{
+    EncArgs a{};
+    a.tf = which == Enc::Input ? m->in.t : which == Enc::Hybrid ? m->hyb.t : m->out.t;
+    a.div = divider(m, which == Enc::Input ? m->ov : 0);
+    a.n_flat = which == Enc::Input ? m->n_in : which == Enc::Hybrid ? m->H : m->n_out;
+    a.n_sub = m->n_sub;
+    if (which == Enc::Input) {
+        a.pmask = m->d_pmask;
+        a.pmask_f32 = m->pmask_f32;
+        a.out = m->d_u;
+        a.out_ls = 1;
+        a.out_lk = m->n_sub;
+        a.parity = m->d_parity;
+        return a;
     }
-    return FV3HIP_OK;
+    a.out_ls = a.n_flat;
+    a.out_lk = 1;
+    if (which == Enc::Hybrid) {
+        a.pmask = m->d_hmask;
+        a.pmask_f32 = m->hmask_f32;
+        a.out = m->d_hyb;
+    }
+    return a;
 }
 
-int launch_encode(EncArgs &a, hipStream_t st)
+// One encoding of the sources: (x, y, z) arrays, or time t of [t, x, y, z] arrays when there are four strides per variable.
+// `target_out`: where the target's goes.  A model without hybrid inputs has no hybrid encoding.
+int encode(fv3hip_reservoir_t m, Enc which, const void *const *sources, const int *dtype, const int64_t *strides,
+           int strides_per_var, int64_t t, double *target_out, hipStream_t st)
 {
+    if (which == Enc::Hybrid && m->H == 0) return FV3HIP_OK;
+    EncArgs a = encode_args(m, which);
+    if (which == Enc::Target) a.out = target_out;
+    const int rc = fill_sources(a.tf.n_var, sources, dtype, strides, strides_per_var, t, a.src, &a.src_all_f32);
+    if (rc) return rc;
     const int64_t n = a.n_sub * a.n_flat;
     hipLaunchKernelGGL(res_encode_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, st, a);
     return check_launch("res_encode_kernel");
@@ -647,9 +672,7 @@ extern "C" int fv3hip_reservoir_create(const fv3hip_reservoir_desc_t *desc, fv3h
 
 extern "C" int fv3hip_reservoir_destroy(fv3hip_reservoir_t m)
 {
-    if (!m) return FV3HIP_OK;
-    for (void *q : m->allocs) (void)hipFree(q);
-    delete m;
+    delete m;  // its DeviceAllocs frees the buffers
     return FV3HIP_OK;
 }
 
@@ -670,25 +693,12 @@ extern "C" int fv3hip_reservoir_plan(fv3hip_reservoir_t m, int64_t out[8])
 
 namespace {
 
-// encode -> (noise) -> input product -> finish; a.src and a.src_all_f32 are filled by the caller
-int increment_launches(fv3hip_reservoir_t m, EncArgs &a, const double *noise, hipStream_t st)
+// The increment of time t of the sources: encode -> (noise) -> input product -> finish.
+int increment_launches(fv3hip_reservoir_t m, const void *const *sources, const int *dtype, const int64_t *strides,
+                       int strides_per_var, int64_t t, const double *noise, hipStream_t st)
 {
-    int rc;
-    a.tf = m->in.t;
-    a.lx = m->lx;
-    a.sub_x = m->rx / m->lx + 2 * m->ov;
-    a.sub_y = m->ry / m->ly + 2 * m->ov;
-    a.step_x = m->rx / m->lx;
-    a.step_y = m->ry / m->ly;
-    a.n_flat = m->n_in;
-    a.n_sub = m->n_sub;
-    a.pmask = m->d_pmask;
-    a.pmask_f32 = m->pmask_f32;
-    a.out = m->d_u;
-    a.out_ls = 1;
-    a.out_lk = m->n_sub;
-    a.parity = m->d_parity;
-    if ((rc = launch_encode(a, st))) return rc;
+    int rc = encode(m, Enc::Input, sources, dtype, strides, strides_per_var, t, nullptr, st);
+    if (rc) return rc;
     if (noise) {
         const int64_t n = (int64_t)m->n_sub * m->n_in;
         hipLaunchKernelGGL(res_add_noise_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, st, m->d_u, noise,
@@ -706,21 +716,8 @@ int increment_launches(fv3hip_reservoir_t m, EncArgs &a, const double *noise, hi
         }
         if ((rc = check_launch("res_in_dense_kernel"))) return rc;
     }
-    FinishArgs f;
-    memset(&f, 0, sizeof(f));
-    f.part = m->dense ? m->d_in_part : nullptr;
-    f.n_split = m->in_split;
-    f.in_ptr = m->d_in_ptr;
-    f.in_idx = m->d_in_idx;
-    f.in_val = m->d_in_val;
-    f.u = m->d_u;
-    f.res_ptr = m->d_res_ptr;
-    f.res_idx = m->d_res_idx;
-    f.res_val = m->d_res_val;
-    f.state = m->d_state;
-    f.parity = m->d_parity;
-    f.S = m->S;
-    f.n_sub = m->n_sub;
+    const FinishArgs f{m->dense ? m->d_in_part : nullptr, m->in_split, m->d_in_ptr, m->d_in_idx, m->d_in_val, m->d_u,
+                       m->d_res_ptr, m->d_res_idx, m->d_res_val, m->d_state, m->d_parity, m->S, m->n_sub};
     hipLaunchKernelGGL(res_finish_kernel, dim3((unsigned)ceil_div(m->S, kBlock), (unsigned)m->n_sub), dim3(kBlock), 0, st, f);
     return check_launch("res_finish_kernel");
 }
@@ -732,10 +729,7 @@ extern "C" int fv3hip_reservoir_increment(fv3hip_reservoir_t m, const void *cons
 {
     int rc = check_device(m);
     if (rc) return rc;
-    EncArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = fill_sources(m->in.t, sources, src_dtype, strides, a.src, &a.src_all_f32))) return rc;
-    return increment_launches(m, a, nullptr, as_stream(stream));
+    return increment_launches(m, sources, src_dtype, strides, 3, 0, nullptr, as_stream(stream));
 }
 
 extern "C" int fv3hip_reservoir_predict(fv3hip_reservoir_t m, const void *const *hybrid_sources, const int *hybrid_dtype,
@@ -744,60 +738,23 @@ extern "C" int fv3hip_reservoir_predict(fv3hip_reservoir_t m, const void *const 
 {
     int rc = check_device(m);
     if (rc) return rc;
-    FV3HIP_REQUIRE(outputs && out_strides, "null output pointer");
-    EpiArgs e;
-    memset(&e, 0, sizeof(e));
-    for (int v = 0; v < m->out.t.n_var; ++v) {
-        FV3HIP_REQUIRE(outputs[v], "output %d is null", v);
-        e.out[v] = outputs[v];
-        e.ox[v] = out_strides[3 * v];
-        e.oy[v] = out_strides[3 * v + 1];
-        e.oz[v] = out_strides[3 * v + 2];
+    EpiArgs e{m->d_out_part, m->d_bias, m->out_split, m->ldc, m->n_out, m->n_sub, m->out.t,
+              m->lx, m->rx / m->lx, m->ry / m->ly, {}, {}, {}, {}};
+    XyzDst dst[kMaxVars];
+    if ((rc = fill_outputs(m->out.t.n_var, outputs, out_strides, dst))) return rc;
+    for (int v = 0; v < m->out.t.n_var; ++v) {  // the kernel reads one array per field
+        e.out[v] = dst[v].p;
+        e.ox[v] = dst[v].sx;
+        e.oy[v] = dst[v].sy;
+        e.oz[v] = dst[v].sz;
     }
     const hipStream_t st = as_stream(stream);
-    const int bx = m->rx / m->lx, by = m->ry / m->ly;
-    if (m->H > 0) {
-        EncArgs a;
-        memset(&a, 0, sizeof(a));
-        if ((rc = fill_sources(m->hyb.t, hybrid_sources, hybrid_dtype, hybrid_strides, a.src, &a.src_all_f32))) return rc;
-        a.tf = m->hyb.t;
-        a.lx = m->lx;
-        a.sub_x = a.step_x = bx;
-        a.sub_y = a.step_y = by;
-        a.n_flat = m->H;
-        a.n_sub = m->n_sub;
-        a.pmask = m->d_hmask;
-        a.pmask_f32 = m->hmask_f32;
-        a.out = m->d_hyb;
-        a.out_ls = m->H;
-        a.out_lk = 1;
-        if ((rc = launch_encode(a, st))) return rc;
-    }
-    ReadArgs r;
-    r.C = m->d_C;
-    r.state = m->d_state;
-    r.parity = m->d_parity;
-    r.hyb = m->d_hyb;
-    r.part = m->d_out_part;
-    r.ldc = m->ldc;
-    r.S = m->S;
-    r.H = m->H;
-    r.n_sub = m->n_sub;
-    r.j_chunk = m->out_chunk;
-    r.square = m->square;
+    if ((rc = encode(m, Enc::Hybrid, hybrid_sources, hybrid_dtype, hybrid_strides, 3, 0, nullptr, st))) return rc;
+    const ReadArgs r{m->d_C, m->d_state, m->d_parity, m->d_hyb, m->d_out_part, m->ldc,
+                     m->S, m->H, m->n_sub, m->out_chunk, m->square};
     const dim3 grid((unsigned)ceil_div(m->ldc / 2, kBlock), (unsigned)m->out_split, (unsigned)m->n_sub);
     hipLaunchKernelGGL(res_readout_kernel, grid, dim3(kBlock), 0, st, r);
     if ((rc = check_launch("res_readout_kernel"))) return rc;
-    e.part = m->d_out_part;
-    e.bias = m->d_bias;
-    e.n_split = m->out_split;
-    e.ldc = m->ldc;
-    e.n_out = m->n_out;
-    e.n_sub = m->n_sub;
-    e.tf = m->out.t;
-    e.lx = m->lx;
-    e.sub_x = bx;
-    e.sub_y = by;
     hipLaunchKernelGGL(res_epilogue_kernel, dim3((unsigned)ceil_div(m->n_sub * m->n_out, kBlock)), dim3(kBlock), 0, st, e);
     return check_launch("res_epilogue_kernel");
 }
@@ -833,39 +790,6 @@ extern "C" int fv3hip_reservoir_reset_state(fv3hip_reservoir_t m, void *stream)
     return FV3HIP_OK;
 }
 
-namespace {
-
-// the sources of time t of [t, x, y, z] arrays (strides: four per variable) as fill_sources takes them
-int fill_sources_at(const Tf &tf, const void *const *p, const int *dtype, const int64_t *strides, int64_t t, Src *src, int *all_f32)
-{
-    FV3HIP_REQUIRE(p && dtype && strides, "null source pointer");
-    const void *at[kMaxVars];
-    int64_t xyz[3 * kMaxVars];
-    for (int v = 0; v < tf.n_var; ++v) {
-        FV3HIP_REQUIRE(p[v], "source %d is null", v);
-        FV3HIP_REQUIRE(is_float(dtype[v]), "source %d: dtype must be F32 or F64", v);
-        const int64_t bytes = dtype[v] == FV3HIP_F64 ? 8 : 4;
-        at[v] = static_cast<const char *>(p[v]) + t * strides[4 * v] * bytes;
-        for (int q = 0; q < 3; ++q) xyz[3 * v + q] = strides[4 * v + 1 + q];
-    }
-    return fill_sources(tf, at, dtype, xyz, src, all_f32);
-}
-
-// an encoding over the subdomains without overlap, [subdomain][feature] (the hybrid path of the readout)
-void no_overlap_args(fv3hip_reservoir_t m, const Tf &tf, int64_t n_flat, EncArgs &a)
-{
-    a.tf = tf;
-    a.lx = m->lx;
-    a.sub_x = a.step_x = m->rx / m->lx;
-    a.sub_y = a.step_y = m->ry / m->ly;
-    a.n_flat = n_flat;
-    a.n_sub = m->n_sub;
-    a.out_ls = n_flat;
-    a.out_lk = 1;
-}
-
-}  // namespace
-
 extern "C" int fv3hip_reservoir_train_series(fv3hip_reservoir_t m, const void *const *sources, const int *src_dtype,
                                              const int64_t *strides, const double *noise, const void *const *hybrid_sources,
                                              const int *hybrid_dtype, const int64_t *hybrid_strides, int64_t n_times,
@@ -878,30 +802,11 @@ extern "C" int fv3hip_reservoir_train_series(fv3hip_reservoir_t m, const void *c
     const hipStream_t st = as_stream(stream);
     const int64_t J = (int64_t)m->S + m->H;
     for (int64_t t = 0; t < n_times; ++t) {
-        EncArgs a;
-        memset(&a, 0, sizeof(a));
-        if ((rc = fill_sources_at(m->in.t, sources, src_dtype, strides, t, a.src, &a.src_all_f32))) return rc;
-        if ((rc = increment_launches(m, a, noise ? noise + t * m->n_sub * m->n_in : nullptr, st))) return rc;
-        if (m->H > 0) {
-            EncArgs h;
-            memset(&h, 0, sizeof(h));
-            if ((rc = fill_sources_at(m->hyb.t, hybrid_sources, hybrid_dtype, hybrid_strides, t, h.src, &h.src_all_f32)))
-                return rc;
-            no_overlap_args(m, m->hyb.t, m->H, h);
-            h.pmask = m->d_hmask;
-            h.pmask_f32 = m->hmask_f32;
-            h.out = m->d_hyb;
-            if ((rc = launch_encode(h, st))) return rc;
-        }
-        PackArgs p;
-        p.state = m->d_state;
-        p.parity = m->d_parity;
-        p.hyb = m->d_hyb;
-        p.row = X + t * m->n_sub * J;
-        p.S = m->S;
-        p.H = m->H;
-        p.n_sub = m->n_sub;
-        p.square = square_even_elements ? 1 : 0;
+        const double *noise_t = noise ? noise + t * m->n_sub * m->n_in : nullptr;
+        if ((rc = increment_launches(m, sources, src_dtype, strides, 4, t, noise_t, st))) return rc;
+        if ((rc = encode(m, Enc::Hybrid, hybrid_sources, hybrid_dtype, hybrid_strides, 4, t, nullptr, st))) return rc;
+        const PackArgs p{m->d_state, m->d_parity, m->d_hyb, X + t * m->n_sub * J, m->S, m->H, m->n_sub,
+                         square_even_elements ? FV3HIP_RESERVOIR_SQUARE_ELEMENTS : FV3HIP_RESERVOIR_SQUARE_NONE};
         hipLaunchKernelGGL(res_pack_kernel, dim3((unsigned)ceil_div(m->n_sub * J, kBlock)), dim3(kBlock), 0, st, p);
         if ((rc = check_launch("res_pack_kernel"))) return rc;
     }
@@ -916,12 +821,8 @@ extern "C" int fv3hip_reservoir_encode_targets(fv3hip_reservoir_t m, const void 
     FV3HIP_REQUIRE(n_times >= 0 && n_times < (1ll << 30), "bad n_times %lld", (long long)n_times);
     FV3HIP_REQUIRE(Y || n_times == 0, "null Y");
     for (int64_t t = 0; t < n_times; ++t) {
-        EncArgs a;
-        memset(&a, 0, sizeof(a));
-        if ((rc = fill_sources_at(m->out.t, sources, src_dtype, strides, t, a.src, &a.src_all_f32))) return rc;
-        no_overlap_args(m, m->out.t, m->n_out, a);
-        a.out = Y + t * m->n_sub * m->n_out;
-        if ((rc = launch_encode(a, as_stream(stream)))) return rc;
+        if ((rc = encode(m, Enc::Target, sources, src_dtype, strides, 4, t, Y + t * m->n_sub * m->n_out, as_stream(stream))))
+            return rc;
     }
     return FV3HIP_OK;
 }

@@ -276,6 +276,58 @@ class ScaleSpatialConcatZTransformer:
 # ---------------------------------------------------------------------------------------------
 
 
+def _ptr(a, ct):
+    return a.ctypes.data_as(ctypes.POINTER(ct))
+
+
+def _fill_variables(d, sizes, keep: list):
+    """``n_variables`` and ``var_nz`` of a transformer or codec descriptor."""
+    nz = np.asarray(sizes, np.intc)
+    keep.append(nz)
+    d.n_variables, d.var_nz = len(nz), _ptr(nz, ctypes.c_int)
+
+
+def _xyz_args(tensors: Sequence[torch.Tensor], ndim: int, what: str):
+    """(pointer table, dtype codes, strides) of device arrays as the library's entry points take their sources: (x, y, z)
+    arrays (``ndim`` 3) or [t, x, y, z] series (``ndim`` 4), float32 or float64, strided as they come."""
+    n = len(tensors)
+    strides = []
+    for t in tensors:
+        if t.dim() != ndim:
+            dims = "(x, y, z)" if ndim == 3 else "(t, x, y, z)"
+            raise ValueError(f"{what} must be {dims} arrays, got shape {tuple(t.shape)}")
+        if t.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{what} must be float32 or float64, got {t.dtype}")
+        strides += list(t.stride())
+    return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors]),
+            (ctypes.c_int * n)(*[_lib.F64 if t.dtype == torch.float64 else _lib.F32 for t in tensors]),
+            (ctypes.c_int64 * (ndim * n))(*strides))
+
+
+def _out_args(tensors: Sequence[torch.Tensor]):
+    """(pointer table, strides) of (x, y, z) device arrays as the entry points take their outputs."""
+    n = len(tensors)
+    return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors]),
+            (ctypes.c_int64 * (3 * n))(*[s for t in tensors for s in t.stride()]))
+
+
+def _create(fn: str, device, *args):
+    """A handle of ``fn`` (which takes ``args``, then the address of the handle), created on ``device``."""
+    h = ctypes.c_void_p()
+    with torch.cuda.device(device):
+        _require_device(torch.empty(1, device=device))
+        _lib.call(fn, *args, ctypes.byref(h))
+    return h
+
+
+def _destroy(fn: str, handle) -> None:
+    if handle:
+        try:
+            getattr(_lib.load(), fn)(handle)
+        except Exception:
+            pass
+
+
 def _npz_load(path):
     with np.load(path, allow_pickle=False) as z:
         return {k: z[k] for k in z.files}
@@ -318,17 +370,10 @@ class _ColumnCodec:
         if device.index not in handles:
             keep = []
             d = _lib.CodecDesc()
-            d.n_variables = self.n_variables
-            nz = np.asarray(self.original_feature_sizes, np.intc)
-            keep.append(nz)
-            d.var_nz = _ptr(nz, ctypes.c_int)
+            _fill_variables(d, self.original_feature_sizes, keep)
             d.n_latent = self.n_latent_dims
             self._fill(d, keep)
-            h = ctypes.c_void_p()
-            with torch.cuda.device(device):
-                _require_device(torch.empty(1, device=device))
-                _lib.call("fv3hip_codec_create", ctypes.byref(d), ctypes.byref(h))
-            handles[device.index] = h
+            handles[device.index] = _create("fv3hip_codec_create", device, ctypes.byref(d))
         return handles[device.index]
 
     def encode_device(self, tensors: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -346,7 +391,7 @@ class _ColumnCodec:
               or not out.is_contiguous()):
             raise ValueError(f"the latent buffer must be a contiguous {self.latent_dtype} array of shape "
                              f"{(nx, ny, self.n_latent_dims)}")
-        _lib.call_on(dev, "fv3hip_codec_encode", self._handle_on(dev), *ReservoirModel._sources(tensors), nx, ny,
+        _lib.call_on(dev, "fv3hip_codec_encode", self._handle_on(dev), *_xyz_args(tensors, 3, "inputs"), nx, ny,
                      out.data_ptr(), _stream(dev))
         return out
 
@@ -366,11 +411,8 @@ class _ColumnCodec:
             if tuple(t.shape) != (nx, ny, nz) or t.dtype != self.output_dtype:
                 raise ValueError(f"output array {i} must be {self.output_dtype} of shape {(nx, ny, nz)}")
         _require_device(*outs)
-        k = len(outs)
         _lib.call_on(dev, "fv3hip_codec_decode", self._handle_on(dev), latent.data_ptr(),
-                     _lib.F64 if latent.dtype == torch.float64 else _lib.F32, nx, ny,
-                     (ctypes.c_void_p * k)(*[t.data_ptr() for t in outs]),
-                     (ctypes.c_int64 * (3 * k))(*[s for t in outs for s in t.stride()]), _stream(dev))
+                     _lib.F64 if latent.dtype == torch.float64 else _lib.F32, nx, ny, *_out_args(outs), _stream(dev))
         return list(outs)
 
     @staticmethod
@@ -408,10 +450,7 @@ class _ColumnCodec:
 
     def __del__(self):
         for h in self.__dict__.get("_handles", {}).values():
-            try:
-                _lib.load().fv3hip_codec_destroy(h)
-            except Exception:
-                pass
+            _destroy("fv3hip_codec_destroy", h)
 
 
 def _f32_list(arrays, what):
@@ -755,18 +794,11 @@ SQUARE_NONE, SQUARE_SUBDOMAINS, SQUARE_ELEMENTS = 0, 1, 2
 WIN_AUTO, WIN_DENSE, WIN_CSR = 0, 1, 2
 
 
-def _ptr(a, ct):
-    return a.ctypes.data_as(ctypes.POINTER(ct))
-
-
 def _fill_transformer(td, tf, keep: list):
     if tf is None:
         return
     td.kind = tf.kind
-    td.n_variables = tf.n_variables
-    nz = np.asarray(tf.original_feature_sizes, np.intc)
-    keep.append(nz)
-    td.var_nz = _ptr(nz, ctypes.c_int)
+    _fill_variables(td, tf.original_feature_sizes, keep)
     if tf.kind == 1:
         td.nx, td.ny = tf.spatial_features[0], tf.spatial_features[1]
         c = np.ascontiguousarray(np.asarray(tf.center).reshape(-1), np.float32)
@@ -854,25 +886,7 @@ class ReservoirModel:
             keep.append(st)
             d.state = _ptr(st, ctypes.c_double)
         self.n_out = n_out
-        with torch.cuda.device(self.device):
-            _require_device(torch.empty(1, device=self.device))
-            h = ctypes.c_void_p()
-            _lib.call("fv3hip_reservoir_create", ctypes.byref(d), ctypes.byref(h))
-            self._handle = h
-
-    @staticmethod
-    def _sources(tensors: Sequence[torch.Tensor]):
-        n = len(tensors)
-        strides = []
-        for t in tensors:
-            if t.dim() != 3:
-                raise ValueError(f"inputs must be (x, y, z) arrays, got shape {tuple(t.shape)}")
-            if t.dtype not in (torch.float32, torch.float64):
-                raise TypeError(f"inputs must be float32 or float64, got {t.dtype}")
-            strides += list(t.stride())
-        return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors]),
-                (ctypes.c_int * n)(*[_lib.F64 if t.dtype == torch.float64 else _lib.F32 for t in tensors]),
-                (ctypes.c_int64 * (3 * n))(*strides))
+        self._handle = _create("fv3hip_reservoir_create", self.device, ctypes.byref(d))
 
     _PLAN_FIELDS = ("dense", "in_sb", "in_chunk", "in_split", "out_chunk", "out_split", "ldw", "ldc")
 
@@ -888,7 +902,7 @@ class ReservoirModel:
         """One ``increment_state`` from device (x, y, z) arrays over the overlapped rank extent (shapes checked by the
         caller)."""
         dev = _require_device(*inputs)
-        _lib.call_on(dev, "fv3hip_reservoir_increment", self._handle, *self._sources(inputs), _stream(dev))
+        _lib.call_on(dev, "fv3hip_reservoir_increment", self._handle, *_xyz_args(inputs, 3, "inputs"), _stream(dev))
 
     def predict(self, hybrid_inputs: Optional[Sequence[torch.Tensor]] = None,
                 outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
@@ -905,15 +919,12 @@ class ReservoirModel:
             if len(outs) != len(sizes) or any(tuple(t.shape) != (rx, ry, nz) or t.dtype != dtype
                                               for t, nz in zip(outs, sizes)):
                 raise ValueError(f"outs must be {dtype} arrays of shapes {[(rx, ry, nz) for nz in sizes]}")
-        k = len(outs)
-        out_args = ((ctypes.c_void_p * k)(*[t.data_ptr() for t in outs]),
-                    (ctypes.c_int64 * (3 * k))(*[s for t in outs for s in t.stride()]))
         if self.n_hybrid:
             _require_device(*hybrid_inputs)
-            src = self._sources(hybrid_inputs)
+            src = _xyz_args(hybrid_inputs, 3, "inputs")
         else:
             src = (None, None, None)
-        _lib.call_on(self.device, "fv3hip_reservoir_predict", self._handle, *src, *out_args, _stream(self.device))
+        _lib.call_on(self.device, "fv3hip_reservoir_predict", self._handle, *src, *_out_args(outs), _stream(self.device))
         return outs
 
     def get_state(self) -> torch.Tensor:
@@ -939,17 +950,10 @@ class ReservoirModel:
         index by the model's extents alone."""
         if len(tensors) != len(sizes):
             raise ValueError(f"Expected {len(sizes)} {what} arrays but got {len(tensors)}")
-        strides = []
         for i, (t, nz) in enumerate(zip(tensors, sizes)):
             if tuple(t.shape) != (n_times, *extent, nz):
                 raise ValueError(f"{what} array {i} has shape {tuple(t.shape)}, expected {(n_times, *extent, nz)}")
-            if t.dtype not in (torch.float32, torch.float64):
-                raise TypeError(f"{what} arrays must be float32 or float64, got {t.dtype}")
-            strides += list(t.stride())
-        n = len(tensors)
-        return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors]),
-                (ctypes.c_int * n)(*[_lib.F64 if t.dtype == torch.float64 else _lib.F32 for t in tensors]),
-                (ctypes.c_int64 * (4 * n))(*strides))
+        return _xyz_args(tensors, 4, f"{what} arrays")
 
     def train_series(self, inputs: Sequence[torch.Tensor], hybrid_inputs: Optional[Sequence[torch.Tensor]] = None,
                      noise: Optional[torch.Tensor] = None, square_even_elements: bool = False) -> torch.Tensor:
@@ -991,12 +995,7 @@ class ReservoirModel:
         return out
 
     def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h:
-            try:
-                _lib.load().fv3hip_reservoir_destroy(h)
-            except Exception:
-                pass
+        _destroy("fv3hip_reservoir_destroy", getattr(self, "_handle", None))
 
 
 class GramAccumulator:
@@ -1013,12 +1012,8 @@ class GramAccumulator:
         self.n_subdomains, self.n_features, self.n_outputs = int(n_subdomains), int(n_features), int(n_outputs)
         self.add_bias = bool(add_bias)
         self.n_rows = self.n_features + int(self.add_bias)
-        with torch.cuda.device(self.device):
-            _require_device(torch.empty(1, device=self.device))
-            h = ctypes.c_void_p()
-            _lib.call("fv3hip_gram_create", self.n_subdomains, self.n_features, self.n_outputs, int(self.add_bias),
-                      ctypes.byref(h))
-            self._handle = h
+        self._handle = _create("fv3hip_gram_create", self.device, self.n_subdomains, self.n_features, self.n_outputs,
+                               int(self.add_bias))
 
     def reset(self) -> None:
         _lib.call_on(self.device, "fv3hip_gram_reset", self._handle, _stream(self.device))
@@ -1055,9 +1050,4 @@ class GramAccumulator:
         return a, b
 
     def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h:
-            try:
-                _lib.load().fv3hip_gram_destroy(h)
-            except Exception:
-                pass
+        _destroy("fv3hip_gram_destroy", getattr(self, "_handle", None))
