@@ -16,7 +16,7 @@ from .novelty import (MinMaxNoveltyDetector, NoveltyDetector, OCSVMNoveltyDetect
                       taper_ramp)
 from .transformed import OutOfSampleModel, TransformedPredictor
 from .forest import RandomForest, RandomForestHyperparameters, train_random_forest
-from .conv import HipConvolutionalModel, conv_spec_from_arrays
+from .conv import ConvolutionalHyperparameters, HipConvolutionalModel, conv_spec_from_arrays, train_convolutional_model
 from .precipitative import (HipPrecipitativeModel, PrecipitativeHyperparameters, precipitative_spec_from_arrays,
                             train_precipitative_model)
 from .graph import (GraphHyperparameters, GraphUNetTwin, HipGraphAutoregressor, graph_unet_spec_from_state_dict,
@@ -49,4 +49,5 @@ __all__ = [
     "ReservoirHyperparameters", "ReservoirTrainingConfig", "SynchronizationTracker", "TransformerGroup", "train_reservoir_model",
     "InputSensitivity", "JacobianInputSensitivity", "RandomForestInputSensitivity",
     "RandomForestHyperparameters", "train_random_forest",
+    "ConvolutionalHyperparameters", "train_convolutional_model",
 ]

@@ -4,17 +4,20 @@
 (_shared/xr_prediction.py:120-129).  ``HipConvolutionalModel`` is that predictor on the MI355X: the network runs in
 ``fv3hip_conv_predict``, which reads the dataset's arrays in place and takes the halo cells from the neighbouring faces of a
 resident cube, or -- with the cube sharded by tile over ``torch.distributed`` ranks -- from strips exchanged in one
-all-gather (``parallel.exchange_edge_strips``).  Training stays offline; the artifact is ``name`` ("hip-convolutional") +
-``config.yaml`` (the reference's four keys) + ``spec.yaml`` + ``weights.npz``.
+all-gather (``parallel.exchange_edge_strips``).  ``train_convolutional_model`` is the training function
+(convolutional.py:101-150): Adam on the std-scaled MSE with the ``TransposeInvariant`` kernel constraint, through torch's
+autograd or -- ``backend="hip"`` -- through the project's own kernels (``conv_train.ConvTrainer``).  The
+artifact is ``name`` ("hip-convolutional") + ``config.yaml`` (the reference's four keys) + ``spec.yaml`` + ``weights.npz``.
 """
+import dataclasses
 import os
-from typing import Hashable, Iterable, Optional, Sequence
+from typing import Any, Dict, Hashable, Iterable, List, Optional, Sequence
 
 import numpy as np
 import torch
 import yaml
 
-from ..conv import ConvInput, ConvModel, ConvOutput, ConvSpec
+from ..conv import ConvInput, ConvModel, ConvOutput, ConvSpec, halos_required
 from ..cubedsphere._device import compute_device, download_all, on_device
 from ..xr_compat import DataArray, Dataset, from_compat, to_compat
 from . import io
@@ -205,3 +208,258 @@ def conv_spec_from_arrays(
     return ConvSpec(inputs, [np.asarray(k, np.float32) for k in hidden_kernels],
                     None if hidden_biases is None else [np.asarray(b, np.float32) for b in hidden_biases], outputs,
                     activation=activation)
+
+
+# ---------------------------------------------------------------------------------------------
+# offline training (PyTorch-ROCm, or the project's own kernels with backend="hip")
+# ---------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class ConvolutionalHyperparameters:
+    """fv3fit's ``ConvolutionalHyperparameters`` (convolutional.py:27-61) with its ``ConvolutionalNetworkConfig``
+    (convolutional_network.py:59-101), ``TrainingLoopConfig`` and Adam's learning rate flattened into one class.  The fields
+    after ``seed`` are accepted so that a reference configuration reads, but only at their defaults (see ``_REJECTED``)."""
+
+    input_variables: List[str]
+    output_variables: List[str]
+    filters: int = 32
+    depth: int = 3                      # convolutional layers, the 1 x 1 output layer included
+    kernel_size: int = 3
+    activation_function: str = "relu"
+    transpose_invariant: bool = True
+    epochs: int = 3
+    batch_size: int = 1                 # tile-samples per step
+    learning_rate: float = 1e-3
+    normalization_fit_samples: int = 30   # one sample is one tile
+    seed: int = 0
+    diffusive: bool = False
+    gaussian_noise: float = 0.0
+    spectral_normalization: bool = False
+    kernel_regularizer: Optional[Any] = None
+    clip_config: Dict[Hashable, Any] = dataclasses.field(default_factory=dict)
+    loss_type: str = "mse"
+    loss_scaling: str = "standard"
+
+
+# field -> the values it may have (the reference's defaults); the reference's conv graph never clips its outputs (build_model
+# takes no clip_config, convolutional.py:153-210), so a clip_config would change the targets only
+_REJECTED = {"diffusive": (False,), "gaussian_noise": (0.0, 0), "spectral_normalization": (False,), "kernel_regularizer": (None, "none"),
+             "clip_config": ({}, None), "loss_type": ("mse",), "loss_scaling": ("standard",)}
+_TWIN_ACTIVATIONS = {"relu": torch.relu, "linear": lambda v: v, "tanh": torch.tanh}
+
+
+def _check_hyperparameters(hp: ConvolutionalHyperparameters, backend: str) -> None:
+    for name, allowed in _REJECTED.items():
+        value = getattr(hp, name)
+        if not any(type(value) is type(a) and value == a for a in allowed):
+            raise NotImplementedError(f"{name}={value!r} is not supported by train_convolutional_model (only {allowed[0]!r})")
+    if hp.filters == 0:
+        raise NotImplementedError("filters=0 causes a floating point exception, and we haven't written a workaround")
+    halos_required(hp.kernel_size, hp.depth)
+    if hp.activation_function not in _TWIN_ACTIVATIONS:
+        raise ValueError(f"activation_function {hp.activation_function!r} is not supported; supported: {sorted(_TWIN_ACTIVATIONS)}")
+    if backend == "hip" and hp.activation_function not in ("relu", "linear"):
+        raise ValueError(f"backend='hip' trains with activation_function 'relu' or 'linear', got {hp.activation_function!r}; "
+                         "use backend='torch'")
+    if hp.batch_size < 1 or hp.epochs < 0:
+        raise ValueError("batch_size must be positive and epochs not negative")
+
+
+def _cubes_for_training(batches, names: Sequence[str]) -> List[np.ndarray]:
+    """Every variable as float32 ``[sample, tile, x, y, z]`` (a variable without ``z`` gets a trailing axis of 1:
+    convolutional.py:77-78), the batches concatenated along ``sample``."""
+    from ..xr_compat import to_compat
+
+    cols: List[List[np.ndarray]] = [[] for _ in names]
+    for ds in batches:
+        ds = to_compat(ds)
+        for i, name in enumerate(names):
+            da = ds[name]
+            for dim in ("tile", "x", "y"):
+                if dim not in da.dims:
+                    raise ValueError(f"variable {name!r} must have 'tile', 'x', and 'y' dimensions, got {tuple(da.dims)}")
+            zs = [d for d in da.dims if d in ("z", "z_interface")]
+            lead = [d for d in da.dims if d not in ("tile", "x", "y") and d not in zs]
+            a = np.asarray(da.transpose(*lead, "tile", "x", "y", *zs).values)
+            nz = a.shape[-1] if zs else 1
+            n_tiles, nx, ny = (da.sizes[d] for d in ("tile", "x", "y"))
+            cols[i].append(a.reshape(-1, n_tiles, nx, ny, nz).astype(np.float32))
+    return [np.concatenate(c, axis=0) for c in cols]
+
+
+@dataclasses.dataclass
+class _ConvTraining:
+    """What both backends of ``train_convolutional_model`` start from: the fitted normalisation, the normalised halo-padded
+    inputs, the targets and the freshly initialised layers (created on the host, so that the start does not depend on the
+    device)."""
+
+    n_halo: int
+    xin: np.ndarray                 # [tile-sample, nx + 2 h, ny + 2 h, C] padded, then normalised
+    y: List[np.ndarray]             # [tile-sample, nx, ny, nfeat] each
+    x_mean: List[np.ndarray]
+    x_std: List[np.ndarray]
+    y_mean: List[np.ndarray]
+    y_std: List[np.ndarray]
+    loss_std: List[np.ndarray]
+    hidden: List[torch.nn.Conv2d]   # weight [f, c, a, b]: the Keras kernel is weight.permute(2, 3, 1, 0)
+    heads: List[torch.nn.Conv2d]
+
+
+def _keras_kernel(conv: torch.nn.Conv2d) -> np.ndarray:
+    return np.ascontiguousarray(conv.weight.detach().cpu().numpy().transpose(2, 3, 1, 0))
+
+
+def _prepare_conv_training(hp: ConvolutionalHyperparameters, train_batches) -> _ConvTraining:
+    """convolutional.py:64-98, 126-137 and shared/utils.py:84-105 on the host."""
+    from ..cubedsphere.halos import append_halos
+
+    torch.manual_seed(hp.seed)
+    h = halos_required(hp.kernel_size, hp.depth)
+    X5 = _cubes_for_training(train_batches, hp.input_variables)
+    y5 = _cubes_for_training(train_batches, hp.output_variables)
+    for a in X5 + y5:
+        if a.shape[1] != 6:
+            raise ValueError(f"dataset must have 6 tiles to halo update, got {a.shape[1]}")
+
+    def pad_and_fold(a):   # [sample, tile, x, y, z] -> [sample * tile, x + 2 h, y + 2 h, z]
+        if h > 0 and a.shape[2] == a.shape[3]:
+            a = append_halos(np.ascontiguousarray(a.transpose(1, 0, 4, 2, 3)), h).transpose(1, 0, 3, 4, 2)
+        elif h > 0:   # (not a cube: reported below with the reference's message)
+            a = np.pad(a, ((0, 0), (0, 0), (h, h), (h, h), (0, 0)))
+        return np.ascontiguousarray(a.reshape((-1,) + a.shape[2:]))
+
+    X = [pad_and_fold(a) for a in X5]
+    y = [np.ascontiguousarray(a.reshape((-1,) + a.shape[2:])) for a in y5]
+    for item in X + y:
+        if item.shape[1] != item.shape[2]:
+            raise ValueError(f"x and y dimensions should be the same length, got shape {item.shape}")
+    nfit = hp.normalization_fit_samples
+    flat = lambda a: a[:nfit].reshape(-1, a.shape[-1])   # halo cells and the raw-zero corners are part of the fit, as in the reference's X
+    x_mean = [flat(a).mean(axis=0).astype(np.float32) for a in X]
+    x_std = [flat(a).std(axis=0).astype(np.float32) for a in X]
+    y_mean = [flat(a).mean(axis=0).astype(np.float32) for a in y]
+    y_std = [flat(a).std(axis=0).astype(np.float32) for a in y]
+    loss_std = [np.std(flat(a), axis=0, dtype=np.float32) for a in y]
+    eps = np.float32(1e-7)
+    xin = np.concatenate([(a - m) / (s + eps) for a, m, s in zip(X, x_mean, x_std)], axis=-1)   # padded first, normalised after
+
+    def layer(c_in, c_out, k):   # Keras Conv2D default: glorot_uniform (fans k k c_in, k k c_out), zero bias
+        conv = torch.nn.Conv2d(c_in, c_out, k)
+        torch.nn.init.xavier_uniform_(conv.weight)
+        torch.nn.init.zeros_(conv.bias)
+        return conv
+
+    hidden, fan = [], xin.shape[-1]
+    for _ in range(hp.depth - 1):
+        hidden.append(layer(fan, hp.filters, hp.kernel_size))
+        fan = hp.filters
+    heads = [layer(fan, a.shape[-1], 1) for a in y]
+    return _ConvTraining(n_halo=h, xin=np.ascontiguousarray(xin, np.float32), y=y, x_mean=x_mean, x_std=x_std, y_mean=y_mean,
+                         y_std=y_std, loss_std=loss_std, hidden=hidden, heads=heads)
+
+
+def _conv_weights(prep: _ConvTraining):
+    """The four weight lists of ``conv_spec_from_arrays`` from the (trained or fresh) torch layers."""
+    return ([_keras_kernel(c) for c in prep.hidden], [c.bias.detach().cpu().numpy().copy() for c in prep.hidden],
+            [_keras_kernel(c)[0, 0] for c in prep.heads], [c.bias.detach().cpu().numpy().copy() for c in prep.heads])
+
+
+def _conv_batches(hp: ConvolutionalHyperparameters, n: int, dev: torch.device):
+    """The minibatches of tile-samples, the same for both backends."""
+    g = torch.Generator().manual_seed(hp.seed)
+    for _ in range(hp.epochs):
+        perm = torch.randperm(n, generator=g).to(dev)
+        for i in range(0, n, hp.batch_size):
+            yield perm[i:i + hp.batch_size]
+
+
+def _train_conv_torch(hp: ConvolutionalHyperparameters, prep: _ConvTraining, dev: torch.device):
+    """Adam on the std-scaled MSE through ``torch.nn.functional.conv2d`` and autograd; the kernel constraint after
+    ``opt.step()``, where Keras applies it."""
+    F = torch.nn.functional
+    xin = torch.from_numpy(prep.xin).to(dev).permute(0, 3, 1, 2)   # [s, c, x, y]
+    hidden, heads = [c.to(dev) for c in prep.hidden], [c.to(dev) for c in prep.heads]
+    targets = [torch.from_numpy(a).to(dev) for a in prep.y]
+    t_mean = [torch.from_numpy(m).to(dev) for m in prep.y_mean]
+    t_std = [torch.from_numpy(s).to(dev) for s in prep.y_std]
+    l_std = [torch.from_numpy(np.maximum(s, 1e-12)).to(dev) for s in prep.loss_std]
+    act = _TWIN_ACTIVATIONS[hp.activation_function]
+    params = [p for c in hidden + heads for p in c.parameters()]
+    opt = torch.optim.Adam(params, lr=hp.learning_rate)
+    for idx in _conv_batches(hp, xin.shape[0], dev):
+        a = xin[idx]
+        for c in hidden:
+            a = act(F.conv2d(a, c.weight, c.bias))
+        loss = 0.0
+        for j, head in enumerate(heads):
+            pred = F.conv2d(a, head.weight, head.bias).permute(0, 2, 3, 1) * t_std[j] + t_mean[j]
+            loss = loss + torch.mean(((pred - targets[j][idx]) / l_std[j]) ** 2)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        if hp.transpose_invariant:
+            with torch.no_grad():
+                for c in hidden:
+                    c.weight.copy_(0.5 * (c.weight + c.weight.transpose(2, 3)))
+    return _conv_weights(prep)
+
+
+def conv_mse_loss(prep: _ConvTraining):
+    """The loss of ``_train_conv_torch`` as the per-feature arrays the device step takes (``fv3net_amd.train.MseLoss``)."""
+    from ..train import MseLoss
+
+    nfs = [a.shape[-1] for a in prep.y]
+    inv = [(1.0 / np.maximum(s, 1e-12).astype(np.float64) ** 2).astype(np.float32) for s in prep.loss_std]
+    total = sum(nfs)
+    return MseLoss(scale=np.concatenate(prep.y_std), center=np.concatenate(prep.y_mean), inv_cstd2=np.concatenate(inv),
+                   lo=np.full(total, -np.inf, np.float32), hi=np.full(total, np.inf, np.float32), keep=np.ones(total, np.float32),
+                   kept=np.concatenate([np.full(nf, nf, np.float64) for nf in nfs]))
+
+
+def conv_trainer(hp: ConvolutionalHyperparameters, prep: _ConvTraining, dev: torch.device):
+    """The device training state of ``backend="hip"``: the layers of ``prep``, the resident inputs and targets, the loss."""
+    from ..conv_train import ConvTrainer
+
+    kernels, biases, out_k, out_b = _conv_weights(prep)
+    targets = np.concatenate([a.reshape(-1, a.shape[-1]) for a in prep.y], axis=1)
+    return ConvTrainer(kernels, biases, np.concatenate(out_k, axis=1), np.concatenate(out_b), prep.xin, targets, conv_mse_loss(prep),
+                       device=dev, max_batch=min(hp.batch_size, prep.xin.shape[0]), learning_rate=hp.learning_rate,
+                       relu=hp.activation_function == "relu", transpose_invariant=hp.transpose_invariant)
+
+
+def _train_conv_hip(hp: ConvolutionalHyperparameters, prep: _ConvTraining, dev: torch.device):
+    """The same tile-samples in the same order through ``fv3net_amd.conv_train.ConvTrainer`` (csrc/conv_train.hip)."""
+    trainer = conv_trainer(hp, prep, dev)
+    for idx in _conv_batches(hp, prep.xin.shape[0], dev):
+        trainer.step(idx)
+    return trainer.parameters([a.shape[-1] for a in prep.y])
+
+
+def train_convolutional_model(hyperparameters: ConvolutionalHyperparameters, train_batches, device: Optional[str] = None,
+                              backend: Optional[str] = None) -> HipConvolutionalModel:
+    """Pad every tile of ``train_batches`` (datasets whose variables have ``tile``, ``x``, ``y`` and, unless single-level, ``z``
+    dimensions, plus any sample dimensions) with cube halos, fit the normalisation on the first ``normalization_fit_samples``
+    tile-samples, train ``Conv2D(filters, k, valid, activation) x (depth - 1) -> 1 x 1 Conv2D per output`` with Adam on the
+    std-scaled MSE, and return the predictor (convolutional.py:101-210).
+
+    ``backend``: ``None`` / ``"torch"`` steps through ``torch.nn.functional.conv2d``, autograd and ``torch.optim.Adam``; ``"hip"``
+    through the project's own kernels (needs a GPU).  Preparation, initialisation and the minibatch sequence are shared: both
+    start from bitwise-equal parameters and see the same tile-samples in the same order."""
+    hp = hyperparameters
+    if backend not in (None, "torch", "hip"):
+        raise ValueError(f"backend must be None, 'torch' or 'hip', got {backend!r}")
+    backend = backend or "torch"
+    _check_hyperparameters(hp, backend)
+    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    if backend == "hip" and dev.type != "cuda":
+        from .. import ops
+
+        ops._require_device(torch.empty(0, device=dev))  # raises: there is no CPU path
+    prep = _prepare_conv_training(hp, train_batches)
+
+    def model(weights):
+        spec = conv_spec_from_arrays(hp.input_variables, prep.x_mean, prep.x_std, weights[0], weights[1], hp.output_variables,
+                                     weights[2], weights[3], prep.y_mean, prep.y_std, activation=hp.activation_function)
+        return HipConvolutionalModel(hp.input_variables, hp.output_variables, spec, unstacked_dims=("x", "y", "z"), n_halo=prep.n_halo)
+
+    model(_conv_weights(prep))   # (a network that cannot be saved -- depth = 1 -- fails here, before any step)
+    return model((_train_conv_hip if backend == "hip" else _train_conv_torch)(hp, prep, dev))

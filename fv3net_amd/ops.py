@@ -1240,6 +1240,122 @@ def train_adam(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: tor
                  float(beta2), float(eps), _stream(dev))
 
 
+# ---------------------------------------------------------------------------------------------
+# training the convolutional network (csrc/conv_train.hip): the caller owns every tensor, nothing is allocated or synchronised
+# ---------------------------------------------------------------------------------------------
+def train_conv_chunk_pixels() -> int:
+    """Output pixels per chunk of ``train_conv_backward_weight``: a larger batch needs its workspace."""
+    return int(_lib.load().fv3hip_train_conv_chunk_pixels())
+
+
+def train_conv_backward_weight_workspace_floats(n: int, x: int, y: int, k: int, c: int, f: int) -> int:
+    """For ``n`` samples of a layer INPUT of ``x`` by ``y`` cells."""
+    return int(_lib.load().fv3hip_train_conv_backward_weight_workspace_bytes(int(n), int(x), int(y), int(k), int(c), int(f))) // 4
+
+
+def _cells_f32(t: torch.Tensor, what: str, channels: Optional[int] = None):
+    """((samples, x, y, channels), (sample, x, y strides)) of a float32 [sample, x, y, channel] tensor or view whose channels are
+    contiguous."""
+    if t.dtype != torch.float32 or t.dim() != 4:
+        raise TypeError(f"{what} must be a 4-D float32 tensor [sample, x, y, channel], got {t.dtype} with {t.dim()} dimensions")
+    shape = tuple(int(v) for v in t.shape)
+    if min(shape) < 1:
+        raise ValueError(f"{what} is empty: {shape}")
+    if shape[3] > 1 and t.stride(3) != 1:
+        raise ValueError(f"{what}: the channels must be contiguous")
+    # (the stride of an axis of length 1 is never multiplied by anything but 0: any valid value does)
+    strides = [int(t.stride(d)) if shape[d] > 1 else 0 for d in range(3)]
+    strides[2] = max(strides[2], shape[3])
+    if min(strides) < 0 or (shape[2] > 1 and int(t.stride(2)) < shape[3]):
+        raise ValueError(f"{what}: strides {tuple(t.stride())} do not hold {shape[3]} contiguous channels")
+    if channels is not None and shape[3] != channels:
+        raise ValueError(f"{what} has {shape[3]} channels, expected {channels}")
+    return shape, strides
+
+
+def _conv_kernel_f32(w: torch.Tensor, what: str):
+    """(k, c, f, ld) of a float32 kernel [k, k, c_in, f] (Keras layout) that is a matrix [k k c_in][f] with a leading dimension."""
+    if w.dtype != torch.float32 or w.dim() != 4 or w.shape[0] != w.shape[1]:
+        raise TypeError(f"{what} must be a float32 kernel [k, k, c_in, f], got {w.dtype} {tuple(w.shape)}")
+    k, _, c, f = (int(v) for v in w.shape)
+    if min(k, c, f) < 1:
+        raise ValueError(f"{what} is empty: {tuple(w.shape)}")
+    if f > 1 and w.stride(3) != 1:
+        raise ValueError(f"{what}: the filters must be contiguous")
+    ld = int(w.stride(2)) if c > 1 else (int(w.stride(1)) if k > 1 else f)
+    want = (k * c * ld, c * ld, ld)
+    if ld < f or any(int(w.shape[d]) > 1 and int(w.stride(d)) != want[d] for d in range(3)):
+        raise ValueError(f"{what}: strides {tuple(w.stride())} are not those of a matrix [k k c_in][f] with one leading dimension")
+    return k, c, f, ld
+
+
+def train_conv_forward(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor,
+                       idx: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+    """``out[s, x, y] = act(sum_{i,j} a[sample(s), x + i, y + j] @ w[i, j] + bias)`` ("valid"), ``sample(s) = idx[s]`` (int64, on
+    the device) or ``s``; ``a`` ``[samples, X, Y, c]``, ``out`` ``[>= batch, X - k + 1, Y - k + 1, f]``, views with padding allowed."""
+    dev = _require_device(*(t for t in (a, w, bias, out, idx) if t is not None))
+    k, c, f, ldw = _conv_kernel_f32(w, "w")
+    (a_samples, X, Y, _), sa = _cells_f32(a, "a", c)
+    n = _batch_rows(idx, a_samples)
+    (h_samples, ox, oy, _), sh = _cells_f32(out, "out", f)
+    if h_samples < n or (ox, oy) != (X - k + 1, Y - k + 1):
+        raise ValueError(f"out is {tuple(out.shape)}; a batch of {n} samples of {X} x {Y} cells under a {k} x {k} kernel gives "
+                         f"{(n, X - k + 1, Y - k + 1, f)}")
+    _lib.call_on(dev, "fv3hip_train_conv_forward", _ptr(a), *sa, a_samples, _ptr(idx), _ptr(w), ldw, _ptr(_vec(bias, "bias", f)),
+                 _ptr(out), *sh, n, X, Y, k, c, f, _lib.ACT_RELU if relu else _lib.ACT_LINEAR, _stream(dev))
+    return out
+
+
+def train_conv_backward_data(dh: torch.Tensor, w: torch.Tensor, p: Optional[torch.Tensor], out: torch.Tensor) -> torch.Tensor:
+    """``out`` = the gradient with respect to the layer's input ``[n, X, Y, c]`` from ``dh`` ``[n, X - k + 1, Y - k + 1, f]``,
+    an exact 0 where ``p > 0`` is false (``p``: the post-ReLU input of the layer, of ``out``'s extent; None: no mask)."""
+    dev = _require_device(*(t for t in (dh, w, p, out) if t is not None))
+    k, c, f, ldw = _conv_kernel_f32(w, "w")
+    (n, ox, oy, _), sdh = _cells_f32(dh, "dh", f)
+    (a_samples, X, Y, _), sda = _cells_f32(out, "out", c)
+    if a_samples < n or (ox, oy) != (X - k + 1, Y - k + 1):
+        raise ValueError(f"out is {tuple(out.shape)}, dh {tuple(dh.shape)}: not the input and output of a {k} x {k} kernel")
+    sp = [0, 0, 0]
+    if p is not None:
+        (p_samples, px, py, _), sp = _cells_f32(p, "p", c)
+        if p_samples < n or (px, py) != (X, Y):
+            raise ValueError(f"p is {tuple(p.shape)}, out {tuple(out.shape)}")
+    _lib.call_on(dev, "fv3hip_train_conv_backward_data", _ptr(dh), *sdh, _ptr(w), ldw, _ptr(p), *sp, _ptr(out), *sda, n, X, Y, k, c, f,
+                 _stream(dev))
+    return out
+
+
+def train_conv_backward_weight(a: torch.Tensor, dh: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor],
+                               idx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """``dw[i, j] = sum_{s,x,y} a[sample(s), x + i, y + j].T @ dh[s, x, y]``, ``db = dh.sum((0, 1, 2))`` (None: skipped); a batch
+    of more than ``train_conv_chunk_pixels()`` output pixels needs a float32 ``workspace`` of
+    ``train_conv_backward_weight_workspace_floats(n, X, Y, k, c, f)`` values."""
+    dev = _require_device(*(t for t in (a, dh, dw, db, idx, workspace) if t is not None))
+    k, c, f, lddw = _conv_kernel_f32(dw, "dw")
+    (a_samples, X, Y, _), sa = _cells_f32(a, "a", c)
+    n = _batch_rows(idx, a_samples)
+    (dh_samples, ox, oy, _), sdh = _cells_f32(dh, "dh", f)
+    if dh_samples < n or (ox, oy) != (X - k + 1, Y - k + 1):
+        raise ValueError(f"dh is {tuple(dh.shape)}; a batch of {n} samples of {X} x {Y} cells under a {k} x {k} kernel gives "
+                         f"{(n, X - k + 1, Y - k + 1, f)}")
+    ws_bytes = 0
+    if workspace is not None:
+        if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+            raise TypeError("workspace must be a contiguous float32 tensor")
+        ws_bytes = workspace.numel() * 4
+    _lib.call_on(dev, "fv3hip_train_conv_backward_weight", _ptr(a), *sa, a_samples, _ptr(idx), _ptr(dh), *sdh, _ptr(dw), lddw,
+                 _ptr(_vec(db, "db", f)), _ptr(workspace), ws_bytes, n, X, Y, k, c, f, _stream(dev))
+    return dw, db
+
+
+def train_conv_constrain(w: torch.Tensor) -> torch.Tensor:
+    """``w <- 0.5 * (w + w.transpose(0, 1))`` in place (the reference's ``TransposeInvariant``), bitwise symmetric."""
+    dev = _require_device(w)
+    k, c, f, ldw = _conv_kernel_f32(w, "w")
+    _lib.call_on(dev, "fv3hip_train_conv_constrain", _ptr(w), ldw, k, c, f, _stream(dev))
+    return w
+
+
 class HipTimer:
     """HIP events recorded on torch's current stream (used by bench.py)."""
 

@@ -1222,6 +1222,47 @@ int fv3hip_train_mse_grad(const float *yhat, int64_t ldy, const float *scale, co
 int fv3hip_train_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step, double lr, double beta1,
                       double beta2, double eps, void *stream);
 
+/* ---- training the convolutional network (fv3fit's "convolutional" training function, keras/_models/convolutional.py:101-210,
+ * shared/convolutional_network.py:59-195).  Stateless like fv3hip_train_linear_*: the caller owns every
+ * DEVICE pointer, the workspace included; nothing is allocated or synchronised; all arguments are checked on the host before any
+ * HIP call.  Activations are float32, channel-last [sample][x][y][channel], each buffer with its element strides for sample, x
+ * and y (_ss, _sx, _sy; the channel stride is 1, sy >= channels), so padded views work.  Kernels are [a][b][c_in][f] (Keras
+ * Conv2D: first kernel axis along x, cross-correlation, "valid") with a leading dimension ldw >= f on the last axis.  X, Y are
+ * the extents of the layer's INPUT; its output has X - k + 1 by Y - k + 1 cells; k is odd.  Every contraction is an implicit
+ * GEMM on the exact-float32 MFMA in a fixed order (no im2col buffer, no atomics): results are bitwise reproducible and depend
+ * on the shapes only.  Each entry is one launch (backward_weight: two with more than one chunk) on `stream`, so a whole step
+ * captures as a chain.
+ *   idx (int64, DEVICE, or null): sample s of the batch is sample idx[s] of A; an index outside [0, a_samples) reads as a sample
+ *   of zeros.
+ *   fv3hip_train_conv_forward          H[s][x][y][f] = act(sum_{a,b,c} A[row(s)][x + a][y + b][c] W[a][b][c][f] + bias[f]); act
+ *                                      FV3HIP_ACT_LINEAR or _RELU (v < 0 ? 0 : v: a NaN stays); bias may be null.
+ *   fv3hip_train_conv_backward_data    dA[s][x][y][c] = sum_{a,b,f} dH[s][x - a][y - b][f] W[a][b][c][f] over the terms whose dH
+ *                                      cell exists, and an exact 0 where P[s][x][y][c] > 0 is false (relu'(0) = 0 as in torch; a
+ *                                      NaN activation masks too).  P: the post-ReLU activation that fed the layer (the extent of
+ *                                      dA), or null for no mask.
+ *   fv3hip_train_conv_backward_weight  dW[a][b][c][f] = sum_{s,x,y} A[row(s)][x + a][y + b][c] dH[s][x][y][f]; db[f] =
+ *                                      sum_{s,x,y} dH[s][x][y][f] (null: skipped).  The batch's output pixels (s, x, y) are cut
+ *                                      into chunks of fv3hip_train_conv_chunk_pixels() (512): one chunk writes dW and db
+ *                                      directly; more write each chunk's partial to `workspace` (at least
+ *                                      fv3hip_train_conv_backward_weight_workspace_bytes(n, X, Y, k, c, f) bytes) and a second
+ *                                      kernel adds the partials in ascending chunk order.
+ *   fv3hip_train_conv_constrain        TransposeInvariant in place: w[a][b] and w[b][a] both become 0.5f * (w[a][b] + w[b][a])
+ *                                      for every (c, f) -- bitwise symmetric, and bitwise 0.5 * (w + w.transpose(0, 1)).
+ */
+int fv3hip_train_conv_chunk_pixels(void);
+size_t fv3hip_train_conv_backward_weight_workspace_bytes(int64_t n, int X, int Y, int k, int c, int f);
+int fv3hip_train_conv_forward(const float *A, int64_t a_ss, int64_t a_sx, int64_t a_sy, int64_t a_samples, const int64_t *idx,
+                              const float *W, int64_t ldw, const float *bias, float *H, int64_t h_ss, int64_t h_sx, int64_t h_sy,
+                              int64_t n, int X, int Y, int k, int c, int f, int act, void *stream);
+int fv3hip_train_conv_backward_data(const float *dH, int64_t dh_ss, int64_t dh_sx, int64_t dh_sy, const float *W, int64_t ldw,
+                                    const float *P, int64_t p_ss, int64_t p_sx, int64_t p_sy, float *dA, int64_t da_ss, int64_t da_sx,
+                                    int64_t da_sy, int64_t n, int X, int Y, int k, int c, int f, void *stream);
+int fv3hip_train_conv_backward_weight(const float *A, int64_t a_ss, int64_t a_sx, int64_t a_sy, int64_t a_samples, const int64_t *idx,
+                                      const float *dH, int64_t dh_ss, int64_t dh_sx, int64_t dh_sy, float *dW, int64_t lddw, float *db,
+                                      float *workspace, size_t workspace_bytes, int64_t n, int X, int Y, int k, int c, int f,
+                                      void *stream);
+int fv3hip_train_conv_constrain(float *W, int64_t ldw, int k, int c, int f, void *stream);
+
 /* ---- training random forests (fv3fit's "sklearn_random_forest"; sklearn's RandomForestRegressor.fit: squared error, exact
  * best split, all features).  Stateless like fv3hip_train_*: the caller owns every DEVICE buffer below, nothing is allocated or
  * synchronised, the arguments are checked on the host before any HIP call.  One tree grows level by level:
