@@ -33,6 +33,7 @@ constexpr int kTileRows = 32;      // positions staged in LDS at a time
 constexpr int kBestBlock = 128;
 constexpr int kScanBlock = 1024;   // ft_children_kernel
 constexpr size_t kMaxLds = 64 * 1024;
+constexpr int kMaxOutputs = 3821;  // the most outputs of which one tile row fits kMaxLds (tile_shape)
 constexpr uint8_t kLeft = 0, kRight = 1, kGone = 2;
 
 typedef fv3hip_forest_train_t Ws;
@@ -331,6 +332,7 @@ __global__ __launch_bounds__(kScanBlock) void ft_children_kernel(Ws w, Level L)
 {
     __shared__ int64_t sh[kScanBlock];
     int64_t splits = 0, samples = 0;   // over the nodes before this round's
+    int overflow = 0;
     for (int64_t k0 = 0; k0 < L.K; k0 += kScanBlock) {
         const int64_t k = k0 + threadIdx.x;
         const bool in = k < L.K;
@@ -347,17 +349,19 @@ __global__ __launch_bounds__(kScanBlock) void ft_children_kernel(Ws w, Level L)
                 L.node_next[2 * i] = (int32_t)child, L.node_next[2 * i + 1] = (int32_t)(child + 1);
                 L.seg_next[2 * i] = at, L.seg_next[2 * i + 1] = at + nl;
             } else {
-                w.level[3] = 1;   // (cannot happen with buffers sized as the header says)
+                overflow = 1;   // (cannot happen with buffers sized as the header says)
             }
             w.dst_left[k] = at, w.dst_right[k] = at + nl;
         }
         splits += tot_splits, samples += tot_samples;
     }
+    overflow = __syncthreads_or(overflow);
     if (threadIdx.x == 0) {
         if (2 * splits < w.k_cap + 1) L.seg_next[2 * splits] = samples;
         w.level[0] = 2 * splits;
         w.level[1] = samples;
         w.level[2] = L.n_nodes + 2 * splits;
+        w.level[3] = overflow;   // written every level: the record does not depend on what the buffer held
     }
 }
 
@@ -450,12 +454,31 @@ __global__ __launch_bounds__(kChunk) void ft_scatter_kernel(Ws w, Part P)
     if ((uint64_t)dest < (uint64_t)w.n) P.dst[(int64_t)f * w.n + dest] = s;
 }
 
+// what ft_scan_kernel keeps in LDS beside the tile, and one row of the tile (the leading dimension is odd: the 32 rows of one
+// column fall on distinct banks)
+constexpr size_t scan_fixed_bytes(int O) { return (size_t)(O + 2) * 8 + kChunk * 8 + (kChunk + 1) * 4 + kChunk * 4 + kChunk; }
+constexpr size_t scan_row_bytes(int O) { return (size_t)((O + 2) | 1) * 8; }
+static_assert(scan_fixed_bytes(kMaxOutputs) + scan_row_bytes(kMaxOutputs) <= kMaxLds &&
+                  scan_fixed_bytes(kMaxOutputs + 1) + scan_row_bytes(kMaxOutputs + 1) > kMaxLds,
+              "kMaxOutputs is not the greatest output count with a tile of one row");
+
+// rows of the LDS tile and its leading dimension for O <= kMaxOutputs outputs
+void tile_shape(int O, int *rows, int *ldt, size_t *bytes)
+{
+    *ldt = (O + 2) | 1;
+    const size_t fixed = scan_fixed_bytes(O), per_row = scan_row_bytes(O);
+    const size_t r = (kMaxLds - fixed) / per_row;
+    *rows = (int)(r < (size_t)kTileRows ? r : (size_t)kTileRows);
+    *bytes = fixed + (size_t)*rows * per_row;
+}
+
 int check_ws(const Ws *w)
 {
     FV3HIP_REQUIRE(w, "null workspace");
     FV3HIP_REQUIRE(w->n >= 1 && w->n < ((int64_t)1 << 31), "n must be in [1, 2^31), got %lld", (long long)w->n);
     FV3HIP_REQUIRE(w->F >= 1 && w->F <= 65535, "the feature count must be in [1, 65535], got %d", w->F);
-    FV3HIP_REQUIRE(w->O >= 1 && w->O <= 4096, "the output count must be in [1, 4096], got %d", w->O);
+    FV3HIP_REQUIRE(w->O >= 1 && w->O <= kMaxOutputs, "the output count must be in [1, %d] (one row of the scan's LDS tile), got %d",
+                   kMaxOutputs, w->O);
     FV3HIP_REQUIRE(w->k_cap >= 1 && w->node_cap >= 1 && w->node_cap < ((int64_t)1 << 31), "bad k_cap %lld or node_cap %lld",
                    (long long)w->k_cap, (long long)w->node_cap);
     FV3HIP_REQUIRE(w->xt && w->y && w->ysq && w->order && w->weight && w->list_a && w->list_b && w->side && w->pos_node &&
@@ -475,18 +498,6 @@ int partition(const Ws &w, const Part &P, hipStream_t st)
     hipLaunchKernelGGL(ft_count_carry_kernel, dim3((unsigned)ceil_div(w.F, kChunk)), dim3(kChunk), 0, st, w, P);
     hipLaunchKernelGGL(ft_scatter_kernel, grid, dim3(kChunk), 0, st, w, P);
     return check_launch("forest-training partition kernels");
-}
-
-// rows of the LDS tile and its leading dimension for O outputs; 0 rows: O is too large
-void tile_shape(int O, int *rows, int *ldt, size_t *bytes)
-{
-    const int OC = O + 2;
-    *ldt = OC | 1;   // odd: the 32 rows of one column fall on distinct banks
-    const size_t fixed = (size_t)OC * 8 + kChunk * 8 + (kChunk + 1) * 4 + kChunk * 4 + kChunk;
-    const size_t per_row = (size_t)*ldt * 8;
-    size_t r = (kMaxLds - fixed) / per_row;
-    *rows = (int)(r < (size_t)kTileRows ? r : (size_t)kTileRows);
-    *bytes = fixed + (size_t)*rows * per_row;
 }
 
 }  // namespace
@@ -532,7 +543,6 @@ extern "C" int fv3hip_forest_train_level(const fv3hip_forest_train_t *ws, int pa
     L.min_split = min_samples_split, L.min_leaf = min_samples_leaf;
     size_t lds;
     tile_shape(w.O, &L.rows, &L.ldt, &lds);
-    FV3HIP_REQUIRE(L.rows >= 1, "%d outputs do not fit the scan's LDS tile", w.O);
     const hipStream_t st = as_stream(stream);
     const int nF = L.is_final ? 1 : w.F;   // a last level needs its nodes' statistics only
     const int OC = w.O + 2;

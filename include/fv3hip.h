@@ -1281,7 +1281,11 @@ int fv3hip_train_conv_constrain(float *W, int64_t ldw, int k, int c, int f, void
  * level by level (left, right, in node order); the caller renumbers.  Every sum has a fixed order; there are no atomics on
  * floating-point values.
  * Buffer sizes, with C = fv3hip_forest_train_chunk() and chunks = ceil(n / C): k_cap >= the most open nodes of a level (at most
- * min(n_inbag, 2^max_depth)), node_cap >= the nodes of the tree (at most min(2 n_inbag - 1, 2^(max_depth + 1) - 1)). */
+ * min(n_inbag, 2^max_depth)), node_cap >= the nodes of the tree (at most min(2 n_inbag - 1, 2^(max_depth + 1) - 1)).
+ * Limits, checked by both entry points before any launch (FV3HIP_EINVAL, nothing written): n < 2^31, F <= 65535 and
+ * O <= 3821 -- one row of the scan's LDS tile, O + 2 doubles, has to fit 64 KB beside the chunk's ids and weights.
+ * A level writes its whole `level` record, the fourth entry included (1: a buffer was too small for the children), and reads
+ * nothing but the inputs, the a / b set of its parity and the tree records it wrote itself: no buffer needs to be zeroed. */
 typedef struct {
     int64_t n;               /* samples */
     int F, O;                /* features, outputs */
@@ -1299,8 +1303,8 @@ typedef struct {
     double *carry;           /* [F][chunks][O + 2] */
     int32_t *count;          /* [F][chunks] */
     double *proxy;           /* [F][n] */
-    double *best_proxy;      /* [k_cap][F] */
-    int64_t *best_pos;       /* [k_cap][F] */
+    double *best_proxy;      /* [k_cap][F]; -inf where no position of the node is admissible in the feature */
+    int64_t *best_pos;       /* [k_cap][F]; INT64_MAX there */
     int64_t *n_left, *dst_left, *dst_right;   /* [k_cap] */
     int64_t k_cap, node_cap;
     /* the tree, [node_cap] each (value: [node_cap][O]) */

@@ -44,6 +44,10 @@ CASES = [
     Case("n1000_o65_split10_half", 1000, 5, 65, max_depth=6, min_samples_split=10, max_samples=0.5, seed=8),
     Case("n1000_grid_no_bootstrap", 1000, 5, 2, bootstrap=False, grid=0.125, seed=9),
     Case("n100_o300_short_tile", 100, 3, 300, max_depth=5, seed=10),   # 302 columns: two per thread, an LDS tile of 24 rows
+    # a level of more than 1024 open nodes (asserted in test_host_forest_train_levels.py): ft_children_kernel scans in rounds of
+    # 1024 and carries the counts across them
+    Case("n4096_over_1024_open_nodes", 4096, 2, 1, bootstrap=False, seed=24, n_trees=1),
+    Case("n40_f300", 40, 300, 1, seed=12),   # more features than the 256 of one ft_count_carry_kernel block
 ]
 
 

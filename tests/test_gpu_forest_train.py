@@ -92,6 +92,26 @@ def test_all_features_constant_makes_the_root_a_leaf(device):
         assert tree["feature"].tolist() == [-2] and tree["children_left"].tolist() == [-1]
 
 
+def test_negative_and_positive_zero_are_one_value(device):
+    """A column of -0.0, +0.0 and a few other values: the zeros of either sign sort together (ties by sample index), no cut
+    falls between them, and the partition is sklearn's."""
+    X, y = _edge_data(200, 3, 2, 25)
+    rng = np.random.default_rng(25)
+    X[:, 1] = rng.choice(np.array([-1.0, -0.0, 0.0, 1.0], np.float32), size=200)
+    y[:, 0] += np.where(X[:, 1] == 0, 0.0, 2.0 * X[:, 1])
+    zeros = X[:, 1] == 0
+    assert np.signbit(X[zeros, 1]).sum() >= 20 and (~np.signbit(X[zeros, 1])).sum() >= 20
+    _, _, grown, arrays = _compare(X, y, 2, 25, dict(max_depth=5), device)
+    leaves = _leaves_on_device(arrays, X, 2, device)
+    for t, tree in enumerate(grown):
+        on_zeros = tree["feature"] == 1
+        assert on_zeros.any() and (np.abs(tree["threshold"][on_zeros]) == 0.5).all()
+        # a sample reaches the same leaf whichever sign its zero has
+        flipped = X.copy()
+        flipped[zeros, 1] = -flipped[zeros, 1]
+        np.testing.assert_array_equal(_leaves_on_device(arrays, flipped, 2, device)[t], leaves[t])
+
+
 def test_a_node_with_a_constant_target_is_a_leaf(device):
     """Integer targets: the sums are exact, so a pure node has impurity exactly 0 <= DBL_EPSILON here and in sklearn."""
     X, _ = _edge_data(300, 3, 1, 22)
