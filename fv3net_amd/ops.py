@@ -599,6 +599,13 @@ def halo_pick(rows: torch.Tensor, nbr, row, flip) -> torch.Tensor:
     dev = _require_device(rows)
     rows = rows.contiguous()
     n_local = len(nbr) // 2
+    # refused here, before anything is allocated or launched: the kernel indexes ``rows`` with these entries
+    if rows.dim() < 3 or rows.shape[1] != 4 or rows.element_size() not in (4, 8):
+        raise ValueError(f"rows must be [tile, 4, ..., n] of 4- or 8-byte words, got {tuple(rows.shape)} of {rows.dtype}")
+    if len(nbr) != 2 * n_local or len(row) != len(nbr) or len(flip) != len(nbr) or n_local > 6:
+        raise ValueError(f"nbr, row and flip must hold one entry per side of at most 6 local tiles, got {len(nbr)}, {len(row)}, {len(flip)}")
+    if any(not 0 <= int(v) < min(int(rows.shape[0]), 6) for v in nbr) or any(not 0 <= int(v) < 4 for v in row):
+        raise ValueError(f"neighbour tiles must lie in [0, {min(int(rows.shape[0]), 6)}) and their vectors in [0, 4), got {list(nbr)}, {list(row)}")
     n = int(rows.shape[-1])
     mid = tuple(rows.shape[2:-1])
     out = torch.empty((2, n_local) + mid + (n,), dtype=rows.dtype, device=dev)
