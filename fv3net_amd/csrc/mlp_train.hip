@@ -235,9 +235,12 @@ __global__ __launch_bounds__(kBlock) void train_loss_finish_kernel(const double 
 
 // torch.optim.Adam's default update (no weight decay, no amsgrad) at step t = step[0] + 1, rounded as torch's kernels round
 // it: the first moment is exp_avg.lerp_(grad, 1 - beta1) = fma(1 - beta1, g - m, m), which is beta1 m + (1 - beta1) g with one
-// rounding fewer; the second is v beta2 + ((1 - beta2) g) g; the update p - (step_size m) / (sqrt(v) / bc2_sqrt + eps)
+// rounding fewer; the second is v beta2 + ((1 - beta2) g) g; the update p - (step_size m) / (sqrt(v) / bc2_sqrt + eps).
+// DECAY: torch.optim.AdamW's decoupled weight decay first, p *= (float)(1 - lr weight_decay), one rounded product.
+template <bool DECAY>
 __global__ __launch_bounds__(kBlock) void train_adam_kernel(float *p, const float *grad, float *m, float *v, int64_t count,
-                                                             const int64_t *step, double lr, double beta1, double beta2, double eps)
+                                                             const int64_t *step, double lr, double beta1, double beta2, double eps,
+                                                             float decay)
 {
     __shared__ float consts[2];
     if (threadIdx.x == 0) {
@@ -255,7 +258,8 @@ __global__ __launch_bounds__(kBlock) void train_adam_kernel(float *p, const floa
         m[e] = mm;
         v[e] = vv;
         const float denom = sqrtf(vv) / bc2_sqrt + epsf;
-        p[e] -= step_size * mm / denom;
+        const float pe = DECAY ? p[e] * decay : p[e];
+        p[e] = pe - step_size * mm / denom;
     }
 }
 
@@ -381,8 +385,23 @@ extern "C" int fv3hip_train_adam(float *params, const float *grad, float *m, flo
     FV3HIP_REQUIRE(params && grad && m && v && step, "a buffer is null");
     FV3HIP_REQUIRE(count >= 1, "count must be positive, got %lld", (long long)count);
     FV3HIP_REQUIRE(lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0, "lr, eps >= 0 and betas in [0, 1) expected");
-    hipLaunchKernelGGL(train_adam_kernel, dim3(grid_stride_blocks(count)), dim3(kBlock), 0, as_stream(stream), params, grad, m, v, count,
-                       step, lr, beta1, beta2, eps);
+    hipLaunchKernelGGL(train_adam_kernel<false>, dim3(grid_stride_blocks(count)), dim3(kBlock), 0, as_stream(stream), params, grad, m, v,
+                       count, step, lr, beta1, beta2, eps, 1.f);
+    int rc;
+    if ((rc = check_launch("train_adam_kernel"))) return rc;
+    hipLaunchKernelGGL(train_step_advance_kernel, dim3(1), dim3(1), 0, as_stream(stream), step);
+    return check_launch("train_step_advance_kernel");
+}
+
+extern "C" int fv3hip_train_adamw(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step, double lr,
+                                  double beta1, double beta2, double eps, double weight_decay, void *stream)
+{
+    FV3HIP_REQUIRE(params && grad && m && v && step, "a buffer is null");
+    FV3HIP_REQUIRE(count >= 1, "count must be positive, got %lld", (long long)count);
+    FV3HIP_REQUIRE(lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0 && weight_decay >= 0,
+                   "lr, eps, weight_decay >= 0 and betas in [0, 1) expected");
+    hipLaunchKernelGGL(train_adam_kernel<true>, dim3(grid_stride_blocks(count)), dim3(kBlock), 0, as_stream(stream), params, grad, m, v,
+                       count, step, lr, beta1, beta2, eps, (float)(1.0 - lr * weight_decay));
     int rc;
     if ((rc = check_launch("train_adam_kernel"))) return rc;
     hipLaunchKernelGGL(train_step_advance_kernel, dim3(1), dim3(1), 0, as_stream(stream), step);

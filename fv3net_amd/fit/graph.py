@@ -386,16 +386,38 @@ def _multistep_loss(model, batch, multistep):
     return total / multistep
 
 
+_HIP_OPTIMIZER_KWARGS = ("lr", "betas", "eps", "weight_decay")
+
+
 def train_graph_model(hyperparameters: GraphHyperparameters, train_batches: Sequence[Mapping[str, Any]],
                       validation_batches: Optional[Sequence[Mapping[str, Any]]] = None,
-                      device: Optional[str] = None) -> HipGraphAutoregressor:
-    """Fit the scalers on up to ``normalization_fit_samples`` samples, train ``GraphUNetTwin`` on the normalised state with the
+                      device: Optional[str] = None, backend: Optional[str] = None) -> HipGraphAutoregressor:
+    """Fit the scalers on up to ``normalization_fit_samples`` samples, train the network on the normalised state with the
     multistep MSE and, where validation data is given, keep the weights of the epoch that validated best (train.py:65-119,
-    training_loop.py:151-198).  Batches map every state variable to ``[batch, time, tile, x, y(, z)]``."""
+    training_loop.py:151-198).  Batches map every state variable to ``[batch, time, tile, x, y(, z)]``.
+
+    ``backend``: ``"torch"`` (the default, also for ``None``) steps ``GraphUNetTwin`` through autograd and ``torch.optim``;
+    ``"hip"`` steps ``graph_train.GraphTrainer`` (this project's kernels; ``optimizer`` ``"AdamW"`` or
+    ``"Adam"`` with ``lr``, ``betas``, ``eps``, ``weight_decay``).  The scalers, the initialisation of the network on the host
+    under ``torch.manual_seed(seed)``, the ``torch.randperm`` sequence and the keep-the-best rule are one piece of code, so both
+    backends start from bitwise-equal parameters and see the same batches."""
     hp = hyperparameters
+    backend = "torch" if backend is None else backend
+    if backend not in ("torch", "hip"):
+        raise ValueError(f"backend must be 'torch' or 'hip', got {backend!r}")
     check_architecture(hp.aggregator, hp.pooling_size, hp.pooling_stride, hp.activation)
+    if backend == "hip":
+        if hp.optimizer not in ("AdamW", "Adam"):
+            raise NotImplementedError(f"optimizer {hp.optimizer!r} is not built for backend 'hip'; supported: 'AdamW', 'Adam'")
+        for key in hp.optimizer_kwargs:
+            if key not in _HIP_OPTIMIZER_KWARGS:
+                raise NotImplementedError(f"optimizer argument {key!r} is not built for backend 'hip'; supported: {_HIP_OPTIMIZER_KWARGS}")
     torch.manual_seed(hp.seed)
     dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    if backend == "hip":
+        from ..ops import _require_device
+
+        _require_device(torch.empty(1, device=dev))
     names = list(hp.state_variables)
     to_np = lambda a: np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a)
     head = {name: np.concatenate([to_np(b[name]) for b in train_batches], axis=0)[:hp.normalization_fit_samples] for name in names}
@@ -405,25 +427,46 @@ def train_graph_model(hyperparameters: GraphHyperparameters, train_batches: Sequ
     check_cube_shape(tuple(train.shape[2:]), "training data")
     if train.shape[1] < hp.multistep + 1:
         raise ValueError(f"samples of {train.shape[1]} times do not hold {hp.multistep} steps")
-    model = GraphUNetTwin(int(train.shape[-1]), hp.depth, hp.min_filters, hp.activation).to(dev)
-    opt = getattr(torch.optim, hp.optimizer)(model.parameters(), **hp.optimizer_kwargs)
+    model = GraphUNetTwin(int(train.shape[-1]), hp.depth, hp.min_filters, hp.activation)   # initialised on the host
+    to_spec = lambda state: graph_unet_spec_from_state_dict(names, state, scalers, hp.depth, hp.min_filters, hp.activation)
+    if backend == "hip":
+        from ..graph_train import GraphTrainer
+
+        trainer = GraphTrainer(to_spec(model.state_dict()), train, multistep=hp.multistep, max_batch=hp.samples_per_batch, device=dev,
+                               optimizer=hp.optimizer, **hp.optimizer_kwargs)
+        take_step = trainer.step
+        validate = lambda: trainer.validation_loss(valid)
+        snapshot = lambda: trainer.params.clone()
+        restore = lambda best: trainer.params.copy_(best)
+    else:
+        model = model.to(dev)
+        opt = getattr(torch.optim, hp.optimizer)(model.parameters(), **hp.optimizer_kwargs)
+
+        def take_step(idx):
+            opt.zero_grad()
+            loss = _multistep_loss(model, train[idx], hp.multistep)
+            loss.backward()
+            opt.step()
+
+        def validate():
+            model.eval()
+            with torch.no_grad():
+                return float(_multistep_loss(model, valid, hp.multistep))
+
+        snapshot = lambda: copy.deepcopy(model.state_dict())
+        restore = model.load_state_dict
     g = torch.Generator().manual_seed(hp.seed)
     best, best_loss = None, float("inf")
     for _ in range(hp.n_epoch):
         model.train()
         perm = torch.randperm(train.shape[0], generator=g).to(dev)
         for i in range(0, train.shape[0], hp.samples_per_batch):
-            opt.zero_grad()
-            loss = _multistep_loss(model, train[perm[i:i + hp.samples_per_batch]], hp.multistep)
-            loss.backward()
-            opt.step()
+            take_step(perm[i:i + hp.samples_per_batch])
         if valid is not None:
-            model.eval()
-            with torch.no_grad():
-                val_loss = float(_multistep_loss(model, valid, hp.multistep))
+            val_loss = validate()
             if val_loss < best_loss:
-                best_loss, best = val_loss, copy.deepcopy(model.state_dict())
+                best_loss, best = val_loss, snapshot()
     if best is not None:
-        model.load_state_dict(best)
-    spec = graph_unet_spec_from_state_dict(names, model.state_dict(), scalers, hp.depth, hp.min_filters, hp.activation)
+        restore(best)
+    spec = trainer.spec() if backend == "hip" else to_spec(model.state_dict())
     return HipGraphAutoregressor(names, spec)

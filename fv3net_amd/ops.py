@@ -1363,6 +1363,116 @@ def train_conv_constrain(w: torch.Tensor) -> torch.Tensor:
     return w
 
 
+# ---------------------------------------------------------------------------------------------
+# training the graph U-Net (csrc/graph_train.hip): the caller owns every tensor, nothing is allocated or synchronised.  A cube
+# buffer is passed as a slice (``cube._Slice``: tensor, ld, channel offset, sample stride; stride 0: densely packed cubes).
+# ---------------------------------------------------------------------------------------------
+def graph_train_chunk_cells() -> int:
+    """Cells per chunk of the graph weight gradients: a larger batch needs their workspace."""
+    return int(_lib.load().fv3hip_graph_train_chunk_cells())
+
+
+def graph_sage_backward_weight_workspace_floats(n_samples: int, n: int, c_in: int, c_out: int) -> int:
+    return int(_lib.load().fv3hip_graph_sage_backward_weight_workspace_bytes(int(n_samples), int(n), int(c_in), int(c_out))) // 4
+
+
+def graph_up2_backward_weight_workspace_floats(n_samples: int, n: int, c_in: int, c_out: int) -> int:
+    """For ``n_samples`` cubes of a layer INPUT (``low``) of ``n`` cells per edge."""
+    return int(_lib.load().fv3hip_graph_up2_backward_weight_workspace_bytes(int(n_samples), int(n), int(c_in), int(c_out))) // 4
+
+
+def _cube_slice(sl, what: str, n_samples: int, n: int, c: int):
+    """(pointer, ld, off, stride) of a slice, checked against its tensor: ``c`` channels of ``n_samples`` cubes must fit."""
+    t = sl.tensor
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32, got {t.dtype}")
+    if sl.off < 0 or sl.off + c > sl.ld:
+        raise ValueError(f"{what}: channels [{sl.off}, {sl.off + c}) do not fit a row of {sl.ld}")
+    cube = 6 * n * n * sl.ld
+    stride = sl.stride or cube
+    if stride < cube or (t.is_contiguous() and n_samples and (n_samples - 1) * stride + cube > t.numel()):
+        raise ValueError(f"{what}: {n_samples} cubes of {n} x {n} cells and {sl.ld} channels do not fit a tensor of shape {tuple(t.shape)}")
+    return ctypes.c_void_p(sl.ptr), sl.ld, sl.off, sl.stride
+
+
+def _dense_weight(t: torch.Tensor, what: str, shape) -> torch.Tensor:
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _caller_workspace(workspace: Optional[torch.Tensor]):
+    if workspace is None:
+        return None, 0
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise TypeError("workspace must be a contiguous float32 tensor")
+    return workspace, workspace.numel() * 4
+
+
+def graph_sage_backward_data(dh, w_self: torch.Tensor, w_neigh: torch.Tensor, p, p_act: int, dst, n_samples: int, n: int,
+                             c_in: int, c_out: int, accumulate: bool = False) -> None:
+    """``dst = (dh W_self^T + mean5(dh) W_neigh^T) act'(p)`` (``p``: a slice or None); ``accumulate``: added to ``dst``."""
+    dev = _require_device(dh.tensor, w_self, w_neigh, dst.tensor, *([p.tensor] if p is not None else []))
+    _dense_weight(w_self, "w_self", (c_in, c_out)), _dense_weight(w_neigh, "w_neigh", (c_in, c_out))
+    ps = _cube_slice(p, "p", n_samples, n, c_in) if p is not None else (None, 0, 0, 0)
+    _lib.call_on(dev, "fv3hip_graph_sage_backward_data", *_cube_slice(dh, "dh", n_samples, n, c_out), _ptr(w_self), _ptr(w_neigh),
+                 *ps, int(p_act), *_cube_slice(dst, "dst", n_samples, n, c_in), int(bool(accumulate)), n_samples, n, c_in, c_out,
+                 _stream(dev))
+
+
+def graph_sage_backward_weight(x, g, dw_self: torch.Tensor, dw_neigh: torch.Tensor, db: Optional[torch.Tensor], n_samples: int,
+                               n: int, c_in: int, c_out: int, workspace: Optional[torch.Tensor] = None,
+                               accumulate: bool = False) -> None:
+    """``dw_self = x^T g``, ``dw_neigh = mean5(x)^T g``, ``db = sum g`` over the cells of the batch; ``accumulate``: added."""
+    dev = _require_device(x.tensor, g.tensor, dw_self, dw_neigh, *(t for t in (db, workspace) if t is not None))
+    _dense_weight(dw_self, "dw_self", (c_in, c_out)), _dense_weight(dw_neigh, "dw_neigh", (c_in, c_out))
+    ws, ws_bytes = _caller_workspace(workspace)
+    _lib.call_on(dev, "fv3hip_graph_sage_backward_weight", *_cube_slice(x, "x", n_samples, n, c_in),
+                 *_cube_slice(g, "g", n_samples, n, c_out), _ptr(dw_self), _ptr(dw_neigh), _ptr(_vec(db, "db", c_out)),
+                 int(bool(accumulate)), _ptr(ws), ws_bytes, n_samples, n, c_in, c_out, _stream(dev))
+
+
+def graph_up2_backward_data(dcat, w: torch.Tensor, p, p_act: int, dst, n_samples: int, n: int, c_in: int, c_out: int) -> None:
+    """``dst[i][j][ci] = (sum dcat[2i+di][2j+dj][co] w[ci][di][dj][co]) act'(p)``; ``n``: the edge of ``dst``."""
+    dev = _require_device(dcat.tensor, w, dst.tensor, *([p.tensor] if p is not None else []))
+    _dense_weight(w, "w", (c_in, 2, 2, c_out))
+    ps = _cube_slice(p, "p", n_samples, n, c_in)[:3] if p is not None else (None, 0, 0)
+    _lib.call_on(dev, "fv3hip_graph_up2_backward_data", *_cube_slice(dcat, "dcat", n_samples, 2 * n, c_out)[:3], _ptr(w), *ps,
+                 int(p_act), *_cube_slice(dst, "dst", n_samples, n, c_in)[:3], n_samples, n, c_in, c_out, _stream(dev))
+
+
+def graph_up2_backward_weight(low, dcat, dw: torch.Tensor, db: Optional[torch.Tensor], n_samples: int, n: int, c_in: int,
+                              c_out: int, workspace: torch.Tensor, accumulate: bool = False) -> None:
+    """``dw[ci][di][dj][co] = sum low[i][j][ci] dcat[2i+di][2j+dj][co]``, ``db = sum dcat``; ``n``: the edge of ``low``."""
+    dev = _require_device(low.tensor, dcat.tensor, dw, workspace, *([db] if db is not None else []))
+    _dense_weight(dw, "dw", (c_in, 2, 2, c_out))
+    ws, ws_bytes = _caller_workspace(workspace)
+    _lib.call_on(dev, "fv3hip_graph_up2_backward_weight", *_cube_slice(low, "low", n_samples, n, c_in)[:3],
+                 *_cube_slice(dcat, "dcat", n_samples, 2 * n, c_out)[:3], _ptr(dw), _ptr(_vec(db, "db", c_out)),
+                 int(bool(accumulate)), _ptr(ws), ws_bytes, n_samples, n, c_in, c_out, _stream(dev))
+
+
+def graph_pool2_backward(dpool, p, p_act: int, dst, n_samples: int, n: int, c: int) -> None:
+    """``dst = (dst + 0.25 dpool[x / 2][y / 2]) act'(p)`` in place; ``n``: the edge of ``dst``."""
+    dev = _require_device(dpool.tensor, dst.tensor, *([p.tensor] if p is not None else []))
+    ps = _cube_slice(p, "p", n_samples, n, c)[:3] if p is not None else (None, 0, 0)
+    _lib.call_on(dev, "fv3hip_graph_pool2_backward", *_cube_slice(dpool, "dpool", n_samples, n // 2, c)[:3], *ps, int(p_act),
+                 *_cube_slice(dst, "dst", n_samples, n, c)[:3], n_samples, n, c, _stream(dev))
+
+
+def train_adamw(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor, lr: float = 1e-3,
+                beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 1e-2) -> None:
+    """``torch.optim.AdamW``'s default update of one flat float32 buffer: ``p *= 1 - lr weight_decay``, then ``train_adam``."""
+    dev = _require_device(params, grad, m, v, step)
+    count = int(params.numel())
+    for t, name in ((params, "params"), (grad, "grad"), (m, "m"), (v, "v")):
+        _vec(t, name, count)
+    if step.dtype != torch.int64 or step.numel() != 1:
+        raise TypeError("step must be an int64 tensor of one element")
+    _lib.call_on(dev, "fv3hip_train_adamw", _ptr(params), _ptr(grad), _ptr(m), _ptr(v), count, _ptr(step), float(lr), float(beta1),
+                 float(beta2), float(eps), float(weight_decay), _stream(dev))
+
+
 class HipTimer:
     """HIP events recorded on torch's current stream (used by bench.py)."""
 

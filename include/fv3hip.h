@@ -1263,6 +1263,59 @@ int fv3hip_train_conv_backward_weight(const float *A, int64_t a_ss, int64_t a_sx
                                       void *stream);
 int fv3hip_train_conv_constrain(float *W, int64_t ldw, int k, int c, int f, void *stream);
 
+/* ---- training the graph U-Net (fv3fit's "graph" training function, pytorch/graph/train.py:65-119, training_loop.py:75-198;
+ * DESIGN.md section 24): the backward of fv3hip_graph_sage / _up2 / _pool2 and AdamW.  Stateless like fv3hip_graph_* and
+ * fv3hip_train_*: the caller owns every DEVICE pointer, the workspace included; nothing is allocated or synchronised; all
+ * arguments are checked on the host before any HIP call; a layer that would read what it writes gives FV3HIP_EINVAL, an unknown
+ * activation code FV3HIP_EUNSUPPORTED.  Activations and their gradients are float32, channel-last, addressed as (base, ld,
+ * channel offset, sample stride; 0: densely packed cubes) as in fv3hip_graph_sage; weights and their gradients are dense
+ * [c_in][c_out] (up2: [c_in][2][2][c_out]).  Every contraction runs on the exact-float32 MFMA in a fixed order; there are no
+ * atomics, so results are bitwise reproducible and depend on the shapes only.  n is the edge of the layer's INPUT cube (up2: of
+ * `low`; its output and dcat have 2 n).  act'(P) is taken from the stored post-activation P that fed the layer, with its
+ * activation code p_act: relu [P > 0] (relu'(0) = 0 as in torch; a NaN masks too), tanh 1 - P^2, linear 1; P null: no mask.
+ *   fv3hip_graph_sage_backward_data    dst = (dH W_self^T + mean5(dH) W_neigh^T) act'(P), mean5 as the forward takes it (the
+ *                                      five-point graph is symmetric, so mean5 is its own adjoint); dH is the masked gradient
+ *                                      of the layer's output.  accumulate != 0: dst = dst + that (the rollout's state gradient).
+ *   fv3hip_graph_sage_backward_weight  dW_self = X^T G, dW_neigh = mean5(X)^T G, db = sum over the cells of G (null: skipped),
+ *                                      summed over the S 6 n^2 cells of the batch in memory order, cut into chunks of
+ *                                      fv3hip_graph_train_chunk_cells() (512): one chunk writes the results directly; more
+ *                                      write each chunk's partial to `workspace` (at least
+ *                                      fv3hip_graph_sage_backward_weight_workspace_bytes(S, n, c_in, c_out) bytes) and a second
+ *                                      kernel adds the partials in ascending chunk order.  accumulate != 0: every result is
+ *                                      old + sum (the steps of a multistep rollout, in the order of the calls).
+ *                                      The three results and the workspace must not overlap x, g or each other.
+ *   fv3hip_graph_up2_backward_data     dst[i][j][ci] = (sum_{di,dj,co} dcat[2i+di][2j+dj][co] w[ci][di][dj][co]) act'(P)
+ *   fv3hip_graph_up2_backward_weight   dW[ci][di][dj][co] = sum_{s,t,i,j} low[i][j][ci] dcat[2i+di][2j+dj][co]; db[co] = sum of
+ *                                      dcat = the four (di, dj) column sums added in order.  Always through `workspace`
+ *                                      (fv3hip_graph_up2_backward_weight_workspace_bytes) and the second kernel.
+ *   fv3hip_graph_pool2_backward        dst = (dst + 0.25f dpool[x / 2][y / 2]) act'(P), in place: the skip connection's part is
+ *                                      in dst first, the pool's is added second.
+ *   fv3hip_train_adamw                 torch.optim.AdamW's default update: p = p * (float)(1 - lr weight_decay), then
+ *                                      fv3hip_train_adam's update with the same device step counter.
+ */
+int fv3hip_graph_train_chunk_cells(void);
+size_t fv3hip_graph_sage_backward_weight_workspace_bytes(int64_t n_samples, int n, int c_in, int c_out);
+size_t fv3hip_graph_up2_backward_weight_workspace_bytes(int64_t n_samples, int n, int c_in, int c_out);
+int fv3hip_graph_sage_backward_data(const float *dh, int64_t dh_ld, int64_t dh_off, int64_t dh_sample_stride, const float *w_self,
+                                    const float *w_neigh, const float *p, int64_t p_ld, int64_t p_off, int64_t p_sample_stride,
+                                    int p_act, float *dst, int64_t dst_ld, int64_t dst_off, int64_t dst_sample_stride,
+                                    int accumulate, int64_t n_samples, int n, int c_in, int c_out, void *stream);
+int fv3hip_graph_sage_backward_weight(const float *x, int64_t x_ld, int64_t x_off, int64_t x_sample_stride, const float *g,
+                                      int64_t g_ld, int64_t g_off, int64_t g_sample_stride, float *dw_self, float *dw_neigh,
+                                      float *db, int accumulate, float *workspace, size_t workspace_bytes, int64_t n_samples,
+                                      int n, int c_in, int c_out, void *stream);
+int fv3hip_graph_up2_backward_data(const float *dcat, int64_t dcat_ld, int64_t dcat_off, const float *w, const float *p,
+                                   int64_t p_ld, int64_t p_off, int p_act, float *dst, int64_t dst_ld, int64_t dst_off,
+                                   int64_t n_samples, int n, int c_in, int c_out, void *stream);
+int fv3hip_graph_up2_backward_weight(const float *low, int64_t low_ld, int64_t low_off, const float *dcat, int64_t dcat_ld,
+                                     int64_t dcat_off, float *dw, float *db, int accumulate, float *workspace,
+                                     size_t workspace_bytes, int64_t n_samples, int n, int c_in, int c_out, void *stream);
+int fv3hip_graph_pool2_backward(const float *dpool, int64_t dpool_ld, int64_t dpool_off, const float *p, int64_t p_ld,
+                                int64_t p_off, int p_act, float *dst, int64_t dst_ld, int64_t dst_off, int64_t n_samples, int n,
+                                int c, void *stream);
+int fv3hip_train_adamw(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step, double lr, double beta1,
+                       double beta2, double eps, double weight_decay, void *stream);
+
 /* ---- training random forests (fv3fit's "sklearn_random_forest"; sklearn's RandomForestRegressor.fit: squared error, exact
  * best split, all features).  Stateless like fv3hip_train_*: the caller owns every DEVICE buffer below, nothing is allocated or
  * synchronised, the arguments are checked on the host before any HIP call.  One tree grows level by level:
