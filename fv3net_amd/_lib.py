@@ -420,6 +420,10 @@ SIGNATURES = {
                                       c_void_p]),
     "fv3hip_train_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_double, c_double, c_double, c_double,
                                   c_void_p]),
+    "fv3hip_train_precip_loss_grad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                              c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                              c_int, c_int, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "fv3hip_train_conv_chunk_pixels": (c_int, []),
     "fv3hip_train_conv_backward_weight_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int, c_int]),
     "fv3hip_train_conv_forward": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,

@@ -23,7 +23,7 @@ constexpr int kBlock = 256;
 constexpr int kBM = 64, kBN = 64, kBK = 16, kBKLog2 = 4;
 constexpr int kFill = kBM * kBK / kBlock;   // panel elements per thread and chunk
 constexpr int kChunkRows = 512;       // fv3hip_train_chunk_rows()
-constexpr int kLossBlocks = 1024;     // most blocks of train_mse_grad_kernel = doubles of its workspace
+constexpr int kLossBlocks = 1024;     // most blocks of the two loss kernels = doubles of their workspace
 constexpr int kKP = kBK + 1;          // row stride of a panel stored [tile index][k]: odd, so that 32 tile indices hit 32 banks
 constexpr int kMP = 96;               // row stride of a panel stored [k][tile index]: 32 mod 64 banks keeps the two lane halves apart
 constexpr int kPanel = kBK * kMP;     // floats per panel (>= 64 * kKP)
@@ -233,6 +233,105 @@ __global__ __launch_bounds__(kBlock) void train_loss_finish_kernel(const double 
     if (tid == 0) loss[0] = part[0];
 }
 
+// The loss behind the closure of the precipitative model (fv3fit's "precipitative" training function, precipitative.py:181-279;
+// DESIGN.md section 25) and its gradient with respect to the raw output yhat = [ t (nz) | q (nz) | dead (has_dead) | cp (nz) ] of the
+// concatenated head layer.  One wave per batch row, four rows per block, lane = level (mod 64): every load and store along the
+// features is coalesced.  Pass 1 forms the products cp[k] delp[k] 64 levels at a time, parks them in the wave's strip of LDS and
+// every lane adds the strip in ascending order into one float32 accumulator from +0 -- the predictor's order
+// (precip_closure_kernel in fit.hip), so the integral is the same bits, and every lane holds it without a broadcast.  Pass 2
+// reads the row again (it is in L1 / L2) and writes the gradient, which needs the finished integral in every level of cp.
+struct PrecipLossArgs {
+    const float *yhat, *scale1, *center1, *scale2, *center2, *inv1, *inv2, *delp, *pp, *t1, *t2, *t3;
+    const int64_t *idx;
+    float *dy, *dq1, *dq2, *precip;
+    double *partial;
+    int64_t ldy, ldd, ldt, lddy, rows, n;
+    int nz, couple, has_dead;
+    float inv3, l1, l2, w12, w3;
+};
+
+constexpr int kWave = 64, kRowsPerBlock = kBlock / kWave;
+
+// the gradient of (l1 |x| + l2 x^2) / n, sign(0) = 0 (a NaN stays one)
+__device__ __forceinline__ float precip_reg_grad(float x, float l1, float l2, float n)
+{
+    const float s = x > 0.f ? 1.f : (x < 0.f ? -1.f : x);
+    return (l1 * s + 2.f * l2 * x) / n;
+}
+
+__global__ __launch_bounds__(kBlock) void train_precip_loss_grad_kernel(const PrecipLossArgs a)
+{
+    __shared__ double part[kBlock];
+    __shared__ float strips[kBlock];
+    const float c_heat = (float)(-2.5e6 / 1004.6);  // -LV / CPD, as in fit.hip
+    const float c_g = (float)(-1.0 / 9.80665);      // -1 / g
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    float *strip = strips + wave * kWave;
+    const int nz = a.nz, cp0 = 2 * nz + a.has_dead;
+    const bool reg = a.l1 != 0.f || a.l2 != 0.f;
+    const float nf = (float)a.n;
+    const double inv_n = 1.0 / (double)a.n;
+    double sum = 0.0;
+    for (int64_t row0 = (int64_t)blockIdx.x * kRowsPerBlock; row0 < a.n; row0 += (int64_t)gridDim.x * kRowsPerBlock) {
+        const int64_t row = row0 + wave;
+        const bool live = row < a.n;   // (the block's waves walk the same number of rows: the barriers below are uniform)
+        const int64_t r = live ? (a.idx ? a.idx[row] : row) : -1;
+        const bool in = r >= 0 && r < a.rows;
+        const float *y = a.yhat + (live ? row : 0) * a.ldy;
+        const float *d = a.delp + (in ? r : 0) * a.ldd;
+        float acc = 0.0f;
+        for (int k0 = 0; k0 < nz; k0 += kWave) {
+            const int k = k0 + lane;
+            float p = 0.f;
+            if (live && k < nz) p = (y[cp0 + k] * a.scale2[k] + a.center2[k]) * (in ? d[k] : 0.f);
+            __syncthreads();   // the strip's last reader is done
+            strip[lane] = p;
+            __syncthreads();
+            const int m = nz - k0 < kWave ? nz - k0 : kWave;
+            for (int j = 0; j < m; ++j) acc = acc + strip[j];
+        }
+        if (!live) continue;
+        const float precip = (in ? a.pp[r] : 0.f) + c_g * acc;
+        const float e3 = precip - (in ? a.t3[r] : NAN);
+        const float g3 = 2.f * e3 * a.inv3 * a.w3;
+        float *dy = a.dy + row * a.lddy;
+        if (lane == 0) {
+            sum += (double)e3 * (double)e3 * (double)a.inv3 * (double)a.w3;
+            if (a.precip) a.precip[row] = precip;
+            if (a.has_dead) {
+                const float x = y[2 * nz];
+                dy[2 * nz] = reg ? precip_reg_grad(x, a.l1, a.l2, nf) : 0.f;
+                if (reg) sum += ((double)a.l1 * fabs((double)x) + (double)a.l2 * (double)x * (double)x) * inv_n;
+            }
+        }
+        const float *t1 = a.t1 + (in ? r : 0) * a.ldt, *t2 = a.t2 + (in ? r : 0) * a.ldt;
+        for (int k = lane; k < nz; k += kWave) {
+            const float th = y[k], qh = y[nz + k], s1 = a.scale1[k], s2 = a.scale2[k], c2 = a.center2[k];
+            const float t = th * s1 + a.center1[k], q = qh * s2 + c2, cp = y[cp0 + k] * s2 + c2;
+            const float dq1 = a.couple ? t + c_heat * cp : t, dq2 = a.couple ? q + cp : q;
+            const float e1 = dq1 - (in ? t1[k] : NAN), e2 = dq2 - (in ? t2[k] : NAN);
+            const float inv1 = a.inv1[k], inv2 = a.inv2[k];
+            const float g1 = 2.f * e1 * inv1 * a.w12, g2 = 2.f * e2 * inv2 * a.w12;
+            float dt = g1 * s1, dq = g2 * s2;
+            if (reg) {
+                dt = dt + precip_reg_grad(th, a.l1, a.l2, nf);
+                dq = dq + precip_reg_grad(qh, a.l1, a.l2, nf);
+                sum += ((double)a.l1 * (fabs((double)th) + fabs((double)qh)) +
+                        (double)a.l2 * ((double)th * (double)th + (double)qh * (double)qh)) * inv_n;
+            }
+            dy[k] = dt;
+            dy[nz + k] = dq;
+            dy[cp0 + k] = ((a.couple ? c_heat * g1 + g2 : 0.f) + (c_g * (in ? d[k] : 0.f)) * g3) * s2;
+            sum += (double)e1 * (double)e1 * (double)inv1 * (double)a.w12 + (double)e2 * (double)e2 * (double)inv2 * (double)a.w12;
+            if (a.dq1) a.dq1[row * nz + k] = dq1;
+            if (a.dq2) a.dq2[row * nz + k] = dq2;
+        }
+    }
+    part[tid] = sum;
+    block_tree_sum(part, tid);
+    if (tid == 0) a.partial[blockIdx.x] = part[0];
+}
+
 // torch.optim.Adam's default update (no weight decay, no amsgrad) at step t = step[0] + 1, rounded as torch's kernels round
 // it: the first moment is exp_avg.lerp_(grad, 1 - beta1) = fma(1 - beta1, g - m, m), which is beta1 m + (1 - beta1) g with one
 // rounding fewer; the second is v beta2 + ((1 - beta2) g) g; the update p - (step_size m) / (sqrt(v) / bc2_sqrt + eps).
@@ -375,6 +474,41 @@ extern "C" int fv3hip_train_mse_grad(const float *yhat, int64_t ldy, const float
     const int blocks = (int)(want < kLossBlocks ? want : kLossBlocks);
     hipLaunchKernelGGL(train_mse_grad_kernel, dim3(blocks), dim3(kBlock), 0, as_stream(stream), a);
     if ((rc = check_launch("train_mse_grad_kernel"))) return rc;
+    hipLaunchKernelGGL(train_loss_finish_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), loss_workspace, blocks, loss);
+    return check_launch("train_loss_finish_kernel");
+}
+
+extern "C" int fv3hip_train_precip_loss_grad(const float *yhat, int64_t ldy, const float *scale1, const float *center1, const float *scale2,
+                                             const float *center2, const float *inv_cstd2_1, const float *inv_cstd2_2, float inv_cstd2_3,
+                                             const float *delp, int64_t ldd, const float *physics_precip, const float *T1, const float *T2,
+                                             int64_t ldt, const float *T3, int64_t rows, const int64_t *idx, int couple, int has_dead,
+                                             float l1, float l2, float *dY, int64_t lddy, double *loss, double *loss_workspace, float *dq1,
+                                             float *dq2, float *precip, int64_t n, int nz, void *stream)
+{
+    int rc;
+    if ((rc = check_layer(n, 1, nz))) return rc;
+    FV3HIP_REQUIRE(has_dead == 0 || has_dead == 1, "has_dead must be 0 or 1, got %d", has_dead);
+    FV3HIP_REQUIRE(couple == 0 || couple == 1, "couple must be 0 or 1, got %d", couple);
+    const int f = 3 * nz + has_dead;
+    if ((rc = check_ld("yhat", yhat, ldy, f)) || (rc = check_ld("dY", dY, lddy, f)) || (rc = check_ld("delp", delp, ldd, nz)) ||
+        (rc = check_ld("T1", T1, ldt, nz)) || (rc = check_ld("T2", T2, ldt, nz)))
+        return rc;
+    FV3HIP_REQUIRE(scale1 && center1 && scale2 && center2 && inv_cstd2_1 && inv_cstd2_2, "a per-level array is null");
+    FV3HIP_REQUIRE(physics_precip && T3, "physics_precip or T3 is null");
+    FV3HIP_REQUIRE(loss && loss_workspace, "loss or its workspace is null");
+    FV3HIP_REQUIRE(rows >= 1 && (idx || rows >= n), "the resident arrays have %lld rows, the batch %lld", (long long)rows, (long long)n);
+    FV3HIP_REQUIRE(l1 >= 0.f && l2 >= 0.f && std::isfinite(l1) && std::isfinite(l2), "l1 and l2 must be finite and >= 0, got %g, %g",
+                   (double)l1, (double)l2);
+    PrecipLossArgs a{};
+    a.yhat = yhat, a.scale1 = scale1, a.center1 = center1, a.scale2 = scale2, a.center2 = center2, a.inv1 = inv_cstd2_1, a.inv2 = inv_cstd2_2;
+    a.delp = delp, a.pp = physics_precip, a.t1 = T1, a.t2 = T2, a.t3 = T3, a.idx = idx, a.dy = dY, a.dq1 = dq1, a.dq2 = dq2, a.precip = precip;
+    a.partial = loss_workspace, a.ldy = ldy, a.ldd = ldd, a.ldt = ldt, a.lddy = lddy, a.rows = rows, a.n = n;
+    a.nz = nz, a.couple = couple, a.has_dead = has_dead, a.inv3 = inv_cstd2_3, a.l1 = l1, a.l2 = l2;
+    a.w12 = (float)(1.0 / ((double)n * (double)nz)), a.w3 = (float)(1.0 / (double)n);
+    const int64_t want = ceil_div(n, kRowsPerBlock);
+    const int blocks = (int)(want < kLossBlocks ? want : kLossBlocks);
+    hipLaunchKernelGGL(train_precip_loss_grad_kernel, dim3(blocks), dim3(kBlock), 0, as_stream(stream), a);
+    if ((rc = check_launch("train_precip_loss_grad_kernel"))) return rc;
     hipLaunchKernelGGL(train_loss_finish_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), loss_workspace, blocks, loss);
     return check_launch("train_loss_finish_kernel");
 }

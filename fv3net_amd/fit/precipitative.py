@@ -15,10 +15,11 @@ never reaches an output (``unpacked_output[2]`` is unused) and is not stored.
   on the same stream, in place over the residual heads.  The sum's order is fixed (float32, ascending levels, products
   rounded), so a numpy float32 loop reproduces it bit for bit.
 * ``precipitative_spec_from_arrays``: the exporter's entry.
-* ``train_precipitative_model``: the offline step in PyTorch (the only place PyTorch computes anything).
+* ``train_precipitative_model``: the offline step, through PyTorch or (``backend="hip"``) through the project's own kernels with
+  the loss behind the closure in one launch (``fv3hip_train_precip_loss_grad``).
 """
 import dataclasses
-from typing import Dict, Hashable, Iterable, List, Mapping, Optional, Sequence
+from typing import Dict, Hashable, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -29,6 +30,7 @@ from ..mlp import MlpModel, MlpSpec
 from ..xr_compat import DataArray, Dataset, from_compat, to_compat
 from . import io
 from .dense import _stack_for_training, read_artifact, spec_from_arrays, write_artifact
+from .input_sensitivity import InputSensitivity, nondimensionalize_jacobians
 from .predictor import Predictor
 from .stacking import column_sources, match_prediction_to_input_coords
 
@@ -77,6 +79,7 @@ class HipPrecipitativeModel(Predictor):
         self._n_halo = n_halo
         self._unstacked_dims = list(unstacked_dims) if unstacked_dims is not None else []
         self._model: Optional[MlpModel] = None  # created on first predict (needs the GPU)
+        self._trainer = None                    # created on first input_sensitivity
 
     @property
     def model(self) -> MlpModel:
@@ -110,6 +113,35 @@ class HipPrecipitativeModel(Predictor):
             result[name] = DataArray(shaped[name], dims=dims_of[name])
         return from_compat(match_prediction_to_input_coords(x, result), X)
 
+    # -- sensitivity ------------------------------------------------------------------------
+    def _head_jacobians(self, profiles: Mapping[str, np.ndarray]):
+        """The device part: the three heads' Jacobians and the column-precipitation head's value at the profiles."""
+        from ..train import DenseTrainer, predict_graph_jacobians
+
+        if self._trainer is None:
+            self._trainer = DenseTrainer.from_spec(self.spec, compute_device())
+        values: Dict[str, np.ndarray] = {}
+        jac = predict_graph_jacobians(self.spec, profiles, trainer=self._trainer, values=values)
+        return jac, values[COLUMN_PRECIP_NAME]
+
+    def jacobians(self, profiles: Mapping[str, np.ndarray]):
+        """``{output: {input: d output / d input}}`` of the predict graph at one profile per input: the heads' Jacobians from the
+        device (``fv3net_amd.train.predict_graph_jacobians``), the closure composed on the host (``compose_closure_jacobians``)."""
+        head_jac, cp = self._head_jacobians(profiles)
+        return compose_closure_jacobians(head_jac, cp, profiles[DELP_NAME], self.couple_precip_to_dQ1_dQ2)
+
+    def input_sensitivity(self, stacked_sample) -> InputSensitivity:
+        """The Jacobian of every output with respect to every input at the sample-mean profile, times ``std(input)`` along the
+        columns and over ``std(output)`` along the rows (pure_keras.py:127-145), as ``HipDenseModel.input_sensitivity``."""
+        sample = to_compat(stacked_sample)
+        data = {}
+        for var in list(self.input_variables) + list(self.output_variables):
+            values = sample[var].values
+            data[var] = values.reshape(-1, 1) if values.ndim == 1 else values
+        jac = self.jacobians({name: data[name].mean(axis=0) for name in self.input_variables})
+        std = {name: np.std(values, axis=0) for name, values in data.items()}
+        return InputSensitivity(jacobians=nondimensionalize_jacobians(jac, std))
+
     # -- serialisation ----------------------------------------------------------------------
     def dump(self, path: str) -> None:
         write_artifact(path, self.spec, {"input_variables": list(self.input_variables), "output_variables": list(self.output_variables),
@@ -122,6 +154,34 @@ class HipPrecipitativeModel(Predictor):
         return cls(config["input_variables"], config["output_variables"], spec,
                    couple_precip_to_dQ1_dQ2=config["couple_precip_to_dQ1_dQ2"],
                    unstacked_dims=config.get("unstacked_dims", None), n_halo=config.get("n_halo", 0))
+
+
+def compose_closure_jacobians(head_jacobians: Mapping[str, Mapping[str, np.ndarray]], col_precip: np.ndarray, delp: np.ndarray,
+                              couple: bool) -> Dict[str, Dict[str, np.ndarray]]:
+    """The closure applied to the Jacobians of the three heads (``{head: {source: [nz, len(source)]}}``), in float64:
+
+        J[dQ1] = J_t + c_heat J_cp,  J[dQ2] = J_q + J_cp       (under ``couple``; else the heads' own)
+        J[total_precipitation_rate][src] = c_g sum_k delp[k] J_cp[k, :]   (+ c_g cp[k] in column k of the thickness, + 1 for physics_precip)
+
+    with the float32 constants of the graph, ``delp`` the profile cast to float32 as ``predict`` casts it and ``col_precip`` the
+    column-precipitation head's value at the profile."""
+    c_heat, c_g = np.float64(np.float32(-LV / CPD)), np.float64(np.float32(-1.0 / GRAVITY))
+    d = np.atleast_1d(np.asarray(delp)).astype(np.float32).astype(np.float64)
+    cp = np.asarray(col_precip, np.float64)
+    j_cp = {src: np.asarray(j, np.float64) for src, j in head_jacobians[COLUMN_PRECIP_NAME].items()}
+    out: Dict[str, Dict[str, np.ndarray]] = {T_TENDENCY_NAME: {}, Q_TENDENCY_NAME: {}, PRECIP_NAME: {}}
+    for src, jc in j_cp.items():
+        j_t = np.asarray(head_jacobians[T_TENDENCY_NAME][src], np.float64)
+        j_q = np.asarray(head_jacobians[Q_TENDENCY_NAME][src], np.float64)
+        out[T_TENDENCY_NAME][src] = j_t + c_heat * jc if couple else j_t.copy()
+        out[Q_TENDENCY_NAME][src] = j_q + jc if couple else j_q.copy()
+        row = c_g * (d[None, :] @ jc)
+        if src == DELP_NAME:
+            row = row + c_g * cp[None, :]
+        elif src == PHYS_PRECIP_NAME:
+            row = row + 1.0
+        out[PRECIP_NAME][src] = row
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -157,7 +217,7 @@ def precipitative_spec_from_arrays(
 
 
 # ---------------------------------------------------------------------------------------------
-# offline training (PyTorch-ROCm)
+# offline training (PyTorch-ROCm, or the project's own kernels with backend="hip")
 # ---------------------------------------------------------------------------------------------
 @dataclasses.dataclass
 class PrecipitativeHyperparameters:
@@ -174,6 +234,8 @@ class PrecipitativeHyperparameters:
     couple_precip_to_dQ1_dQ2: bool = True
     unstacked_dims: Sequence[str] = ("z",)
     seed: int = 0
+    # residual_regularizer_config (:124-126) as (name, kwargs): "none", "l1", "l2" or "l1_l2" with Keras's kwargs
+    residual_regularizer: Optional[Tuple[str, Mapping]] = None
 
     @property
     def input_variables(self) -> List[str]:
@@ -184,19 +246,34 @@ class PrecipitativeHyperparameters:
         return list(OUTPUT_VARIABLES)
 
 
-def train_precipitative_model(hyperparameters: PrecipitativeHyperparameters, train_batches: Sequence[Dataset],
-                              device: Optional[str] = None) -> HipPrecipitativeModel:
-    """Fit normalisation on up to ``normalization_fit_samples`` samples and train the graph of precipitative.py:181-279
-    with Adam: ``Dense(width, relu) x (depth-1)``, four linear heads (the one-feature head for total_precipitation_rate
-    reaches no output, receives no gradient and is dropped), the closure from the unclipped ``delp`` inside the training
-    graph, and the std-scaled MSE summed over ``dQ1``, ``dQ2`` and ``total_precipitation_rate`` as ``train_dense_model``
-    computes it.  ``residual_regularizer_config`` and the callbacks of the reference are out of scope."""
-    hp = hyperparameters
+@dataclasses.dataclass
+class _PrecipitativeTraining:
+    """What both backends of ``train_precipitative_model`` start from: the fitted normalisation, the normalised inputs, the raw
+    thickness, the targets and the freshly initialised layers (created on the host, so that the start does not depend on the
+    device).  ``heads``: dQ1, dQ2, the dead one-feature head, the column precipitation -- the order the initialiser draws in."""
+
+    xin: np.ndarray                 # [n, K] normalised, clipped inputs
+    delp: np.ndarray                # [n, nz] unclipped (:246)
+    physics_precip: np.ndarray      # [n]
+    y: List[np.ndarray]             # dQ1 [n, nz], dQ2 [n, nz], total_precipitation_rate [n, 1]
+    x_mean: List[np.ndarray]
+    x_std: List[np.ndarray]
+    y_mean: List[np.ndarray]
+    y_std: List[np.ndarray]
+    loss_std: List[np.ndarray]
+    trunk: torch.nn.Sequential
+    heads: torch.nn.ModuleList
+    l1: float
+    l2: float
+    has_dead: bool
+
+
+def _prepare_precipitative_training(hp: PrecipitativeHyperparameters, train_batches: Sequence[Dataset]) -> _PrecipitativeTraining:
     unknown = [name for name in hp.clip if name not in hp.input_variables]
     if unknown:
         raise ValueError(f"only inputs can be clipped (the predict graph masks no output level), got {unknown}")
+    l1, l2, has_dead = regularizer_coefficients(hp.residual_regularizer)
     torch.manual_seed(hp.seed)
-    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
     names_in, names_out = hp.input_variables, hp.output_variables
     X = _stack_for_training(train_batches, names_in, hp.unstacked_dims)
     y = _stack_for_training(train_batches, names_out, hp.unstacked_dims)
@@ -209,9 +286,7 @@ def train_precipitative_model(hyperparameters: PrecipitativeHyperparameters, tra
     loss_std = [np.std(a[:nfit], axis=0, dtype=np.float32) for a in y]
 
     eps = np.float32(1e-7)
-    xin = torch.from_numpy(np.concatenate([(a - m) / (s + eps) for a, m, s in zip(Xc, x_mean, x_std)], axis=1)).to(dev)
-    delp = torch.from_numpy(X[names_in.index(DELP_NAME)]).to(dev)            # unclipped (:246)
-    physics_precip = torch.from_numpy(X[names_in.index(PHYS_PRECIP_NAME)][:, 0]).to(dev)
+    xin = np.concatenate([(a - m) / (s + eps) for a, m, s in zip(Xc, x_mean, x_std)], axis=1)
     layers: List[torch.nn.Module] = []
     fan = xin.shape[1]
     for _ in range(hp.depth - 1):
@@ -220,19 +295,29 @@ def train_precipitative_model(hyperparameters: PrecipitativeHyperparameters, tra
         torch.nn.init.zeros_(lin.bias)
         layers += [lin, torch.nn.ReLU()]
         fan = hp.width
-    trunk = torch.nn.Sequential(*layers).to(dev)
+    trunk = torch.nn.Sequential(*layers)
     heads = torch.nn.ModuleList()
     for nfeat in [a.shape[1] for a in y] + [y[1].shape[1]]:   # dQ1, dQ2, the dead one-feature head, column precipitation
         lin = torch.nn.Linear(fan, nfeat)
         torch.nn.init.xavier_uniform_(lin.weight)
         torch.nn.init.zeros_(lin.bias)
         heads.append(lin)
-    heads = heads.to(dev)
-    targets = [torch.from_numpy(a).to(dev) for a in y]
+    return _PrecipitativeTraining(xin=xin, delp=X[names_in.index(DELP_NAME)], physics_precip=X[names_in.index(PHYS_PRECIP_NAME)][:, 0],
+                                  y=y, x_mean=x_mean, x_std=x_std, y_mean=y_mean, y_std=y_std, loss_std=loss_std, trunk=trunk,
+                                  heads=heads, l1=l1, l2=l2, has_dead=has_dead)
+
+
+def _train_torch(hp: PrecipitativeHyperparameters, prep: _PrecipitativeTraining, dev: torch.device):
+    """Adam through ``torch.nn.Linear`` and autograd; returns the four weight lists (the heads: dQ1, dQ2, column precipitation)."""
+    xin = torch.from_numpy(prep.xin).to(dev)
+    delp = torch.from_numpy(prep.delp).to(dev)
+    physics_precip = torch.from_numpy(prep.physics_precip).to(dev)
+    trunk, heads = prep.trunk.to(dev), prep.heads.to(dev)
+    targets = [torch.from_numpy(a).to(dev) for a in prep.y]
     targets[2] = targets[2][:, 0]
-    t_mean = [torch.from_numpy(m).to(dev) for m in y_mean]
-    t_std = [torch.from_numpy(s).to(dev) for s in y_std]
-    t_lstd = [torch.from_numpy(np.maximum(s, 1e-12)).to(dev) for s in loss_std]
+    t_mean = [torch.from_numpy(m).to(dev) for m in prep.y_mean]
+    t_std = [torch.from_numpy(s).to(dev) for s in prep.y_std]
+    t_lstd = [torch.from_numpy(np.maximum(s, 1e-12)).to(dev) for s in prep.loss_std]
     t_lstd[2] = t_lstd[2][0]
     c_heat, c_g = float(np.float32(-LV / CPD)), float(np.float32(-1.0 / GRAVITY))
     opt = torch.optim.Adam(list(trunk.parameters()) + list(heads.parameters()), lr=hp.learning_rate)
@@ -243,8 +328,9 @@ def train_precipitative_model(hyperparameters: PrecipitativeHyperparameters, tra
         for i in range(0, n, hp.batch_size):
             idx = perm[i:i + hp.batch_size]
             hidden = trunk(xin[idx])
-            t_tend = heads[0](hidden) * t_std[0] + t_mean[0]
-            q_tend = heads[1](hidden) * t_std[1] + t_mean[1]
+            raw = [heads[0](hidden), heads[1](hidden)]
+            t_tend = raw[0] * t_std[0] + t_mean[0]
+            q_tend = raw[1] * t_std[1] + t_mean[1]
             col_precip = heads[3](hidden) * t_std[1] + t_mean[1]      # dQ2's mean and std (:234-238)
             if hp.couple_precip_to_dQ1_dQ2:
                 t_tend = t_tend + c_heat * col_precip
@@ -253,19 +339,106 @@ def train_precipitative_model(hyperparameters: PrecipitativeHyperparameters, tra
             loss = 0.0
             for pred, j in ((t_tend, 0), (q_tend, 1), (precip, 2)):
                 loss = loss + torch.mean(((pred - targets[j][idx]) / t_lstd[j]) ** 2)
+            if prep.has_dead:   # activity_regularizer on the three dense_network_output_i heads: regularizer(output) / batch size
+                for out in raw + [heads[2](hidden)]:
+                    loss = loss + (prep.l1 * out.abs().sum() + prep.l2 * (out * out).sum()) / idx.shape[0]
             opt.zero_grad()
             loss.backward()
             opt.step()
-
     lin_layers = [m for m in trunk if isinstance(m, torch.nn.Linear)]
     live = [heads[0], heads[1], heads[3]]
-    spec = precipitative_spec_from_arrays(
-        names_in, x_mean, x_std,
-        [m.weight.detach().cpu().numpy().T.copy() for m in lin_layers],
-        [m.bias.detach().cpu().numpy().copy() for m in lin_layers],
-        [h.weight.detach().cpu().numpy().T.copy() for h in live],
-        [h.bias.detach().cpu().numpy().copy() for h in live],
-        y_mean[:2], y_std[:2], clip=hp.clip,
-    )
+    return ([m.weight.detach().cpu().numpy().T.copy() for m in lin_layers], [m.bias.detach().cpu().numpy().copy() for m in lin_layers],
+            [h.weight.detach().cpu().numpy().T.copy() for h in live], [h.bias.detach().cpu().numpy().copy() for h in live])
+
+
+def precipitative_loss(hp: PrecipitativeHyperparameters, prep: _PrecipitativeTraining):
+    """The loss of ``_train_torch`` as the arrays the device step takes (``fv3net_amd.train.PrecipLoss``)."""
+    from ..train import PrecipLoss
+
+    inv = [(1.0 / np.maximum(s, 1e-12).astype(np.float64) ** 2).astype(np.float32) for s in prep.loss_std]
+    return PrecipLoss(scale1=prep.y_std[0], center1=prep.y_mean[0], scale2=prep.y_std[1], center2=prep.y_mean[1], inv_cstd2_1=inv[0],
+                      inv_cstd2_2=inv[1], inv_cstd2_3=float(inv[2][0]), couple=bool(hp.couple_precip_to_dQ1_dQ2), has_dead=prep.has_dead,
+                      l1=prep.l1, l2=prep.l2)
+
+
+def precipitative_trainer(hp: PrecipitativeHyperparameters, prep: _PrecipitativeTraining, dev: torch.device):
+    """The device training state of ``backend="hip"``: the layers of ``prep`` (the dead head only where it is trained), the
+    resident inputs, thickness and targets, the loss."""
+    from ..train import PrecipitativeTrainer
+
+    lins = [m for m in prep.trunk if isinstance(m, torch.nn.Linear)]
+    kernels = [m.weight.detach().numpy().T.copy() for m in lins]
+    biases = [m.bias.detach().numpy().copy() for m in lins]
+    heads = [h for j, h in enumerate(prep.heads) if j != 2 or prep.has_dead]
+    kernels.append(np.concatenate([h.weight.detach().numpy().T for h in heads], axis=1))
+    biases.append(np.concatenate([h.bias.detach().numpy() for h in heads]))
+    return PrecipitativeTrainer(kernels, biases, device=dev, xin=prep.xin, delp=prep.delp, physics_precip=prep.physics_precip,
+                                targets=prep.y, loss=precipitative_loss(hp, prep), max_batch=min(hp.batch_size, prep.xin.shape[0]),
+                                learning_rate=hp.learning_rate)
+
+
+def _head_sizes(prep: _PrecipitativeTraining) -> List[int]:
+    nz = prep.y[0].shape[1]
+    return [nz, nz] + ([1] if prep.has_dead else []) + [nz]
+
+
+def _train_hip(hp: PrecipitativeHyperparameters, prep: _PrecipitativeTraining, dev: torch.device):
+    """The same minibatches in the same order through ``fv3net_amd.train.PrecipitativeTrainer`` (csrc/mlp_train.hip)."""
+    trainer = precipitative_trainer(hp, prep, dev)
+    n = prep.xin.shape[0]
+    g = torch.Generator().manual_seed(hp.seed)
+    for _ in range(hp.epochs):
+        perm = torch.randperm(n, generator=g).to(dev)
+        for i in range(0, n, hp.batch_size):
+            trainer.step(perm[i:i + hp.batch_size])
+    hidden_k, hidden_b, out_k, out_b = trainer.parameters(_head_sizes(prep))
+    if prep.has_dead:   # dropped on export
+        out_k, out_b = out_k[:2] + out_k[3:], out_b[:2] + out_b[3:]
+    return hidden_k, hidden_b, out_k, out_b
+
+
+def regularizer_coefficients(config: Optional[Tuple[str, Mapping]]) -> Tuple[float, float, bool]:
+    """``(l1, l2, set)`` of a ``residual_regularizer``: Keras's ``regularizers.l1(l1=0.01)``, ``l2(l2=0.01)`` and
+    ``l1_l2(l1=0.01, l2=0.01)``; ``None`` and ``"none"`` are no regulariser."""
+    if config is None:
+        return 0.0, 0.0, False
+    name, kwargs = config
+    kwargs = dict(kwargs or {})
+    allowed = {"none": (), "l1": ("l1",), "l2": ("l2",), "l1_l2": ("l1", "l2")}
+    if name not in allowed:
+        raise ValueError(f"residual_regularizer must be one of {sorted(allowed)}, got {name!r}")
+    unknown = [k for k in kwargs if k not in allowed[name]]
+    if unknown:
+        raise ValueError(f"regulariser {name!r} takes {list(allowed[name])}, got {unknown}")
+    l1 = float(kwargs.get("l1", 0.01)) if "l1" in allowed[name] else 0.0
+    l2 = float(kwargs.get("l2", 0.01)) if "l2" in allowed[name] else 0.0
+    if not (l1 >= 0 and l2 >= 0 and np.isfinite(l1) and np.isfinite(l2)):
+        raise ValueError(f"regulariser coefficients must be finite and >= 0, got l1={l1}, l2={l2}")
+    return l1, l2, name != "none"
+
+
+def train_precipitative_model(hyperparameters: PrecipitativeHyperparameters, train_batches: Sequence[Dataset],
+                              device: Optional[str] = None, backend: Optional[str] = None) -> HipPrecipitativeModel:
+    """Fit normalisation on up to ``normalization_fit_samples`` samples and train the graph of precipitative.py:181-279
+    with Adam: ``Dense(width, relu) x (depth-1)``, four linear heads, the closure from the unclipped ``delp`` inside the training
+    graph, and the std-scaled MSE summed over ``dQ1``, ``dQ2`` and ``total_precipitation_rate`` as ``train_dense_model``
+    computes it.  The one-feature head for total_precipitation_rate reaches no output: without ``residual_regularizer`` it
+    receives no gradient; with it, it is trained through the activity regulariser alone.  It is dropped on export either way.
+
+    ``backend``: ``None`` / ``"torch"`` steps through ``torch.nn.Linear``, autograd and ``torch.optim.Adam``; ``"hip"`` through
+    the project's own kernels (``fv3net_amd.train.PrecipitativeTrainer``; needs a GPU).  Normalisation, initialisation (all four
+    heads are drawn, in the reference's order) and the minibatch sequence are shared: both start from bitwise-equal parameters and
+    see the same rows in the same order.  The callbacks and ``validation_batches`` of the reference are out of scope."""
+    hp = hyperparameters
+    if backend not in (None, "torch", "hip"):
+        raise ValueError(f"backend must be None, 'torch' or 'hip', got {backend!r}")
+    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    if backend == "hip" and dev.type != "cuda":
+        ops._require_device(torch.empty(0, device=dev))  # raises: there is no CPU path
+    prep = _prepare_precipitative_training(hp, train_batches)
+    weights = (_train_hip if backend == "hip" else _train_torch)(hp, prep, dev)
+    names_in, names_out = hp.input_variables, hp.output_variables
+    spec = precipitative_spec_from_arrays(names_in, prep.x_mean, prep.x_std, weights[0], weights[1], weights[2], weights[3],
+                                          prep.y_mean[:2], prep.y_std[:2], clip=hp.clip)
     return HipPrecipitativeModel(names_in, names_out, spec, couple_precip_to_dQ1_dQ2=hp.couple_precip_to_dQ1_dQ2,
                                  unstacked_dims=hp.unstacked_dims)

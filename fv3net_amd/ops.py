@@ -1233,6 +1233,52 @@ def train_mse_grad(yhat: torch.Tensor, scale, center, inv_cstd2, lo, hi, keep, w
     return dy, loss
 
 
+def train_precip_loss_grad(yhat: torch.Tensor, scale1, center1, scale2, center2, inv_cstd2_1, inv_cstd2_2, inv_cstd2_3: float,
+                           delp: torch.Tensor, physics_precip: torch.Tensor, t1: torch.Tensor, t2: torch.Tensor, t3: torch.Tensor,
+                           dy: torch.Tensor, loss: torch.Tensor, loss_workspace: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                           couple: bool = True, has_dead: bool = False, l1: float = 0.0, l2: float = 0.0,
+                           dq1: Optional[torch.Tensor] = None, dq2: Optional[torch.Tensor] = None,
+                           precip: Optional[torch.Tensor] = None, n: Optional[int] = None):
+    """The loss behind the closure of the precipitative model and its gradient (see ``fv3hip_train_precip_loss_grad``): writes
+    ``dy`` and the float64 ``loss[0]``.  ``yhat`` / ``dy``: ``[n, 3 nz + has_dead]`` laid out ``t | q | dead | cp``; the six
+    per-level arrays are float32 ``[nz]``; ``delp``, ``t1``, ``t2`` ``[rows, nz]`` (``t1`` and ``t2`` with one row stride) and
+    ``physics_precip``, ``t3`` ``[rows]`` are read through ``idx``.  ``dq1``, ``dq2`` (contiguous ``[n, nz]``) and ``precip``
+    (``[n]``) receive the predictions where given."""
+    tensors = (yhat, scale1, center1, scale2, center2, inv_cstd2_1, inv_cstd2_2, delp, physics_precip, t1, t2, t3, dy, loss,
+               loss_workspace, idx, dq1, dq2, precip)
+    dev = _require_device(*(t for t in tensors if t is not None))
+    has_dead = bool(has_dead)
+    y_rows, f, ldy = _rows_f32(yhat, "yhat")
+    nz, rem = divmod(f - int(has_dead), 3)
+    if rem or nz < 1:
+        raise ValueError(f"yhat has {f} features: not three blocks of levels{' and the dead head' if has_dead else ''}")
+    rows, _, ldd = _rows_f32(delp, "delp", nz)
+    t_rows, _, ldt = _rows_f32(t1, "t1", nz)
+    t2_rows, _, ldt2 = _rows_f32(t2, "t2", nz)
+    if ldt2 != ldt or t_rows != rows or t2_rows != rows:
+        raise ValueError("delp, t1 and t2 must have the same rows, t1 and t2 one row stride")
+    _vec(physics_precip, "physics_precip", rows)
+    _vec(t3, "t3", rows)
+    n = int(n) if n is not None else _batch_rows(idx, y_rows)
+    _batch_rows(idx, 0)
+    d_rows, _, lddy = _rows_f32(dy, "dy", f)
+    if y_rows < n or d_rows < n or (idx is not None and int(idx.shape[0]) < n) or (idx is None and rows < n):
+        raise ValueError(f"the batch has {n} rows; yhat {y_rows}, dy {d_rows}")
+    if loss.dtype != torch.float64 or loss.numel() < 1 or loss_workspace.dtype != torch.float64 or \
+            loss_workspace.numel() < train_loss_workspace_doubles() or not loss_workspace.is_contiguous():
+        raise ValueError(f"loss must be float64 and loss_workspace {train_loss_workspace_doubles()} contiguous float64 values")
+    for t, name in ((dq1, "dq1"), (dq2, "dq2")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n, nz) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 [{n}, {nz}] tensor")
+    _vec(precip, "precip", n)
+    vecs = [_vec(t, name, nz) for t, name in ((scale1, "scale1"), (center1, "center1"), (scale2, "scale2"), (center2, "center2"),
+                                             (inv_cstd2_1, "inv_cstd2_1"), (inv_cstd2_2, "inv_cstd2_2"))]
+    _lib.call_on(dev, "fv3hip_train_precip_loss_grad", _ptr(yhat), ldy, *(_ptr(v) for v in vecs), float(inv_cstd2_3), _ptr(delp), ldd,
+                 _ptr(physics_precip), _ptr(t1), _ptr(t2), ldt, _ptr(t3), rows, _ptr(idx), int(bool(couple)), int(has_dead), float(l1),
+                 float(l2), _ptr(dy), lddy, _ptr(loss), _ptr(loss_workspace), _ptr(dq1), _ptr(dq2), _ptr(precip), n, nz, _stream(dev))
+    return dy, loss
+
+
 def train_adam(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor, lr: float = 1e-3,
                beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
     """``torch.optim.Adam``'s default update of one flat float32 buffer; ``step`` is an int64 device scalar holding the number of

@@ -1,4 +1,5 @@
-"""Training state of the dense column network on the device, and its Jacobian (csrc/mlp_train.hip).
+"""Training state of the dense column network on the device, and its Jacobian (csrc/mlp_train.hip);
+``PrecipitativeTrainer`` is the same state with the loss behind the precipitative closure (section 25).
 
 ``DenseTrainer`` owns every tensor the stateless ``fv3hip_train_*`` entry points work on: one flat float32 parameter buffer
 (per layer the kernel ``[in][out]`` followed by its bias; the heads are one concatenated layer, as ``MlpSpec.out_kernel`` is),
@@ -115,20 +116,24 @@ class DenseTrainer:
     def backward(self, idx: torch.Tensor) -> None:
         """Forward, loss and the gradient of every parameter for the minibatch ``idx``, into ``self.grads``."""
         n = int(idx.shape[0])
-        wn = self._wnorm.get(n)
-        if wn is None:
-            wn = self._wnorm[n] = torch.from_numpy(self._mse.wnorm(n)).to(self.device)
-        la = self._loss_arrays
         last = len(self.shapes) - 1
         self._forward(self.xin, idx, n)
-        ops.train_mse_grad(self._h[last][:n], la["scale"], la["center"], la["inv_cstd2"], la["lo"], la["hi"], la["keep"], wn,
-                           self.targets, self._dh[last][:n], self._loss, self._loss_ws, idx=idx)
+        self._loss_grad(idx, n)
         for l in range(last, -1, -1):
             if l == 0:
                 ops.train_linear_backward_weight(self.xin, self._dh[0][:n], self.dw[0], self.db[0], idx=idx, workspace=self._ws)
             else:
                 ops.train_linear_backward_weight(self._h[l - 1][:n], self._dh[l][:n], self.dw[l], self.db[l], workspace=self._ws)
                 ops.train_linear_backward_data(self._dh[l][:n], self.w[l], self._h[l - 1][:n] if self.relu else None, self._dh[l - 1][:n])
+
+    def _loss_grad(self, idx: torch.Tensor, n: int) -> None:
+        """The loss stage: from the head layer's output ``_h[-1][:n]`` to its gradient ``_dh[-1][:n]`` and ``_loss``."""
+        wn = self._wnorm.get(n)
+        if wn is None:
+            wn = self._wnorm[n] = torch.from_numpy(self._mse.wnorm(n)).to(self.device)
+        la = self._loss_arrays
+        ops.train_mse_grad(self._h[-1][:n], la["scale"], la["center"], la["inv_cstd2"], la["lo"], la["hi"], la["keep"], wn,
+                           self.targets, self._dh[-1][:n], self._loss, self._loss_ws, idx=idx)
 
     def capture(self, idx: torch.Tensor) -> "torch.cuda.CUDAGraph":
         """A HIP graph of ``step(idx)`` reading the row numbers from ``idx``'s memory: refill ``idx`` in place and ``replay()``.
@@ -198,13 +203,69 @@ class DenseTrainer:
         return cots[0].cpu().numpy(), acts[last].cpu().numpy()[0]
 
 
-def predict_graph_jacobians(spec, profiles: Mapping[str, np.ndarray], device="cuda",
-                            trainer: Optional[DenseTrainer] = None) -> Dict[str, Dict[str, np.ndarray]]:
+@dataclasses.dataclass
+class PrecipLoss:
+    """What ``fv3hip_train_precip_loss_grad`` takes besides the data: the de-normalisation of dQ1 (``1``) and of dQ2 and the column
+    precipitation (``2``), ``1 / max(std, 1e-12) ** 2`` of the three targets, the coupling and the activity regulariser."""
+
+    scale1: np.ndarray
+    center1: np.ndarray
+    scale2: np.ndarray
+    center2: np.ndarray
+    inv_cstd2_1: np.ndarray
+    inv_cstd2_2: np.ndarray
+    inv_cstd2_3: float
+    couple: bool = True
+    has_dead: bool = False
+    l1: float = 0.0
+    l2: float = 0.0
+
+
+class PrecipitativeTrainer(DenseTrainer):
+    """The dense trainer with the loss behind the precipitative closure.  The head layer is
+    ``[ dQ1 (nz) | dQ2 (nz) | dead (1, with loss.has_dead) | column precipitation (nz) ]``; besides the normalised inputs the
+    trainer holds the raw ``delp [rows, nz]``, ``physics_precip [rows]`` and the targets ``dQ1``, ``dQ2`` ``[rows, nz]`` and
+    ``total_precipitation_rate [rows]``."""
+
+    def __init__(self, kernels: Sequence[np.ndarray], biases: Sequence[np.ndarray], device="cuda", *, xin: np.ndarray, delp: np.ndarray,
+                 physics_precip: np.ndarray, targets: Sequence[np.ndarray], loss: PrecipLoss, max_batch: int = 512,
+                 learning_rate: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8):
+        super().__init__(kernels, biases, device=device, max_batch=max_batch, learning_rate=learning_rate, betas=betas, eps=eps)
+        dev = self.device
+        nz = int(np.shape(loss.scale1)[0])
+        if self.f_out != 3 * nz + int(bool(loss.has_dead)):
+            raise ValueError(f"the head layer has {self.f_out} features, the loss {nz} levels (has_dead={bool(loss.has_dead)})")
+        self.nz, self.precip_loss = nz, loss
+        self.xin = torch.from_numpy(np.ascontiguousarray(xin, np.float32)).to(dev)
+        rows = int(self.xin.shape[0])
+        t1, t2, t3 = targets
+        # dQ1 and dQ2 side by side in one array: one row stride for both
+        self.targets = torch.from_numpy(np.ascontiguousarray(np.concatenate([t1, t2], axis=1), np.float32)).to(dev)
+        self.t3 = torch.from_numpy(np.ascontiguousarray(np.reshape(t3, -1), np.float32)).to(dev)
+        self.delp = torch.from_numpy(np.ascontiguousarray(delp, np.float32)).to(dev)
+        self.physics_precip = torch.from_numpy(np.ascontiguousarray(np.reshape(physics_precip, -1), np.float32)).to(dev)
+        if self.xin.shape[1] != self.k_in or tuple(self.targets.shape) != (rows, 2 * nz) or tuple(self.delp.shape) != (rows, nz) or \
+                self.t3.shape[0] != rows or self.physics_precip.shape[0] != rows:
+            raise ValueError("xin, delp, physics_precip and the targets do not match the network or each other")
+        self._loss_arrays = {name: torch.from_numpy(np.ascontiguousarray(getattr(loss, name), np.float32)).to(dev)
+                             for name in ("scale1", "center1", "scale2", "center2", "inv_cstd2_1", "inv_cstd2_2")}
+
+    def _loss_grad(self, idx: torch.Tensor, n: int) -> None:
+        la, pl, nz = self._loss_arrays, self.precip_loss, self.nz
+        ops.train_precip_loss_grad(self._h[-1][:n], la["scale1"], la["center1"], la["scale2"], la["center2"], la["inv_cstd2_1"],
+                                   la["inv_cstd2_2"], pl.inv_cstd2_3, self.delp, self.physics_precip, self.targets[:, :nz],
+                                   self.targets[:, nz:], self.t3, self._dh[-1][:n], self._loss, self._loss_ws, idx=idx, couple=pl.couple,
+                                   has_dead=pl.has_dead, l1=pl.l1, l2=pl.l2)
+
+
+def predict_graph_jacobians(spec, profiles: Mapping[str, np.ndarray], device="cuda", trainer: Optional[DenseTrainer] = None,
+                            values: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, Dict[str, np.ndarray]]:
     """``{output: {source: d output / d source}}`` of an ``MlpSpec``'s predict graph at one profile per source (``[nfeat]``,
     cast to float32 as ``predict`` casts): input clip, ``log(max(x, eps))`` where the spec asks for it, normalisation, network,
     de-normalisation, limits and masked levels.  Each array is ``[nfeat_out][len(profile)]`` in float64; columns of levels
     that no input reads, rows of masked levels and rows of outputs outside a limit (bounds inclusive) are exactly 0.  Residual
-    outputs and the hidden output are left out."""
+    outputs and the hidden output are left out.  ``values`` (a dict) receives each output's de-normalised float32 value at the
+    profile, before limits and masks."""
     trainer = trainer or DenseTrainer.from_spec(spec, device)
     prof = {name: np.atleast_1d(np.asarray(profiles[name])).astype(np.float32) for name in dict.fromkeys(i.source for i in spec.inputs)}
     cols, slopes = [], []
@@ -234,6 +295,8 @@ def predict_graph_jacobians(spec, profiles: Mapping[str, np.ndarray], device="cu
         scale = np.ones(o.nfeat, np.float32) if o.scale is None else np.broadcast_to(np.asarray(o.scale, np.float32), (o.nfeat,))
         center = np.zeros(o.nfeat, np.float32) if o.center is None else np.broadcast_to(np.asarray(o.center, np.float32), (o.nfeat,))
         p = y * scale + center
+        if values is not None:
+            values[o.name] = p
         factor = scale.astype(np.float64)
         if o.min is not None:
             factor = np.where(p >= np.float32(o.min), factor, 0.0)

@@ -1204,6 +1204,31 @@ int fv3hip_cyclegan_input(const float *state, int64_t state_ld, int64_t state_of
  *                                        v = b2 v + ((1 - b2) g) g;
  *                                        p -= (float)(lr / (1 - b1^t)) * m / (sqrt(v) / (float)sqrt(1 - b2^t) + eps), every
  *                                        product rounded; then step[0] += 1 on the device (int64), so a captured step replays.
+ *   fv3hip_train_precip_loss_grad        the loss behind the closure of fv3fit's "precipitative" model (keras/_models/
+ *                                        precipitative.py:181-279) and its gradient.  yhat [n][ldy] is the
+ *                                        raw output of the concatenated head layer, [ t (nz) | q (nz) | dead (1, only with
+ *                                        has_dead) | cp (nz) ]; dY [n][lddy] has the same layout.  scale1 / center1, scale2 /
+ *                                        center2, inv_cstd2_1, inv_cstd2_2 are [nz]; the cp block is denormalised with scale2 /
+ *                                        center2.  delp [rows][ldd] (the raw thickness), physics_precip [rows], T1 / T2
+ *                                        [rows][ldt] and T3 [rows] are the resident arrays, read through idx: a row outside
+ *                                        [0, rows) reads delp and physics_precip as 0 and its targets as NaN.  Per batch row,
+ *                                        every product and sum rounded to float32, c_heat = (float)(-2.5e6 / 1004.6), c_g =
+ *                                        (float)(-1 / 9.80665), w12 = (float)(1 / (n nz)), w3 = (float)(1 / n):
+ *                                          t = t^ scale1 + center1, q = q^ scale2 + center2, cp = cp^ scale2 + center2
+ *                                          dq1 = couple ? t + c_heat cp : t,  dq2 = couple ? q + cp : q
+ *                                          acc = +0; for k ascending: acc = acc + cp[k] delp[k];  precip = pp + c_g acc
+ *                                            (fv3hip_precip_closure's order: the same bits on the same heads)
+ *                                          e1 = dq1 - T1, e2 = dq2 - T2, e3 = precip - T3
+ *                                          g1 = 2 e1 inv1 w12, g2 = 2 e2 inv2 w12, g3 = 2 e3 inv3 w3   (left to right)
+ *                                          dt^ = g1 scale1 + r(t^), dq^ = g2 scale2 + r(q^), ddead = r(dead)
+ *                                          dcp^ = ((couple ? c_heat g1 + g2 : 0) + (c_g delp) g3) scale2
+ *                                          r(x) = (l1 sign(x) + 2 l2 x) / n, sign(0) = 0; with l1 = l2 = 0 no r is added and
+ *                                          ddead = 0
+ *                                        loss[0] (float64) = sum of e1^2 inv1 w12, e2^2 inv2 w12, e3^2 inv3 w3 and
+ *                                        (l1 |x| + l2 x^2) / n over t^, q^ and dead, accumulated in float64: per-block partials
+ *                                        in loss_workspace (fv3hip_train_loss_workspace_doubles() doubles), then one block adds
+ *                                        them in order.  couple, has_dead 0 / 1; l1, l2 >= 0.  dq1, dq2 [n][nz] and precip [n]
+ *                                        (each may be null) receive the predictions.  nz >= 1.  Two launches.
  */
 int fv3hip_train_chunk_rows(void);
 size_t fv3hip_train_backward_weight_workspace_bytes(int64_t n, int k, int o);
@@ -1221,6 +1246,12 @@ int fv3hip_train_mse_grad(const float *yhat, int64_t ldy, const float *scale, co
                           int64_t n, int f, void *stream);
 int fv3hip_train_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step, double lr, double beta1,
                       double beta2, double eps, void *stream);
+int fv3hip_train_precip_loss_grad(const float *yhat, int64_t ldy, const float *scale1, const float *center1, const float *scale2,
+                                  const float *center2, const float *inv_cstd2_1, const float *inv_cstd2_2, float inv_cstd2_3,
+                                  const float *delp, int64_t ldd, const float *physics_precip, const float *T1, const float *T2,
+                                  int64_t ldt, const float *T3, int64_t rows, const int64_t *idx, int couple, int has_dead, float l1,
+                                  float l2, float *dY, int64_t lddy, double *loss, double *loss_workspace, float *dq1, float *dq2,
+                                  float *precip, int64_t n, int nz, void *stream);
 
 /* ---- training the convolutional network (fv3fit's "convolutional" training function, keras/_models/convolutional.py:101-210,
  * shared/convolutional_network.py:59-195).  Stateless like fv3hip_train_linear_*: the caller owns every
