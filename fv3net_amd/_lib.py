@@ -214,6 +214,20 @@ class ForestTrain(ctypes.Structure):
     )
 
 
+class EmulatorHead(ctypes.Structure):
+    """``fv3hip_emulator_head_t``: one head of ``fv3hip_train_emulator_loss_grad`` (device pointers as integers)."""
+
+    _fields_ = (
+        [(k, c_int) for k in ("kind", "col0", "ncol", "single_level", "slot", "slot_after", "is_loss", "is_loss_after")]
+        + [("weight", c_double), ("weight_after", c_double)]
+        + [(k, c_void_p) for k in ("scale", "center", "target", "inv", "before", "target_after", "inv_after")]
+        + [(k, c_int64) for k in ("ld_target", "ld_before", "ld_target_after")]
+    )
+
+
+EMULATOR_MAX_HEADS = 16
+EMULATOR_HEAD_MSE_DENSE, EMULATOR_HEAD_MSE_LOCAL, EMULATOR_HEAD_XENT = 0, 1, 2
+
 # name -> (restype, argtypes); every name here must be declared in include/fv3hip.h
 SIGNATURES = {
     "fv3hip_last_error": (c_char_p, []),
@@ -424,6 +438,9 @@ SIGNATURES = {
                                               c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                               c_int, c_int, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "fv3hip_train_emulator_loss_workspace_doubles": (c_int, []),
+    "fv3hip_train_emulator_loss_grad": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, POINTER(EmulatorHead), c_int, c_int, c_int64,
+                                                c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fv3hip_train_conv_chunk_pixels": (c_int, []),
     "fv3hip_train_conv_backward_weight_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int, c_int]),
     "fv3hip_train_conv_forward": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,

@@ -332,6 +332,141 @@ __global__ __launch_bounds__(kBlock) void train_precip_loss_grad_kernel(const Pr
     if (tid == 0) a.partial[blockIdx.x] = part[0];
 }
 
+// The multi-variable loss of the microphysics emulators (fv3fit's "transformed" training function: emulation/losses.py:33-146
+// CustomLoss / _MultiVariableLoss) and its gradient with respect to the raw output of the concatenated
+// head layer.  Every head owns a run of blocks (block0[h] .. block0[h + 1]), so a block works on one head and its two partials
+// belong to that head's two terms.  An MSE head is walked one (network row, column) per thread, columns fastest (dense heads:
+// coalesced along the row); the thread evaluates the direct and the after term, so a dY element has one writer.  A
+// cross-entropy point is one thread, which reads its C logits three times (maximum, sum, gradient: the second and third
+// reads hit L1) rather than holding them in an array, which would live in scratch.
+constexpr int kEmuHeads = FV3HIP_EMULATOR_MAX_HEADS, kEmuSlots = 2 * kEmuHeads;
+constexpr int kEmuFinishThreads = 64;   // one wave: a thread per slot
+constexpr int kEmuBlocksPerHead = 64;   // most blocks of one head; workspace = kEmuHeads * kEmuBlocksPerHead * 2 doubles
+
+struct EmuLossArgs {
+    fv3hip_emulator_head_t head[kEmuHeads];
+    float wgrad_d[kEmuHeads], wgrad_a[kEmuHeads];
+    int block0[kEmuHeads + 1];
+    int n_heads, levels;
+    const float *yhat;
+    const int64_t *idx;
+    float *dy;
+    double *partial;
+    int64_t ldy, lddy, rows, n;
+};
+
+__global__ __launch_bounds__(kBlock) void train_emulator_loss_grad_kernel(const EmuLossArgs a)
+{
+    __shared__ double part[kBlock];
+    const int tid = threadIdx.x;
+    int h = 0;
+    while (h + 1 < a.n_heads && (int)blockIdx.x >= a.block0[h + 1]) ++h;
+    const fv3hip_emulator_head_t &hd = a.head[h];
+    const int block = (int)blockIdx.x - a.block0[h], blocks = a.block0[h + 1] - a.block0[h];
+    const int L = a.levels, C = hd.ncol;
+    const float wd = a.wgrad_d[h], wa = a.wgrad_a[h];
+    double sum_d = 0.0, sum_a = 0.0;
+    if (hd.kind == FV3HIP_EMULATOR_HEAD_XENT) {
+        const int64_t total = a.n * L;
+        for (int64_t m = (int64_t)block * kBlock + tid; m < total; m += (int64_t)blocks * kBlock) {
+            const int64_t b = m / L;
+            const int z = (int)(m % L);
+            const int64_t r = a.idx ? a.idx[b] : b;
+            const bool in = r >= 0 && r < a.rows;
+            const float *x = a.yhat + m * a.ldy + hd.col0;
+            const float *t = hd.target + (in ? r * hd.ld_target + (int64_t)z * C : 0);
+            float mx = x[0];
+            for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);   // (a NaN logit reaches s below)
+            float s = 0.f, st = 0.f;
+            for (int c = 0; c < C; ++c) {
+                s = s + expf(x[c] - mx);
+                st = st + (in ? t[c] : NAN);
+            }
+            const float lse = mx + logf(s);
+            for (int c = 0; c < C; ++c) {
+                const float xc = x[c], tc = in ? t[c] : NAN;
+                sum_d += (double)(tc * (lse - xc));
+                if (a.dy) a.dy[m * a.lddy + hd.col0 + c] = hd.is_loss ? (expf(xc - lse) * st - tc) * wd : 0.f;
+            }
+        }
+    } else {
+        const bool local = hd.kind == FV3HIP_EMULATOR_HEAD_MSE_LOCAL;
+        const bool has_d = hd.slot >= 0, has_a = hd.slot_after >= 0;
+        const int64_t total = a.n * L * C;   // dense: L = 1; local: C = 1
+        for (int64_t e = (int64_t)block * kBlock + tid; e < total; e += (int64_t)blocks * kBlock) {
+            const int64_t m = e / C;
+            const int j = (int)(e % C);
+            const int64_t b = local ? m / L : m;
+            const int z = local ? (int)(m % L) : 0;
+            const int t = local ? z : j;         // the tables' index, and the column of a target row
+            float g = 0.f;
+            if ((has_d || has_a) && !(local && hd.single_level && z != 0)) {
+                const int64_t r = a.idx ? a.idx[b] : b;
+                const bool in = r >= 0 && r < a.rows;
+                const float y = a.yhat[m * a.ldy + hd.col0 + j];
+                const float p = hd.scale ? y * hd.scale[t] + hd.center[t] : y;
+                if (has_d) {
+                    const float d = p - (in ? hd.target[r * hd.ld_target + t] : NAN);
+                    const float inv = hd.inv[t];
+                    sum_d += (double)(d * d * inv);
+                    if (hd.is_loss) g = 2.f * d * inv * wd;   // (a metric term is reported and sends nothing into dY)
+                }
+                if (has_a) {
+                    const float aft = (in ? hd.before[r * hd.ld_before + t] : 0.f) + p;
+                    const float ea = aft - (in ? hd.target_after[r * hd.ld_target_after + t] : NAN);
+                    const float inv = hd.inv_after[t];
+                    sum_a += (double)(ea * ea * inv);
+                    if (hd.is_loss_after) g = g + 2.f * ea * inv * wa;
+                }
+                if (hd.scale) g = g * hd.scale[t];
+            }
+            if (a.dy) a.dy[m * a.lddy + hd.col0 + j] = g;
+        }
+    }
+    part[tid] = sum_d;
+    block_tree_sum(part, tid);
+    if (tid == 0) a.partial[2 * (int64_t)blockIdx.x] = part[0];
+    __syncthreads();
+    part[tid] = sum_a;
+    block_tree_sum(part, tid);
+    if (tid == 0) a.partial[2 * (int64_t)blockIdx.x + 1] = part[0];
+}
+
+struct EmuFinishArgs {
+    double wval[kEmuSlots], weight[kEmuSlots];
+    int is_loss[kEmuSlots];                      // 0: a metric slot, which does not enter the loss
+    int first[kEmuSlots], count[kEmuSlots];      // the slot's partials: partial[first + 2 i], i < count
+    int n_slots;
+    const double *partial;
+    double *values, *loss, *accum;
+};
+
+// values[slot] = (the slot's partials added in ascending block order) * wval; loss = the loss slots' weight * value added in
+// slot order; one thread then adds loss and the values into accum (if given) in that order
+__global__ __launch_bounds__(kEmuFinishThreads) void train_emulator_loss_finish_kernel(const EmuFinishArgs f)
+{
+    __shared__ double vals[kEmuSlots];
+    const int s = threadIdx.x;
+    if (s < f.n_slots) {
+        const double *p = f.partial + f.first[s];
+        double sum = 0.0;
+        for (int i = 0; i < f.count[s]; ++i) sum += p[2 * i];
+        vals[s] = sum * f.wval[s];
+        f.values[s] = vals[s];
+    }
+    __syncthreads();
+    if (s == 0) {
+        double loss = 0.0;
+        for (int i = 0; i < f.n_slots; ++i)
+            if (f.is_loss[i]) loss += f.weight[i] * vals[i];
+        f.loss[0] = loss;
+        if (f.accum) {
+            f.accum[0] += loss;
+            for (int i = 0; i < f.n_slots; ++i) f.accum[1 + i] += vals[i];
+        }
+    }
+}
+
 // torch.optim.Adam's default update (no weight decay, no amsgrad) at step t = step[0] + 1, rounded as torch's kernels round
 // it: the first moment is exp_avg.lerp_(grad, 1 - beta1) = fma(1 - beta1, g - m, m), which is beta1 m + (1 - beta1) g with one
 // rounding fewer; the second is v beta2 + ((1 - beta2) g) g; the update p - (step_size m) / (sqrt(v) / bc2_sqrt + eps).
@@ -511,6 +646,103 @@ extern "C" int fv3hip_train_precip_loss_grad(const float *yhat, int64_t ldy, con
     if ((rc = check_launch("train_precip_loss_grad_kernel"))) return rc;
     hipLaunchKernelGGL(train_loss_finish_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), loss_workspace, blocks, loss);
     return check_launch("train_loss_finish_kernel");
+}
+
+extern "C" int fv3hip_train_emulator_loss_workspace_doubles(void) { return kEmuHeads * kEmuBlocksPerHead * 2; }
+
+extern "C" int fv3hip_train_emulator_loss_grad(const float *yhat, int64_t ldy, int64_t n, int levels, int f,
+                                               const fv3hip_emulator_head_t *heads, int n_heads, int n_slots, int64_t rows,
+                                               const int64_t *idx, float *dY, int64_t lddy, double *values, double *loss, double *accum,
+                                               double *workspace, void *stream)
+{
+    int rc;
+    const int64_t limit = (int64_t)1 << 24;
+    FV3HIP_REQUIRE(n >= 1 && n <= limit && levels >= 1 && levels <= limit && n * levels <= limit,
+                   "batch rows, levels and their product must be in [1, 2^24], got %lld, %d", (long long)n, levels);
+    FV3HIP_REQUIRE(f >= 1 && f <= (1 << 20), "head features must be in [1, 2^20], got %d", f);
+    if ((rc = check_ld("yhat", yhat, ldy, f))) return rc;
+    if (dY && (rc = check_ld("dY", dY, lddy, f))) return rc;
+    FV3HIP_REQUIRE(heads && n_heads >= 1, "the head table is null or empty");
+    FV3HIP_REQUIRE(n_heads <= kEmuHeads, "%d heads: the head table holds at most %d", n_heads, kEmuHeads);
+    FV3HIP_REQUIRE(n_slots >= 0 && n_slots <= kEmuSlots, "%d slots: at most %d", n_slots, kEmuSlots);
+    FV3HIP_REQUIRE(values && loss && workspace, "values, loss or the workspace is null");
+    FV3HIP_REQUIRE(rows >= 1 && (idx || rows >= n), "the resident arrays have %lld rows, the batch %lld", (long long)rows, (long long)n);
+
+    EmuLossArgs a{};
+    EmuFinishArgs fin{};
+    bool used[kEmuSlots] = {};
+    int end = 0;
+    a.block0[0] = 0;
+    for (int h = 0; h < n_heads; ++h) {
+        const fv3hip_emulator_head_t &hd = heads[h];
+        FV3HIP_REQUIRE(hd.ncol >= 1 && hd.col0 >= 0, "head %d: columns [%d, %d + %d)", h, hd.col0, hd.col0, hd.ncol);
+        FV3HIP_REQUIRE(hd.col0 >= end, "head %d starts at column %d: it overlaps the head before it, which ends at %d", h, hd.col0, end);
+        FV3HIP_REQUIRE(hd.col0 == end, "columns [%d, %d) belong to no head", end, hd.col0);
+        FV3HIP_REQUIRE((int64_t)hd.col0 + hd.ncol <= f, "head %d ends at column %lld, past the %d head features", h,
+                       (long long)hd.col0 + hd.ncol, f);
+        end = hd.col0 + hd.ncol;
+        const bool xent = hd.kind == FV3HIP_EMULATOR_HEAD_XENT, local = hd.kind == FV3HIP_EMULATOR_HEAD_MSE_LOCAL;
+        FV3HIP_REQUIRE(xent || local || hd.kind == FV3HIP_EMULATOR_HEAD_MSE_DENSE, "head %d: unknown kind %d", h, hd.kind);
+        FV3HIP_REQUIRE(hd.single_level == 0 || (hd.single_level == 1 && local), "head %d: single_level goes with a local MSE head", h);
+        int64_t count, extent;
+        if (xent) {
+            FV3HIP_REQUIRE(hd.ncol >= 2 && hd.ncol <= 32, "head %d: a cross-entropy head has 2 to 32 channels, got %d", h, hd.ncol);
+            FV3HIP_REQUIRE(hd.slot >= 0 && hd.slot_after < 0 && !hd.scale && !hd.center,
+                           "head %d: a cross-entropy head has a direct term only and is unscaled", h);
+            count = n * levels, extent = (int64_t)levels * hd.ncol;
+        } else if (local) {
+            FV3HIP_REQUIRE(hd.ncol == 1, "head %d: a local MSE head has one column, got %d", h, hd.ncol);
+            count = hd.single_level ? n : n * levels, extent = hd.single_level ? 1 : levels;
+        } else {
+            FV3HIP_REQUIRE(levels == 1, "head %d: a dense MSE head needs levels == 1, got %d", h, levels);
+            count = n * hd.ncol, extent = hd.ncol;
+        }
+        FV3HIP_REQUIRE(!hd.scale == !hd.center, "head %d: scale and center go together", h);
+        const int slots[2] = {hd.slot, hd.slot_after};
+        const double weights[2] = {hd.weight, hd.weight_after};
+        const int is_loss[2] = {hd.is_loss, hd.is_loss_after};
+        for (int which = 0; which < 2; ++which) {
+            const int s = slots[which];
+            if (s < 0) continue;
+            FV3HIP_REQUIRE(s < n_slots && !used[s], "head %d: slot %d is out of range or used twice (%d slots)", h, s, n_slots);
+            FV3HIP_REQUIRE(std::isfinite(weights[which]) && weights[which] >= 0.0, "head %d: weight %g must be finite and >= 0", h,
+                           weights[which]);
+            FV3HIP_REQUIRE(is_loss[which] == 0 || is_loss[which] == 1, "head %d: is_loss must be 0 or 1", h);
+            used[s] = true;
+            if (which == 0) {
+                FV3HIP_REQUIRE(hd.target && (xent || hd.inv), "head %d: the direct term's target or inv is null", h);
+                FV3HIP_REQUIRE(hd.ld_target >= extent, "head %d: ld_target %lld does not hold %lld values", h, (long long)hd.ld_target,
+                               (long long)extent);
+            } else {
+                FV3HIP_REQUIRE(hd.target_after && hd.before && hd.inv_after, "head %d: the after term's target, before or inv is null", h);
+                FV3HIP_REQUIRE(hd.ld_target_after >= extent && hd.ld_before >= extent,
+                               "head %d: ld_target_after %lld or ld_before %lld does not hold %lld values", h,
+                               (long long)hd.ld_target_after, (long long)hd.ld_before, (long long)extent);
+            }
+            const float wgrad = is_loss[which] ? (float)(weights[which] / (double)count) : 0.f;
+            (which == 0 ? a.wgrad_d : a.wgrad_a)[h] = wgrad;
+            fin.wval[s] = 1.0 / (double)count;
+            fin.weight[s] = weights[which];
+            fin.is_loss[s] = is_loss[which];
+            fin.first[s] = 2 * a.block0[h] + which;
+        }
+        a.head[h] = hd;
+        const int64_t want = ceil_div(n * levels * (xent ? 1 : hd.ncol), kBlock);
+        const int blocks = (int)(want < kEmuBlocksPerHead ? want : kEmuBlocksPerHead);
+        a.block0[h + 1] = a.block0[h] + blocks;
+        for (int which = 0; which < 2; ++which)
+            if (slots[which] >= 0) fin.count[slots[which]] = blocks;
+    }
+    FV3HIP_REQUIRE(end == f, "the heads end at column %d, the head layer has %d features", end, f);
+    for (int s = 0; s < n_slots; ++s) FV3HIP_REQUIRE(used[s], "slot %d of %d belongs to no term", s, n_slots);
+
+    a.n_heads = n_heads, a.levels = levels, a.yhat = yhat, a.idx = idx, a.dy = dY, a.partial = workspace;
+    a.ldy = ldy, a.lddy = lddy, a.rows = rows, a.n = n;
+    fin.n_slots = n_slots, fin.partial = workspace, fin.values = values, fin.loss = loss, fin.accum = accum;
+    hipLaunchKernelGGL(train_emulator_loss_grad_kernel, dim3(a.block0[n_heads]), dim3(kBlock), 0, as_stream(stream), a);
+    if ((rc = check_launch("train_emulator_loss_grad_kernel"))) return rc;
+    hipLaunchKernelGGL(train_emulator_loss_finish_kernel, dim3(1), dim3(kEmuFinishThreads), 0, as_stream(stream), fin);
+    return check_launch("train_emulator_loss_finish_kernel");
 }
 
 extern "C" int fv3hip_train_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step, double lr,

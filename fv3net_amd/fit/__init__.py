@@ -19,6 +19,8 @@ from .forest import RandomForest, RandomForestHyperparameters, train_random_fore
 from .conv import ConvolutionalHyperparameters, HipConvolutionalModel, conv_spec_from_arrays, train_convolutional_model
 from .precipitative import (HipPrecipitativeModel, PrecipitativeHyperparameters, precipitative_spec_from_arrays,
                             train_precipitative_model)
+from .emulator_train import (ArchitectureConfig, CustomLoss, MicrophysicsConfig, NormFactory, OptimizerConfig, SliceConfig,
+                             TransformedParameters, TransformedTrainingResult, train_transformed_model)
 from .graph import (GraphHyperparameters, GraphUNetTwin, HipGraphAutoregressor, graph_unet_spec_from_state_dict,
                     state_dict_from_spec, train_graph_model, twin_from_spec)
 from .cyclegan import (GeneratorTwin, HipCycleGAN, cyclegan_spec_from_state_dict, cyclegan_state_dict_from_spec,
@@ -50,4 +52,6 @@ __all__ = [
     "InputSensitivity", "JacobianInputSensitivity", "RandomForestInputSensitivity",
     "RandomForestHyperparameters", "train_random_forest",
     "ConvolutionalHyperparameters", "train_convolutional_model",
+    "ArchitectureConfig", "CustomLoss", "MicrophysicsConfig", "NormFactory", "OptimizerConfig", "SliceConfig", "TransformedParameters",
+    "TransformedTrainingResult", "train_transformed_model",
 ]

@@ -1,0 +1,799 @@
+"""Training the microphysics emulators: fv3fit's ``"transformed"`` training function (external/fv3fit/fv3fit/train_microphysics.py:
+451-521, ``TransformedParameters`` / ``MicrophysicsConfig`` / ``CustomLoss``) for the architectures ``dense``, ``linear`` and
+``dense-local`` -- DESIGN.md section 26.
+
+* The configuration layer: plain dataclasses with the reference's field names and defaults; ``TransformedParameters.from_dict``
+  takes the body of a reference training YAML.
+* ``train_transformed_model``: a shared host preparation (forward transforms, normalisations fitted on the first
+  ``min(150 000, rows)`` rows, initial weights, resident network input), then one of two backends that start from bitwise-equal
+  parameters and see the same minibatches: ``_train_torch`` (torch expressions, autograd, ``optim.Adam``; runs on the CPU too)
+  and ``_train_hip`` (``fv3net_amd.train.EmulatorTrainer``: the dense trainer's GEMM and Adam kernels and one loss launch,
+  ``fv3hip_train_emulator_loss_grad``).  It returns the trained ``HipEmulator`` / ``HipLocalEmulator``, the composed transform and
+  the Keras-shaped history.
+
+What is this project's reading rather than the reference's behaviour (TensorFlow is on no machine we have):
+
+* The minibatches are ``torch.randperm`` per epoch from a generator seeded with ``seed``, as in ``train_dense_model``; the
+  reference's shuffle buffer (``shuffle_buffer_size``) is not reproduced.
+* ``history`` holds the arithmetic mean over the epoch's steps; how Keras weights a short last batch was not checked.
+* Adam is ``torch.optim.Adam``'s update (``train_adam_kernel``) with Keras's defaults (``epsilon = 1e-7``); Keras 2.8 places
+  epsilon slightly differently (``sqrt(v_hat) + eps`` against ``sqrt(v) / sqrt(1 - b2^t) + eps`` agree, its non-amsgrad kernel
+  folds the bias corrections into the step size and leaves ``eps`` uncorrected).
+* ``TerminateOnNaN`` looks per batch in the reference; here training stops after the first epoch whose mean loss is not finite.
+* The one-hot truth of a logit variable is expected in the data as ``[sample, z, channel]``: the class-producing transforms are
+  not built.
+"""
+import dataclasses
+from typing import Any, Dict, List, Mapping, Optional, Sequence, Set, Tuple
+
+import numpy as np
+import torch
+
+from .. import ops
+from ..emulation.models import HipEmulator, HipLocalEmulator
+from ..emulation.transforms import ComposedTransform, Difference, LogTransform, TransformedVariableConfig, transforms_from_config
+from ..local_mlp import LocalInput, LocalMlpSpec, LocalOutput
+from ..mlp import InputSpec, MlpSpec, OutputSpec, ResidualSpec
+from ..ops import EmulatorHead
+
+STD_DEV_METHODS = ("per_feature", "all", "all_center_all", "max", "mean", "none")   # StdDevMethod
+MEAN_METHODS = ("per_feature", "all", "none")                                       # MeanMethod
+NORMALIZATION_FIT_ROWS = 150_000    # train_ds.batch(150_000), train_microphysics.py:481
+_RNN_ARCHITECTURES = ("rnn", "rnn-v1", "rnn-v1-shared-weights")
+_ARCHITECTURES = ("dense", "linear", "dense-local") + _RNN_ARCHITECTURES
+# TrainConfig's own keys (data location, logging): read past by name, never by default
+_TRAIN_CONFIG_KEYS = ("train_url", "test_url", "transform", "nfiles", "nfiles_valid", "log_level", "save_only", "data_format",
+                      "nc_file_match")
+
+
+def _sample_2d(sample) -> np.ndarray:
+    a = np.asarray(sample, np.float64)
+    return a.reshape(a.shape[0], -1) if a.ndim != 2 else a
+
+
+def fit_center(sample, method: str) -> np.ndarray:
+    """``_compute_center`` (emulation/layers/normalization.py:146-152): accumulated in float64, rounded to float32."""
+    a = _sample_2d(sample)
+    if method == "per_feature":
+        return a.mean(axis=0).astype(np.float32)
+    if method == "all":
+        return np.float32(a.mean())
+    if method == "none":
+        return np.float32(0.0)
+    raise ValueError(f"MeanMethod must be one of {MEAN_METHODS}, got {method!r}")
+
+
+def fit_scale(sample, method: str) -> np.ndarray:
+    """``_compute_scale`` (normalization.py:105-164).  ``all`` centres on the per-feature mean rounded to float32, as
+    ``standard_deviation_all_features`` does."""
+    a = _sample_2d(sample)
+    if method == "per_feature":
+        return a.std(axis=0).astype(np.float32)
+    if method == "all":
+        mean = a.mean(axis=0).astype(np.float32).astype(np.float64)
+        return np.float32(np.sqrt(np.mean((a - mean) ** 2)))
+    if method == "all_center_all":
+        return np.float32(a.std())
+    if method == "max":
+        return np.float32(a.std(axis=0).max())
+    if method == "mean":
+        return np.float32(a.std(axis=0).mean())
+    if method == "none":
+        return np.float32(1.0)
+    raise ValueError(f"StdDevMethod must be one of {STD_DEV_METHODS}, got {method!r}")
+
+
+@dataclasses.dataclass
+class NormFactory:
+    """normalization.py:84-93; the methods are the ``StdDevMethod`` / ``MeanMethod`` names as strings."""
+
+    scale: str
+    center: str = "per_feature"
+    epsilon: Optional[float] = None
+
+    def __post_init__(self):
+        if self.scale not in STD_DEV_METHODS:
+            raise ValueError(f"StdDevMethod must be one of {STD_DEV_METHODS}, got {self.scale!r}")
+        if self.center not in MEAN_METHODS:
+            raise ValueError(f"MeanMethod must be one of {MEAN_METHODS}, got {self.center!r}")
+
+    def build(self, sample) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``(center, scale, forward scale)`` in float32: ``NormLayer.forward`` divides by ``scale + epsilon``, ``backward``
+        multiplies by ``scale`` (normalization.py:40-49)."""
+        center, scale = fit_center(sample, self.center), fit_scale(sample, self.scale)
+        forward = scale if self.epsilon is None else (scale + np.float32(self.epsilon)).astype(np.float32)
+        return center, scale, forward
+
+
+@dataclasses.dataclass
+class SliceConfig:
+    start: Optional[int] = None
+    stop: Optional[int] = None
+    step: Optional[int] = None
+
+    @property
+    def slice(self) -> slice:
+        return slice(self.start, self.stop, self.step)
+
+
+@dataclasses.dataclass
+class OptimizerConfig:
+    name: str = "Adam"
+    kwargs: Mapping[str, Any] = dataclasses.field(default_factory=dict)
+    learning_rate_schedule: Optional[Mapping] = None
+
+
+@dataclasses.dataclass
+class ArchitectureConfig:
+    """emulation/layers/architecture.py:444-471.  ``kwargs`` of the supported architectures: ``width`` (256), ``depth`` (2),
+    ``activation`` ("relu") of ``MLPBlock``; "linear" takes none."""
+
+    name: str
+    kwargs: Mapping[str, Any] = dataclasses.field(default_factory=dict)
+    output_channels: Mapping[str, int] = dataclasses.field(default_factory=dict)
+    kernel_regularizer: Mapping[str, Any] = dataclasses.field(default_factory=lambda: {"name": "none"})
+
+    def __post_init__(self):
+        if self.name not in _ARCHITECTURES:
+            raise KeyError(f"Unrecognized architecture key: {self.name}")
+
+
+@dataclasses.dataclass
+class MicrophysicsConfig:
+    """emulation/models/microphysics.py:24-59."""
+
+    input_variables: List[str] = dataclasses.field(default_factory=list)
+    direct_out_variables: List[str] = dataclasses.field(default_factory=list)
+    architecture: ArchitectureConfig = dataclasses.field(default_factory=lambda: ArchitectureConfig(name="linear"))
+    normalize_default: Optional[NormFactory] = dataclasses.field(default_factory=lambda: NormFactory(scale="all", center="per_feature"))
+    selection_map: Mapping[str, SliceConfig] = dataclasses.field(default_factory=dict)
+    normalize_map: Mapping[str, NormFactory] = dataclasses.field(default_factory=dict)
+    timestep_increment_sec: int = 900
+    unscaled_outputs: List[str] = dataclasses.field(default_factory=list)
+
+    @property
+    def output_variables(self) -> List[str]:
+        return list(self.direct_out_variables) + list(self.unscaled_outputs)
+
+    def norm_factory(self, name: str) -> Optional[NormFactory]:
+        return self.normalize_map.get(name, self.normalize_default)
+
+
+@dataclasses.dataclass
+class CustomLoss:
+    """emulation/losses.py:33-68."""
+
+    optimizer: OptimizerConfig = dataclasses.field(default_factory=lambda: OptimizerConfig("Adam"))
+    normalization: NormFactory = dataclasses.field(default_factory=lambda: NormFactory(scale="all", center="per_feature"))
+    normalization_map: Mapping[str, NormFactory] = dataclasses.field(default_factory=dict)
+    loss_variables: List[str] = dataclasses.field(default_factory=list)
+    metric_variables: List[str] = dataclasses.field(default_factory=list)
+    weights: Mapping[str, float] = dataclasses.field(default_factory=dict)
+    logit_variables: List[str] = dataclasses.field(default_factory=list)
+    bias_metric_variables: List[str] = dataclasses.field(default_factory=list)
+
+
+def _refuse(what: str):
+    raise NotImplementedError(f"{what} is not implemented by train_transformed_model (DESIGN.md section 26 lists what is)")
+
+
+def _transform_name(entry: Mapping) -> Optional[str]:
+    """The reference class a ``tensor_transform`` entry would build, for the ones that are refused; None for the two built."""
+    keys = set(entry)
+    if keys == {"to", "before", "after"}:
+        return None
+    if "transform" in keys and "source" in keys and keys <= {"source", "transform", "to"}:
+        inner = set(entry["transform"] or {})
+        return None if inner <= {"epsilon"} else "LimitValueTransform" if inner <= {"lower", "upper"} else f"univariate transform {sorted(inner)}"
+    if "condition_on" in keys or "bins" in keys:
+        return "ConditionallyScaled"
+    if "sphum_source" in keys:
+        return "CloudWaterDiffPrecpd"
+    if "gscond_route" in keys:
+        return "GscondRoute"
+    if "precpd_only" in keys:
+        return "PrecpdOnly"
+    if "cloud_in" in keys or "cloud_out" in keys:
+        return "MicrophysicsClassesV1OneHot" if entry.get("to") == "gscond_classes" else "MicrophysicsClasssesV1"
+    if "relative_humidity" in keys:
+        return "RelativeHumidity"
+    if "limit_cloud" in keys or {"cloud", "humidity", "temperature"} <= keys:
+        return "CloudLimiter"
+    return f"tensor transform {sorted(keys)}"
+
+
+def _norm_from_dict(d) -> Optional[NormFactory]:
+    if d is None or isinstance(d, NormFactory):
+        return d
+    unknown = set(d) - {"scale", "center", "epsilon"}
+    if unknown:
+        raise ValueError(f"NormFactory has no fields {sorted(unknown)}")
+    return NormFactory(**d)
+
+
+def _strict(cls, d: Mapping, what: str) -> Dict:
+    d = dict(d or {})
+    unknown = set(d) - {f.name for f in dataclasses.fields(cls)}
+    if unknown:
+        raise ValueError(f"{what} has no fields {sorted(unknown)}")
+    return d
+
+
+@dataclasses.dataclass
+class TransformedParameters:
+    """train_microphysics.py:120-182.  ``use_wandb``, ``wandb``, ``checkpoint_model``, ``checkpoint_interval``, ``out_url`` and
+    ``verbose`` are accepted so that a reference configuration parses; they do nothing here.  ``seed`` is this project's:
+    initial weights and the minibatch order follow from it.  ``tensor_transform`` holds ``emulation.transforms`` objects
+    (``Difference``, ``TransformedVariableConfig`` with ``LogTransform``)."""
+
+    tensor_transform: List[Any] = dataclasses.field(default_factory=list)
+    filters: List[Any] = dataclasses.field(default_factory=list)
+    model: Optional[MicrophysicsConfig] = None
+    loss: CustomLoss = dataclasses.field(default_factory=CustomLoss)
+    epochs: int = 1
+    batch_size: int = 128
+    valid_freq: int = 5
+    verbose: int = 2
+    shuffle_buffer_size: Optional[int] = 13824
+    checkpoint_model: bool = True
+    checkpoint_interval: int = 1
+    out_url: str = ""
+    use_wandb: bool = True
+    wandb: Mapping[str, Any] = dataclasses.field(default_factory=dict)
+    seed: int = 0
+
+    # -- the set logic of train_microphysics.py:233-261 for Difference and TransformedVariableConfig -----------------------
+    def _backward_names(self, requested: Set[str]) -> Set[str]:
+        requested = set(requested)
+        for t in self.tensor_transform[::-1]:
+            if isinstance(t, Difference):
+                if t.to in requested:
+                    requested = (requested - {t.to}) | {t.before, t.after}
+            elif t.to in requested:   # (a transform in place, ``to`` None, asks for nothing else)
+                requested = (requested - {t.to}) | {t.source}
+        return requested
+
+    def _backward_input_names(self) -> Set[str]:
+        names: Set[str] = set()
+        available: Set[str] = set()
+        for t in self.tensor_transform[::-1]:
+            if isinstance(t, Difference):
+                names |= {t.to, t.before} - available
+                available |= {t.after}
+        return names
+
+    def _backward_output_names(self) -> Set[str]:
+        return {t.after for t in self.tensor_transform if isinstance(t, Difference)}
+
+    @property
+    def _model(self) -> MicrophysicsConfig:
+        if self.model is None:
+            raise ValueError(".model not provided.")
+        return self.model
+
+    @property
+    def input_variables(self) -> Set[str]:
+        model_inputs, model_outputs = set(self._model.input_variables), set(self._model.output_variables)
+        return self._backward_names(model_inputs) | self._backward_names(self._backward_input_names() - model_outputs)
+
+    @property
+    def model_variables(self) -> Set[str]:
+        must_make = set(self.loss.loss_variables) - self._backward_output_names()
+        return self._backward_names(set(self._model.input_variables) | set(self._model.output_variables) | self._backward_input_names()
+                                    | self._backward_names(must_make))
+
+    @property
+    def transform(self) -> ComposedTransform:
+        return ComposedTransform(list(self.tensor_transform))
+
+    def check_supported(self) -> None:
+        """Raise ``NotImplementedError`` naming the first configured feature outside the scope of DESIGN.md section 26."""
+        model, loss = self._model, self.loss
+        arch = model.architecture
+        if arch.name in _RNN_ARCHITECTURES:
+            _refuse(f"architecture {arch.name!r} (backpropagation through the level sweep)")
+        if str((arch.kernel_regularizer or {}).get("name", "none")).lower() != "none":
+            _refuse(f"kernel_regularizer {arch.kernel_regularizer.get('name')!r}")
+        if self.filters:
+            _refuse(f"filters ({len(self.filters)} configured)")
+        if loss.bias_metric_variables:
+            _refuse(f"bias_metric_variables {list(loss.bias_metric_variables)}")
+        if loss.optimizer.name != "Adam":
+            _refuse(f"optimizer {loss.optimizer.name!r}")
+        if loss.optimizer.learning_rate_schedule is not None:
+            _refuse("learning_rate_schedule")
+        unknown = set(loss.optimizer.kwargs) - {"learning_rate", "beta_1", "beta_2", "epsilon"}
+        if unknown:
+            _refuse(f"Adam arguments {sorted(unknown)}")
+        for t in self.tensor_transform:
+            if not (isinstance(t, Difference) or (isinstance(t, TransformedVariableConfig) and isinstance(t.transform, LogTransform))):
+                _refuse(f"tensor transform {type(t).__name__}" + (f" with {type(t.transform).__name__}" if hasattr(t, "transform") else ""))
+        kwargs = dict(arch.kwargs)
+        if arch.name == "linear" and kwargs:
+            raise TypeError("No keyword arguments accepted for linear model")
+        if set(kwargs) - {"width", "depth", "activation"}:
+            raise TypeError(f"MLPBlock takes width, depth and activation, got {sorted(kwargs)}")
+        if kwargs.get("activation", "relu") != "relu":
+            _refuse(f"activation {kwargs['activation']!r}")
+
+    @classmethod
+    def from_dict(cls, mapping: Mapping) -> "TransformedParameters":
+        """From the body of a reference training YAML (the mapping under ``config:`` where the file has one).  Reads the fields of
+        this class, reads past ``TrainConfig``'s data-location and logging keys by name, raises ``ValueError`` on any other key
+        and ``NotImplementedError`` naming a feature outside the scope."""
+        d = dict(mapping)
+        for key in _TRAIN_CONFIG_KEYS:
+            d.pop(key, None)
+        d = _strict(cls, d, "TransformedParameters")
+        entries = list(d.pop("tensor_transform", None) or [])
+        for e in entries:
+            name = _transform_name(e)
+            if name is not None:
+                _refuse(f"tensor transform {name}")
+        if d.get("filters"):
+            _refuse(f"filters ({d['filters']})")
+        d.pop("filters", None)
+
+        loss_d = dict(d.pop("loss", None) or {})
+        if "zhao_carr_loss" in loss_d or "masked_weight" in loss_d:   # (the reference dispatches on the dummy field)
+            _refuse("ZhaoCarrLoss")
+        loss_d = _strict(CustomLoss, loss_d, "CustomLoss")
+        if "optimizer" in loss_d:
+            loss_d["optimizer"] = OptimizerConfig(**_strict(OptimizerConfig, loss_d["optimizer"], "OptimizerConfig"))
+        if "normalization" in loss_d:
+            loss_d["normalization"] = _norm_from_dict(loss_d["normalization"])
+        loss_d["normalization_map"] = {k: _norm_from_dict(v) for k, v in (loss_d.get("normalization_map") or {}).items()}
+        loss = CustomLoss(**loss_d)
+
+        model = None
+        if d.get("model") is not None:
+            model_d = _strict(MicrophysicsConfig, d["model"], "MicrophysicsConfig")
+            if "architecture" in model_d:
+                model_d["architecture"] = ArchitectureConfig(**_strict(ArchitectureConfig, model_d["architecture"], "ArchitectureConfig"))
+            if "normalize_default" in model_d:
+                model_d["normalize_default"] = _norm_from_dict(model_d["normalize_default"])
+            model_d["normalize_map"] = {k: _norm_from_dict(v) for k, v in (model_d.get("normalize_map") or {}).items()}
+            model_d["selection_map"] = {k: v if isinstance(v, SliceConfig) else SliceConfig(**_strict(SliceConfig, v, "SliceConfig"))
+                                        for k, v in (model_d.get("selection_map") or {}).items()}
+            model = MicrophysicsConfig(**model_d)
+        d.pop("model", None)
+        hp = cls(tensor_transform=transforms_from_config(entries).transforms, model=model, loss=loss, **d)
+        if model is not None:
+            hp.check_supported()
+        return hp
+
+
+# ---------------------------------------------------------------------------------------------
+# shared preparation
+# ---------------------------------------------------------------------------------------------
+def forward_transform32(hp: TransformedParameters, data: Mapping[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """The forward transforms in float32, in order, each where its inputs are present (``ComposedTransform.forward``):
+    ``log(max(x, eps))`` and ``to = after - before``."""
+    out = {k: np.asarray(v, np.float32) for k, v in data.items()}
+    for t in hp.tensor_transform:
+        if isinstance(t, Difference):
+            if t.after in out and t.before in out:
+                out[t.to] = out[t.after] - out[t.before]
+        elif t.source in out:
+            out[t.to or t.source] = np.log(np.maximum(out[t.source], np.float32(t.transform.epsilon)))
+    return out
+
+
+def _concat_batches(batches: Sequence[Mapping[str, np.ndarray]], names: Set[str]) -> Dict[str, np.ndarray]:
+    batches = list(batches)
+    if not batches:
+        raise ValueError("no batches")
+    missing = sorted(n for n in names if n not in batches[0])
+    if missing:
+        raise KeyError(f"the batches lack {missing}")
+    return {n: np.concatenate([np.asarray(b[n], np.float32) for b in batches], axis=0) for n in sorted(names)}
+
+
+def _columns(a: np.ndarray) -> np.ndarray:
+    return a[:, None] if a.ndim == 1 else a
+
+
+@dataclasses.dataclass
+class _EmulatorTraining:
+    """What both backends start from.  ``heads`` hold numpy arrays whose rows are the training rows followed by the validation
+    rows; ``xin`` likewise (``[rows * levels, K]`` for dense-local)."""
+
+    arch: str
+    levels: int
+    rows_train: int
+    rows_valid: int
+    xin: np.ndarray
+    heads: List[EmulatorHead]
+    slot_names: List[str]
+    head_sizes: List[int]
+    kernels: List[np.ndarray]      # hidden layers, then the concatenated head layer; [in, out]
+    biases: List[np.ndarray]
+    inputs: List[Any]              # InputSpec / LocalInput
+    outputs: List[Any]             # OutputSpec / LocalOutput
+    residuals: List[ResidualSpec]
+    adam: Dict[str, float]
+
+
+def _broadcast(v, n: int) -> np.ndarray:
+    return np.array(np.broadcast_to(np.asarray(v, np.float32), (n,)))
+
+
+def _input_source(hp: TransformedParameters, name: str) -> Tuple[str, str, float]:
+    """``(source, transform, eps)`` of the model input ``name`` in terms of the untransformed state."""
+    for t in hp.tensor_transform:
+        if isinstance(t, Difference) and t.to == name:
+            _refuse(f"the difference {name!r} as a model input")
+        if isinstance(t, TransformedVariableConfig) and (t.to or t.source) == name:
+            return t.source, "log", float(t.transform.epsilon)
+    return name, "none", 0.0
+
+
+def _prepare(hp: TransformedParameters, train_batches, validation_batches) -> _EmulatorTraining:
+    hp.check_supported()
+    model, loss, arch = hp._model, hp.loss, hp._model.architecture
+    local = arch.name == "dense-local"
+    for t in hp.tensor_transform:
+        if isinstance(t, TransformedVariableConfig) and (t.to or t.source) in model.output_variables:
+            _refuse(f"LogTransform on the model output {(t.to or t.source)!r}")
+    differences = {t.to: t for t in hp.tensor_transform if isinstance(t, Difference)}
+    after_of = {t.after: t for t in differences.values()}
+    scored = list(loss.loss_variables) + list(loss.logit_variables) + list(loss.metric_variables)
+    if len(set(scored)) != len(scored):
+        raise ValueError(f"a variable is listed twice among the loss, logit and metric variables: {scored}")
+    needed = set(hp.model_variables) | set(loss.logit_variables)
+    for name in scored:
+        if name in after_of:
+            needed |= {after_of[name].before, name}
+        else:
+            needed |= hp._backward_names({name})
+    raw = _concat_batches(train_batches, needed)
+    rows_train = next(iter(raw.values())).shape[0]
+    rows_valid = 0
+    if validation_batches is not None:
+        valid = _concat_batches(validation_batches, needed)
+        rows_valid = next(iter(valid.values())).shape[0]
+        raw = {k: np.concatenate([raw[k], valid[k]], axis=0) for k in raw}
+    data = forward_transform32(hp, raw)
+    nfit = min(NORMALIZATION_FIT_ROWS, rows_train)
+
+    # -- the network input -----------------------------------------------------------------------
+    names_in = sorted(model.input_variables)   # combine_inputs / combine_sequence_inputs
+    if local and model.selection_map:
+        _refuse("selection_map with dense-local")
+    levels = 1
+    if local:
+        levels = max(_columns(data[n]).shape[1] for n in names_in)
+    inputs, cols = [], []
+    for name in names_in:
+        a = _columns(data[name])
+        if a.ndim != 2:
+            raise ValueError(f"input {name!r} must be [sample, feature] or [sample], got {a.shape}")
+        factory = model.norm_factory(name)
+        center = forward = None
+        x = a
+        if factory is not None:
+            center, _, forward = factory.build(a[:nfit])
+            x = ((a - center) / forward).astype(np.float32)
+        source, transform, eps = _input_source(hp, name)
+        if local:
+            if a.shape[1] not in (1, levels):
+                raise ValueError(f"input {name!r} has {a.shape[1]} levels, the others {levels}")
+            cols.append(np.broadcast_to(x, (x.shape[0], levels)))
+            inputs.append(LocalInput(name=name, source=source, transform=transform, eps=eps,
+                                     center=None if center is None else np.atleast_1d(center),
+                                     scale=None if forward is None else np.atleast_1d(forward)))
+        else:
+            sel = model.selection_map[name].slice if name in model.selection_map else slice(None)
+            start, stop, step = sel.indices(a.shape[1])
+            if step != 1:
+                _refuse(f"selection_map[{name!r}] with step {step}")
+            nfeat = max(stop - start, 0)
+            cols.append(x[:, start:stop])
+            inputs.append(InputSpec(source=source, nfeat=nfeat, start=start, transform=transform, eps=eps,
+                                    center=None if center is None else _broadcast(center, a.shape[1])[start:stop],
+                                    scale=None if forward is None else _broadcast(forward, a.shape[1])[start:stop]))
+    if local:
+        xin = np.ascontiguousarray(np.stack(cols, axis=2).reshape(-1, len(cols)), np.float32)   # row r * nz + z
+    else:
+        xin = np.ascontiguousarray(np.concatenate(cols, axis=1), np.float32)
+
+    # -- the heads: direct_out_variables + unscaled_outputs ----------------------------------------
+    heads: List[EmulatorHead] = []
+    outputs, residuals, head_sizes = [], [], []
+    head_of: Dict[str, int] = {}
+    col0 = 0
+    for name in model.output_variables:
+        scaled = name in model.direct_out_variables
+        a = data[name]
+        channels = int(arch.output_channels.get(name, 1)) if local else 1
+        if (a.ndim == 3) != (channels > 1) or (a.ndim == 3 and (not local or a.shape[1:] != (levels, channels))):
+            raise ValueError(f"output {name!r} has shape {a.shape}; {channels} channel(s) on {levels} level(s) expected "
+                             "(a logit variable is [sample, z, channel] under dense-local)")
+        center = scale = None
+        factory = model.norm_factory(name) if scaled else None
+        if factory is not None:
+            if channels > 1:
+                _refuse(f"a normalised multi-channel output ({name!r}: list it under unscaled_outputs)")
+            center, scale, _ = factory.build(_columns(a)[:nfit])   # FieldOutput: backward, y * scale + center
+        diff = differences.get(name)
+        if local:
+            a2 = _columns(a) if channels == 1 else a
+            if channels == 1 and a2.shape[1] != levels:
+                _refuse(f"the single-level output {name!r} under dense-local (LocalMlpModel predicts none)")
+            ncol = channels
+            heads.append(EmulatorHead(kind="xent" if channels > 1 else "mse_local", col0=col0, ncol=ncol,
+                                      scale=None if scale is None else _broadcast(scale, levels),
+                                      center=None if center is None else _broadcast(center, levels)))
+            outputs.append(LocalOutput(name=name, channels=channels, scale=None if scale is None else np.atleast_1d(scale),
+                                       center=None if center is None else np.atleast_1d(center),
+                                       after=diff.after if diff else None, before=diff.before if diff else None))
+        else:
+            ncol = _columns(a).shape[1]
+            heads.append(EmulatorHead(kind="mse", col0=col0, ncol=ncol, scale=None if scale is None else _broadcast(scale, ncol),
+                                      center=None if center is None else _broadcast(center, ncol)))
+            outputs.append(OutputSpec(name=name, nfeat=ncol, scale=heads[-1].scale, center=heads[-1].center))
+            if diff:
+                residuals.append(ResidualSpec(name=diff.after, source=diff.before, output=name))
+        head_of[name] = len(heads) - 1
+        head_sizes.append(ncol)
+        col0 += ncol
+    if len(heads) > ops._lib.EMULATOR_MAX_HEADS:
+        raise ValueError(f"{len(heads)} outputs: the loss kernel's head table holds {ops._lib.EMULATOR_MAX_HEADS}")
+
+    # -- the loss terms, in slot order: loss, logit, metric variables ------------------------------
+    slot_names: List[str] = []
+    for name in scored:
+        slot = len(slot_names)
+        is_loss = name not in loss.metric_variables
+        weight = float(loss.weights.get(name, 1.0))
+        if not (np.isfinite(weight) and weight >= 0):
+            raise ValueError(f"the weight of {name!r} must be finite and >= 0, got {weight}")
+        if name in loss.logit_variables:
+            if name not in head_of or heads[head_of[name]].kind != "xent":
+                raise ValueError(f"logit variable {name!r} is no multi-channel output of a dense-local model")
+            h = heads[head_of[name]]
+            h.slot, h.target, h.weight, h.is_loss = slot, np.ascontiguousarray(data[name], np.float32), weight, True
+            slot_names.append(name)
+            continue
+        inv_of = loss.normalization_map.get(name, loss.normalization)
+        target = np.ascontiguousarray(_columns(data[name]), np.float32)
+        _, _, forward = inv_of.build(target[:nfit])     # NormalizedMSE: both sides through NormLayer.forward
+        if name in head_of:
+            h = heads[head_of[name]]
+            if h.kind == "xent":
+                raise ValueError(f"{name!r} is a multi-channel output: list it under logit_variables")
+            nt = levels if local else h.ncol
+            inv = (1.0 / _broadcast(forward, nt).astype(np.float64) ** 2).astype(np.float32)
+            h.slot, h.target, h.inv, h.weight, h.is_loss = slot, target, inv, weight, is_loss
+        elif name in after_of and after_of[name].to in head_of:
+            t = after_of[name]
+            h = heads[head_of[t.to]]
+            nt = levels if local else h.ncol
+            inv = (1.0 / _broadcast(forward, nt).astype(np.float64) ** 2).astype(np.float32)
+            h.slot_after, h.target_after, h.inv_after, h.weight_after, h.is_loss_after = slot, target, inv, weight, is_loss
+            h.before = np.ascontiguousarray(_columns(data[t.before]), np.float32)
+            if h.before.shape != target.shape:
+                raise ValueError(f"{t.before!r} {h.before.shape} and {name!r} {target.shape} differ in shape")
+        else:
+            raise ValueError(f"{name!r} is neither a model output nor the `after` field of a Difference on one")
+        slot_names.append(name)
+
+    # -- initial weights: Keras Dense / Conv1D(k = 1) defaults, glorot_uniform kernels and zero biases ----------------
+    torch.manual_seed(hp.seed)
+    kwargs = dict(arch.kwargs)
+    depth = 0 if arch.name == "linear" else int(kwargs.get("depth", 2))
+    width = int(kwargs.get("width", 256))
+    if local and depth < 1:
+        _refuse("dense-local without a hidden layer")
+
+    def glorot(fan_in: int, fan_out: int) -> np.ndarray:
+        w = torch.empty(fan_out, fan_in)
+        torch.nn.init.xavier_uniform_(w)
+        return np.ascontiguousarray(w.numpy().T)
+
+    kernels, biases, fan = [], [], xin.shape[1]
+    for _ in range(depth):
+        kernels.append(glorot(fan, width))
+        biases.append(np.zeros(width, np.float32))
+        fan = width
+    kernels.append(np.concatenate([glorot(fan, c) for c in head_sizes], axis=1))
+    biases.append(np.zeros(sum(head_sizes), np.float32))
+
+    okw = dict(loss.optimizer.kwargs)
+    adam = {"learning_rate": float(okw.get("learning_rate", 1e-3)), "beta_1": float(okw.get("beta_1", 0.9)),
+            "beta_2": float(okw.get("beta_2", 0.999)), "epsilon": float(okw.get("epsilon", 1e-7))}
+    return _EmulatorTraining(arch=arch.name, levels=levels, rows_train=rows_train, rows_valid=rows_valid, xin=xin, heads=heads,
+                             slot_names=slot_names, head_sizes=head_sizes, kernels=kernels, biases=biases, inputs=inputs, outputs=outputs,
+                             residuals=residuals, adam=adam)
+
+
+# ---------------------------------------------------------------------------------------------
+# the loss as torch expressions (the twin of fv3hip_train_emulator_loss_grad)
+# ---------------------------------------------------------------------------------------------
+def heads_to_torch(heads: Sequence[EmulatorHead], device, dtype=torch.float32) -> List[EmulatorHead]:
+    def up(a):
+        return None if a is None else torch.as_tensor(np.array(a), dtype=dtype, device=device)
+
+    arrays = ("scale", "center", "target", "inv", "before", "target_after", "inv_after")
+    return [dataclasses.replace(h, **{k: up(getattr(h, k)) for k in arrays}) for h in heads]
+
+
+def emulator_loss_torch(yhat: torch.Tensor, heads: Sequence[EmulatorHead], idx: torch.Tensor, levels: int = 1):
+    """``(loss, values)``: the multi-variable loss on the head layer's output ``yhat [n * levels, F]`` for the batch rows
+    ``idx``, ``values`` in slot order.  ``heads`` hold tensors of ``yhat``'s dtype (``heads_to_torch``)."""
+    n = int(idx.shape[0])
+    terms: Dict[int, Tuple[torch.Tensor, float, bool]] = {}
+    for h in heads:
+        y = yhat[:, h.col0:h.col0 + h.ncol]
+        if h.kind == "xent":
+            x = y.reshape(n, levels, h.ncol)
+            t = h.target[idx]
+            lse = torch.logsumexp(x, dim=-1, keepdim=True)
+            terms[h.slot] = ((t * (lse - x)).sum(dim=-1).mean(), h.weight, h.is_loss)
+            continue
+        if h.kind == "mse_local":
+            y = y.reshape(n, levels)
+            pick = (lambda v: v[..., 0:1]) if h.single_level else (lambda v: v)
+        else:
+            pick = (lambda v: v)
+        p = pick(y if h.scale is None else y * h.scale + h.center)
+        if h.slot is not None:
+            d = p - h.target[idx].reshape(p.shape)
+            terms[h.slot] = ((d * d * pick(h.inv)).mean(), h.weight, h.is_loss)
+        if h.slot_after is not None:
+            e = (h.before[idx].reshape(p.shape) + p) - h.target_after[idx].reshape(p.shape)
+            terms[h.slot_after] = ((e * e * pick(h.inv_after)).mean(), h.weight_after, h.is_loss_after)
+    values = [terms[s][0] for s in range(len(terms))]
+    loss = yhat.new_zeros(())
+    for s in range(len(terms)):
+        if terms[s][2]:
+            loss = loss + terms[s][1] * terms[s][0]
+    return loss, values
+
+
+def _history_append(history: Dict[str, list], means: Mapping[str, float], prefix: str = "") -> None:
+    for key, v in means.items():
+        history.setdefault(prefix + (key if key == "loss" else f"{key}_loss"), []).append(float(v))
+
+
+def _new_history(prep: "_EmulatorTraining") -> Dict[str, list]:
+    return {"loss": [], **{f"{name}_loss": [] for name in prep.slot_names}}
+
+
+def _minibatches(hp: TransformedParameters, prep: _EmulatorTraining, dev):
+    """Per epoch: the training minibatches (``torch.randperm`` from the seeded generator), then -- where this epoch validates --
+    the validation rows in order."""
+    g = torch.Generator().manual_seed(hp.seed)
+    n, nv = prep.rows_train, prep.rows_valid
+    for epoch in range(hp.epochs):
+        perm = torch.randperm(n, generator=g).to(dev)
+        train = [perm[i:i + hp.batch_size] for i in range(0, n, hp.batch_size)]
+        valid = []
+        if nv and (epoch + 1) % hp.valid_freq == 0:
+            rows = torch.arange(n, n + nv, dtype=torch.int64, device=dev)
+            valid = [rows[i:i + hp.batch_size] for i in range(0, nv, hp.batch_size)]
+        yield train, valid
+
+
+def _train_torch(hp: TransformedParameters, prep: _EmulatorTraining, dev: torch.device):
+    """Adam through torch expressions and autograd; returns ``(kernels, biases, history)``."""
+    L = prep.levels
+    xin = torch.from_numpy(prep.xin).to(dev)
+    xin3 = xin.view(-1, L, xin.shape[1])
+    heads = heads_to_torch(prep.heads, dev)
+    ws = [torch.from_numpy(k.copy()).to(dev).requires_grad_() for k in prep.kernels]
+    bs = [torch.from_numpy(b.copy()).to(dev).requires_grad_() for b in prep.biases]
+    a = prep.adam
+    opt = torch.optim.Adam(ws + bs, lr=a["learning_rate"], betas=(a["beta_1"], a["beta_2"]), eps=a["epsilon"])
+
+    def forward(idx):
+        h = xin3[idx].reshape(-1, xin.shape[1])
+        for l, (w, b) in enumerate(zip(ws, bs)):
+            h = h @ w + b
+            if l + 1 < len(ws):
+                h = torch.relu(h)
+        return emulator_loss_torch(h, heads, idx, L)
+
+    def means(sums, count):
+        return {"loss": sums[0] / count, **{name: sums[1 + s] / count for s, name in enumerate(prep.slot_names)}}
+
+    history = _new_history(prep)
+    for train, valid in _minibatches(hp, prep, dev):
+        sums = torch.zeros(1 + len(prep.slot_names), dtype=torch.float64)
+        for idx in train:
+            loss, values = forward(idx)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            sums += torch.stack([loss.detach()] + [v.detach() for v in values]).double().cpu()
+        _history_append(history, means(sums.tolist(), len(train)))
+        if valid:
+            sums = torch.zeros_like(sums)
+            with torch.no_grad():
+                for idx in valid:
+                    loss, values = forward(idx)
+                    sums += torch.stack([loss] + list(values)).double().cpu()
+            _history_append(history, means(sums.tolist(), len(valid)), "val_")
+        if not np.isfinite(history["loss"][-1]):
+            history["terminated_on_nan"] = True
+            break
+    return [w.detach().cpu().numpy() for w in ws], [b.detach().cpu().numpy() for b in bs], history
+
+
+def emulator_trainer(hp: TransformedParameters, prep: _EmulatorTraining, dev: torch.device):
+    """The device training state of ``backend="hip"``."""
+    from ..train import EmulatorTrainer
+
+    a = prep.adam
+    return EmulatorTrainer(prep.kernels, prep.biases, device=dev, xin=prep.xin, heads=prep.heads, slot_names=prep.slot_names,
+                           levels=prep.levels, max_batch=max(1, min(hp.batch_size, max(prep.rows_train, prep.rows_valid))),
+                           learning_rate=a["learning_rate"], betas=(a["beta_1"], a["beta_2"]), eps=a["epsilon"])
+
+
+def _train_hip(hp: TransformedParameters, prep: _EmulatorTraining, dev: torch.device):
+    """The same minibatches in the same order through ``fv3net_amd.train.EmulatorTrainer`` (csrc/mlp_train.hip); the epoch means
+    come from the device accumulator: one read-back per epoch."""
+    trainer = emulator_trainer(hp, prep, dev)
+    history = _new_history(prep)
+    for train, valid in _minibatches(hp, prep, dev):
+        for idx in train:
+            trainer.step(idx)
+        _history_append(history, trainer.epoch_means())
+        if valid:
+            for idx in valid:
+                trainer.evaluate(idx)
+            _history_append(history, trainer.epoch_means(), "val_")
+        if not np.isfinite(history["loss"][-1]):
+            history["terminated_on_nan"] = True
+            break
+    hidden_k, hidden_b, out_k, out_b = trainer.parameters()
+    return hidden_k + out_k, hidden_b + out_b, history
+
+
+@dataclasses.dataclass
+class TransformedTrainingResult:
+    """What ``train_transformed_model`` returns: the trained emulator (a callable on the untransformed state that returns the
+    model's outputs and the ``after`` fields; ``dump`` / ``emulation.models.load_emulator`` work on it), the composed tensor
+    transform and the history (a dict of lists, one entry per epoch; ``val_*`` one per validated epoch)."""
+
+    emulator: Any
+    transform: ComposedTransform
+    history: Dict[str, list]
+
+
+def emulator_from_weights(prep: _EmulatorTraining, kernels: Sequence[np.ndarray], biases: Sequence[np.ndarray]):
+    hidden_k = [np.ascontiguousarray(k, np.float32) for k in kernels[:-1]]
+    hidden_b = [np.ascontiguousarray(b, np.float32) for b in biases[:-1]]
+    out_k, out_b = np.ascontiguousarray(kernels[-1], np.float32), np.ascontiguousarray(biases[-1], np.float32)
+    if prep.arch == "dense-local":
+        spec = LocalMlpSpec(inputs=prep.inputs, hidden_kernels=hidden_k, hidden_biases=hidden_b, outputs=prep.outputs, out_kernel=out_k,
+                            out_bias=out_b)
+        spec.validate()
+        return HipLocalEmulator(spec)
+    spec = MlpSpec(inputs=prep.inputs, hidden_kernels=hidden_k, hidden_biases=hidden_b, outputs=prep.outputs, out_kernel=out_k,
+                   out_bias=out_b, residuals=prep.residuals)
+    spec.validate()
+    return HipEmulator(spec)
+
+
+def train_transformed_model(hyperparameters: TransformedParameters, train_batches: Sequence[Mapping[str, np.ndarray]],
+                            validation_batches: Optional[Sequence[Mapping[str, np.ndarray]]] = None, device: Optional[str] = None,
+                            backend: Optional[str] = None) -> TransformedTrainingResult:
+    """fv3fit's ``"transformed"`` training function for the ``dense``, ``linear`` and ``dense-local`` architectures with
+    ``CustomLoss`` (see the module docstring for the scope and for what is this project's reading of Keras).
+
+    ``train_batches`` / ``validation_batches``: sequences of mappings from name to ``[sample, feature]``, ``[sample]`` or -- the
+    one-hot truth of a logit variable -- ``[sample, z, channel]`` arrays; cast to float32 and concatenated.
+
+    ``backend``: ``None`` / ``"torch"`` trains through torch expressions, autograd and ``torch.optim.Adam`` (on the CPU too);
+    ``"hip"`` through the project's own kernels (needs a GPU).  Preparation, initial weights and minibatch order are shared."""
+    hp = hyperparameters
+    if backend not in (None, "torch", "hip"):
+        raise ValueError(f"backend must be None, 'torch' or 'hip', got {backend!r}")
+    hp.check_supported()   # before anything is uploaded
+    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    if backend == "hip" and dev.type != "cuda":
+        ops._require_device(torch.empty(0, device=dev))  # raises: there is no CPU path
+    prep = _prepare(hp, train_batches, validation_batches)
+    kernels, biases, history = (_train_hip if backend == "hip" else _train_torch)(hp, prep, dev)
+    return TransformedTrainingResult(emulator=emulator_from_weights(prep, kernels, biases), transform=hp.transform, history=history)

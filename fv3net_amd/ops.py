@@ -6,6 +6,7 @@ memory and the stream; no torch kernel does any of the arithmetic.  There is no 
 tensors must live on a ``cuda`` (ROCm) device.
 """
 import ctypes
+import dataclasses
 import os
 import math
 from typing import Optional, Sequence
@@ -1276,6 +1277,119 @@ def train_precip_loss_grad(yhat: torch.Tensor, scale1, center1, scale2, center2,
     _lib.call_on(dev, "fv3hip_train_precip_loss_grad", _ptr(yhat), ldy, *(_ptr(v) for v in vecs), float(inv_cstd2_3), _ptr(delp), ldd,
                  _ptr(physics_precip), _ptr(t1), _ptr(t2), ldt, _ptr(t3), rows, _ptr(idx), int(bool(couple)), int(has_dead), float(l1),
                  float(l2), _ptr(dy), lddy, _ptr(loss), _ptr(loss_workspace), _ptr(dq1), _ptr(dq2), _ptr(precip), n, nz, _stream(dev))
+    return dy, loss
+
+
+def train_emulator_loss_workspace_doubles() -> int:
+    return int(_lib.load().fv3hip_train_emulator_loss_workspace_doubles())
+
+
+@dataclasses.dataclass
+class EmulatorHead:
+    """One head of ``train_emulator_loss_grad`` (``fv3hip_emulator_head_t``).  ``kind``: ``"mse"`` (dense: ``ncol`` features,
+    tables ``[ncol]``, target rows ``[rows, ncol]``), ``"mse_local"`` (one column; tables ``[levels]``, target rows
+    ``[rows, levels]``, or ``[rows]`` / ``[rows, 1]`` with ``single_level``) or ``"xent"`` (``ncol`` channels, target
+    ``[rows, levels, ncol]``).  The direct term exists where ``slot`` is given, the after term where ``slot_after`` is; a term
+    with ``is_loss`` false is a metric."""
+
+    kind: str
+    col0: int
+    ncol: int = 1
+    single_level: bool = False
+    scale: Optional[torch.Tensor] = None
+    center: Optional[torch.Tensor] = None
+    slot: Optional[int] = None
+    target: Optional[torch.Tensor] = None
+    inv: Optional[torch.Tensor] = None
+    weight: float = 1.0
+    is_loss: bool = True
+    slot_after: Optional[int] = None
+    before: Optional[torch.Tensor] = None
+    target_after: Optional[torch.Tensor] = None
+    inv_after: Optional[torch.Tensor] = None
+    weight_after: float = 1.0
+    is_loss_after: bool = True
+
+
+_EMULATOR_KINDS = {"mse": _lib.EMULATOR_HEAD_MSE_DENSE, "mse_local": _lib.EMULATOR_HEAD_MSE_LOCAL, "xent": _lib.EMULATOR_HEAD_XENT}
+
+
+class EmulatorHeadTable:
+    """The head table of ``train_emulator_loss_grad`` in the library's form, built once: the descriptors as a host array (it goes
+    to the kernel by value), the tensors they point into kept alive, their common device and row count."""
+
+    def __init__(self, heads: Sequence[EmulatorHead], levels: int = 1):
+        self.heads, self.levels = list(heads), int(levels)
+        self.array = (_lib.EmulatorHead * max(len(self.heads), 1))()
+        self.n_slots = sum((h.slot is not None) + (h.slot_after is not None) for h in self.heads)
+        self.f = sum(int(h.ncol) for h in self.heads)
+        tensors, rows = [], set()
+
+        def resident(t, what, inner):
+            """(pointer, row stride) of a float32 array [rows, *inner] (or [rows] for one value a row) with contiguous rows."""
+            if t is None:
+                return None, 0
+            if t.dtype != torch.float32 or (t.dim() == 1 and _prod(inner) != 1) or (t.dim() > 1 and tuple(t.shape[1:]) != tuple(inner)):
+                raise ValueError(f"{what} must be a float32 [rows, {', '.join(str(i) for i in inner)}] tensor, got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+            if t.dim() > 1 and not t[0].is_contiguous():
+                raise ValueError(f"{what}: the values of a row must be contiguous")
+            tensors.append(t)
+            rows.add(int(t.shape[0]))
+            return t.data_ptr(), max(int(t.stride(0)), _prod(inner)) if t.shape[0] > 1 else _prod(inner)
+
+        for d, h in zip(self.array, self.heads):
+            if h.kind not in _EMULATOR_KINDS:
+                raise ValueError(f"head kind must be one of {sorted(_EMULATOR_KINDS)}, got {h.kind!r}")
+            d.kind, d.col0, d.ncol, d.single_level = _EMULATOR_KINDS[h.kind], int(h.col0), int(h.ncol), int(bool(h.single_level))
+            d.slot = -1 if h.slot is None else int(h.slot)
+            d.slot_after = -1 if h.slot_after is None else int(h.slot_after)
+            d.is_loss, d.is_loss_after = int(bool(h.is_loss)), int(bool(h.is_loss_after))
+            d.weight, d.weight_after = float(h.weight), float(h.weight_after)
+            nt = int(h.ncol) if h.kind == "mse" else self.levels   # the tables' length
+            inner = (self.levels, int(h.ncol)) if h.kind == "xent" else (1,) if h.single_level else (nt,)
+            for key in ("scale", "center", "inv", "inv_after"):
+                t = _vec(getattr(h, key), key, nt)
+                if t is not None:
+                    tensors.append(t)
+                setattr(d, key, None if t is None else t.data_ptr())
+            d.target, d.ld_target = resident(h.target, "target", inner)
+            d.before, d.ld_before = resident(h.before, "before", inner)
+            d.target_after, d.ld_target_after = resident(h.target_after, "target_after", inner)
+        if len(rows) > 1:
+            raise ValueError(f"the resident arrays differ in their rows: {sorted(rows)}")
+        self.rows = rows.pop() if rows else None   # (no resident array: any batch fits)
+        self.tensors = tensors
+        self.device = _require_device(*tensors) if tensors else None
+
+
+def train_emulator_loss_grad(yhat: torch.Tensor, table: EmulatorHeadTable, dy: Optional[torch.Tensor], values: torch.Tensor,
+                             loss: torch.Tensor, workspace: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                             accum: Optional[torch.Tensor] = None, n: Optional[int] = None):
+    """The multi-variable loss of the microphysics emulators and its gradient (see ``fv3hip_train_emulator_loss_grad``).
+    ``yhat`` / ``dy``: ``[n * levels, >= f]`` network rows (``dy`` None: loss only); ``values`` float64 ``[n_slots]``, ``loss``
+    float64 ``[1]``, ``accum`` float64 ``[1 + n_slots]`` or None, ``workspace`` ``train_emulator_loss_workspace_doubles()``
+    float64 values; ``idx`` the row table of the ``n`` batch rows."""
+    dev = _require_device(*(t for t in (yhat, dy, values, loss, workspace, idx, accum) if t is not None))
+    if table.device is not None and table.device != dev:
+        raise RuntimeError(f"the head table lives on {table.device}, the call on {dev}")
+    y_rows, y_feats, ldy = _rows_f32(yhat, "yhat")
+    levels = table.levels
+    _batch_rows(idx, 0)
+    n = int(n) if n is not None else (int(idx.shape[0]) if idx is not None else y_rows // levels)
+    if n < 1 or y_rows < n * levels or y_feats < table.f or (idx is not None and int(idx.shape[0]) < n):
+        raise ValueError(f"the batch has {n} rows of {levels} levels and {table.f} head features; yhat is {tuple(yhat.shape)}")
+    lddy = 0
+    if dy is not None:
+        d_rows, d_feats, lddy = _rows_f32(dy, "dy")
+        if d_rows < n * levels or d_feats < table.f:
+            raise ValueError(f"dy is {tuple(dy.shape)}, the batch needs [{n * levels}, {table.f}]")
+    for t, name, count in ((values, "values", table.n_slots), (loss, "loss", 1), (workspace, "workspace", train_emulator_loss_workspace_doubles()),
+                           (accum, "accum", 1 + table.n_slots)):
+        if t is not None and (t.dtype != torch.float64 or t.numel() < count or not t.is_contiguous()):
+            raise ValueError(f"{name} must hold {count} contiguous float64 values")
+    _lib.call_on(dev, "fv3hip_train_emulator_loss_grad", _ptr(yhat), ldy, n, levels, table.f, table.array, len(table.heads), table.n_slots,
+                 n if table.rows is None else table.rows, _ptr(idx), _ptr(dy), lddy, _ptr(values), _ptr(loss), _ptr(accum), _ptr(workspace), _stream(dev))
     return dy, loss
 
 

@@ -1,5 +1,6 @@
 """Training state of the dense column network on the device, and its Jacobian (csrc/mlp_train.hip);
-``PrecipitativeTrainer`` is the same state with the loss behind the precipitative closure (section 25).
+``PrecipitativeTrainer`` is the same state with the loss behind the precipitative closure (section 25), ``EmulatorTrainer`` with the
+multi-variable loss of the microphysics emulators (section 26).
 
 ``DenseTrainer`` owns every tensor the stateless ``fv3hip_train_*`` entry points work on: one flat float32 parameter buffer
 (per layer the kernel ``[in][out]`` followed by its bias; the heads are one concatenated layer, as ``MlpSpec.out_kernel`` is),
@@ -256,6 +257,103 @@ class PrecipitativeTrainer(DenseTrainer):
                                    la["inv_cstd2_2"], pl.inv_cstd2_3, self.delp, self.physics_precip, self.targets[:, :nz],
                                    self.targets[:, nz:], self.t3, self._dh[-1][:n], self._loss, self._loss_ws, idx=idx, couple=pl.couple,
                                    has_dead=pl.has_dead, l1=pl.l1, l2=pl.l2)
+
+
+class EmulatorTrainer(DenseTrainer):
+    """The dense trainer with the multi-variable loss of the microphysics emulators (``ops.train_emulator_loss_grad``, DESIGN.md
+    section 26).  ``heads``: ``ops.EmulatorHead`` descriptors holding numpy arrays (uploaded here); ``slot_names[s]`` names the
+    variable of slot ``s``.  ``levels = 1``: the "dense" / "linear" architectures, ``xin [rows, K]``.  ``levels = nz``:
+    "dense-local", ``xin [rows * nz, n_inputs]`` (row ``r * nz + z``); the inherited GEMMs then run on ``n * nz`` network rows
+    whose row table ``idx * nz + arange(nz)`` is written into a preallocated buffer, and ``max_batch`` still counts batch rows.
+
+    Every ``step`` / ``backward`` / ``evaluate`` adds its loss and values into a device accumulator; ``epoch_means`` reads and
+    clears it.  The number of calls is counted on the host: after replaying a captured step pass ``epoch_means(steps=...)``."""
+
+    def __init__(self, kernels: Sequence[np.ndarray], biases: Sequence[np.ndarray], device="cuda", *, xin: np.ndarray, heads: Sequence,
+                 slot_names: Sequence[str], levels: int = 1, max_batch: int = 512, learning_rate: float = 1e-3,
+                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-7, relu: bool = True):
+        self.levels, self.batch_cap = int(levels), int(max_batch)
+        super().__init__(kernels, biases, device=device, max_batch=self.batch_cap * self.levels, learning_rate=learning_rate, betas=betas,
+                         eps=eps, relu=relu)
+        dev = self.device
+        self.xin = torch.from_numpy(np.ascontiguousarray(xin, np.float32)).to(dev)
+        if self.xin.dim() != 2 or self.xin.shape[1] != self.k_in or self.xin.shape[0] % self.levels:
+            raise ValueError(f"xin {tuple(self.xin.shape)} does not match {self.k_in} inputs and {self.levels} levels")
+        self.rows = int(self.xin.shape[0]) // self.levels
+
+        def up(a):
+            return None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
+
+        arrays = ("scale", "center", "target", "inv", "before", "target_after", "inv_after")
+        self.heads = [dataclasses.replace(h, **{k: up(getattr(h, k)) for k in arrays}) for h in heads]
+        self.table = ops.EmulatorHeadTable(self.heads, self.levels)
+        if self.table.f != self.f_out or (self.table.rows is not None and self.table.rows != self.rows):
+            raise ValueError(f"the heads cover {self.table.f} features of {self.table.rows} rows, the network has {self.f_out} "
+                             f"and {self.rows}")
+        self.slot_names = list(slot_names)
+        if len(self.slot_names) != self.table.n_slots:
+            raise ValueError(f"{len(self.slot_names)} slot names for {self.table.n_slots} slots")
+        ns = self.table.n_slots
+        self._values = torch.zeros(max(ns, 1), dtype=torch.float64, device=dev)
+        self._accum = torch.zeros(1 + ns, dtype=torch.float64, device=dev)
+        self._accum_calls = 0
+        self._emu_ws = torch.zeros(ops.train_emulator_loss_workspace_doubles(), dtype=torch.float64, device=dev)
+        self._batch_idx: Optional[torch.Tensor] = None
+        if self.levels > 1:
+            self._level = torch.arange(self.levels, dtype=torch.int64, device=dev)
+            self._row0 = torch.zeros(self.batch_cap, dtype=torch.int64, device=dev)
+            self._net_idx = torch.zeros(self.batch_cap * self.levels, dtype=torch.int64, device=dev)
+
+    def _network_rows(self, idx: torch.Tensor) -> torch.Tensor:
+        n = int(idx.shape[0])
+        if not 1 <= n <= self.batch_cap:
+            raise ValueError(f"a batch of {n} rows does not fit the buffers of {self.batch_cap}")
+        if self.levels == 1:
+            return idx
+        net = self._net_idx[:n * self.levels]
+        torch.mul(idx, self.levels, out=self._row0[:n])
+        torch.add(self._row0[:n].unsqueeze(1), self._level, out=net.view(n, self.levels))
+        return net
+
+    def backward(self, idx: torch.Tensor) -> None:
+        self._batch_idx = idx
+        super().backward(self._network_rows(idx))
+
+    def _loss_grad(self, net_idx: torch.Tensor, m: int) -> None:
+        ops.train_emulator_loss_grad(self._h[-1][:m], self.table, self._dh[-1][:m], self._values, self._loss, self._emu_ws,
+                                     idx=self._batch_idx, accum=self._accum)
+        self._accum_calls += 1
+
+    def loss_stage(self, idx: torch.Tensor):
+        """The loss launch alone on the head layer's output that the last ``step`` / ``backward`` / ``evaluate`` of a batch of
+        this size left: ``(yhat, dY)``, views of the trainer's buffers ``[n * levels, F]``; ``loss`` and ``values`` are updated
+        (and the accumulator: it counts as a call)."""
+        m = int(idx.shape[0]) * self.levels
+        self._batch_idx = idx
+        self._loss_grad(None, m)
+        return self._h[-1][:m], self._dh[-1][:m]
+
+    def evaluate(self, idx: torch.Tensor, accumulate: bool = True) -> None:
+        """Forward and loss only on the rows ``idx``: no gradient is written, no parameter or moment touched."""
+        net = self._network_rows(idx)
+        m = int(net.shape[0])
+        self._forward(self.xin, net, m)
+        ops.train_emulator_loss_grad(self._h[-1][:m], self.table, None, self._values, self._loss, self._emu_ws, idx=idx,
+                                     accum=self._accum if accumulate else None)
+        self._accum_calls += int(accumulate)
+
+    def values(self) -> Dict[str, float]:
+        """The per-variable values of the last call, read back."""
+        host = self._values.cpu().numpy()
+        return {name: float(host[s]) for s, name in enumerate(self.slot_names)}
+
+    def epoch_means(self, steps: Optional[int] = None) -> Dict[str, float]:
+        """``{"loss": ..., name: ...}``: the accumulator divided by the calls since it was last cleared; clears it."""
+        calls = self._accum_calls if steps is None else int(steps)
+        host = self._accum.cpu().numpy() / max(calls, 1)
+        self._accum.zero_()
+        self._accum_calls = 0
+        return {"loss": float(host[0]), **{name: float(host[1 + s]) for s, name in enumerate(self.slot_names)}}
 
 
 def predict_graph_jacobians(spec, profiles: Mapping[str, np.ndarray], device="cuda", trainer: Optional[DenseTrainer] = None,

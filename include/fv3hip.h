@@ -1253,6 +1253,71 @@ int fv3hip_train_precip_loss_grad(const float *yhat, int64_t ldy, const float *s
                                   float l2, float *dY, int64_t lddy, double *loss, double *loss_workspace, float *dq1, float *dq2,
                                   float *precip, int64_t n, int nz, void *stream);
 
+/* ---- the multi-variable loss of the microphysics emulators (fv3fit's "transformed" training function, train_microphysics.py:
+ * 451-521; CustomLoss / _MultiVariableLoss, emulation/losses.py:33-146) and its gradient with respect to
+ * the raw output of the concatenated head layer.  Stateless like the other fv3hip_train_* entries: the caller owns every DEVICE
+ * pointer, nothing is allocated, copied or synchronised, every argument is checked on the host before any HIP call, and the two
+ * launches can be captured.  The head table is a HOST array; it goes to the kernel by value.
+ *
+ *   yhat [n * levels][ldy]   network row m = b * levels + z of batch row b and level z; levels = 1 for the "dense" and "linear"
+ *                            architectures, nz for "dense-local".
+ *   idx                      the row table of the n batch rows (int64, DEVICE) or null: batch row b is row idx[b] of the resident
+ *                            arrays; an index outside [0, rows) reads its targets as NaN and `before` as 0.
+ *   dY [n * levels][lddy]    null: loss only.  Else it receives the gradient of `loss` for every column < f (0 for a head
+ *                            without a loss term); columns >= f are never written.
+ *   heads                    n_heads <= FV3HIP_EMULATOR_MAX_HEADS descriptors in ascending column order that tile [0, f) exactly.
+ *
+ * A head owns columns [col0, col0 + ncol) and is one of
+ *   FV3HIP_EMULATOR_HEAD_MSE_DENSE  (levels == 1) ncol features; its tables (scale, center, inv, inv_after) and target rows are
+ *                                   indexed by the feature j.
+ *   FV3HIP_EMULATOR_HEAD_MSE_LOCAL  (ncol == 1)   tables and target rows are indexed by the level z.  single_level: only z = 0
+ *                                   carries the terms (RNNOutput.call reads rnn_outputs[..., 0:1, :]), the count is n, target
+ *                                   rows hold one value, and dY is 0 at the other levels.
+ *   FV3HIP_EMULATOR_HEAD_XENT       (2 <= ncol <= 32 channels) softmax cross-entropy per (row, level) point against
+ *                                   target [rows][ld_target] holding [levels][ncol] per row; direct term only, no tables.
+ * An MSE head has an optional direct term (slot >= 0: target, inv) and an optional after term (slot_after >= 0: before,
+ * target_after, inv_after), Difference.backward's after = before + difference.  weight must be finite and >= 0; is_loss 0 makes
+ * the term a metric: it is reported and adds nothing to dY (its g term below is skipped, so a NaN of a metric target stays out
+ * of dY).  With count = n ncol (dense), n levels (local, cross-entropy) or n (single level), wgrad = (float)(weight / count) and
+ * wval = 1 / count, per element in float32, every product and sum rounded and taken left to right (t: the table index, r: the
+ * resident row):
+ *     p  = scale ? yhat * scale[t] + center[t] : yhat
+ *     d  = p - target[r][t]                        value_d += d^2 inv[t];         g  = 2 d inv[t] wgrad
+ *     a  = before[r][t] + p;  e = a - target_after[r][t]
+ *                                                  value_a += e^2 inv_after[t];   g  = g + 2 e inv_after[t] wgrad_after
+ *     dY = scale ? g * scale[t] : g
+ * and per cross-entropy point with logits x_c and truth t_c (c ascending):
+ *     mx = max_c x_c;  s = sum_c expf(x_c - mx);  lse = mx + logf(s);  st = sum_c t_c
+ *     value += t_c (lse - x_c) for every c;        dY_c = (expf(x_c - lse) st - t_c) wgrad
+ * The values are float64 sums of these float32 terms: per lane, then the block's fixed tree, one partial per block and term in
+ * `workspace` (fv3hip_train_emulator_loss_workspace_doubles() doubles); the second launch adds each slot's partials in ascending
+ * block order and writes values[slot] = sum * wval and loss[0] = the sum over the loss slots, in slot order, of weight *
+ * values[slot].  The slots of the table must be 0 .. n_slots - 1, each used once.  accum (DEVICE, 1 + n_slots doubles, or null):
+ * loss and every value are added into it by one thread in that order, so an epoch's means need no read-back per step.  No
+ * atomics: the result depends on the shapes only.  A NaN or inf in one element reaches dY in that element only (in that point's
+ * channels for cross-entropy) and its own slot only.
+ * Bounds: 1 <= n, levels and n * levels <= 2^24; 1 <= f <= 2^20; ldy, lddy >= f; ld_target, ld_target_after, ld_before at least
+ * the extent of a row (ncol; levels; 1 for a single level; levels * ncol for cross-entropy); rows >= 1, and rows >= n without a
+ * row table. */
+#define FV3HIP_EMULATOR_MAX_HEADS 16
+#define FV3HIP_EMULATOR_HEAD_MSE_DENSE 0
+#define FV3HIP_EMULATOR_HEAD_MSE_LOCAL 1
+#define FV3HIP_EMULATOR_HEAD_XENT 2
+typedef struct {
+    int kind, col0, ncol, single_level;
+    int slot, slot_after;             /* -1: no such term */
+    int is_loss, is_loss_after;
+    double weight, weight_after;
+    const float *scale, *center;      /* both or neither */
+    const float *target, *inv;
+    const float *before, *target_after, *inv_after;
+    int64_t ld_target, ld_before, ld_target_after;
+} fv3hip_emulator_head_t;
+int fv3hip_train_emulator_loss_workspace_doubles(void);
+int fv3hip_train_emulator_loss_grad(const float *yhat, int64_t ldy, int64_t n, int levels, int f, const fv3hip_emulator_head_t *heads,
+                                    int n_heads, int n_slots, int64_t rows, const int64_t *idx, float *dY, int64_t lddy,
+                                    double *values, double *loss, double *accum, double *workspace, void *stream);
+
 /* ---- training the convolutional network (fv3fit's "convolutional" training function, keras/_models/convolutional.py:101-210,
  * shared/convolutional_network.py:59-195).  Stateless like fv3hip_train_linear_*: the caller owns every
  * DEVICE pointer, the workspace included; nothing is allocated or synchronised; all arguments are checked on the host before any
