@@ -469,6 +469,19 @@ SIGNATURES = {
                                             c_int64, c_int, c_int, c_void_p]),
     "fv3hip_train_adamw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_double, c_double, c_double, c_double,
                                    c_double, c_void_p]),
+    "fv3hip_cyclegan_train_chunk_cells": (c_int, []),
+    "fv3hip_cyclegan_train_backward_data_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int, c_int]),
+    "fv3hip_cyclegan_train_backward_weight_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int, c_int]),
+    "fv3hip_cyclegan_train_conv": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                           c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fv3hip_cyclegan_train_backward_data": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                                    c_void_p, c_size_t, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fv3hip_cyclegan_train_backward_weight": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                                      c_void_p, c_void_p, c_size_t, c_int64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                      c_void_p]),
+    "fv3hip_cyclegan_train_norm_backward": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                                    c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64,
+                                                    c_int, c_int, c_void_p]),
     "fv3hip_forest_train_chunk": (c_int, []),
     "fv3hip_forest_train_begin": (c_int, [POINTER(ForestTrain), c_int64, c_void_p]),
     "fv3hip_forest_train_level": (c_int, [POINTER(ForestTrain), c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_int64,

@@ -14,6 +14,7 @@
 // way, with the statistics and the bias cell of the face the value comes from.
 //   regular     k x k, stride 1, halo (k - 1) / 2:  output (x, y) reads (x + dx - h, y + dy - h)
 //   strided     4 x 4, stride 2, halo 1:            output (x, y) reads (2 x - 1 + dx, 2 y - 1 + dy)
+//               (3 x 3 as well behind fv3hip_cyclegan_train_conv: the discriminator's default)
 //   transposed  ConvTranspose2d(4, stride 2) of the input padded by one halo line, cropped by 3: per axis output 2 m takes
 //               tap 1 of cell m and tap 3 of cell m - 1, output 2 m + 1 tap 0 of cell m + 1 and tap 2 of cell m; the four
 //               output parities are four 2 x 2 convolutions (gridDim.z) with their own weight blocks
@@ -111,8 +112,8 @@ __global__ __launch_bounds__(kBlock) void cyclegan_conv_kernel(const ConvArgs a)
                 sx = x + tap / a.k - a.h;
                 sy = y + tap % a.k - a.h;
             } else if (a.kind == FV3HIP_CYCLEGAN_CONV_STRIDED) {
-                sx = 2 * x - 1 + (tap >> 2);
-                sy = 2 * y - 1 + (tap & 3);
+                sx = 2 * x - 1 + tap / a.k;
+                sy = 2 * y - 1 + tap % a.k;
             } else {
                 const int ta = tap >> 1, tb = tap & 1;
                 sx = x + (px ? 1 - ta : -ta);
@@ -353,12 +354,13 @@ bool same_slice(const Slice &a, const Slice &b)
     return a.p == b.p && a.ld == b.ld && a.off == b.off && a.ss == b.ss && a.c == b.c && a.n == b.n;
 }
 
-// both convolution entry points: every argument is checked here, before any HIP call
+// all convolution entry points: every argument is checked here, before any HIP call.  train: the forward of the training
+// layers (fv3hip_cyclegan_train_conv), which also takes the 3 x 3 strided convolution
 int launch_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, const float *in_mean,
                 const float *in_rstd, const float *in_bias, int in_relu, const float *w, const float *bias, const float *out_bias,
                 float *dst, int64_t dst_ld, int64_t dst_off, int64_t dst_sample_stride, int64_t n_samples, int n, int c_in, int c_out,
                 int kind, int k, int halo_mode, const float *ctx_cell, int c_cell, const float *ctx_uniform, int c_uni,
-                const float *w_ctx, void *stream)
+                const float *w_ctx, void *stream, bool train = false)
 {
     FV3HIP_REQUIRE(c_in >= 1 && c_out >= 1 && c_in <= (1 << 16) && c_out <= (1 << 16), "c_in and c_out must be in [1, 2^16], got %d, %d",
                    c_in, c_out);
@@ -371,7 +373,11 @@ int launch_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_s
     if (kind == FV3HIP_CYCLEGAN_CONV_REGULAR) {
         if (k != 3 && k != 5 && k != 7) return fail(FV3HIP_EUNSUPPORTED, "regular convolution with k = %d: 3, 5 and 7 are built", k);
     } else if (kind == FV3HIP_CYCLEGAN_CONV_STRIDED || kind == FV3HIP_CYCLEGAN_CONV_TRANSPOSED) {
-        if (k != 4) return fail(FV3HIP_EUNSUPPORTED, "strided and transposed convolutions are built for k = 4, got %d", k);
+        if (train && kind == FV3HIP_CYCLEGAN_CONV_STRIDED) {
+            if (k != 3 && k != 4) return fail(FV3HIP_EUNSUPPORTED, "strided convolution with k = %d: 3 and 4 are built", k);
+        } else if (k != 4) {
+            return fail(FV3HIP_EUNSUPPORTED, "strided and transposed convolutions are built for k = 4, got %d", k);
+        }
         h = 1;
         if (kind == FV3HIP_CYCLEGAN_CONV_STRIDED) {
             FV3HIP_REQUIRE(n % 2 == 0, "n must be even for the stride-2 convolution, got %d", n);
@@ -458,6 +464,14 @@ extern "C" int fv3hip_cyclegan_conv(const float *src, int64_t src_ld, int64_t sr
 {
     return launch_conv(src, src_ld, src_off, src_sample_stride, in_mean, in_rstd, in_bias, in_relu, w, bias, out_bias, dst, dst_ld,
                        dst_off, dst_sample_stride, n_samples, n, c_in, c_out, kind, k, halo_mode, nullptr, 0, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int fv3hip_cyclegan_train_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, const float *w,
+                                          const float *bias, float *dst, int64_t dst_ld, int64_t dst_off, int64_t dst_sample_stride,
+                                          int64_t n_samples, int n, int c_in, int c_out, int kind, int k, int halo_mode, void *stream)
+{
+    return launch_conv(src, src_ld, src_off, src_sample_stride, nullptr, nullptr, nullptr, 0, w, bias, nullptr, dst, dst_ld, dst_off,
+                       dst_sample_stride, n_samples, n, c_in, c_out, kind, k, halo_mode, nullptr, 0, nullptr, 0, nullptr, stream, true);
 }
 
 extern "C" int fv3hip_cyclegan_conv_context(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride,

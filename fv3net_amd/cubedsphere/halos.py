@@ -76,6 +76,62 @@ def append_halos_tensor(field: torch.Tensor, n_halo: int) -> torch.Tensor:
     return fill_halos(field, halo_strips(edge_strips(field, n_halo), range(6)))
 
 
+class _PaddedTile(torch.autograd.Function):
+    """One tile of ``append_halos_tensor`` as an autograd node of its own: forward ``[6, ..., n, n] -> [..., n + 2 h, n + 2 h]``
+    for tile ``t``; backward the tile's own cells and the four neighbours' strips it shows, zero elsewhere.  The tiles are
+    dimension ``tile_dim`` of the input as it is given, so that the node hangs on the caller's tensor itself."""
+
+    @staticmethod
+    def forward(ctx, field, n_halo, t, tile_dim):
+        field = field.movedim(tile_dim, 0)
+        ctx.n_halo, ctx.t, ctx.tile_dim, ctx.meta = n_halo, t, tile_dim, (field.shape, field.dtype, field.device)
+        return fill_halos(field[t:t + 1], halo_strips(edge_strips(field, n_halo), [t]))[0]
+
+    @staticmethod
+    def backward(ctx, d):
+        h, t = ctx.n_halo, ctx.t
+        shape, dtype, device = ctx.meta
+        n = shape[-1]
+        mid = slice(h, h + n)
+        g = torch.zeros(shape, dtype=dtype, device=device)
+        g[t] = d[..., mid, mid]
+        lines = lambda pick: torch.stack([pick(dl) for dl in range(h)], dim=-2)   # noqa: E731  [..., h, n], line 0 next to the tile
+        shown = [lines(lambda dl: d[..., h - 1 - dl, mid]), lines(lambda dl: d[..., h + n + dl, mid]),
+                 lines(lambda dl: d[..., mid, h - 1 - dl]), lines(lambda dl: d[..., mid, h + n + dl])]
+        for side, (axis, high) in enumerate(SIDES):
+            nbr, nbr_axis = FV3_FACE_CONNECTIONS[t][axis][high]
+            rows = shown[side] if nbr_axis == axis else shown[side].flip(-1)
+            k = _ROW[(nbr_axis, "first" if high else "last")]    # the neighbour's edge strip (edge_strips): line d inward
+            if k == 0:
+                g[nbr][..., 0:h, :] = rows
+            elif k == 1:
+                g[nbr][..., n - h:n, :] = rows.flip(-2)
+            elif k == 2:
+                g[nbr][..., :, 0:h] = rows.transpose(-1, -2)
+            else:
+                g[nbr][..., :, n - h:n] = rows.flip(-2).transpose(-1, -2)
+        return g.movedim(0, ctx.tile_dim), None, None, None
+
+
+def append_halos_tensor_reference_order(field: torch.Tensor, n_halo: int, tile_dim: int = 0) -> torch.Tensor:
+    """``append_halos_tensor`` (the same values; the tiles are dimension ``tile_dim`` of ``field`` and of the result) whose
+    gradient reaches ``field`` as the reference's torch module ``AppendHalos`` (modules.py:425-543) sends it.
+
+    A cell within ``n_halo`` of two edges is shown three times -- itself and once in the halo of each of two neighbours -- and a
+    sum of three floats depends on which two are added first; a tensor that something else reads as well (the input of a
+    residual block) gets a further term.  ``append_halos_tensor`` is a few batched gathers, so autograd adds a cell's own term,
+    then the y sides', then the x sides', and hands the sum over as one term.  The reference builds tile after tile from
+    slices of its input, so autograd adds, one by one and after whatever was created later, the terms of the tiles that show
+    the cell (the cell's own tile for its own position) by descending tile number.  Here every padded tile is an autograd node
+    of its own, created in tile order, which gives that order; the plain-torch twins pad with this function, and a float64
+    training step of theirs then repeats the reference's bit for bit."""
+    if field.shape[tile_dim] != 6:
+        raise ValueError(f"dimension {tile_dim} must hold the six tiles of the cube, got {field.shape[tile_dim]}")
+    if n_halo == 0:
+        return field
+    return torch.stack([_PaddedTile.apply(field, n_halo, t, tile_dim) for t in range(6)], dim=tile_dim)
+
+
 def append_halos(ds, n_halo: int, x_dim: str = "x", y_dim: str = "y"):
     """``fv3fit._shared.halos.append_halos``: a dataset (or data array) with ``tile``, ``x`` and ``y`` dimensions and exactly six
     tiles, padded by ``n_halo`` along ``x`` and ``y``; coordinates are dropped; ``n_halo = 0`` returns the input.  A bare

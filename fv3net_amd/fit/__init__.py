@@ -25,6 +25,9 @@ from .graph import (GraphHyperparameters, GraphUNetTwin, HipGraphAutoregressor, 
                     state_dict_from_spec, train_graph_model, twin_from_spec)
 from .cyclegan import (GeneratorTwin, HipCycleGAN, cyclegan_spec_from_state_dict, cyclegan_state_dict_from_spec,
                        generator_spec_from_state_dict)
+from .cyclegan_train import (CycleGANGeneratorConfig, CycleGANHyperparameters, CycleGANNetworkConfig, CycleGANOptimizerConfig,
+                             CycleGANSchedulerConfig, CycleGANTrainer, CycleGANTrainingConfig, DiscriminatorConfig, DiscriminatorTwin,
+                             HipDiscriminator, ImagePool, LossConfig, train_cyclegan)
 from .fmr import (HipFullModelReplacement, RecurrentGeneratorTwin, fmr_spec_from_state_dict, fmr_state_dict_from_spec,
                   recurrent_generator_spec_from_state_dict, recurrent_twin_from_spec)
 from .reservoir import (BatchLinearRegressor, BatchLinearRegressorHyperparameters, CubedsphereSubdomainConfig, DenseAutoencoder,
@@ -44,6 +47,8 @@ __all__ = [
     "GraphHyperparameters", "GraphUNetTwin", "HipGraphAutoregressor", "graph_unet_spec_from_state_dict", "state_dict_from_spec",
     "train_graph_model", "twin_from_spec",
     "GeneratorTwin", "HipCycleGAN", "cyclegan_spec_from_state_dict", "cyclegan_state_dict_from_spec", "generator_spec_from_state_dict",
+    "CycleGANGeneratorConfig", "CycleGANHyperparameters", "CycleGANNetworkConfig", "CycleGANOptimizerConfig", "CycleGANSchedulerConfig",
+    "CycleGANTrainer", "CycleGANTrainingConfig", "DiscriminatorConfig", "DiscriminatorTwin", "HipDiscriminator", "ImagePool", "LossConfig", "train_cyclegan",
     "HipFullModelReplacement", "RecurrentGeneratorTwin", "fmr_spec_from_state_dict", "fmr_state_dict_from_spec",
     "recurrent_generator_spec_from_state_dict", "recurrent_twin_from_spec",
     "DenseAutoencoder", "DenseAutoencoderHyperparameters", "SkTransformer", "train_dense_autoencoder",

@@ -18,7 +18,7 @@ import torch
 import yaml
 
 from ..cubedsphere._device import compute_device, download_all, on_device
-from ..cubedsphere.halos import append_halos_tensor
+from ..cubedsphere.halos import append_halos_tensor, append_halos_tensor_reference_order
 from ..cyclegan import (N_GEOGRAPHIC_FEATURES, SECONDS_PER_DAY, CycleGanModel, CycleGanSpec, GeneratorSpec, check_architecture,
                         check_convolution_type, check_grid, layer_plan, seconds_since_1970, theta_from_seconds)
 from ..xr_compat import DataArray, Dataset, from_compat, to_compat
@@ -46,12 +46,28 @@ class _Fold(nn.Module):
 
 
 class _AppendHalos(nn.Module):
+    """``reference_order_gradients`` (off unless a trainer turns it on, ``set_reference_order_gradients``): pad tile by tile, so
+    that autograd adds a cell's gradient terms in the order of the reference's ``AppendHalos``; the values are the same."""
+
     def __init__(self, n_halo: int):
         super().__init__()
         self.n_halo = n_halo
+        self.reference_order_gradients = False
 
     def forward(self, x):   # [batch, tile, channel, x, y]
+        if self.reference_order_gradients:
+            return append_halos_tensor_reference_order(x, self.n_halo, tile_dim=1)
         return append_halos_tensor(x.movedim(1, 0), self.n_halo).movedim(0, 1)
+
+
+def set_reference_order_gradients(network: nn.Module, on: bool = True) -> nn.Module:
+    """Every halo padding of a twin: batched (``append_halos_tensor``, the default) or tile by tile in the reference's order of
+    gradient accumulation (``append_halos_tensor_reference_order``: bitwise the reference's float64 gradients, six autograd
+    nodes and six full-size zero tensors per pad in the backward pass)."""
+    for module in network.modules():
+        if isinstance(module, _AppendHalos):
+            module.reference_order_gradients = bool(on)
+    return network
 
 
 class _Crop(nn.Module):
@@ -288,10 +304,19 @@ class HipCycleGAN(Predictor):
     _WEIGHTS_FILENAME = "weights.npz"
     _REFERENCE_MODEL_FILENAME = "weight.pt"
 
-    def __init__(self, state_variables: Sequence[str], model: CycleGanSpec):
+    _DISCRIMINATOR_PREFIX = "discriminators."
+
+    def __init__(self, state_variables: Sequence[str], model: CycleGanSpec, discriminators: Optional[Mapping[str, Any]] = None):
+        """``discriminators`` (optional; ``fit.train_cyclegan`` gives them, ``predict`` never reads them): ``{"config": the
+        fields of ``DiscriminatorTwin``, "state_dict": {"discriminator_a.<key>": array, "discriminator_b.<key>": array}}``."""
         super().__init__(list(state_variables), list(state_variables))
         self.state_variables = list(state_variables)
         self.spec = model
+        self.discriminators = None if discriminators is None else {
+            "config": dict(discriminators["config"]),
+            "state_dict": {str(k): np.ascontiguousarray(np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v),
+                                                        np.float32) for k, v in discriminators["state_dict"].items()}}
+        self.history: Optional[Dict[str, list]] = None   # per-epoch losses, where the model was trained here
         if [str(v) for v in self.state_variables] != model.state_variables:
             raise ValueError(f"state variables {self.state_variables} differ from the network's {model.state_variables}")
         self._model: Optional[CycleGanModel] = None   # created on first predict (needs the GPU)
@@ -374,6 +399,9 @@ class HipCycleGAN(Predictor):
     def dump(self, path: str) -> None:
         os.makedirs(path, exist_ok=True)
         meta, arrays = self.spec.to_arrays()
+        if self.discriminators is not None:   # (written only when present: an artifact without them is byte for byte as before)
+            meta["discriminators"] = self.discriminators["config"]
+            arrays.update({self._DISCRIMINATOR_PREFIX + k: v for k, v in self.discriminators["state_dict"].items()})
         np.savez(os.path.join(path, self._WEIGHTS_FILENAME), **arrays)
         with open(os.path.join(path, self._SPEC_FILENAME), "w") as f:
             yaml.safe_dump(meta, f)
@@ -394,4 +422,9 @@ class HipCycleGAN(Predictor):
             meta = yaml.safe_load(f)
         with np.load(os.path.join(path, cls._WEIGHTS_FILENAME), allow_pickle=False) as z:
             arrays = {k: z[k] for k in z.files}
-        return cls(config["state_variables"], CycleGanSpec.from_arrays(meta, arrays))
+        discriminators = None
+        if "discriminators" in meta:
+            n = len(cls._DISCRIMINATOR_PREFIX)
+            discriminators = {"config": meta["discriminators"],
+                              "state_dict": {k[n:]: v for k, v in arrays.items() if k.startswith(cls._DISCRIMINATOR_PREFIX)}}
+        return cls(config["state_variables"], CycleGanSpec.from_arrays(meta, arrays), discriminators)

@@ -1633,6 +1633,88 @@ def train_adamw(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: to
                  float(beta2), float(eps), float(weight_decay), _stream(dev))
 
 
+# ---------------------------------------------------------------------------------------------
+# training the CycleGAN (csrc/cyclegan_train.hip): the caller owns every tensor, nothing is allocated or
+# synchronised.  Cube buffers are ``cube._Slice``s; ``n`` is the edge of the layer input ``x``; ``kind`` is a key of
+# ``cyclegan.KINDS``; ``halo``: cube halos (True) or zero padding.
+# ---------------------------------------------------------------------------------------------
+def _cyclegan_geometry(kind: str, n: int, halo: bool):
+    """(kind code, halo code, edge of dy)."""
+    codes = {"regular": (_lib.CYCLEGAN_CONV_REGULAR, n), "strided": (_lib.CYCLEGAN_CONV_STRIDED, n // 2),
+             "transposed": (_lib.CYCLEGAN_CONV_TRANSPOSED, 2 * n)}
+    if kind not in codes:
+        raise ValueError(f"unknown convolution kind {kind!r}: {sorted(codes)} are built")
+    return codes[kind][0], _lib.CYCLEGAN_HALO_CUBE if halo else _lib.CYCLEGAN_HALO_ZEROS, codes[kind][1]
+
+
+def _cyclegan_weight(t: torch.Tensor, what: str, kind: str, k: int, c_in: int, c_out: int) -> torch.Tensor:
+    shape = (2, 2, 2, 2, c_in, c_out) if kind == "transposed" else (k, k, c_in, c_out)
+    return _dense_weight(t, what, shape)
+
+
+def cyclegan_train_chunk_cells() -> int:
+    """Rows per partial of the CycleGAN weight gradients."""
+    return int(_lib.load().fv3hip_cyclegan_train_chunk_cells())
+
+
+def cyclegan_train_backward_data_workspace_floats(n_samples: int, n: int, c_in: int, kind: str, k: int, halo: bool) -> int:
+    code, mode, _ = _cyclegan_geometry(kind, n, halo)
+    return int(_lib.load().fv3hip_cyclegan_train_backward_data_workspace_bytes(int(n_samples), int(n), int(c_in), code, int(k), mode)) // 4
+
+
+def cyclegan_train_backward_weight_workspace_floats(n_samples: int, n: int, c_in: int, c_out: int, kind: str, k: int) -> int:
+    code, _, _ = _cyclegan_geometry(kind, n, True)
+    return int(_lib.load().fv3hip_cyclegan_train_backward_weight_workspace_bytes(int(n_samples), int(n), int(c_in), int(c_out), code,
+                                                                                 int(k))) // 4
+
+
+def cyclegan_train_conv(x, w: torch.Tensor, bias: Optional[torch.Tensor], y, n_samples: int, n: int, c_in: int, c_out: int, kind: str,
+                        k: int, halo: bool) -> None:
+    """``y = conv(x~, w) + bias``: ``fv3hip_cyclegan_conv`` without the loader's transform, plus the 3 x 3 strided kind."""
+    dev = _require_device(x.tensor, w, y.tensor, *([bias] if bias is not None else []))
+    code, mode, n_out = _cyclegan_geometry(kind, n, halo)
+    _cyclegan_weight(w, "w", kind, k, c_in, c_out)
+    _lib.call_on(dev, "fv3hip_cyclegan_train_conv", *_cube_slice(x, "x", n_samples, n, c_in), _ptr(w), _ptr(_vec(bias, "bias", c_out)),
+                 *_cube_slice(y, "y", n_samples, n_out, c_out), n_samples, n, c_in, c_out, code, int(k), mode, _stream(dev))
+
+
+def cyclegan_train_backward_data(dy, w: torch.Tensor, dx, n_samples: int, n: int, c_in: int, c_out: int, kind: str, k: int, halo: bool,
+                                 workspace: Optional[torch.Tensor] = None) -> None:
+    """``dx`` = the adjoint of the convolution in its input, across the seams; cube halos need ``workspace``."""
+    dev = _require_device(dy.tensor, w, dx.tensor, *([workspace] if workspace is not None else []))
+    code, mode, n_out = _cyclegan_geometry(kind, n, halo)
+    _cyclegan_weight(w, "w", kind, k, c_in, c_out)
+    ws, ws_bytes = _caller_workspace(workspace)
+    _lib.call_on(dev, "fv3hip_cyclegan_train_backward_data", *_cube_slice(dy, "dy", n_samples, n_out, c_out), _ptr(w),
+                 *_cube_slice(dx, "dx", n_samples, n, c_in), _ptr(ws), ws_bytes, n_samples, n, c_in, c_out, code, int(k), mode,
+                 _stream(dev))
+
+
+def cyclegan_train_backward_weight(x, dy, dw: torch.Tensor, db: Optional[torch.Tensor], n_samples: int, n: int, c_in: int, c_out: int,
+                                   kind: str, k: int, halo: bool, workspace: torch.Tensor) -> None:
+    """``dw`` in the forward's weight layout and ``db = sum dy`` (or None), both overwritten."""
+    dev = _require_device(x.tensor, dy.tensor, dw, workspace, *([db] if db is not None else []))
+    code, mode, n_out = _cyclegan_geometry(kind, n, halo)
+    _cyclegan_weight(dw, "dw", kind, k, c_in, c_out)
+    ws, ws_bytes = _caller_workspace(workspace)
+    _lib.call_on(dev, "fv3hip_cyclegan_train_backward_weight", *_cube_slice(x, "x", n_samples, n, c_in),
+                 *_cube_slice(dy, "dy", n_samples, n_out, c_out), _ptr(dw), _ptr(_vec(db, "db", c_out)), _ptr(ws), ws_bytes, n_samples, n,
+                 c_in, c_out, code, int(k), mode, _stream(dev))
+
+
+def cyclegan_train_norm_backward(dy, x, mean: torch.Tensor, rstd: torch.Tensor, bias: Optional[torch.Tensor], slope: float, dx,
+                                 dbias: Optional[torch.Tensor], n_samples: int, n: int, c: int) -> None:
+    """The adjoint of ``act((x - mean) * rstd + bias)`` (leaky ReLU of ``slope``; 1: none) in ``x``; ``dbias``: in the bias."""
+    dev = _require_device(dy.tensor, x.tensor, mean, rstd, dx.tensor, *(t for t in (bias, dbias) if t is not None))
+    _dense_weight(mean, "mean", (n_samples, 6, c)), _dense_weight(rstd, "rstd", (n_samples, 6, c))
+    for t, what in ((bias, "bias"), (dbias, "dbias")):
+        if t is not None:
+            _dense_weight(t, what, (6, n, n, c))
+    _lib.call_on(dev, "fv3hip_cyclegan_train_norm_backward", *_cube_slice(dy, "dy", n_samples, n, c), *_cube_slice(x, "x", n_samples, n, c),
+                 _ptr(mean), _ptr(rstd), _ptr(bias), float(slope), *_cube_slice(dx, "dx", n_samples, n, c), _ptr(dbias), n_samples, n, c,
+                 _stream(dev))
+
+
 class HipTimer:
     """HIP events recorded on torch's current stream (used by bench.py)."""
 

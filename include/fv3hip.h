@@ -1412,6 +1412,57 @@ int fv3hip_graph_pool2_backward(const float *dpool, int64_t dpool_ld, int64_t dp
 int fv3hip_train_adamw(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step, double lr, double beta1,
                        double beta2, double eps, double weight_decay, void *stream);
 
+/* ---- training fv3fit's CycleGAN (pytorch/cyclegan/train_cyclegan.py, cyclegan_trainer.py): the adjoints of the fv3hip_cyclegan_*
+ * layers, with their conventions: channel-last float32 slices (pointer, ld, channel offset, sample stride; 0 = contiguous
+ * cubes), the caller owns every DEVICE buffer, all arguments are checked on the host before any HIP call, nothing is allocated
+ * or synchronised.  Every contraction runs on the exact-float32 MFMA with separately rounded products in a fixed order; there
+ * are no atomics, so results are bitwise reproducible and a sample's results do not depend on the batch it is in.  `n` is the
+ * edge of the layer INPUT x; dy has the forward's output edge (n, n / 2 or 2 n).  kind / k / halo_mode / weight layout as
+ * fv3hip_cyclegan_conv, plus _STRIDED k = 3 (halo 1: output (x, y) reads cells 2 x - 1 ... 2 x + 1; w [3][3][c_in][c_out]; the
+ * discriminator's default).  Write x~ for the halo-extended face and T(o, t) for the padded position tap t of output o reads.
+ *   fv3hip_cyclegan_train_conv            the forward: fv3hip_cyclegan_conv without the loader's transform and the per-cell
+ *                                         output bias, bit for bit, plus _STRIDED k = 3.
+ *   fv3hip_cyclegan_train_backward_data   dx[s,g,q] = sum over the padded positions (f, p) that show cell (g, q) -- its own, and
+ *                                         with _HALO_CUBE one halo position on the neighbouring face across every edge the cell
+ *                                         lies within the halo width of (none at halo corners) -- of
+ *                                         sum_{(o,t): T(o,t) = p} W_t dy[s,f,o].  One writer per element: the terms of one
+ *                                         position are summed tap by tap, channel fastest; the positions are added in the order
+ *                                         own, x-low, x-high, y-low, y-high.  _HALO_CUBE needs a workspace of
+ *                                         fv3hip_cyclegan_train_backward_data_workspace_bytes(...) bytes (the gradient of the
+ *                                         padded field); _HALO_ZEROS needs none.  The weights are read in the forward's layout.
+ *   fv3hip_cyclegan_train_backward_weight dw_t[ci][co] = sum_{s,f,o} x~[s,f,T(o,t)][ci] dy[s,f,o][co] in the forward's weight
+ *                                         layout (the parity split of _TRANSPOSED included) and db[co] = sum dy in float64, rounded once (db null: not
+ *                                         wanted).  The rows (sample, tile, x, y) are cut into chunks of
+ *                                         fv3hip_cyclegan_train_chunk_cells() whose partials, in the workspace of
+ *                                         fv3hip_cyclegan_train_backward_weight_workspace_bytes(...) bytes, are added in
+ *                                         ascending order.  dw and db are overwritten.
+ *   fv3hip_cyclegan_train_norm_backward   the adjoint of y = act(x^ + bias), x^ = (x - mean) * rstd, act a leaky ReLU of `slope`
+ *                                         in [0, 1] (0: ReLU, 1: none): g = dy act'(x^ + bias) with the mask taken from the
+ *                                         float32 pre-activation as fv3hip_cyclegan_apply forms it (positive: 1, else slope);
+ *                                         dx = rstd ((g - mean_face(g)) - x^ mean_face(g x^)) in float64, rounded once, the two face means accumulated in
+ *                                         float64 in the fixed order of fv3hip_cyclegan_stats.  mean / rstd [sample][6][c];
+ *                                         bias [6][n][n][c] or null; dbias [6][n][n][c] or null: sum of g over the samples in
+ *                                         ascending order.  dx must not overlap dy or x.
+ */
+int fv3hip_cyclegan_train_chunk_cells(void);
+size_t fv3hip_cyclegan_train_backward_data_workspace_bytes(int64_t n_samples, int n, int c_in, int kind, int k, int halo_mode);
+size_t fv3hip_cyclegan_train_backward_weight_workspace_bytes(int64_t n_samples, int n, int c_in, int c_out, int kind, int k);
+int fv3hip_cyclegan_train_conv(const float *src, int64_t src_ld, int64_t src_off, int64_t src_sample_stride, const float *w,
+                               const float *bias, float *dst, int64_t dst_ld, int64_t dst_off, int64_t dst_sample_stride,
+                               int64_t n_samples, int n, int c_in, int c_out, int kind, int k, int halo_mode, void *stream);
+int fv3hip_cyclegan_train_backward_data(const float *dy, int64_t dy_ld, int64_t dy_off, int64_t dy_sample_stride, const float *w,
+                                        float *dx, int64_t dx_ld, int64_t dx_off, int64_t dx_sample_stride, float *workspace,
+                                        size_t workspace_bytes, int64_t n_samples, int n, int c_in, int c_out, int kind, int k,
+                                        int halo_mode, void *stream);
+int fv3hip_cyclegan_train_backward_weight(const float *x, int64_t x_ld, int64_t x_off, int64_t x_sample_stride, const float *dy,
+                                          int64_t dy_ld, int64_t dy_off, int64_t dy_sample_stride, float *dw, float *db,
+                                          float *workspace, size_t workspace_bytes, int64_t n_samples, int n, int c_in, int c_out,
+                                          int kind, int k, int halo_mode, void *stream);
+int fv3hip_cyclegan_train_norm_backward(const float *dy, int64_t dy_ld, int64_t dy_off, int64_t dy_sample_stride, const float *x,
+                                        int64_t x_ld, int64_t x_off, int64_t x_sample_stride, const float *mean, const float *rstd,
+                                        const float *bias, float slope, float *dx, int64_t dx_ld, int64_t dx_off,
+                                        int64_t dx_sample_stride, float *dbias, int64_t n_samples, int n, int c, void *stream);
+
 /* ---- training random forests (fv3fit's "sklearn_random_forest"; sklearn's RandomForestRegressor.fit: squared error, exact
  * best split, all features).  Stateless like fv3hip_train_*: the caller owns every DEVICE buffer below, nothing is allocated or
  * synchronised, the arguments are checked on the host before any HIP call.  One tree grows level by level:
