@@ -22,6 +22,7 @@ CONV_HALO_INPUT, CONV_HALO_STRIPS, CONV_HALO_CUBE = 0, 1, 2
 ARITH_EXACT, ARITH_FAST = 0, 1
 CYCLEGAN_CONV_REGULAR, CYCLEGAN_CONV_STRIDED, CYCLEGAN_CONV_TRANSPOSED = 0, 1, 2
 CYCLEGAN_HALO_ZEROS, CYCLEGAN_HALO_CUBE = 0, 1
+FMR_LOSS_MSE, FMR_LOSS_MAE = 0, 1
 CODEC_DENSE, CODEC_AFFINE = 0, 1
 FOREST_TRAIN_SUMS, FOREST_TRAIN_SCAN, FOREST_TRAIN_SPLIT, FOREST_TRAIN_ALL = 1, 2, 4, 7
 ABI_VERSION = 3
@@ -482,6 +483,13 @@ SIGNATURES = {
     "fv3hip_cyclegan_train_norm_backward": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                                     c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64,
                                                     c_int, c_int, c_void_p]),
+    "fv3hip_cyclegan_train_backward_weight_context_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fv3hip_cyclegan_train_backward_weight_context": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                                              c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                              c_size_t, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fv3hip_fmr_loss_grad_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "fv3hip_fmr_loss_grad": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64,
+                                     c_int64, c_int, c_double, c_int, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fv3hip_forest_train_chunk": (c_int, []),
     "fv3hip_forest_train_begin": (c_int, [POINTER(ForestTrain), c_int64, c_void_p]),
     "fv3hip_forest_train_level": (c_int, [POINTER(ForestTrain), c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_int64,

@@ -19,6 +19,14 @@
 // table (written once per block); db is the chunk's sum of dy in float64 (cyclegan_bias_grad_kernel).  The chunks' partials are added in
 // ascending order by cyclegan_chunk_sum_kernel.  No atomics anywhere: every result is bitwise reproducible and a sample's dx
 // does not depend on the batch it is in.
+//
+// Training the recurrent (FMR) generator, DESIGN.md section 28.  A layer with context channels (fv3hip_cyclegan_conv_context)
+// has c_cell + c_uni further rows of x~ per tap: cyclegan_bwd_weight_kernel<true> lets the A loader run past c_in, into the
+// per-cell table at the row's cell or the uniform values, both zero where the row shows no cell -- as the forward resolves
+// them -- and writes those rows into their own block dw_ctx [taps][c_cell + c_uni][c_out].  The context has no gradient, so
+// backward-data is unchanged.  fmr_loss_kernel is the window loss (identity on time 0, target on the later times) and its
+// gradient added to the discriminator's, one writer per element; fmr_loss_finish_kernel adds the blocks' float64 partials
+// in ascending order.
 #include <cmath>
 
 #include "common.h"
@@ -294,7 +302,12 @@ __global__ __launch_bounds__(kBlock) void cyclegan_fold_kernel(const float *pad,
 struct BwdWeightArgs {
     const float *x, *dy;     // channel offsets applied
     int64_t x_ld, x_ss, dy_ld, dy_ss;
-    float *dw, *db, *ws;     // ws [chunk][blocks * c_in + 2][c_out]: the dW partial, then one float64 per channel (two words)
+    float *dw, *db, *ws;     // ws [chunk][blocks * (c_in + c_ctx) + 2][c_out]: the dW partial, the context rows' partial, then one
+                             // float64 per channel (two words)
+    const float *ctx_cell;   // [6][n][n][c_cell] or null
+    const float *ctx_uni;    // [c_ctx - c_cell] or null
+    float *dw_ctx;           // [blocks][c_ctx][c_out] or null
+    int c_cell, c_ctx;       // per-cell context channels; all context channels
     Geom g;
     int mg;                  // edge of the grid the rows are flattened over: n_out, n for the transposed kind
     int c_in, c_out, blocks, mtiles, n_chunks;
@@ -302,10 +315,16 @@ struct BwdWeightArgs {
     CubeSeams seams;
 };
 
-// floats of one chunk's partial: dW [blocks][c_in][c_out], then the float64 sum of dy per channel as (high, low) words -- the
-// offset of that part may be odd, so it is not addressed as doubles
-__host__ __device__ inline int64_t partial_floats(int blocks, int c_in, int c_out) { return ((int64_t)blocks * c_in + 2) * c_out; }
+// floats of one chunk's partial: dW [blocks][c_in][c_out], the context rows [blocks][c_ctx][c_out], then the float64 sum of dy
+// per channel as (high, low) words -- the offset of that part may be odd, so it is not addressed as doubles
+__host__ __device__ inline int64_t partial_floats(int blocks, int c_in, int c_ctx, int c_out)
+{
+    return ((int64_t)blocks * (c_in + c_ctx) + 2) * c_out;
+}
 
+// CTX: the A rows run on past c_in into the context channels (mtiles covers c_in + c_ctx); without it this is the kernel as it
+// was, and a source row's sum does not depend on which of the two ran
+template <bool CTX>
 __global__ __launch_bounds__(kBlock) void cyclegan_bwd_weight_kernel(const BwdWeightArgs a)
 {
     __shared__ int xcell[kChunk], ycell[kChunk], smp[kChunk];   // per row of the chunk: the cell of x~ (-1: a zero), of dy, the sample
@@ -348,6 +367,10 @@ __global__ __launch_bounds__(kBlock) void cyclegan_bwd_weight_kernel(const BwdWe
             const int r = c0 + kk, ci = ci0 + i;
             float v = 0.f;
             if (r < len && ci < a.c_in && xcell[r] >= 0) v = a.x[(int64_t)smp[r] * a.x_ss + (int64_t)xcell[r] * a.x_ld + ci];
+            if (CTX && r < len && ci >= a.c_in && ci - a.c_in < a.c_ctx && xcell[r] >= 0) {
+                const int j = ci - a.c_in;
+                v = j < a.c_cell ? a.ctx_cell[(int64_t)xcell[r] * a.c_cell + j] : a.ctx_uni[j - a.c_cell];
+            }
             ap[kk * kMP + i] = v;
             const int nn = n0 + i;
             float u = 0.f;
@@ -367,11 +390,13 @@ __global__ __launch_bounds__(kBlock) void cyclegan_bwd_weight_kernel(const BwdWe
     // epilogue: D[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     const int nn = n0 + wn * 32 + l31;
     if (nn >= a.c_out) return;
-    float *ws = a.ws + (int64_t)blockIdx.z * partial_floats(a.blocks, a.c_in, a.c_out);
+    float *ws = a.ws + (int64_t)blockIdx.z * partial_floats(a.blocks, a.c_in, a.c_ctx, a.c_out);
+    float *wc = ws + (int64_t)a.blocks * a.c_in * a.c_out;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int ci = ci0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
         if (ci < a.c_in) ws[((int64_t)wblock * a.c_in + ci) * a.c_out + nn] = acc[r];
+        if (CTX && ci >= a.c_in && ci - a.c_in < a.c_ctx) wc[((int64_t)wblock * a.c_ctx + ci - a.c_in) * a.c_out + nn] = acc[r];
     }
 }
 
@@ -405,7 +430,8 @@ __global__ __launch_bounds__(kBlock) void cyclegan_bias_grad_kernel(const BwdWei
     __syncthreads();
     if (grp == 0 && nn < a.c_out) {
         const double tot = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
-        float *out = a.ws + (int64_t)blockIdx.y * partial_floats(a.blocks, a.c_in, a.c_out) + (int64_t)a.blocks * a.c_in * a.c_out + 2 * nn;
+        float *out = a.ws + (int64_t)blockIdx.y * partial_floats(a.blocks, a.c_in, a.c_ctx, a.c_out) +
+                     (int64_t)a.blocks * (a.c_in + a.c_ctx) * a.c_out + 2 * nn;
         out[0] = __int_as_float(__double2hiint(tot));
         out[1] = __int_as_float(__double2loint(tot));
     }
@@ -414,13 +440,17 @@ __global__ __launch_bounds__(kBlock) void cyclegan_bias_grad_kernel(const BwdWei
 // the chunks' partials added in ascending order; db in float64, rounded once
 __global__ __launch_bounds__(kBlock) void cyclegan_chunk_sum_kernel(const BwdWeightArgs a)
 {
-    const int64_t nw = (int64_t)a.blocks * a.c_in * a.c_out, part = partial_floats(a.blocks, a.c_in, a.c_out);
+    const int64_t ns = (int64_t)a.blocks * a.c_in * a.c_out, nw = ns + (int64_t)a.blocks * a.c_ctx * a.c_out;
+    const int64_t part = partial_floats(a.blocks, a.c_in, a.c_ctx, a.c_out);
     const int64_t total = nw + (a.db ? a.c_out : 0);
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
         if (e < nw) {
             float s = a.ws[e];
             for (int z = 1; z < a.n_chunks; ++z) s += a.ws[z * part + e];
-            a.dw[e] = s;
+            if (e < ns)
+                a.dw[e] = s;
+            else
+                a.dw_ctx[e - ns] = s;
         } else {
             double s = 0.0;
             for (int z = 0; z < a.n_chunks; ++z) {
@@ -523,11 +553,11 @@ size_t data_workspace_bytes(int64_t n_samples, const Geom &g, int c_in)
     return (size_t)n_samples * 6 * (size_t)(np * np) * (size_t)c_in * sizeof(float);
 }
 
-size_t weight_workspace_bytes(int64_t n_samples, const Geom &g, int c_in, int c_out)
+size_t weight_workspace_bytes(int64_t n_samples, const Geom &g, int c_in, int c_ctx, int c_out)
 {
     const int64_t mg = g.kind == FV3HIP_CYCLEGAN_CONV_TRANSPOSED ? g.n : g.n_out;
     const int64_t chunks = ceil_div(n_samples * 6 * mg * mg, kChunk);
-    return (size_t)chunks * (size_t)partial_floats(g.k * g.k, c_in, c_out) * sizeof(float);
+    return (size_t)chunks * (size_t)partial_floats(g.k * g.k, c_in, c_ctx, c_out) * sizeof(float);
 }
 
 struct Span {
@@ -568,7 +598,7 @@ extern "C" size_t fv3hip_cyclegan_train_backward_weight_workspace_bytes(int64_t 
     Geom g;
     if (n_samples < 1 || n < 1 || n > kLimits.max_n || c_in < 1 || c_out < 1 || check_geometry(n, kind, k, FV3HIP_CYCLEGAN_HALO_CUBE, g))
         return 0;
-    return weight_workspace_bytes(n_samples, g, c_in, c_out);
+    return weight_workspace_bytes(n_samples, g, c_in, 0, c_out);
 }
 
 extern "C" int fv3hip_cyclegan_train_backward_data(const float *dy, int64_t dy_ld, int64_t dy_off, int64_t dy_sample_stride,
@@ -635,17 +665,26 @@ extern "C" int fv3hip_cyclegan_train_backward_data(const float *dy, int64_t dy_l
     return FV3HIP_OK;
 }
 
-extern "C" int fv3hip_cyclegan_train_backward_weight(const float *x, int64_t x_ld, int64_t x_off, int64_t x_sample_stride, const float *dy,
-                                                     int64_t dy_ld, int64_t dy_off, int64_t dy_sample_stride, float *dw, float *db,
-                                                     float *workspace, size_t workspace_bytes, int64_t n_samples, int n, int c_in,
-                                                     int c_out, int kind, int k, int halo_mode, void *stream)
+// both weight-gradient entry points: every argument is checked here, before any launch
+static int launch_backward_weight(const float *x, int64_t x_ld, int64_t x_off, int64_t x_sample_stride, const float *dy, int64_t dy_ld,
+                                  int64_t dy_off, int64_t dy_sample_stride, const float *ctx_cell, int c_cell, const float *ctx_uniform,
+                                  int c_uni, float *dw, float *dw_ctx, float *db, float *workspace, size_t workspace_bytes,
+                                  int64_t n_samples, int n, int c_in, int c_out, int kind, int k, int halo_mode, void *stream)
 {
     int rc;
     Geom g;
     if ((rc = check_channels(c_in, c_out))) return rc;
     FV3HIP_REQUIRE(dw, "null weight gradient");
-    if ((rc = check_cube(n_samples, n, kLimits)) || (rc = check_geometry(n, kind, k, halo_mode, g)) ||
-        (rc = check_slice("x", x, x_ld, x_off, c_in)) || (rc = check_slice("dy", dy, dy_ld, dy_off, c_out)) ||
+    FV3HIP_REQUIRE(c_cell >= 0 && c_uni >= 0 && c_cell <= (1 << 12) && c_uni <= (1 << 12),
+                   "c_cell and c_uni must be in [0, 2^12], got %d, %d", c_cell, c_uni);
+    FV3HIP_REQUIRE((ctx_cell != nullptr) == (c_cell > 0), "ctx_cell is %s with c_cell = %d", ctx_cell ? "given" : "null", c_cell);
+    FV3HIP_REQUIRE((ctx_uniform != nullptr) == (c_uni > 0), "ctx_uniform is %s with c_uni = %d", ctx_uniform ? "given" : "null", c_uni);
+    const int c_ctx = c_cell + c_uni;
+    FV3HIP_REQUIRE((dw_ctx != nullptr) == (c_ctx > 0), "dw_ctx is %s with %d context channels", dw_ctx ? "given" : "null", c_ctx);
+    if ((rc = check_cube(n_samples, n, kLimits)) || (rc = check_geometry(n, kind, k, halo_mode, g))) return rc;
+    if (c_ctx > 0 && kind != FV3HIP_CYCLEGAN_CONV_REGULAR)
+        return fail(FV3HIP_EUNSUPPORTED, "context channels are built for the regular convolution, got kind %d", kind);
+    if ((rc = check_slice("x", x, x_ld, x_off, c_in)) || (rc = check_slice("dy", dy, dy_ld, dy_off, c_out)) ||
         (rc = check_stride("x", &x_sample_stride, n, x_ld)) || (rc = check_stride("dy", &dy_sample_stride, g.n_out, dy_ld)))
         return rc;
     FV3HIP_REQUIRE(n_samples >= 1, "n_samples must be positive");
@@ -654,9 +693,10 @@ extern "C" int fv3hip_cyclegan_train_backward_weight(const float *x, int64_t x_l
     a.x = x + x_off, a.dy = dy + dy_off;
     a.x_ld = x_ld, a.x_ss = x_sample_stride, a.dy_ld = dy_ld, a.dy_ss = dy_sample_stride;
     a.dw = dw, a.db = db, a.ws = workspace;
+    a.ctx_cell = ctx_cell, a.ctx_uni = ctx_uniform, a.dw_ctx = dw_ctx, a.c_cell = c_cell, a.c_ctx = c_ctx;
     a.g = g;
     a.mg = kind == FV3HIP_CYCLEGAN_CONV_TRANSPOSED ? n : g.n_out;
-    a.c_in = c_in, a.c_out = c_out, a.blocks = k * k, a.mtiles = (int)ceil_div(c_in, 64);
+    a.c_in = c_in, a.c_out = c_out, a.blocks = k * k, a.mtiles = (int)ceil_div(c_in + c_ctx, 64);
     a.rows = n_samples * 6 * a.mg * a.mg;
     const int64_t chunks = ceil_div(a.rows, kChunk);
     FV3HIP_REQUIRE(chunks <= 65535, "%lld cells are more than 65535 chunks of %d", (long long)a.rows, kChunk);
@@ -664,25 +704,60 @@ extern "C" int fv3hip_cyclegan_train_backward_weight(const float *x, int64_t x_l
                    c_out);
     a.n_chunks = (int)chunks;
     a.seams = cube_seams();
-    const size_t need = weight_workspace_bytes(n_samples, g, c_in, c_out);
+    const size_t need = weight_workspace_bytes(n_samples, g, c_in, c_ctx, c_out);
     FV3HIP_REQUIRE(workspace && workspace_bytes >= need, "%lld cells need a workspace of %zu bytes, got %zu", (long long)a.rows, need,
                    workspace ? workspace_bytes : (size_t)0);
     const Span spans[] = {span("x", x, cube_span(n_samples, n, x_ld, x_sample_stride)),
                           span("dy", dy, cube_span(n_samples, g.n_out, dy_ld, dy_sample_stride)),
-                          span("the weight gradient", dw, (int64_t)a.blocks * c_in * c_out), span("db", db, c_out),
+                          span("the cell context", ctx_cell, 6LL * n * n * c_cell), span("the uniform context", ctx_uniform, c_uni),
+                          span("the weight gradient", dw, (int64_t)a.blocks * c_in * c_out),
+                          span("the context rows' gradient", dw_ctx, (int64_t)a.blocks * c_ctx * c_out), span("db", db, c_out),
                           span("the workspace", workspace, (int64_t)(need / sizeof(float)))};
-    if ((rc = check_spans(spans, 5, 2))) return rc;
+    if ((rc = check_spans(spans, 8, 4))) return rc;
     const dim3 grid((unsigned)(a.blocks * a.mtiles), (unsigned)ceil_div(c_out, 64), (unsigned)chunks);
-    hipLaunchKernelGGL(cyclegan_bwd_weight_kernel, grid, dim3(kBlock), 0, as_stream(stream), a);
-    if ((rc = check_launch("cyclegan_bwd_weight_kernel"))) return rc;
+    if (c_ctx > 0)
+        hipLaunchKernelGGL(cyclegan_bwd_weight_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), a);
+    else
+        hipLaunchKernelGGL(cyclegan_bwd_weight_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), a);
+    if ((rc = check_launch(c_ctx > 0 ? "cyclegan_bwd_weight_kernel (context)" : "cyclegan_bwd_weight_kernel"))) return rc;
     if (db) {
         hipLaunchKernelGGL(cyclegan_bias_grad_kernel, dim3((unsigned)ceil_div(c_out, 64), (unsigned)chunks), dim3(kBlock), 0,
                            as_stream(stream), a);
         if ((rc = check_launch("cyclegan_bias_grad_kernel"))) return rc;
     }
-    hipLaunchKernelGGL(cyclegan_chunk_sum_kernel, dim3(grid_stride_blocks((int64_t)(a.blocks * c_in + 1) * c_out)), dim3(kBlock), 0,
-                       as_stream(stream), a);
+    hipLaunchKernelGGL(cyclegan_chunk_sum_kernel, dim3(grid_stride_blocks((int64_t)(a.blocks * (c_in + c_ctx) + 1) * c_out)), dim3(kBlock),
+                       0, as_stream(stream), a);
     return check_launch("cyclegan_chunk_sum_kernel");
+}
+
+extern "C" int fv3hip_cyclegan_train_backward_weight(const float *x, int64_t x_ld, int64_t x_off, int64_t x_sample_stride, const float *dy,
+                                                     int64_t dy_ld, int64_t dy_off, int64_t dy_sample_stride, float *dw, float *db,
+                                                     float *workspace, size_t workspace_bytes, int64_t n_samples, int n, int c_in,
+                                                     int c_out, int kind, int k, int halo_mode, void *stream)
+{
+    return launch_backward_weight(x, x_ld, x_off, x_sample_stride, dy, dy_ld, dy_off, dy_sample_stride, nullptr, 0, nullptr, 0, dw, nullptr,
+                                  db, workspace, workspace_bytes, n_samples, n, c_in, c_out, kind, k, halo_mode, stream);
+}
+
+extern "C" size_t fv3hip_cyclegan_train_backward_weight_context_workspace_bytes(int64_t n_samples, int n, int c_in, int c_cell, int c_uni,
+                                                                                int c_out, int k)
+{
+    Geom g;
+    if (n_samples < 1 || n < 1 || n > kLimits.max_n || c_in < 1 || c_out < 1 || c_cell < 0 || c_uni < 0 || c_cell > (1 << 12) ||
+        c_uni > (1 << 12) || check_geometry(n, FV3HIP_CYCLEGAN_CONV_REGULAR, k, FV3HIP_CYCLEGAN_HALO_CUBE, g))
+        return 0;
+    return weight_workspace_bytes(n_samples, g, c_in, c_cell + c_uni, c_out);
+}
+
+extern "C" int fv3hip_cyclegan_train_backward_weight_context(const float *x, int64_t x_ld, int64_t x_off, int64_t x_sample_stride,
+                                                             const float *dy, int64_t dy_ld, int64_t dy_off, int64_t dy_sample_stride,
+                                                             const float *ctx_cell, int c_cell, const float *ctx_uniform, int c_uni,
+                                                             float *dw, float *dw_ctx, float *db, float *workspace,
+                                                             size_t workspace_bytes, int64_t n_samples, int n, int c_in, int c_out,
+                                                             int kind, int k, int halo_mode, void *stream)
+{
+    return launch_backward_weight(x, x_ld, x_off, x_sample_stride, dy, dy_ld, dy_off, dy_sample_stride, ctx_cell, c_cell, ctx_uniform, c_uni,
+                                  dw, dw_ctx, db, workspace, workspace_bytes, n_samples, n, c_in, c_out, kind, k, halo_mode, stream);
 }
 
 extern "C" int fv3hip_cyclegan_train_norm_backward(const float *dy, int64_t dy_ld, int64_t dy_off, int64_t dy_sample_stride, const float *x,
@@ -727,4 +802,155 @@ extern "C" int fv3hip_cyclegan_train_norm_backward(const float *dy, int64_t dy_l
         return check_launch("cyclegan_norm_dbias_kernel");
     }
     return FV3HIP_OK;
+}
+
+// ---- the window loss of the recurrent generator (recurrent/train_fmr.py: identity on time 0, target on the later times) ----
+namespace {
+
+constexpr int kLossPer = 8;   // elements per thread: a block covers kBlock * kLossPer consecutive elements of (window, time, element)
+
+struct LossArgs {
+    const float *fake, *real, *dgan;   // dgan (or null) and dfake have fake's strides
+    float *dfake;                      // null: the values only
+    int64_t fake_ws, fake_ts, real_ws, real_ts;
+    int64_t n_times, n_elems, total;   // total = n_windows * n_times * n_elems
+    int kind[2];                       // identity, target
+    double coef[2];                    // weight / count
+    double *partials;                  // [blocks][2]
+    double *values;
+    int64_t n_blocks;
+};
+
+// per element, in float64: the loss term |f - r| or (f - r)^2 and dfake = dgan + coef sign(f - r) or dgan + 2 coef (f - r),
+// rounded once.  A thread adds its kLossPer terms in ascending order, the block its 256 threads' sums pairwise in a fixed tree.
+__global__ __launch_bounds__(kBlock) void fmr_loss_kernel(const LossArgs a)
+{
+    __shared__ double red[2][kBlock];
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * (kBlock * kLossPer);
+    const int64_t per_window = a.n_times * a.n_elems;
+    double sum[2] = {0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < kLossPer; ++j) {
+        const int64_t e = base + (int64_t)j * kBlock + tid;
+        if (e >= a.total) break;
+        const int64_t w = e / per_window, rem = e - w * per_window;
+        const int64_t t = rem / a.n_elems, i = rem - t * a.n_elems;
+        const int64_t fo = w * a.fake_ws + t * a.fake_ts + i;
+        const double d = (double)a.fake[fo] - (double)a.real[w * a.real_ws + t * a.real_ts + i];
+        const int which = t == 0 ? 0 : 1;
+        const bool mse = a.kind[which] == FV3HIP_FMR_LOSS_MSE;
+        sum[which] += mse ? d * d : fabs(d);
+        if (a.dfake) {
+            const double g = a.dgan ? (double)a.dgan[fo] : 0.0;
+            const double s = d > 0.0 ? 1.0 : d < 0.0 ? -1.0 : d;   // (a NaN stays a NaN; sign(0) = 0 as torch's L1Loss)
+            a.dfake[fo] = (float)(mse ? g + (2.0 * a.coef[which]) * d : g + a.coef[which] * s);
+        }
+    }
+    red[0][tid] = sum[0];
+    red[1][tid] = sum[1];
+    __syncthreads();
+    for (int half = kBlock / 2; half > 0; half >>= 1) {
+        if (tid < half) {
+            red[0][tid] += red[0][tid + half];
+            red[1][tid] += red[1][tid + half];
+        }
+        __syncthreads();
+    }
+    if (tid < 2) a.partials[2 * (int64_t)blockIdx.x + tid] = red[tid][0];
+}
+
+// one wave: lane l adds the partials of blocks l, l + 64, ... in ascending order, lane 0 the 64 lane sums in ascending order
+__global__ __launch_bounds__(64) void fmr_loss_finish_kernel(const LossArgs a)
+{
+    __shared__ double red[2][64];
+    const int lane = threadIdx.x;
+    double s0 = 0.0, s1 = 0.0;
+    for (int64_t b = lane; b < a.n_blocks; b += 64) {
+        s0 += a.partials[2 * b];
+        s1 += a.partials[2 * b + 1];
+    }
+    red[0][lane] = s0;
+    red[1][lane] = s1;
+    __syncthreads();
+    if (lane < 2) {
+        double tot = 0.0;
+        for (int j = 0; j < 64; ++j) tot += red[lane][j];
+        a.values[lane] = a.coef[lane] * tot;
+    }
+}
+
+int64_t loss_blocks(int64_t n_windows, int64_t n_times, int64_t n_elems) { return ceil_div(n_windows * n_times * n_elems, (int64_t)kBlock * kLossPer); }
+
+// the (window, time) grid of `n_elems` contiguous floats each must not fold onto itself: one of the two strides is the inner one
+int check_window_strides(const char *what, int64_t ws, int64_t ts, int64_t n_windows, int64_t n_times, int64_t n_elems)
+{
+    const bool window_major = ts >= n_elems && (n_windows == 1 || ws >= n_times * ts);
+    const bool time_major = ws >= n_elems && ts >= n_windows * ws;
+    FV3HIP_REQUIRE(window_major || time_major,
+                   "%s: strides (window %lld, time %lld) fold %lld windows x %lld times of %lld floats onto themselves", what, (long long)ws,
+                   (long long)ts, (long long)n_windows, (long long)n_times, (long long)n_elems);
+    return FV3HIP_OK;
+}
+
+int64_t window_span(int64_t ws, int64_t ts, int64_t n_windows, int64_t n_times, int64_t n_elems)
+{
+    return (n_windows - 1) * ws + (n_times - 1) * ts + n_elems;
+}
+
+}  // namespace
+
+extern "C" size_t fv3hip_fmr_loss_grad_workspace_bytes(int64_t n_windows, int64_t n_times, int64_t n_elements)
+{
+    if (n_windows < 1 || n_times < 2 || n_elements < 1 || n_windows > (1 << 20) || n_times > (1 << 20) || n_elements > (1LL << 31)) return 0;
+    return (size_t)loss_blocks(n_windows, n_times, n_elements) * 2 * sizeof(double);
+}
+
+extern "C" int fv3hip_fmr_loss_grad(const float *fake, int64_t fake_window_stride, int64_t fake_time_stride, const float *real,
+                                    int64_t real_window_stride, int64_t real_time_stride, const float *dgan, float *dfake,
+                                    int64_t n_windows, int64_t n_times, int64_t n_elements, int identity_kind, double identity_weight,
+                                    int target_kind, double target_weight, double *values, double *workspace, size_t workspace_bytes,
+                                    void *stream)
+{
+    FV3HIP_REQUIRE(fake && real && values, "null fake, real or values");
+    FV3HIP_REQUIRE(n_windows >= 1 && n_windows <= (1 << 20), "n_windows must be in [1, 2^20], got %lld", (long long)n_windows);
+    FV3HIP_REQUIRE(n_times >= 2 && n_times <= (1 << 20),
+                   "n_times must be in [2, 2^20] (the target loss is a mean over the times after the first), got %lld", (long long)n_times);
+    FV3HIP_REQUIRE(n_elements >= 1 && n_elements <= (1LL << 31), "n_elements must be in [1, 2^31], got %lld", (long long)n_elements);
+    const int64_t total = n_windows * n_times * n_elements;
+    FV3HIP_REQUIRE(total <= (1LL << 40), "%lld elements are more than 2^40", (long long)total);
+    for (int kind : {identity_kind, target_kind})
+        FV3HIP_REQUIRE(kind == FV3HIP_FMR_LOSS_MSE || kind == FV3HIP_FMR_LOSS_MAE, "unknown loss kind %d", kind);
+    FV3HIP_REQUIRE(std::isfinite(identity_weight) && std::isfinite(target_weight), "the loss weights must be finite");
+    FV3HIP_REQUIRE(dfake || !dgan, "dgan is given without dfake");
+    int rc;
+    if ((rc = check_window_strides("fake", fake_window_stride, fake_time_stride, n_windows, n_times, n_elements)) ||
+        (rc = check_window_strides("real", real_window_stride, real_time_stride, n_windows, n_times, n_elements)))
+        return rc;
+    const int64_t blocks = loss_blocks(n_windows, n_times, n_elements);
+    const size_t need = (size_t)blocks * 2 * sizeof(double);
+    FV3HIP_REQUIRE(workspace && workspace_bytes >= need, "%lld elements need a workspace of %zu bytes, got %zu", (long long)total, need,
+                   workspace ? workspace_bytes : (size_t)0);
+    FV3HIP_REQUIRE(blocks <= 0x7fffffff, "%lld elements are too many blocks", (long long)total);
+    const int64_t fspan = window_span(fake_window_stride, fake_time_stride, n_windows, n_times, n_elements);
+    const Span spans[] = {span("fake", fake, fspan),
+                          span("real", real, window_span(real_window_stride, real_time_stride, n_windows, n_times, n_elements)),
+                          span("dgan", dgan == dfake ? nullptr : dgan, fspan),   // in place: an element is read by its one writer
+                          span("dfake", dfake, fspan), span("the values", (const float *)values, 4),
+                          span("the workspace", (const float *)workspace, (int64_t)(need / sizeof(float)))};
+    if ((rc = check_spans(spans, 6, 3))) return rc;
+
+    LossArgs a;
+    memset(&a, 0, sizeof(a));
+    a.fake = fake, a.real = real, a.dgan = dgan, a.dfake = dfake;
+    a.fake_ws = fake_window_stride, a.fake_ts = fake_time_stride, a.real_ws = real_window_stride, a.real_ts = real_time_stride;
+    a.n_times = n_times, a.n_elems = n_elements, a.total = total;
+    a.kind[0] = identity_kind, a.kind[1] = target_kind;
+    a.coef[0] = identity_weight / (double)(n_windows * n_elements);
+    a.coef[1] = target_weight / (double)(n_windows * (n_times - 1) * n_elements);
+    a.partials = workspace, a.values = values, a.n_blocks = blocks;
+    hipLaunchKernelGGL(fmr_loss_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), a);
+    if ((rc = check_launch("fmr_loss_kernel"))) return rc;
+    hipLaunchKernelGGL(fmr_loss_finish_kernel, dim3(1), dim3(64), 0, as_stream(stream), a);
+    return check_launch("fmr_loss_finish_kernel");
 }

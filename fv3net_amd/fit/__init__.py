@@ -30,6 +30,8 @@ from .cyclegan_train import (CycleGANGeneratorConfig, CycleGANHyperparameters, C
                              HipDiscriminator, ImagePool, LossConfig, train_cyclegan)
 from .fmr import (HipFullModelReplacement, RecurrentGeneratorTwin, fmr_spec_from_state_dict, fmr_state_dict_from_spec,
                   recurrent_generator_spec_from_state_dict, recurrent_twin_from_spec)
+from .fmr_train import (FMRHyperparameters, FMRNetworkConfig, FMRTrainer, FMRTrainingConfig, RecurrentDiscriminatorConfig,
+                        RecurrentGeneratorConfig, train_fmr)
 from .reservoir import (BatchLinearRegressor, BatchLinearRegressorHyperparameters, CubedsphereSubdomainConfig, DenseAutoencoder,
                         DenseAutoencoderHyperparameters, HybridReservoirComputingModel, HybridReservoirDatasetAdapter,
                         NotFittedError, Reservoir, ReservoirComputingModel, ReservoirDatasetAdapter, ReservoirHyperparameters,
@@ -51,6 +53,8 @@ __all__ = [
     "CycleGANTrainer", "CycleGANTrainingConfig", "DiscriminatorConfig", "DiscriminatorTwin", "HipDiscriminator", "ImagePool", "LossConfig", "train_cyclegan",
     "HipFullModelReplacement", "RecurrentGeneratorTwin", "fmr_spec_from_state_dict", "fmr_state_dict_from_spec",
     "recurrent_generator_spec_from_state_dict", "recurrent_twin_from_spec",
+    "FMRHyperparameters", "FMRNetworkConfig", "FMRTrainer", "FMRTrainingConfig", "RecurrentDiscriminatorConfig", "RecurrentGeneratorConfig",
+    "train_fmr",
     "DenseAutoencoder", "DenseAutoencoderHyperparameters", "SkTransformer", "train_dense_autoencoder",
     "BatchLinearRegressor", "BatchLinearRegressorHyperparameters", "CubedsphereSubdomainConfig", "NotFittedError", "Reservoir",
     "ReservoirHyperparameters", "ReservoirTrainingConfig", "SynchronizationTracker", "TransformerGroup", "train_reservoir_model",

@@ -5,7 +5,8 @@ the dataset's arrays are normalised and packed into windows in place by ``fv3hip
 state through the ``fv3hip_cyclegan_*`` layer kernels (the step layers read their context channels through
 ``fv3hip_cyclegan_conv_context``), and ``fv3hip_graph_unpack`` writes ``predicted`` and ``reference``.  The artifact is ``name``
 ("hip-fmr") + ``config.yaml`` (``state_variables``) + ``spec.yaml`` + ``weights.npz``; it carries the generator, the scalers
-(keyed by the variable's name) and the two ``xyz`` tables the reference reads from a grid catalogue, and no discriminator.
+(keyed by the variable's name) and the two ``xyz`` tables the reference reads from a grid catalogue, and -- only where
+``fit.train_fmr`` wrote it -- the discriminator, from which training resumes.
 
 ``RecurrentGeneratorTwin`` is the generator in plain ``torch.nn`` with the reference's parameter names: the float32 / float64
 chain that the tests and the benchmark compare the kernels with.
@@ -291,11 +292,18 @@ class HipFullModelReplacement(Predictor):
     _SPEC_FILENAME = "spec.yaml"
     _WEIGHTS_FILENAME = "weights.npz"
     _REFERENCE_MODEL_FILENAME = "weight.pt"
+    _DISCRIMINATOR_PREFIX = "discriminator."
 
-    def __init__(self, state_variables: Sequence[str], model: FullModelReplacementSpec):
+    def __init__(self, state_variables: Sequence[str], model: FullModelReplacementSpec, discriminator: Optional[Mapping[str, Any]] = None):
+        """``discriminator`` (optional; ``fit.train_fmr`` gives it so that ``reload_path`` can resume, ``predict`` never reads
+        it): ``{"config": the fields of ``DiscriminatorTwin``, "state_dict": its parameters under the reference's keys}``."""
         super().__init__(list(state_variables), list(state_variables))
         self.state_variables = list(state_variables)
         self.spec = model
+        self.discriminator = None if discriminator is None else {
+            "config": dict(discriminator["config"]),
+            "state_dict": {str(k): np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, np.float32)
+                           for k, v in discriminator["state_dict"].items()}}
         if [str(v) for v in self.state_variables] != model.state_variables:
             raise ValueError(f"state variables {self.state_variables} differ from the network's {model.state_variables}")
         self._model: Optional[FullModelReplacementModel] = None   # created on first predict (needs the GPU)
@@ -391,6 +399,9 @@ class HipFullModelReplacement(Predictor):
     def dump(self, path: str) -> None:
         os.makedirs(path, exist_ok=True)
         meta, arrays = self.spec.to_arrays()
+        if self.discriminator is not None:   # (written only when present: an artifact without it is byte for byte as before)
+            meta["discriminator"] = self.discriminator["config"]
+            arrays.update({self._DISCRIMINATOR_PREFIX + k: v for k, v in self.discriminator["state_dict"].items()})
         np.savez(os.path.join(path, self._WEIGHTS_FILENAME), **arrays)
         with open(os.path.join(path, self._SPEC_FILENAME), "w") as f:
             yaml.safe_dump(meta, f)
@@ -411,4 +422,9 @@ class HipFullModelReplacement(Predictor):
             meta = yaml.safe_load(f)
         with np.load(os.path.join(path, cls._WEIGHTS_FILENAME), allow_pickle=False) as z:
             arrays = {k: z[k] for k in z.files}
-        return cls(config["state_variables"], FullModelReplacementSpec.from_arrays(meta, arrays))
+        discriminator = None
+        if "discriminator" in meta:
+            n = len(cls._DISCRIMINATOR_PREFIX)
+            discriminator = {"config": meta["discriminator"],
+                             "state_dict": {k[n:]: v for k, v in arrays.items() if k.startswith(cls._DISCRIMINATOR_PREFIX)}}
+        return cls(config["state_variables"], FullModelReplacementSpec.from_arrays(meta, arrays), discriminator)

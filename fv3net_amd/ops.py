@@ -1715,6 +1715,102 @@ def cyclegan_train_norm_backward(dy, x, mean: torch.Tensor, rstd: torch.Tensor, 
                  _stream(dev))
 
 
+# ---------------------------------------------------------------------------------------------
+# training the FMR recurrent generator (csrc/cyclegan_train.hip): a regular convolution with context
+# channels -- ``ctx_cell`` ``[6, n, n, c_cell]`` and ``ctx_uniform`` ``[c_uni]`` (either may be None) -- whose weights are the
+# source rows ``w`` ``[k, k, c_in, c_out]`` and the context rows ``w_ctx`` ``[k, k, c_cell + c_uni, c_out]``; and the window loss.
+# ---------------------------------------------------------------------------------------------
+def _context(ctx_cell: Optional[torch.Tensor], ctx_uniform: Optional[torch.Tensor], n: int):
+    """(c_cell, c_uni) of a checked context."""
+    c_cell = c_uni = 0
+    if ctx_cell is not None:
+        c_cell = int(ctx_cell.shape[-1]) if ctx_cell.dim() == 4 else 0
+        _dense_weight(ctx_cell, "ctx_cell", (6, n, n, max(c_cell, 1)))
+    if ctx_uniform is not None:
+        c_uni = int(ctx_uniform.numel())
+        _vec(ctx_uniform, "ctx_uniform", max(c_uni, 1))
+    return c_cell, c_uni
+
+
+def cyclegan_train_conv_context(x, w: torch.Tensor, w_ctx: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                                ctx_cell: Optional[torch.Tensor], ctx_uniform: Optional[torch.Tensor], y, n_samples: int, n: int,
+                                c_in: int, c_out: int, k: int, halo: bool) -> None:
+    """``y = conv(x~ || ctx~, w || w_ctx) + bias``: ``fv3hip_cyclegan_conv_context`` without a loader transform."""
+    tensors = [t for t in (w_ctx, bias, ctx_cell, ctx_uniform) if t is not None]
+    dev = _require_device(x.tensor, w, y.tensor, *tensors)
+    code, mode, _ = _cyclegan_geometry("regular", n, halo)
+    c_cell, c_uni = _context(ctx_cell, ctx_uniform, n)
+    _cyclegan_weight(w, "w", "regular", k, c_in, c_out)
+    if w_ctx is not None:
+        _cyclegan_weight(w_ctx, "w_ctx", "regular", k, c_cell + c_uni, c_out)
+    _lib.call_on(dev, "fv3hip_cyclegan_conv_context", *_cube_slice(x, "x", n_samples, n, c_in), None, None, None, 0, _ptr(w),
+                 _ptr(_vec(bias, "bias", c_out)), None, *_cube_slice(y, "y", n_samples, n, c_out), n_samples, n, c_in, c_out, code, int(k),
+                 mode, _ptr(ctx_cell), c_cell, _ptr(ctx_uniform), c_uni, _ptr(w_ctx), _stream(dev))
+
+
+def cyclegan_train_backward_weight_context_workspace_floats(n_samples: int, n: int, c_in: int, c_cell: int, c_uni: int, c_out: int,
+                                                            k: int) -> int:
+    return int(_lib.load().fv3hip_cyclegan_train_backward_weight_context_workspace_bytes(int(n_samples), int(n), int(c_in), int(c_cell),
+                                                                                         int(c_uni), int(c_out), int(k))) // 4
+
+
+def cyclegan_train_backward_weight_context(x, dy, ctx_cell: Optional[torch.Tensor], ctx_uniform: Optional[torch.Tensor], dw: torch.Tensor,
+                                           dw_ctx: Optional[torch.Tensor], db: Optional[torch.Tensor], n_samples: int, n: int, c_in: int,
+                                           c_out: int, k: int, halo: bool, workspace: torch.Tensor, kind: str = "regular") -> None:
+    """``dw`` and ``dw_ctx`` (the context rows, None without a context) in the forward's layouts and ``db = sum dy`` (or None),
+    all overwritten.  Only the regular ``kind`` takes a context."""
+    tensors = [t for t in (ctx_cell, ctx_uniform, dw_ctx, db) if t is not None]
+    dev = _require_device(x.tensor, dy.tensor, dw, workspace, *tensors)
+    code, mode, n_out = _cyclegan_geometry(kind, n, halo)
+    c_cell, c_uni = _context(ctx_cell, ctx_uniform, n)
+    _cyclegan_weight(dw, "dw", kind, k, c_in, c_out)
+    if dw_ctx is not None:
+        _dense_weight(dw_ctx, "dw_ctx", (dw.shape[0], dw.shape[1], c_cell + c_uni, c_out))
+    ws, ws_bytes = _caller_workspace(workspace)
+    _lib.call_on(dev, "fv3hip_cyclegan_train_backward_weight_context", *_cube_slice(x, "x", n_samples, n, c_in),
+                 *_cube_slice(dy, "dy", n_samples, n_out, c_out), _ptr(ctx_cell), c_cell, _ptr(ctx_uniform), c_uni, _ptr(dw), _ptr(dw_ctx),
+                 _ptr(_vec(db, "db", c_out)), _ptr(ws), ws_bytes, n_samples, n, c_in, c_out, code, int(k), mode, _stream(dev))
+
+
+FMR_LOSS_KINDS = {"mse": _lib.FMR_LOSS_MSE, "mae": _lib.FMR_LOSS_MAE}
+
+
+def fmr_loss_grad(fake: torch.Tensor, real: torch.Tensor, dgan: Optional[torch.Tensor], dfake: Optional[torch.Tensor],
+                  identity_kind: str, identity_weight: float, target_kind: str, target_weight: float,
+                  values: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The window loss of the recurrent generator and its gradient in one launch (``fv3hip_fmr_loss_grad``).  ``fake`` and
+    ``real``: float32 ``[window, time, ...]`` tensors or permuted views of ``[time, window, ...]`` ones whose states (the
+    trailing dimensions) are contiguous; ``dgan`` (or None) and ``dfake`` (None: the values only) with ``fake``'s shape and
+    strides.  Returns ``values``, two float64 on the device: the weighted identity loss (time 0) and target loss (times 1 ...)."""
+    tensors = [t for t in (dgan, dfake, values, workspace) if t is not None]
+    dev = _require_device(fake, real, *tensors)
+    if fake.dim() < 3 or fake.shape != real.shape:
+        raise ValueError(f"fake and real must be [window, time, ...] of one shape, got {tuple(fake.shape)} and {tuple(real.shape)}")
+    W, T, E = int(fake.shape[0]), int(fake.shape[1]), _prod(fake.shape[2:])
+    for t, what in ((fake, "fake"), (real, "real"), (dgan, "dgan"), (dfake, "dfake")):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.shape != fake.shape or not (t[0, 0].is_contiguous() if W and T else True):
+            raise ValueError(f"{what} must be float32 of shape {tuple(fake.shape)} with contiguous states")
+        if what.startswith("d") and t.stride()[:2] != fake.stride()[:2]:
+            raise ValueError(f"{what} must have fake's strides {fake.stride()[:2]}, got {t.stride()[:2]}")
+    for kind in (identity_kind, target_kind):
+        if kind not in FMR_LOSS_KINDS:
+            raise ValueError(f"unknown loss kind {kind!r}: 'mse' and 'mae' are built")
+    need = int(_lib.load().fv3hip_fmr_loss_grad_workspace_bytes(W, T, E)) // 8
+    if values is None:
+        values = torch.empty(2, dtype=torch.float64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.float64, device=dev)
+    for t, what, count in ((values, "values", 2), (workspace, "workspace", None)):
+        if t.dtype != torch.float64 or not t.is_contiguous() or (count is not None and t.numel() != count):
+            raise ValueError(f"{what} must be a contiguous float64 tensor" + (f" of {count} values" if count else ""))
+    _lib.call_on(dev, "fv3hip_fmr_loss_grad", _ptr(fake), fake.stride(0), fake.stride(1), _ptr(real), real.stride(0), real.stride(1),
+                 _ptr(dgan), _ptr(dfake), W, T, E, FMR_LOSS_KINDS[identity_kind], float(identity_weight), FMR_LOSS_KINDS[target_kind],
+                 float(target_weight), _ptr(values), _ptr(workspace), workspace.numel() * 8, _stream(dev))
+    return values
+
+
 class HipTimer:
     """HIP events recorded on torch's current stream (used by bench.py)."""
 

@@ -1463,6 +1463,47 @@ int fv3hip_cyclegan_train_norm_backward(const float *dy, int64_t dy_ld, int64_t 
                                         const float *bias, float slope, float *dx, int64_t dx_ld, int64_t dx_off,
                                         int64_t dx_sample_stride, float *dbias, int64_t n_samples, int n, int c, void *stream);
 
+/* ---- training fv3fit's FMR recurrent generator (pytorch/recurrent/train_fmr.py), with the conventions of the CycleGAN training
+ * entry points above.  The forward of a layer with context channels is fv3hip_cyclegan_conv_context without a loader transform;
+ * the context has no gradient, so its backward-data is fv3hip_cyclegan_train_backward_data on the source rows w.
+ *   fv3hip_cyclegan_train_backward_weight_context
+ *       fv3hip_cyclegan_train_backward_weight plus the gradient of the context rows, in fv3hip_cyclegan_conv_context's layout
+ *       [taps][c_cell + c_uni][c_out] (cell channels first):
+ *           dw_ctx[t][j][co] = sum_{s,f,o} ctx~[s,f,T(o,t)][j] dy[s,f,o][co]
+ *       with ctx~ resolved as the forward resolves it: with _HALO_CUBE the neighbouring face's cell context and the uniform
+ *       value, both zero at corners; with _HALO_ZEROS both zero off the face.  _REGULAR only (k = 3, 5, 7); a context with another
+ *       kind is FV3HIP_EUNSUPPORTED.  The same chunks in the same order, the same float64 db, no atomics; dw, dw_ctx and db are
+ *       overwritten.  With c_cell = c_uni = 0 (ctx_cell, ctx_uniform, dw_ctx null) it is fv3hip_cyclegan_train_backward_weight
+ *       bit for bit.  Workspace: fv3hip_cyclegan_train_backward_weight_context_workspace_bytes(...).
+ *   fv3hip_fmr_loss_grad
+ *       the window loss and its gradient.  fake and real are float32 windows [n_windows][n_times][n_elements] whose states
+ *       (n_elements floats) are contiguous; the window and time strides, in floats, may put either outside (time-major or
+ *       window-major).  dgan (null: zero) and dfake (null: the values only) have fake's strides; dgan may be dfake itself.
+ *           values[0] = identity_weight / N0 * sum over time 0 of l(f - r),       N0 = n_windows * n_elements
+ *           values[1] = target_weight / N1 * sum over times >= 1 of l(f - r),     N1 = n_windows * (n_times - 1) * n_elements
+ *           l = |d| (FV3HIP_FMR_LOSS_MAE) or d^2 (FV3HIP_FMR_LOSS_MSE), every term formed in float64
+ *           dfake = dgan + weight / N * sign(f - r)  (mae; sign(0) = 0)   or   dgan + 2 weight / N * (f - r)  (mse),
+ *                   evaluated in float64 and rounded once, one writer per element
+ *       The sums are float64 partials of blocks of consecutive elements, added in ascending order by one wave: no atomics, the
+ *       result is bitwise reproducible.  values: two DEVICE doubles.  n_times < 2 is refused (the target would be a mean over
+ *       no element).  Workspace: fv3hip_fmr_loss_grad_workspace_bytes(...) bytes of DEVICE memory, 8-byte aligned.
+ */
+#define FV3HIP_FMR_LOSS_MSE 0
+#define FV3HIP_FMR_LOSS_MAE 1
+size_t fv3hip_cyclegan_train_backward_weight_context_workspace_bytes(int64_t n_samples, int n, int c_in, int c_cell, int c_uni,
+                                                                     int c_out, int k);
+int fv3hip_cyclegan_train_backward_weight_context(const float *x, int64_t x_ld, int64_t x_off, int64_t x_sample_stride,
+                                                  const float *dy, int64_t dy_ld, int64_t dy_off, int64_t dy_sample_stride,
+                                                  const float *ctx_cell, int c_cell, const float *ctx_uniform, int c_uni, float *dw,
+                                                  float *dw_ctx, float *db, float *workspace, size_t workspace_bytes,
+                                                  int64_t n_samples, int n, int c_in, int c_out, int kind, int k, int halo_mode,
+                                                  void *stream);
+size_t fv3hip_fmr_loss_grad_workspace_bytes(int64_t n_windows, int64_t n_times, int64_t n_elements);
+int fv3hip_fmr_loss_grad(const float *fake, int64_t fake_window_stride, int64_t fake_time_stride, const float *real,
+                         int64_t real_window_stride, int64_t real_time_stride, const float *dgan, float *dfake, int64_t n_windows,
+                         int64_t n_times, int64_t n_elements, int identity_kind, double identity_weight, int target_kind,
+                         double target_weight, double *values, double *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- training random forests (fv3fit's "sklearn_random_forest"; sklearn's RandomForestRegressor.fit: squared error, exact
  * best split, all features).  Stateless like fv3hip_train_*: the caller owns every DEVICE buffer below, nothing is allocated or
  * synchronised, the arguments are checked on the host before any HIP call.  One tree grows level by level:
