@@ -8,13 +8,14 @@ batch, the chunk workspaces of the weight gradients, the resident normalised, ha
 ``[samples, nx + 2 h, ny + 2 h, C]`` and the targets ``[samples * nx * ny, sum F_out]``.  PyTorch supplies memory and the stream
 only.
 """
-from typing import List, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
 from .train import MseLoss
+from .train_state import DeviceMseLoss, FlatParameters, capture_step, check_batch, split_heads, upload
 
 
 class ConvTrainer:
@@ -55,22 +56,13 @@ class ConvTrainer:
         if tuple(np.shape(targets)) != (self.n_samples * self.n_pix, self.f_out):
             raise ValueError(f"targets are {np.shape(targets)}, expected {(self.n_samples * self.n_pix, self.f_out)}")
 
-        flat = [np.concatenate([np.asarray(w, np.float32).reshape(-1), np.asarray(b, np.float32)])
-                for w, b in zip(hidden_kernels, hidden_biases)]
-        flat.append(np.concatenate([np.asarray(out_kernel, np.float32).reshape(-1), np.asarray(out_bias, np.float32)]))
-        self.params = torch.from_numpy(np.concatenate(flat)).to(dev)
-        self.grads, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
-        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.w, self.b, self.dw, self.db = [], [], [], []
-        off = 0
-        for shape in self.conv_shapes + [self.head_shape]:
-            size = int(np.prod(shape))
-            self.w.append(self.params[off:off + size].view(shape))
-            self.dw.append(self.grads[off:off + size].view(shape))
-            off += size
-            self.b.append(self.params[off:off + shape[-1]])
-            self.db.append(self.grads[off:off + shape[-1]])
-            off += shape[-1]
+        layers = list(zip(list(hidden_kernels) + [out_kernel], list(hidden_biases) + [out_bias]))
+        pairs = [pair for l, (w, b) in enumerate(layers) for pair in ((("w", l), w), (("b", l), b))]   # kernel, then its bias
+        flat = self._flat = FlatParameters(pairs, dev)
+        self.params, self.grads, self.m, self.v, self.step_count = flat.params, flat.grads, flat.m, flat.v, flat.step_count
+        p, g = flat.views(flat.params), flat.views(flat.grads)
+        self.w, self.b = [p["w", l] for l in range(len(layers))], [p["b", l] for l in range(len(layers))]
+        self.dw, self.db = [g["w", l] for l in range(len(layers))], [g["b", l] for l in range(len(layers))]
 
         B = self.max_batch
         self._h = [torch.zeros((B, ex, ey, s[3]), dtype=torch.float32, device=dev)
@@ -89,37 +81,23 @@ class ConvTrainer:
         self._first = torch.zeros(B, dtype=torch.int64, device=dev)
         self._rows = torch.zeros(B * self.n_pix, dtype=torch.int64, device=dev)
 
-        self.xin = torch.from_numpy(np.ascontiguousarray(xin, np.float32)).to(dev)
-        self.targets = torch.from_numpy(np.ascontiguousarray(targets, np.float32)).to(dev)
-        self._mse = loss
-        self._loss_arrays = {name: torch.from_numpy(np.ascontiguousarray(getattr(loss, name), np.float32)).to(dev)
-                             for name in ("scale", "center", "inv_cstd2", "lo", "hi", "keep")}
-        self._wnorm = {}
+        self.xin, self.targets = upload(xin, dev), upload(targets, dev)
+        self._mse = DeviceMseLoss(loss, dev)
 
     # -- one optimiser step ------------------------------------------------------------------
-    def _check(self, idx: torch.Tensor) -> int:
-        n = int(idx.shape[0])
-        if not 1 <= n <= self.max_batch:
-            raise ValueError(f"a batch of {n} tile-samples does not fit the buffers of {self.max_batch}")
-        return n
-
     def step(self, idx: torch.Tensor) -> None:
         """One Adam step on the tile-samples ``idx`` (int64, on the device), then the kernel constraint on every hidden kernel
         (Keras applies a ``kernel_constraint`` after the update); the loss stays on the device."""
         self.backward(idx)
-        ops.train_adam(self.params, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps)
+        self._flat.adam(self.lr, self.betas, self.eps)
         if self.transpose_invariant and self.k > 1:   # (on a 1 x 1 kernel, the heads included, it is the identity)
             for w in self.w[:-1]:
                 ops.train_conv_constrain(w)
 
     def backward(self, idx: torch.Tensor) -> None:
         """Forward, loss and the gradient of every parameter for the tile-samples ``idx``, into ``self.grads``."""
-        n = self._check(idx)
+        n = check_batch(int(idx.shape[0]), self.max_batch, "tile-samples")
         rows_n = n * self.n_pix
-        wn = self._wnorm.get(n)
-        if wn is None:
-            wn = self._wnorm[n] = torch.from_numpy(self._mse.wnorm(rows_n)).to(self.device)
-        la = self._loss_arrays
         n_hidden = len(self.conv_shapes)
         a, table = self.xin, idx
         for l in range(n_hidden):
@@ -132,8 +110,7 @@ class ConvTrainer:
         torch.mul(idx, self.n_pix, out=self._first[:n])
         rows = self._rows[:rows_n]
         torch.add(self._first[:n].unsqueeze(1), self._pix, out=rows.view(n, self.n_pix))
-        ops.train_mse_grad(y, la["scale"], la["center"], la["inv_cstd2"], la["lo"], la["hi"], la["keep"], wn, self.targets, dy,
-                           self._loss, self._loss_ws, idx=rows)
+        self._mse.grad(y, self.targets, dy, self._loss, self._loss_ws, rows)
         ops.train_linear_backward_weight(last, dy, self.dw[-1], self.db[-1], workspace=self._ws)
         ops.train_linear_backward_data(dy, self.w[-1], last if self.relu else None, dlast)
         for l in range(n_hidden - 1, -1, -1):
@@ -144,49 +121,24 @@ class ConvTrainer:
                 ops.train_conv_backward_data(self._dh[l][:n], self.w[l], self._h[l - 1][:n] if self.relu else None, self._dh[l - 1][:n])
 
     def capture(self, idx: torch.Tensor) -> "torch.cuda.CUDAGraph":
-        """A HIP graph of ``step(idx)`` reading the tile-sample numbers from ``idx``'s memory: refill ``idx`` in place and
-        ``replay()``.  One eager step is taken first (on a side stream, as torch asks) so that nothing is initialised under
-        capture; it counts as a step."""
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            self.step(idx)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self.step(idx)
-        return graph
+        """``train_state.capture_step``: a HIP graph of ``step(idx)``, after one eager step that counts as a step."""
+        return capture_step(self, idx)
 
     def loss(self) -> float:
         """The loss of the last step's batch (before its update), read back."""
         return float(self._loss.cpu()[0])
 
     # -- reading the state back ----------------------------------------------------------------
-    def _split(self, flat: torch.Tensor, head_sizes: Optional[Sequence[int]]):
-        host = flat.cpu().numpy()
-        kernels: List[np.ndarray] = []
-        biases: List[np.ndarray] = []
-        off = 0
-        for shape in self.conv_shapes + [self.head_shape]:
-            size = int(np.prod(shape))
-            kernels.append(host[off:off + size].reshape(shape).copy())
-            off += size
-            biases.append(host[off:off + shape[-1]].copy())
-            off += shape[-1]
-        if head_sizes is None:
-            head_sizes = [self.f_out]
-        if sum(head_sizes) != self.f_out:
-            raise ValueError(f"head sizes {list(head_sizes)} do not add up to {self.f_out} output features")
-        cuts = np.cumsum([0] + list(head_sizes))
-        out_k = [kernels[-1][:, a:b].copy() for a, b in zip(cuts[:-1], cuts[1:])]
-        out_b = [biases[-1][a:b].copy() for a, b in zip(cuts[:-1], cuts[1:])]
-        return kernels[:-1], biases[:-1], out_k, out_b
+    def _host(self, buffer: torch.Tensor, head_sizes: Optional[Sequence[int]]):
+        host = self._flat.to_host(buffer)
+        layers = range(len(self.w))
+        return split_heads([host["w", l] for l in layers], [host["b", l] for l in layers], self.f_out, head_sizes)
 
     def parameters(self, head_sizes: Optional[Sequence[int]] = None):
         """``(hidden_kernels, hidden_biases, output_kernels, output_biases)`` as numpy arrays, the order
         ``fit.conv_spec_from_arrays`` takes them in; the concatenated head layer is cut into ``head_sizes``."""
-        return self._split(self.params, head_sizes)
+        return self._host(self.params, head_sizes)
 
     def gradients(self, head_sizes: Optional[Sequence[int]] = None):
         """The gradient buffer in the layout of ``parameters``."""
-        return self._split(self.grads, head_sizes)
+        return self._host(self.grads, head_sizes)

@@ -23,6 +23,7 @@ from ..xr_compat import DataArray, Dataset, from_compat, to_compat
 from . import io
 from .predictor import Predictor
 from .stacking import match_prediction_to_input_coords
+from .training import check_backend, epoch_minibatches, resolve_backend
 
 
 @io.register("hip-convolutional")
@@ -365,11 +366,8 @@ def _conv_weights(prep: _ConvTraining):
 
 def _conv_batches(hp: ConvolutionalHyperparameters, n: int, dev: torch.device):
     """The minibatches of tile-samples, the same for both backends."""
-    g = torch.Generator().manual_seed(hp.seed)
-    for _ in range(hp.epochs):
-        perm = torch.randperm(n, generator=g).to(dev)
-        for i in range(0, n, hp.batch_size):
-            yield perm[i:i + hp.batch_size]
+    for batches in epoch_minibatches(n, hp.batch_size, hp.epochs, hp.seed, dev):
+        yield from batches
 
 
 def _train_conv_torch(hp: ConvolutionalHyperparameters, prep: _ConvTraining, dev: torch.device):
@@ -445,15 +443,8 @@ def train_convolutional_model(hyperparameters: ConvolutionalHyperparameters, tra
     through the project's own kernels (needs a GPU).  Preparation, initialisation and the minibatch sequence are shared: both
     start from bitwise-equal parameters and see the same tile-samples in the same order."""
     hp = hyperparameters
-    if backend not in (None, "torch", "hip"):
-        raise ValueError(f"backend must be None, 'torch' or 'hip', got {backend!r}")
-    backend = backend or "torch"
-    _check_hyperparameters(hp, backend)
-    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-    if backend == "hip" and dev.type != "cuda":
-        from .. import ops
-
-        ops._require_device(torch.empty(0, device=dev))  # raises: there is no CPU path
+    _check_hyperparameters(hp, check_backend(backend))   # (before the device is asked for: what is not built is refused anywhere)
+    backend, dev = resolve_backend(backend, device)
     prep = _prepare_conv_training(hp, train_batches)
 
     def model(weights):

@@ -18,7 +18,8 @@ import torch
 from .. import cyclegan_train as layers
 from ..cyclegan import N_GEOGRAPHIC_FEATURES, SECONDS_PER_DAY, check_convolution_type, theta_from_seconds
 from .cyclegan import (GeneratorTwin, _ConvBlock, _GeographicBias, _halo_convolution, _single_tile_convolution,   # noqa: F401
-                       generator_spec_from_state_dict, set_reference_order_gradients)
+                       generator_spec_from_state_dict, generator_state_dict, set_reference_order_gradients)
+from .training import check_backend, strict_fields
 
 nn = torch.nn
 
@@ -26,16 +27,8 @@ LOSS_KEYS = ("b_to_a_gan_loss", "a_to_b_gan_loss", "discriminator_a_loss", "disc
              "generator_loss", "discriminator_loss", "train_loss")
 
 
-def _strict(cls, d: Optional[Mapping], what: str) -> Dict:
-    d = dict(d or {})
-    unknown = set(d) - {f.name for f in dataclasses.fields(cls)}
-    if unknown:
-        raise ValueError(f"{what} has no fields {sorted(unknown)}")
-    return d
-
-
 def _nested(value, cls, what):
-    return value if isinstance(value, cls) else cls(**_strict(cls, value, what))
+    return value if isinstance(value, cls) else cls(**strict_fields(cls, value, what))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -311,15 +304,7 @@ class CycleGANNetworkConfig:
                  "generator_b_to_a": self.generator.build(n_state, nx, self.convolution_type, lon, xyz),
                  "discriminator_a": self.discriminator.build(n_state, nx, self.convolution_type, lon, xyz),
                  "discriminator_b": self.discriminator.build(n_state, nx, self.convolution_type, lon, xyz)}
-        if state_dict is None:
-            for twin in twins.values():
-                init_weights(twin)
-        else:
-            for key, twin in twins.items():
-                twin.load_state_dict({k[len(key) + 1:]: torch.as_tensor(v) for k, v in state_dict.items() if k.startswith(key + ".")},
-                                     strict=True)
-        for twin in twins.values():
-            set_reference_order_gradients(twin, reference_order_gradients)
+        initialise_twins(twins, state_dict, reference_order_gradients)
         return CycleGANTrainer(twins, self, n_batch, n_state, nx, backend=backend, device=device, dtype=dtype)
 
 
@@ -357,6 +342,21 @@ class CycleGANHyperparameters:
     @property
     def variables(self):
         return tuple(self.state_variables) + ("time",)
+
+
+def initialise_twins(twins: Mapping[str, nn.Module], state_dict: Optional[Mapping[str, Any]], reference_order_gradients: bool) -> None:
+    """The freshly built ``twins`` (name -> network) left as the reference's ``init_weights`` leaves them, one after the other in
+    their order, or -- with ``state_dict`` -- each loaded from the entries under its name; then
+    ``fit.cyclegan.set_reference_order_gradients`` on each."""
+    if state_dict is None:
+        for twin in twins.values():
+            init_weights(twin)
+    else:
+        for key, twin in twins.items():
+            twin.load_state_dict({k[len(key) + 1:]: torch.as_tensor(v) for k, v in state_dict.items() if k.startswith(key + ".")},
+                                 strict=True)
+    for twin in twins.values():
+        set_reference_order_gradients(twin, reference_order_gradients)
 
 
 def init_weights(net: nn.Module, init_gain: float = 0.02):
@@ -423,7 +423,37 @@ def unpack_state(state_a, state_b):
     return state_a[0].flatten(), state_b[0].flatten(), fold(state_a[1]), fold(state_b[1])
 
 
-class CycleGANTrainer:
+class TwinExports:
+    """How a GAN trainer hands out its ``networks`` (name -> network of the backend, in the order of ``NETWORKS``; a name begins
+    with ``generator`` or ``discriminator``) under the keys of its ``twins``.  A trainer sets ``NETWORKS`` and
+    ``generator_state_dict(spec, convolution_type)``, which gives the spec of its HIP generator under the twin's keys."""
+
+    def _export(self, key: str, what: str) -> Dict[str, torch.Tensor]:
+        """One network's parameters (``what = "data"``) or gradients (``"grad"``) under its twin's keys, torch's layout, on the
+        host; a parameter without a gradient is left out."""
+        network, twin = self.networks[key], self.twins[key]
+        if self.backend == "torch":
+            pick = (lambda p: p.grad) if what == "grad" else (lambda p: p.data)
+            return {name: pick(p).detach().cpu().clone() for name, p in network.named_parameters() if pick(p) is not None}
+        holder = _grad_view(network) if what == "grad" else network
+        if holder is None:
+            return {}
+        if key.startswith("generator"):
+            return self.generator_state_dict(holder.to_spec(), self.config.convolution_type)
+        return holder.twin_state_dict(twin)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """All parameters keyed as the reference module's ``state_dict()``."""
+        return {f"{key}.{name}": t for key in self.NETWORKS for name, t in self._export(key, "data").items()}
+
+    def gradients(self, stage: str) -> Dict[str, torch.Tensor]:
+        """The gradients of the stage's networks as they stand, keyed as ``state_dict()``."""
+        if stage not in ("generator", "discriminator"):
+            raise ValueError(f"stage must be 'generator' or 'discriminator', got {stage!r}")
+        return {f"{key}.{name}": t for key in self.NETWORKS if key.startswith(stage) for name, t in self._export(key, "grad").items()}
+
+
+class CycleGANTrainer(TwinExports):
     """``CycleGANTrainer.train_on_batch`` (cyclegan_trainer.py:538-693), line for line, without the results aggregator.
 
     ``twins``: the four initialised plain-torch networks of ``n_state`` channels on faces of ``nx`` cells.  ``backend="torch"`` trains them as they are (on ``device``, in
@@ -434,14 +464,13 @@ class CycleGANTrainer:
     ``gradients(stage)`` then holds that stage's gradients under the reference's ``state_dict`` keys, in torch's layout."""
 
     NETWORKS = ("generator_a_to_b", "generator_b_to_a", "discriminator_a", "discriminator_b")
+    generator_state_dict = staticmethod(generator_state_dict)
 
     def __init__(self, twins: Mapping[str, nn.Module], config: CycleGANNetworkConfig, batch_size: int, n_state: int, nx: int,
                  backend: str = "torch", device=None, dtype=torch.float32):
-        if backend not in ("torch", "hip"):
-            raise ValueError(f"backend must be 'torch' or 'hip', got {backend!r}")
-        self.backend, self.config, self.batch_size = backend, config, batch_size
+        self.backend, self.config, self.batch_size = check_backend(backend), config, batch_size
         self.twins = dict(twins)
-        if backend == "hip":
+        if self.backend == "hip":
             from ..cube import cuda_device
 
             self.device, self.dtype = cuda_device(device or "cuda", "CycleGANTrainer(backend='hip')"), torch.float32
@@ -566,33 +595,6 @@ class CycleGANTrainer:
             "train_loss": float((loss_g + loss_d).detach()),
         }
 
-    # -- parameters and gradients under the reference's keys ------------------------------------------
-    def _export(self, key: str, what: str) -> Dict[str, torch.Tensor]:
-        """One network's parameters (``what = "data"``) or gradients (``"grad"``) under its twin's keys, torch's layout, on the
-        host; a parameter without a gradient is left out."""
-        network, twin = self.networks[key], self.twins[key]
-        if self.backend == "torch":
-            pick = (lambda p: p.grad) if what == "grad" else (lambda p: p.data)
-            return {name: pick(p).detach().cpu().clone() for name, p in network.named_parameters() if pick(p) is not None}
-        holder = _grad_view(network) if what == "grad" else network
-        if holder is None:
-            return {}
-        if key.startswith("generator"):
-            from .cyclegan import generator_state_dict
-
-            return generator_state_dict(holder.to_spec(), self.config.convolution_type)
-        return holder.twin_state_dict(twin)
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """All parameters keyed as ``CycleGANModule.state_dict()``."""
-        return {f"{key}.{name}": t for key in self.NETWORKS for name, t in self._export(key, "data").items()}
-
-    def gradients(self, stage: str) -> Dict[str, torch.Tensor]:
-        """The gradients of the stage's two networks as they stand, keyed as ``state_dict()``."""
-        if stage not in ("generator", "discriminator"):
-            raise ValueError(f"stage must be 'generator' or 'discriminator', got {stage!r}")
-        return {f"{key}.{name}": t for key in self.NETWORKS if key.startswith(stage) for name, t in self._export(key, "grad").items()}
-
 
 def _grad_view(network: nn.Module) -> Optional[nn.Module]:
     """A shallow copy of a HIP network whose parameters are the gradients of the original's (None: there are none yet)."""
@@ -625,6 +627,12 @@ def _normalised(arrays: Mapping[str, np.ndarray], names: Sequence[str], scalers)
         a = (np.asarray(arrays[name], np.float64) - mean) / std
         cols.append(a if a.ndim == 6 else a[..., None])
     return torch.from_numpy(np.ascontiguousarray(np.moveaxis(np.concatenate(cols, axis=-1), -1, 3).astype(np.float32)))
+
+
+def flat_scaler_pairs(scalers: Mapping[str, Any]) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
+    """name -> ``(mean, std)`` of fitted scalers as float64 vectors of one length, as the spec builders take them."""
+    return {k: (np.asarray(m, np.float64).reshape(-1), np.broadcast_to(np.asarray(s, np.float64), np.shape(m)).reshape(-1).copy())
+            for k, (m, s) in scalers.items()}
 
 
 def train_cyclegan(hyperparameters: CycleGANHyperparameters, train_batches, validation_batches=None, device=None,
@@ -686,9 +694,7 @@ def train_cyclegan(hyperparameters: CycleGANHyperparameters, train_batches, vali
 
     def model():
         state = trainer.state_dict()
-        pairs = {k: (np.asarray(m, np.float64).reshape(-1), np.broadcast_to(np.asarray(s, np.float64), np.shape(m)).reshape(-1).copy())
-                 for k, (m, s) in scalers.items()}
-        spec = cyclegan_spec_from_state_dict(state, names, pairs, nx, hp.network.convolution_type, lon, xyz,
+        spec = cyclegan_spec_from_state_dict(state, names, flat_scaler_pairs(scalers), nx, hp.network.convolution_type, lon, xyz,
                                              **dataclasses.asdict(hp.network.generator))
         config = dict(trainer.twins["discriminator_a"].config)
         out = HipCycleGAN(names, spec, {"config": config, "state_dict": {k: v for k, v in state.items() if k.startswith("discriminator")}})

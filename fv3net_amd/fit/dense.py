@@ -27,6 +27,7 @@ from . import io
 from .input_sensitivity import InputSensitivity, nondimensionalize_jacobians
 from .predictor import Predictor
 from .stacking import column_sources, match_prediction_to_input_coords
+from .training import epoch_minibatches, linear_arrays, resolve_backend
 
 
 CONFIG_FILENAME = "config.yaml"
@@ -299,12 +300,8 @@ def _train_torch(hp: DenseHyperparameters, prep: _DenseTraining, dev: torch.devi
     t_std = [torch.from_numpy(s).to(dev) for s in prep.y_std]
     t_cstd = [torch.from_numpy(np.maximum(s, 1e-12)).to(dev) for s in prep.yc_std]
     opt = torch.optim.Adam(list(trunk.parameters()) + list(heads.parameters()), lr=hp.learning_rate)
-    n = xin.shape[0]
-    g = torch.Generator().manual_seed(hp.seed)
-    for _ in range(hp.epochs):
-        perm = torch.randperm(n, generator=g).to(dev)
-        for i in range(0, n, hp.batch_size):
-            idx = perm[i:i + hp.batch_size]
+    for batches in epoch_minibatches(xin.shape[0], hp.batch_size, hp.epochs, hp.seed, dev):
+        for idx in batches:
             hidden = trunk(xin[idx])
             loss = 0.0
             for j, name in enumerate(hp.output_variables):
@@ -318,9 +315,7 @@ def _train_torch(hp: DenseHyperparameters, prep: _DenseTraining, dev: torch.devi
             opt.zero_grad()
             loss.backward()
             opt.step()
-    lin_layers = [m for m in trunk if isinstance(m, torch.nn.Linear)]
-    return ([m.weight.detach().cpu().numpy().T.copy() for m in lin_layers], [m.bias.detach().cpu().numpy().copy() for m in lin_layers],
-            [h.weight.detach().cpu().numpy().T.copy() for h in heads], [h.bias.detach().cpu().numpy().copy() for h in heads])
+    return (*linear_arrays([m for m in trunk if isinstance(m, torch.nn.Linear)]), *linear_arrays(heads))
 
 
 def dense_mse_loss(hp: DenseHyperparameters, prep: _DenseTraining):
@@ -348,11 +343,10 @@ def dense_trainer(hp: DenseHyperparameters, prep: _DenseTraining, dev: torch.dev
     """The device training state of ``backend="hip"``: the layers of ``prep``, the resident inputs and targets, the loss."""
     from ..train import DenseTrainer
 
-    lins = [m for m in prep.trunk if isinstance(m, torch.nn.Linear)]
-    kernels = [m.weight.detach().numpy().T.copy() for m in lins]
-    biases = [m.bias.detach().numpy().copy() for m in lins]
-    kernels.append(np.concatenate([h.weight.detach().numpy().T for h in prep.heads], axis=1))
-    biases.append(np.concatenate([h.bias.detach().numpy() for h in prep.heads]))
+    kernels, biases = linear_arrays([m for m in prep.trunk if isinstance(m, torch.nn.Linear)])
+    head_kernels, head_biases = linear_arrays(prep.heads)
+    kernels.append(np.concatenate(head_kernels, axis=1))
+    biases.append(np.concatenate(head_biases))
     return DenseTrainer(kernels, biases, device=dev, xin=prep.xin, targets=np.concatenate(prep.y, axis=1), loss=dense_mse_loss(hp, prep),
                         max_batch=min(hp.batch_size, prep.xin.shape[0]), learning_rate=hp.learning_rate)
 
@@ -360,12 +354,9 @@ def dense_trainer(hp: DenseHyperparameters, prep: _DenseTraining, dev: torch.dev
 def _train_hip(hp: DenseHyperparameters, prep: _DenseTraining, dev: torch.device):
     """The same minibatches in the same order through ``fv3net_amd.train.DenseTrainer`` (csrc/mlp_train.hip)."""
     trainer = dense_trainer(hp, prep, dev)
-    n = prep.xin.shape[0]
-    g = torch.Generator().manual_seed(hp.seed)
-    for _ in range(hp.epochs):
-        perm = torch.randperm(n, generator=g).to(dev)
-        for i in range(0, n, hp.batch_size):
-            trainer.step(perm[i:i + hp.batch_size])
+    for batches in epoch_minibatches(prep.xin.shape[0], hp.batch_size, hp.epochs, hp.seed, dev):
+        for idx in batches:
+            trainer.step(idx)
     return trainer.parameters([a.shape[1] for a in prep.y])
 
 
@@ -379,20 +370,9 @@ def train_dense_model(hyperparameters: DenseHyperparameters, train_batches: Sequ
     the project's own kernels (needs a GPU).  Normalisation, initialisation and the minibatch sequence are shared: both start
     from bitwise-equal parameters and see the same rows in the same order."""
     hp = hyperparameters
-    if backend not in (None, "torch", "hip"):
-        raise ValueError(f"backend must be None, 'torch' or 'hip', got {backend!r}")
-    if backend == "hip":
-        dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-        if dev.type != "cuda":
-            from .. import ops
-
-            ops._require_device(torch.empty(0, device=dev))  # raises: there is no CPU path
-        prep = _prepare_dense_training(hp, train_batches)
-        weights = _train_hip(hp, prep, dev)
-    else:
-        dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-        prep = _prepare_dense_training(hp, train_batches)
-        weights = _train_torch(hp, prep, dev)
+    backend, dev = resolve_backend(backend, device)
+    prep = _prepare_dense_training(hp, train_batches)
+    weights = (_train_hip if backend == "hip" else _train_torch)(hp, prep, dev)
     spec = spec_from_arrays(hp.input_variables, prep.x_mean, prep.x_std, weights[0], weights[1], hp.output_variables, weights[2],
                             weights[3], prep.y_mean, prep.y_std, clip=hp.clip, limits=hp.limits)
     return HipDenseModel(hp.input_variables, hp.output_variables, spec, unstacked_dims=hp.unstacked_dims)

@@ -35,6 +35,7 @@ from ..emulation.transforms import ComposedTransform, Difference, LogTransform, 
 from ..local_mlp import LocalInput, LocalMlpSpec, LocalOutput
 from ..mlp import InputSpec, MlpSpec, OutputSpec, ResidualSpec
 from ..ops import EmulatorHead
+from .training import check_backend, epoch_minibatches, resolve_backend, strict_fields
 
 STD_DEV_METHODS = ("per_feature", "all", "all_center_all", "max", "mean", "none")   # StdDevMethod
 MEAN_METHODS = ("per_feature", "all", "none")                                       # MeanMethod
@@ -211,14 +212,6 @@ def _norm_from_dict(d) -> Optional[NormFactory]:
     return NormFactory(**d)
 
 
-def _strict(cls, d: Mapping, what: str) -> Dict:
-    d = dict(d or {})
-    unknown = set(d) - {f.name for f in dataclasses.fields(cls)}
-    if unknown:
-        raise ValueError(f"{what} has no fields {sorted(unknown)}")
-    return d
-
-
 @dataclasses.dataclass
 class TransformedParameters:
     """train_microphysics.py:120-182.  ``use_wandb``, ``wandb``, ``checkpoint_model``, ``checkpoint_interval``, ``out_url`` and
@@ -324,7 +317,7 @@ class TransformedParameters:
         d = dict(mapping)
         for key in _TRAIN_CONFIG_KEYS:
             d.pop(key, None)
-        d = _strict(cls, d, "TransformedParameters")
+        d = strict_fields(cls, d, "TransformedParameters")
         entries = list(d.pop("tensor_transform", None) or [])
         for e in entries:
             name = _transform_name(e)
@@ -337,9 +330,9 @@ class TransformedParameters:
         loss_d = dict(d.pop("loss", None) or {})
         if "zhao_carr_loss" in loss_d or "masked_weight" in loss_d:   # (the reference dispatches on the dummy field)
             _refuse("ZhaoCarrLoss")
-        loss_d = _strict(CustomLoss, loss_d, "CustomLoss")
+        loss_d = strict_fields(CustomLoss, loss_d, "CustomLoss")
         if "optimizer" in loss_d:
-            loss_d["optimizer"] = OptimizerConfig(**_strict(OptimizerConfig, loss_d["optimizer"], "OptimizerConfig"))
+            loss_d["optimizer"] = OptimizerConfig(**strict_fields(OptimizerConfig, loss_d["optimizer"], "OptimizerConfig"))
         if "normalization" in loss_d:
             loss_d["normalization"] = _norm_from_dict(loss_d["normalization"])
         loss_d["normalization_map"] = {k: _norm_from_dict(v) for k, v in (loss_d.get("normalization_map") or {}).items()}
@@ -347,13 +340,13 @@ class TransformedParameters:
 
         model = None
         if d.get("model") is not None:
-            model_d = _strict(MicrophysicsConfig, d["model"], "MicrophysicsConfig")
+            model_d = strict_fields(MicrophysicsConfig, d["model"], "MicrophysicsConfig")
             if "architecture" in model_d:
-                model_d["architecture"] = ArchitectureConfig(**_strict(ArchitectureConfig, model_d["architecture"], "ArchitectureConfig"))
+                model_d["architecture"] = ArchitectureConfig(**strict_fields(ArchitectureConfig, model_d["architecture"], "ArchitectureConfig"))
             if "normalize_default" in model_d:
                 model_d["normalize_default"] = _norm_from_dict(model_d["normalize_default"])
             model_d["normalize_map"] = {k: _norm_from_dict(v) for k, v in (model_d.get("normalize_map") or {}).items()}
-            model_d["selection_map"] = {k: v if isinstance(v, SliceConfig) else SliceConfig(**_strict(SliceConfig, v, "SliceConfig"))
+            model_d["selection_map"] = {k: v if isinstance(v, SliceConfig) else SliceConfig(**strict_fields(SliceConfig, v, "SliceConfig"))
                                         for k, v in (model_d.get("selection_map") or {}).items()}
             model = MicrophysicsConfig(**model_d)
         d.pop("model", None)
@@ -663,11 +656,8 @@ def _new_history(prep: "_EmulatorTraining") -> Dict[str, list]:
 def _minibatches(hp: TransformedParameters, prep: _EmulatorTraining, dev):
     """Per epoch: the training minibatches (``torch.randperm`` from the seeded generator), then -- where this epoch validates --
     the validation rows in order."""
-    g = torch.Generator().manual_seed(hp.seed)
     n, nv = prep.rows_train, prep.rows_valid
-    for epoch in range(hp.epochs):
-        perm = torch.randperm(n, generator=g).to(dev)
-        train = [perm[i:i + hp.batch_size] for i in range(0, n, hp.batch_size)]
+    for epoch, train in enumerate(epoch_minibatches(n, hp.batch_size, hp.epochs, hp.seed, dev)):
         valid = []
         if nv and (epoch + 1) % hp.valid_freq == 0:
             rows = torch.arange(n, n + nv, dtype=torch.int64, device=dev)
@@ -788,12 +778,9 @@ def train_transformed_model(hyperparameters: TransformedParameters, train_batche
     ``backend``: ``None`` / ``"torch"`` trains through torch expressions, autograd and ``torch.optim.Adam`` (on the CPU too);
     ``"hip"`` through the project's own kernels (needs a GPU).  Preparation, initial weights and minibatch order are shared."""
     hp = hyperparameters
-    if backend not in (None, "torch", "hip"):
-        raise ValueError(f"backend must be None, 'torch' or 'hip', got {backend!r}")
+    check_backend(backend)
     hp.check_supported()   # before anything is uploaded
-    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-    if backend == "hip" and dev.type != "cuda":
-        ops._require_device(torch.empty(0, device=dev))  # raises: there is no CPU path
+    backend, dev = resolve_backend(backend, device)
     prep = _prepare(hp, train_batches, validation_batches)
     kernels, biases, history = (_train_hip if backend == "hip" else _train_torch)(hp, prep, dev)
     return TransformedTrainingResult(emulator=emulator_from_weights(prep, kernels, biases), transform=hp.transform, history=history)

@@ -22,11 +22,11 @@ import torch
 
 from .. import fmr_train as layers
 from ..cyclegan import check_convolution_type
-from .cyclegan import set_reference_order_gradients
-from .cyclegan_train import (CycleGANOptimizerConfig, DiscriminatorTwin, HipDiscriminator, ImagePool, LossConfig, _grad_view, _nested,
-                             _normalised, init_weights, set_requires_grad)
+from .cyclegan_train import (CycleGANOptimizerConfig, DiscriminatorTwin, HipDiscriminator, ImagePool, LossConfig, TwinExports, _nested,
+                             _normalised, flat_scaler_pairs, initialise_twins, set_requires_grad)
 from .fmr import (RecurrentGeneratorTwin, fmr_spec_from_state_dict, fmr_state_dict_from_spec, recurrent_generator_spec_from_state_dict,
                   recurrent_generator_state_dict)
+from .training import check_backend
 
 nn = torch.nn
 
@@ -115,15 +115,7 @@ class FMRNetworkConfig:
         torch.manual_seed(seed)
         twins = {"generator": self.generator.build(n_state, nx, self.convolution_type, xyz, xyz_bottom),
                  "discriminator": self.discriminator.build(n_state, nx, self.convolution_type)}
-        if state_dict is None:
-            for twin in twins.values():
-                init_weights(twin)
-        else:
-            for key, twin in twins.items():
-                twin.load_state_dict({k[len(key) + 1:]: torch.as_tensor(v) for k, v in state_dict.items() if k.startswith(key + ".")},
-                                     strict=True)
-        for twin in twins.values():
-            set_reference_order_gradients(twin, reference_order_gradients)
+        initialise_twins(twins, state_dict, reference_order_gradients)
         return FMRTrainer(twins, self, n_batch, n_state, nx, backend=backend, device=device, dtype=dtype)
 
 
@@ -175,7 +167,7 @@ class PreparedBatch:
         self.tensor = tensor
 
 
-class FMRTrainer:
+class FMRTrainer(TwinExports):
     """``FMRTrainer.train_on_batch`` (train_fmr.py:222-294) in the reference's order: the generator stage with the discriminator
     frozen, then real, pooled fake (``ImagePool(50)``, queried also when evaluating) and the discriminator's step.
 
@@ -187,11 +179,11 @@ class FMRTrainer:
     optimiser's step: ``gradients(stage)`` then holds that stage's gradients under the reference's ``state_dict`` keys."""
 
     NETWORKS = ("generator", "discriminator")
+    generator_state_dict = staticmethod(recurrent_generator_state_dict)
 
     def __init__(self, twins: Mapping[str, nn.Module], config: FMRNetworkConfig, batch_size: int, n_state: int, nx: int,
                  backend: str = "torch", device=None, dtype=torch.float32):
-        if backend not in ("torch", "hip"):
-            raise ValueError(f"backend must be 'torch' or 'hip', got {backend!r}")
+        backend = check_backend(backend)
         check_convolution_type(config.convolution_type)
         self.backend, self.config, self.batch_size, self.n_state, self.nx = backend, config, batch_size, n_state, nx
         self.twins = dict(twins)
@@ -327,29 +319,7 @@ class FMRTrainer:
                 losses.append(self.train_on_batch(batch, evaluate_only=True))
         return {name: float(np.mean([data[name] for data in losses])) for name in losses[0]}
 
-    # -- parameters and gradients under the reference's keys ------------------------------------------
-    def _export(self, key: str, what: str) -> Dict[str, torch.Tensor]:
-        network, twin = self.networks[key], self.twins[key]
-        if self.backend == "torch":
-            pick = (lambda p: p.grad) if what == "grad" else (lambda p: p.data)
-            return {name: pick(p).detach().cpu().clone() for name, p in network.named_parameters() if pick(p) is not None}
-        holder = _grad_view(network) if what == "grad" else network
-        if holder is None:
-            return {}
-        if key == "generator":
-            return recurrent_generator_state_dict(holder.to_spec(), self.config.convolution_type)
-        return holder.twin_state_dict(twin)
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """All parameters keyed as ``FMRModule.state_dict()``."""
-        return {f"{key}.{name}": t for key in self.NETWORKS for name, t in self._export(key, "data").items()}
-
-    def gradients(self, stage: str) -> Dict[str, torch.Tensor]:
-        """The gradients of the stage's network as they stand, keyed as ``state_dict()``."""
-        if stage not in self.NETWORKS:
-            raise ValueError(f"stage must be 'generator' or 'discriminator', got {stage!r}")
-        return {f"{stage}.{name}": t for name, t in self._export(stage, "grad").items()}
-
+    # (``state_dict`` and ``gradients``: ``TwinExports``, keyed as ``FMRModule.state_dict()``)
 
 # ---------------------------------------------------------------------------------------------
 # the training function
@@ -415,9 +385,7 @@ def train_fmr(hyperparameters: FMRHyperparameters, train_batches, validation_bat
 
     def model():
         state = trainer.state_dict()
-        pairs = {k: (np.asarray(m, np.float64).reshape(-1), np.broadcast_to(np.asarray(s, np.float64), np.shape(m)).reshape(-1).copy())
-                 for k, (m, s) in scalers.items()}
-        spec = fmr_spec_from_state_dict(state, names, pairs, nx, hp.network.convolution_type, xyz, xyz_bottom,
+        spec = fmr_spec_from_state_dict(state, names, flat_scaler_pairs(scalers), nx, hp.network.convolution_type, xyz, xyz_bottom,
                                         **dataclasses.asdict(hp.network.generator))
         prefix = "discriminator."
         out = HipFullModelReplacement(names, spec, {"config": dict(trainer.twins["discriminator"].config),

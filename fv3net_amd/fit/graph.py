@@ -24,6 +24,7 @@ from ..graph import (GraphModel, GraphUNetSpec, GraphVariable, SageLayer, UpLaye
                      layer_plan)
 from ..xr_compat import DataArray, Dataset, from_compat, to_compat
 from . import io
+from .training import check_backend, epoch_minibatches, resolve_backend
 
 _TORCH_ACTIVATIONS = {"relu": torch.nn.ReLU, "tanh": torch.nn.Tanh, "linear": torch.nn.Identity}
 _LEAD_DIMS = ("time", "tile", "x", "y")
@@ -402,9 +403,7 @@ def train_graph_model(hyperparameters: GraphHyperparameters, train_batches: Sequ
     under ``torch.manual_seed(seed)``, the ``torch.randperm`` sequence and the keep-the-best rule are one piece of code, so both
     backends start from bitwise-equal parameters and see the same batches."""
     hp = hyperparameters
-    backend = "torch" if backend is None else backend
-    if backend not in ("torch", "hip"):
-        raise ValueError(f"backend must be 'torch' or 'hip', got {backend!r}")
+    backend = check_backend(backend)
     check_architecture(hp.aggregator, hp.pooling_size, hp.pooling_stride, hp.activation)
     if backend == "hip":
         if hp.optimizer not in ("AdamW", "Adam"):
@@ -413,11 +412,7 @@ def train_graph_model(hyperparameters: GraphHyperparameters, train_batches: Sequ
             if key not in _HIP_OPTIMIZER_KWARGS:
                 raise NotImplementedError(f"optimizer argument {key!r} is not built for backend 'hip'; supported: {_HIP_OPTIMIZER_KWARGS}")
     torch.manual_seed(hp.seed)
-    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-    if backend == "hip":
-        from ..ops import _require_device
-
-        _require_device(torch.empty(1, device=dev))
+    backend, dev = resolve_backend(backend, device)
     names = list(hp.state_variables)
     to_np = lambda a: np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a)
     head = {name: np.concatenate([to_np(b[name]) for b in train_batches], axis=0)[:hp.normalization_fit_samples] for name in names}
@@ -455,13 +450,11 @@ def train_graph_model(hyperparameters: GraphHyperparameters, train_batches: Sequ
 
         snapshot = lambda: copy.deepcopy(model.state_dict())
         restore = model.load_state_dict
-    g = torch.Generator().manual_seed(hp.seed)
     best, best_loss = None, float("inf")
-    for _ in range(hp.n_epoch):
+    for batches in epoch_minibatches(train.shape[0], hp.samples_per_batch, hp.n_epoch, hp.seed, dev):
         model.train()
-        perm = torch.randperm(train.shape[0], generator=g).to(dev)
-        for i in range(0, train.shape[0], hp.samples_per_batch):
-            take_step(perm[i:i + hp.samples_per_batch])
+        for idx in batches:
+            take_step(idx)
         if valid is not None:
             val_loss = validate()
             if val_loss < best_loss:

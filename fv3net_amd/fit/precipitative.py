@@ -33,6 +33,7 @@ from .dense import _stack_for_training, read_artifact, spec_from_arrays, write_a
 from .input_sensitivity import InputSensitivity, nondimensionalize_jacobians
 from .predictor import Predictor
 from .stacking import column_sources, match_prediction_to_input_coords
+from .training import epoch_minibatches, linear_arrays, resolve_backend
 
 LV = 2.5e6          # latent heat of evaporation [J/kg]            (precipitative.py:21)
 CPD = 1004.6        # specific heat of dry air at constant pressure  (:23)
@@ -321,12 +322,8 @@ def _train_torch(hp: PrecipitativeHyperparameters, prep: _PrecipitativeTraining,
     t_lstd[2] = t_lstd[2][0]
     c_heat, c_g = float(np.float32(-LV / CPD)), float(np.float32(-1.0 / GRAVITY))
     opt = torch.optim.Adam(list(trunk.parameters()) + list(heads.parameters()), lr=hp.learning_rate)
-    n = xin.shape[0]
-    g = torch.Generator().manual_seed(hp.seed)
-    for _ in range(hp.epochs):
-        perm = torch.randperm(n, generator=g).to(dev)
-        for i in range(0, n, hp.batch_size):
-            idx = perm[i:i + hp.batch_size]
+    for batches in epoch_minibatches(xin.shape[0], hp.batch_size, hp.epochs, hp.seed, dev):
+        for idx in batches:
             hidden = trunk(xin[idx])
             raw = [heads[0](hidden), heads[1](hidden)]
             t_tend = raw[0] * t_std[0] + t_mean[0]
@@ -345,10 +342,7 @@ def _train_torch(hp: PrecipitativeHyperparameters, prep: _PrecipitativeTraining,
             opt.zero_grad()
             loss.backward()
             opt.step()
-    lin_layers = [m for m in trunk if isinstance(m, torch.nn.Linear)]
-    live = [heads[0], heads[1], heads[3]]
-    return ([m.weight.detach().cpu().numpy().T.copy() for m in lin_layers], [m.bias.detach().cpu().numpy().copy() for m in lin_layers],
-            [h.weight.detach().cpu().numpy().T.copy() for h in live], [h.bias.detach().cpu().numpy().copy() for h in live])
+    return (*linear_arrays([m for m in trunk if isinstance(m, torch.nn.Linear)]), *linear_arrays([heads[0], heads[1], heads[3]]))
 
 
 def precipitative_loss(hp: PrecipitativeHyperparameters, prep: _PrecipitativeTraining):
@@ -366,12 +360,10 @@ def precipitative_trainer(hp: PrecipitativeHyperparameters, prep: _Precipitative
     resident inputs, thickness and targets, the loss."""
     from ..train import PrecipitativeTrainer
 
-    lins = [m for m in prep.trunk if isinstance(m, torch.nn.Linear)]
-    kernels = [m.weight.detach().numpy().T.copy() for m in lins]
-    biases = [m.bias.detach().numpy().copy() for m in lins]
-    heads = [h for j, h in enumerate(prep.heads) if j != 2 or prep.has_dead]
-    kernels.append(np.concatenate([h.weight.detach().numpy().T for h in heads], axis=1))
-    biases.append(np.concatenate([h.bias.detach().numpy() for h in heads]))
+    kernels, biases = linear_arrays([m for m in prep.trunk if isinstance(m, torch.nn.Linear)])
+    head_kernels, head_biases = linear_arrays([h for j, h in enumerate(prep.heads) if j != 2 or prep.has_dead])
+    kernels.append(np.concatenate(head_kernels, axis=1))
+    biases.append(np.concatenate(head_biases))
     return PrecipitativeTrainer(kernels, biases, device=dev, xin=prep.xin, delp=prep.delp, physics_precip=prep.physics_precip,
                                 targets=prep.y, loss=precipitative_loss(hp, prep), max_batch=min(hp.batch_size, prep.xin.shape[0]),
                                 learning_rate=hp.learning_rate)
@@ -385,12 +377,9 @@ def _head_sizes(prep: _PrecipitativeTraining) -> List[int]:
 def _train_hip(hp: PrecipitativeHyperparameters, prep: _PrecipitativeTraining, dev: torch.device):
     """The same minibatches in the same order through ``fv3net_amd.train.PrecipitativeTrainer`` (csrc/mlp_train.hip)."""
     trainer = precipitative_trainer(hp, prep, dev)
-    n = prep.xin.shape[0]
-    g = torch.Generator().manual_seed(hp.seed)
-    for _ in range(hp.epochs):
-        perm = torch.randperm(n, generator=g).to(dev)
-        for i in range(0, n, hp.batch_size):
-            trainer.step(perm[i:i + hp.batch_size])
+    for batches in epoch_minibatches(prep.xin.shape[0], hp.batch_size, hp.epochs, hp.seed, dev):
+        for idx in batches:
+            trainer.step(idx)
     hidden_k, hidden_b, out_k, out_b = trainer.parameters(_head_sizes(prep))
     if prep.has_dead:   # dropped on export
         out_k, out_b = out_k[:2] + out_k[3:], out_b[:2] + out_b[3:]
@@ -430,11 +419,7 @@ def train_precipitative_model(hyperparameters: PrecipitativeHyperparameters, tra
     heads are drawn, in the reference's order) and the minibatch sequence are shared: both start from bitwise-equal parameters and
     see the same rows in the same order.  The callbacks and ``validation_batches`` of the reference are out of scope."""
     hp = hyperparameters
-    if backend not in (None, "torch", "hip"):
-        raise ValueError(f"backend must be None, 'torch' or 'hip', got {backend!r}")
-    dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-    if backend == "hip" and dev.type != "cuda":
-        ops._require_device(torch.empty(0, device=dev))  # raises: there is no CPU path
+    backend, dev = resolve_backend(backend, device)
     prep = _prepare_precipitative_training(hp, train_batches)
     weights = (_train_hip if backend == "hip" else _train_torch)(hp, prep, dev)
     names_in, names_out = hp.input_variables, hp.output_variables

@@ -17,6 +17,7 @@ import torch
 from . import _lib, ops
 from .cube import _Slice
 from .graph import ACTIVATIONS, GraphUNetSpec, SageLayer, UpLayer
+from .train_state import FlatParameters, capture_step, check_batch
 
 _FIELDS = {"sage": ("w_self", "w_neigh", "bias"), "up": ("weight", "bias")}
 
@@ -60,21 +61,13 @@ class GraphTrainer:
 
         # parameters, gradients, moments: one flat buffer each, per-layer views in the order of layer_plan
         self.plan = spec.plan
-        flat = [np.asarray(getattr(spec.layers[name], f), np.float32).reshape(-1) for name, kind, *_ in self.plan for f in _FIELDS[kind]]
-        self.params = torch.from_numpy(np.concatenate(flat)).to(dev)
-        self.grads, self.mom, self.var = (torch.zeros_like(self.params) for _ in range(3))
-        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.w: Dict[str, Dict[str, torch.Tensor]] = {}
-        self.dw: Dict[str, Dict[str, torch.Tensor]] = {}
-        off = 0
-        for name, kind, *_ in self.plan:
-            self.w[name], self.dw[name] = {}, {}
-            for f in _FIELDS[kind]:
-                shape = np.shape(getattr(spec.layers[name], f))
-                size = int(np.prod(shape))
-                self.w[name][f] = self.params[off:off + size].view(shape)
-                self.dw[name][f] = self.grads[off:off + size].view(shape)
-                off += size
+        self._fields = {name: _FIELDS[kind] for name, kind, *_ in self.plan}
+        flat = self._flat = FlatParameters([((name, f), getattr(spec.layers[name], f)) for name, fields in self._fields.items() for f in fields],
+                                           dev)
+        self.params, self.grads, self.mom, self.var, self.step_count = flat.params, flat.grads, flat.m, flat.v, flat.step_count
+        p, g = flat.views(flat.params), flat.views(flat.grads)
+        self.w: Dict[str, Dict[str, torch.Tensor]] = {name: {f: p[name, f] for f in fields} for name, fields in self._fields.items()}
+        self.dw: Dict[str, Dict[str, torch.Tensor]] = {name: {f: g[name, f] for f in fields} for name, fields in self._fields.items()}
 
         # activations of every rollout step and one set of gradients, named alike
         B, m, F = self.B, self.m, self.F
@@ -198,10 +191,7 @@ class GraphTrainer:
         ops._require_device(idx)
         if idx.dtype != torch.int64 or idx.dim() != 1:
             raise TypeError("idx must be a 1-D int64 tensor of sample numbers")
-        S = int(idx.shape[0])
-        if not 1 <= S <= self.B:
-            raise ValueError(f"a batch of {S} samples does not fit the buffers of {self.B}")
-        return S
+        return check_batch(int(idx.shape[0]), self.B, "samples")
 
     def backward(self, idx: torch.Tensor) -> None:
         """The rollout from the samples ``idx`` (int64, on the device), the loss of every step and the gradient of every
@@ -216,25 +206,14 @@ class GraphTrainer:
     def step(self, idx: torch.Tensor) -> None:
         """One optimiser step on the samples ``idx``; the loss stays on the device."""
         self.backward(idx)
-        args = (self.params, self.grads, self.mom, self.var, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps)
         if self.optimizer == "AdamW":
-            ops.train_adamw(*args, self.weight_decay)
+            self._flat.adamw(self.lr, self.betas, self.eps, self.weight_decay)
         else:
-            ops.train_adam(*args)
+            self._flat.adam(self.lr, self.betas, self.eps)
 
     def capture(self, idx: torch.Tensor) -> "torch.cuda.CUDAGraph":
-        """A HIP graph of ``step(idx)`` reading the sample numbers from ``idx``'s memory: refill ``idx`` in place and
-        ``replay()``.  One eager step is taken first (on a side stream, as torch asks) so that nothing is initialised under
-        capture; it counts as a step."""
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            self.step(idx)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self.step(idx)
-        return graph
+        """``train_state.capture_step``: a HIP graph of ``step(idx)``, after one eager step that counts as a step."""
+        return capture_step(self, idx)
 
     def loss(self) -> float:
         """The loss of the last step's batch (before its update), read back: the rollout steps' parts added in order."""
@@ -263,25 +242,17 @@ class GraphTrainer:
         return float(total.cpu())
 
     # -- reading the state back ----------------------------------------------------------------------
-    def _layers(self, flat: torch.Tensor) -> Dict[str, Tuple[np.ndarray, ...]]:
-        host, out, off = flat.cpu().numpy(), {}, 0
-        for name, kind, *_ in self.plan:
-            arrays = []
-            for f in _FIELDS[kind]:
-                shape = tuple(self.w[name][f].shape)
-                size = int(np.prod(shape))
-                arrays.append(host[off:off + size].reshape(shape).copy())
-                off += size
-            out[name] = tuple(arrays)
-        return out
+    def _host(self, buffer: torch.Tensor) -> Dict[str, Tuple[np.ndarray, ...]]:
+        host = self._flat.to_host(buffer)
+        return {name: tuple(host[name, f] for f in fields) for name, fields in self._fields.items()}
 
     def parameters(self) -> Dict[str, Tuple[np.ndarray, ...]]:
         """``layer_plan`` name -> ``(w_self, w_neigh, bias)`` or ``(weight, bias)`` as numpy arrays."""
-        return self._layers(self.params)
+        return self._host(self.params)
 
     def gradients(self) -> Dict[str, Tuple[np.ndarray, ...]]:
         """The gradient buffer in the layout of ``parameters``."""
-        return self._layers(self.grads)
+        return self._host(self.grads)
 
     def spec(self) -> GraphUNetSpec:
         """The network as it stands, with the scalers it was given."""

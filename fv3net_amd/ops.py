@@ -1188,6 +1188,14 @@ def train_linear_backward_data(dh: torch.Tensor, w: torch.Tensor, p: Optional[to
     return out
 
 
+def _caller_workspace(workspace: Optional[torch.Tensor]):
+    if workspace is None:
+        return None, 0
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise TypeError("workspace must be a contiguous float32 tensor")
+    return workspace, workspace.numel() * 4
+
+
 def train_linear_backward_weight(a: torch.Tensor, dh: torch.Tensor, dw: torch.Tensor, db: torch.Tensor,
                                  idx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
     """``dw = a[rows].T @ dh``, ``db = dh.sum(0)``; a batch longer than ``train_chunk_rows()`` needs a float32 ``workspace`` of
@@ -1201,11 +1209,7 @@ def train_linear_backward_weight(a: torch.Tensor, dh: torch.Tensor, dw: torch.Te
     w_rows, _, lddw = _rows_f32(dw, "dw", o)
     if w_rows != k:
         raise ValueError(f"dw has {w_rows} rows, a has {k} features")
-    ws_bytes = 0
-    if workspace is not None:
-        if workspace.dtype != torch.float32 or not workspace.is_contiguous():
-            raise TypeError("workspace must be a contiguous float32 tensor")
-        ws_bytes = workspace.numel() * 4
+    workspace, ws_bytes = _caller_workspace(workspace)
     _lib.call_on(dev, "fv3hip_train_linear_backward_weight", _ptr(a), lda, a_rows, _ptr(idx), _ptr(dh), lddh, _ptr(dw), lddw,
                  _ptr(_vec(db, "db", o)), _ptr(workspace), ws_bytes, n, k, o, _stream(dev))
     return dw, db
@@ -1393,16 +1397,22 @@ def train_emulator_loss_grad(yhat: torch.Tensor, table: EmulatorHeadTable, dy: O
     return dy, loss
 
 
-def train_adam(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor, lr: float = 1e-3,
-               beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
-    """``torch.optim.Adam``'s default update of one flat float32 buffer; ``step`` is an int64 device scalar holding the number of
-    steps taken so far, advanced on the device."""
+def _optimizer_state(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor):
+    """(device, count) of the flat float32 buffers of ``train_adam`` / ``train_adamw`` and their int64 step counter, checked."""
     dev = _require_device(params, grad, m, v, step)
     count = int(params.numel())
     for t, name in ((params, "params"), (grad, "grad"), (m, "m"), (v, "v")):
         _vec(t, name, count)
     if step.dtype != torch.int64 or step.numel() != 1:
         raise TypeError("step must be an int64 tensor of one element")
+    return dev, count
+
+
+def train_adam(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor, lr: float = 1e-3,
+               beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
+    """``torch.optim.Adam``'s default update of one flat float32 buffer; ``step`` is an int64 device scalar holding the number of
+    steps taken so far, advanced on the device."""
+    dev, count = _optimizer_state(params, grad, m, v, step)
     _lib.call_on(dev, "fv3hip_train_adam", _ptr(params), _ptr(grad), _ptr(m), _ptr(v), count, _ptr(step), float(lr), float(beta1),
                  float(beta2), float(eps), _stream(dev))
 
@@ -1505,11 +1515,7 @@ def train_conv_backward_weight(a: torch.Tensor, dh: torch.Tensor, dw: torch.Tens
     if dh_samples < n or (ox, oy) != (X - k + 1, Y - k + 1):
         raise ValueError(f"dh is {tuple(dh.shape)}; a batch of {n} samples of {X} x {Y} cells under a {k} x {k} kernel gives "
                          f"{(n, X - k + 1, Y - k + 1, f)}")
-    ws_bytes = 0
-    if workspace is not None:
-        if workspace.dtype != torch.float32 or not workspace.is_contiguous():
-            raise TypeError("workspace must be a contiguous float32 tensor")
-        ws_bytes = workspace.numel() * 4
+    workspace, ws_bytes = _caller_workspace(workspace)
     _lib.call_on(dev, "fv3hip_train_conv_backward_weight", _ptr(a), *sa, a_samples, _ptr(idx), _ptr(dh), *sdh, _ptr(dw), lddw,
                  _ptr(_vec(db, "db", f)), _ptr(workspace), ws_bytes, n, X, Y, k, c, f, _stream(dev))
     return dw, db
@@ -1559,14 +1565,6 @@ def _dense_weight(t: torch.Tensor, what: str, shape) -> torch.Tensor:
     if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
     return t
-
-
-def _caller_workspace(workspace: Optional[torch.Tensor]):
-    if workspace is None:
-        return None, 0
-    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
-        raise TypeError("workspace must be a contiguous float32 tensor")
-    return workspace, workspace.numel() * 4
 
 
 def graph_sage_backward_data(dh, w_self: torch.Tensor, w_neigh: torch.Tensor, p, p_act: int, dst, n_samples: int, n: int,
@@ -1623,12 +1621,7 @@ def graph_pool2_backward(dpool, p, p_act: int, dst, n_samples: int, n: int, c: i
 def train_adamw(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor, lr: float = 1e-3,
                 beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 1e-2) -> None:
     """``torch.optim.AdamW``'s default update of one flat float32 buffer: ``p *= 1 - lr weight_decay``, then ``train_adam``."""
-    dev = _require_device(params, grad, m, v, step)
-    count = int(params.numel())
-    for t, name in ((params, "params"), (grad, "grad"), (m, "m"), (v, "v")):
-        _vec(t, name, count)
-    if step.dtype != torch.int64 or step.numel() != 1:
-        raise TypeError("step must be an int64 tensor of one element")
+    dev, count = _optimizer_state(params, grad, m, v, step)
     _lib.call_on(dev, "fv3hip_train_adamw", _ptr(params), _ptr(grad), _ptr(m), _ptr(v), count, _ptr(step), float(lr), float(beta1),
                  float(beta2), float(eps), float(weight_decay), _stream(dev))
 

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .train_state import DeviceMseLoss, FlatParameters, capture_step, check_batch, split_heads, upload
 
 
 @dataclasses.dataclass
@@ -53,20 +54,13 @@ class DenseTrainer:
         self.max_batch = int(max_batch)
         dev = self.device
 
-        flat = np.concatenate([np.concatenate([np.asarray(k, np.float32).reshape(-1), np.asarray(b, np.float32)])
-                               for k, b in zip(kernels, biases)])
-        self.params = torch.from_numpy(flat).to(dev)
-        self.grads, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
-        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.w, self.b, self.dw, self.db = [], [], [], []
-        off = 0
-        for k, o in self.shapes:
-            self.w.append(self.params[off:off + k * o].view(k, o))
-            self.dw.append(self.grads[off:off + k * o].view(k, o))
-            off += k * o
-            self.b.append(self.params[off:off + o])
-            self.db.append(self.grads[off:off + o])
-            off += o
+        pairs = [pair for l, (k, b) in enumerate(zip(kernels, biases)) for pair in ((("w", l), k), (("b", l), b))]   # kernel, then its bias
+        flat = self._flat = FlatParameters(pairs, dev)
+        self.params, self.grads, self.m, self.v, self.step_count = flat.params, flat.grads, flat.m, flat.v, flat.step_count
+        layers = range(len(self.shapes))
+        p, g = flat.views(flat.params), flat.views(flat.grads)
+        self.w, self.b = [p["w", l] for l in layers], [p["b", l] for l in layers]
+        self.dw, self.db = [g["w", l] for l in layers], [g["b", l] for l in layers]
 
         self.k_in, self.f_out = self.shapes[0][0], self.shapes[-1][1]
         self._h = [torch.zeros((self.max_batch, o), dtype=torch.float32, device=dev) for _, o in self.shapes]
@@ -77,18 +71,14 @@ class DenseTrainer:
         self._loss_ws = torch.zeros(ops.train_loss_workspace_doubles(), dtype=torch.float64, device=dev)
 
         self.xin = self.targets = None
-        self._loss_arrays: Optional[Dict[str, torch.Tensor]] = None
-        self._wnorm: Dict[int, torch.Tensor] = {}
-        self._mse = loss
+        self._mse: Optional[DeviceMseLoss] = None
         if xin is not None:
             if targets is None or loss is None:
                 raise ValueError("training needs xin, targets and loss together")
-            self.xin = torch.from_numpy(np.ascontiguousarray(xin, np.float32)).to(dev)
-            self.targets = torch.from_numpy(np.ascontiguousarray(targets, np.float32)).to(dev)
+            self.xin, self.targets = upload(xin, dev), upload(targets, dev)
             if self.xin.shape[1] != self.k_in or self.targets.shape[1] != self.f_out or self.xin.shape[0] != self.targets.shape[0]:
                 raise ValueError("xin / targets do not match the network")
-            self._loss_arrays = {name: torch.from_numpy(np.ascontiguousarray(getattr(loss, name), np.float32)).to(dev)
-                                 for name in ("scale", "center", "inv_cstd2", "lo", "hi", "keep")}
+            self._mse = DeviceMseLoss(loss, dev)
         self._jac = None
 
     @classmethod
@@ -108,11 +98,9 @@ class DenseTrainer:
         """One Adam step on the minibatch ``idx`` (int64 row numbers, on the device); the loss stays on the device."""
         if self.xin is None:
             raise RuntimeError("this trainer holds no training data")
-        n = int(idx.shape[0])
-        if not 1 <= n <= self.max_batch:
-            raise ValueError(f"a batch of {n} rows does not fit the buffers of {self.max_batch}")
+        check_batch(int(idx.shape[0]), self.max_batch)
         self.backward(idx)
-        ops.train_adam(self.params, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps)
+        self._flat.adam(self.lr, self.betas, self.eps)
 
     def backward(self, idx: torch.Tensor) -> None:
         """Forward, loss and the gradient of every parameter for the minibatch ``idx``, into ``self.grads``."""
@@ -129,57 +117,30 @@ class DenseTrainer:
 
     def _loss_grad(self, idx: torch.Tensor, n: int) -> None:
         """The loss stage: from the head layer's output ``_h[-1][:n]`` to its gradient ``_dh[-1][:n]`` and ``_loss``."""
-        wn = self._wnorm.get(n)
-        if wn is None:
-            wn = self._wnorm[n] = torch.from_numpy(self._mse.wnorm(n)).to(self.device)
-        la = self._loss_arrays
-        ops.train_mse_grad(self._h[-1][:n], la["scale"], la["center"], la["inv_cstd2"], la["lo"], la["hi"], la["keep"], wn,
-                           self.targets, self._dh[-1][:n], self._loss, self._loss_ws, idx=idx)
+        self._mse.grad(self._h[-1][:n], self.targets, self._dh[-1][:n], self._loss, self._loss_ws, idx)
 
     def capture(self, idx: torch.Tensor) -> "torch.cuda.CUDAGraph":
-        """A HIP graph of ``step(idx)`` reading the row numbers from ``idx``'s memory: refill ``idx`` in place and ``replay()``.
-        One eager step is taken first (on a side stream, as torch asks) so that nothing is initialised under capture; it
-        counts as a step."""
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            self.step(idx)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self.step(idx)
-        return graph
+        """``train_state.capture_step``: a HIP graph of ``step(idx)``, after one eager step that counts as a step."""
+        return capture_step(self, idx)
 
     def loss(self) -> float:
         """The loss of the last step's minibatch (before its update), read back."""
         return float(self._loss.cpu()[0])
 
     # -- reading the state back ----------------------------------------------------------------
-    def _split(self, flat: torch.Tensor, head_sizes: Optional[Sequence[int]]):
-        host = flat.cpu().numpy()
-        kernels, biases, off = [], [], 0
-        for k, o in self.shapes:
-            kernels.append(host[off:off + k * o].reshape(k, o).copy())
-            off += k * o
-            biases.append(host[off:off + o].copy())
-            off += o
-        if head_sizes is None:
-            head_sizes = [self.f_out]
-        if sum(head_sizes) != self.f_out:
-            raise ValueError(f"head sizes {list(head_sizes)} do not add up to {self.f_out} output features")
-        cuts = np.cumsum([0] + list(head_sizes))
-        out_k = [kernels[-1][:, a:b].copy() for a, b in zip(cuts[:-1], cuts[1:])]
-        out_b = [biases[-1][a:b].copy() for a, b in zip(cuts[:-1], cuts[1:])]
-        return kernels[:-1], biases[:-1], out_k, out_b
+    def _host(self, buffer: torch.Tensor, head_sizes: Optional[Sequence[int]]):
+        host = self._flat.to_host(buffer)
+        layers = range(len(self.shapes))
+        return split_heads([host["w", l] for l in layers], [host["b", l] for l in layers], self.f_out, head_sizes)
 
     def parameters(self, head_sizes: Optional[Sequence[int]] = None):
         """``(hidden_kernels, hidden_biases, output_kernels, output_biases)`` as numpy arrays, the order ``fit.spec_from_arrays``
         takes them in; the concatenated head layer is cut into ``head_sizes``."""
-        return self._split(self.params, head_sizes)
+        return self._host(self.params, head_sizes)
 
     def gradients(self, head_sizes: Optional[Sequence[int]] = None):
         """The gradient buffer in the layout of ``parameters``."""
-        return self._split(self.grads, head_sizes)
+        return self._host(self.grads, head_sizes)
 
     # -- Jacobian --------------------------------------------------------------------------------
     def jacobian(self, x_row) -> Tuple[np.ndarray, np.ndarray]:
@@ -237,18 +198,18 @@ class PrecipitativeTrainer(DenseTrainer):
         if self.f_out != 3 * nz + int(bool(loss.has_dead)):
             raise ValueError(f"the head layer has {self.f_out} features, the loss {nz} levels (has_dead={bool(loss.has_dead)})")
         self.nz, self.precip_loss = nz, loss
-        self.xin = torch.from_numpy(np.ascontiguousarray(xin, np.float32)).to(dev)
+        self.xin = upload(xin, dev)
         rows = int(self.xin.shape[0])
         t1, t2, t3 = targets
         # dQ1 and dQ2 side by side in one array: one row stride for both
-        self.targets = torch.from_numpy(np.ascontiguousarray(np.concatenate([t1, t2], axis=1), np.float32)).to(dev)
-        self.t3 = torch.from_numpy(np.ascontiguousarray(np.reshape(t3, -1), np.float32)).to(dev)
-        self.delp = torch.from_numpy(np.ascontiguousarray(delp, np.float32)).to(dev)
-        self.physics_precip = torch.from_numpy(np.ascontiguousarray(np.reshape(physics_precip, -1), np.float32)).to(dev)
+        self.targets = upload(np.concatenate([t1, t2], axis=1), dev)
+        self.t3 = upload(np.reshape(t3, -1), dev)
+        self.delp = upload(delp, dev)
+        self.physics_precip = upload(np.reshape(physics_precip, -1), dev)
         if self.xin.shape[1] != self.k_in or tuple(self.targets.shape) != (rows, 2 * nz) or tuple(self.delp.shape) != (rows, nz) or \
                 self.t3.shape[0] != rows or self.physics_precip.shape[0] != rows:
             raise ValueError("xin, delp, physics_precip and the targets do not match the network or each other")
-        self._loss_arrays = {name: torch.from_numpy(np.ascontiguousarray(getattr(loss, name), np.float32)).to(dev)
+        self._loss_arrays = {name: upload(getattr(loss, name), dev)
                              for name in ("scale1", "center1", "scale2", "center2", "inv_cstd2_1", "inv_cstd2_2")}
 
     def _loss_grad(self, idx: torch.Tensor, n: int) -> None:
@@ -276,13 +237,13 @@ class EmulatorTrainer(DenseTrainer):
         super().__init__(kernels, biases, device=device, max_batch=self.batch_cap * self.levels, learning_rate=learning_rate, betas=betas,
                          eps=eps, relu=relu)
         dev = self.device
-        self.xin = torch.from_numpy(np.ascontiguousarray(xin, np.float32)).to(dev)
+        self.xin = upload(xin, dev)
         if self.xin.dim() != 2 or self.xin.shape[1] != self.k_in or self.xin.shape[0] % self.levels:
             raise ValueError(f"xin {tuple(self.xin.shape)} does not match {self.k_in} inputs and {self.levels} levels")
         self.rows = int(self.xin.shape[0]) // self.levels
 
         def up(a):
-            return None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
+            return None if a is None else upload(a, dev)
 
         arrays = ("scale", "center", "target", "inv", "before", "target_after", "inv_after")
         self.heads = [dataclasses.replace(h, **{k: up(getattr(h, k)) for k in arrays}) for h in heads]
@@ -305,9 +266,7 @@ class EmulatorTrainer(DenseTrainer):
             self._net_idx = torch.zeros(self.batch_cap * self.levels, dtype=torch.int64, device=dev)
 
     def _network_rows(self, idx: torch.Tensor) -> torch.Tensor:
-        n = int(idx.shape[0])
-        if not 1 <= n <= self.batch_cap:
-            raise ValueError(f"a batch of {n} rows does not fit the buffers of {self.batch_cap}")
+        n = check_batch(int(idx.shape[0]), self.batch_cap)
         if self.levels == 1:
             return idx
         net = self._net_idx[:n * self.levels]
